@@ -8,6 +8,11 @@ step   : one FRAME = 64 sub-frame launches of 1 spp (reference default spp=1: sr
 rays   : radiance segments + shadow rays ACTUALLY traced (device queue lengths), not W*H*spp*depth.
 N > 1  : one process per GPU (torch.distributed, backend nccl = RCCL); the frame's pixel tiles are dealt round-robin
          to the ranks (no data-path collective), one gather of the tile accumulators to rank 0 per frame.
+plain  : `bench.py --gpus 1 --steps N --warmup W` sets up, warms up, times the N steps and prints the headline line (value,
+         ms_per_step, per-kernel ms of the timed steps, config) -- nothing else.
+--full : everything measured beside the headline as well: the live rocprofv3 counter passes and the roofline, the measured
+         memory ceilings, the drop-in and interactive call patterns, the other workloads and the CPU baseline.
+--dump-outputs DIR : after the timed steps, the image the last step produced -> DIR/image.npy (float32; see dump_outputs).
 Prints ONE JSON line on rank 0.
 """
 import argparse
@@ -144,7 +149,7 @@ def live_pmc(argv, spp, keep_dir=None):
     if under_profiler():
         sys.stderr.write("[bench] live counters: this process already runs under a profiler -- not nesting\n")
         return None
-    skip = {"--steps", "--warmup", "--spp", "--cpu-budget", "--gpus", "--pmc-keep", "--pmc-save"}
+    skip = {"--steps", "--warmup", "--spp", "--cpu-budget", "--gpus", "--pmc-keep", "--pmc-save", "--dump-outputs"}
     child, it = [], iter(argv)
     for a in it:
         if a in skip:
@@ -520,6 +525,28 @@ def shade_bytes(rays, next_rays, shadow_rays):
     return rays * (28 + 32 + 40) + rays * (128 + 96 + 64) + next_rays * 28 + shadow_rays * 44
 
 
+DUMP_LIMIT_BYTES = 64_000_000  # --dump-outputs writes at most this much in all
+
+
+def dump_outputs(outdir, image, limit=DUMP_LIMIT_BYTES):
+    """--dump-outputs: what the timed path hands its caller -- the H x W float4 image the last step wrote -- as <outdir>/image.npy
+    (float32).  An image above `limit` is written as a fixed sample of its pixels instead: image_sample.npy (n x 4, float32) and
+    image_sample_index.npy (their row-major pixel indices, float64), drawn with a fixed seed so that two builds sample the same pixels.
+    Returns the names of the files written."""
+    os.makedirs(outdir, exist_ok=True)
+    img = np.ascontiguousarray(image, dtype=np.float32)
+    budget = limit - 4096  # (room for the .npy headers)
+    if img.nbytes <= budget:
+        np.save(os.path.join(outdir, "image.npy"), img)
+        return ["image.npy"]
+    px = img.reshape(-1, img.shape[-1])
+    n = budget // (px.shape[1] * px.itemsize + 8)
+    idx = np.sort(np.random.default_rng(0).choice(len(px), n, replace=False))
+    np.save(os.path.join(outdir, "image_sample.npy"), px[idx])
+    np.save(os.path.join(outdir, "image_sample_index.npy"), idx.astype(np.float64))
+    return ["image_sample.npy", "image_sample_index.npy"]
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -533,16 +560,23 @@ def main():
     ap.add_argument("--scene", default="kitchen", help="kitchen | kitchen_unshared | kitchen_arch | cornell | hair | hair_8 | hair_16 | hair_17 | hair_17_xform | hair_17_moved | path to a .skscene dump or a .gltf file")
     ap.add_argument("--waves-per-cu", type=int, default=0)
     ap.add_argument("--opt", action="append", default=[], help="name=value passed to skh_set_option")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what sits beside the headline: counter passes + roofline, memory ceilings, drop-in and interactive legs, "
+                         "other workloads, CPU baseline (the --no-* options below trim a --full run)")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR", help="write the image the last timed step produced to DIR/image.npy")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--cpu-budget", type=float, default=12.0)
     ap.add_argument("--no-pmc", action="store_true", help="do not run the rocprofv3 --pmc child passes (roofline quotes the committed profile)")
-    ap.add_argument("--pmc-child", action="store_true", help=argparse.SUPPRESS)
+    ap.add_argument("--pmc-child", action="store_true", help=argparse.SUPPRESS)  # a counter pass of a --full run: implies --full
     ap.add_argument("--pmc-keep", default=None, help="keep the rocprofv3 output of the child passes in this directory")
     ap.add_argument("--pmc-save", default=None, metavar="TAG", help="write the live counter figures to profiles/pmc_kernels.json under this tag")
     ap.add_argument("--no-drop-in", action="store_true", help="skip the one-render()+map()-per-sub-frame leg")
     ap.add_argument("--no-extra", action="store_true", help="skip the other workloads (kitchen_unshared, kitchen_arch) timed beside the headline")
     ap.add_argument("--strict", action="store_true", help="exit 4 when a LIVE counter fraction (HBM bytes or VALU issue) comes out above 1")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
+    full = args.full or args.pmc_child
 
     rc = maybe_self_launch(args, sys.argv[1:])
     if rc is not None:
@@ -556,7 +590,7 @@ def main():
     sc, arr, workload = load_workload(args.scene, make=(local_rank == 0))  # (per NODE: /tmp is not shared between nodes)
     t_scene = time.time() - t_scene
     global PMC_RESULT
-    if world == 1 and not args.no_pmc and not args.pmc_child:
+    if full and world == 1 and not args.no_pmc and not args.pmc_child:
         PMC_RESULT = live_pmc(sys.argv[1:], args.spp, args.pmc_keep)  # child processes; nothing here has touched the GPU yet
     import torch
 
@@ -672,10 +706,10 @@ def main():
             dist.barrier()
         torch.cuda.synchronize()
 
-    # ---- untimed counting pass: exact traversal counters for the algorithmic-bytes figures (identical every frame, the
+    # ---- untimed counting pass (--full): exact traversal counters for the algorithmic-bytes figures (identical every frame, the
     #      renderer is deterministic); rank 0 only -- they describe rank 0's kernels ----
     cst = None
-    if rank == 0:
+    if rank == 0 and full:
         ctx.set_option("count_traversal", 1)
         ctx.reset_stats()
         ctx.render_subframes(params, args.spp, None)
@@ -714,15 +748,18 @@ def main():
                     "tiles": [int(x) for x in allr[:, 2]]}
     else:
         rays_total = float(rays_local)
+    if rank == 0 and args.dump_outputs:
+        names = dump_outputs(args.dump_outputs, image.cpu().numpy())
+        sys.stderr.write("[bench] outputs of the last timed step: %s in %s\n" % (", ".join(names), args.dump_outputs))
 
     strict_fail = False
     drop_in = None
     interactive = None
-    if rank == 0 and world == 1 and not args.no_drop_in and not args.pmc_child:
+    if full and rank == 0 and world == 1 and not args.no_drop_in and not args.pmc_child:
         drop_in = drop_in_leg(ctx, params, W, H, args.spp, torch, dev)
         interactive = interactive_leg(ctx, sc, W, H, args.depth, torch, dev)
     extra = None
-    if rank == 0 and world == 1 and args.scene == "kitchen" and not args.no_extra and not args.no_drop_in and not args.pmc_child:
+    if full and rank == 0 and world == 1 and args.scene == "kitchen" and not args.no_extra and not args.no_drop_in and not args.pmc_child:
         extra = {name: other_workload_leg(name, W, H, args.spp, args.depth, local_rank) for name in ("kitchen_unshared", "kitchen_arch")}
         # C5 (BASELINE.json configs[4]): the basis-curves workload at ITS depth (3), 64 spp per pass like the headline
         extra["hair"] = other_workload_leg("hair", W, H, args.spp, 3, local_rank)
@@ -730,8 +767,9 @@ def main():
         extra["hair_multi"] = {name: {k: v for k, v in other_workload_leg(name, W, H, args.spp, 3, local_rank).items()
                                       if k in ("workload", "value", "unit", "ms_per_step", "kernel_ms_per_frame", "per_ray", "per_shadow_ray", "bvh_build_ms")}
                                for name in ("hair_8", "hair_16", "hair_17", "hair_17_xform", "hair_17_moved")}
-    if rank == 0:
-        K = max(1, args.steps)
+    K = max(1, args.steps)
+    pmc, roofline, flags = None, None, []
+    if rank == 0 and full:
         # ---- rooflines of the three hot kernels.  Per kernel, from this run's counters and hipEvent times:
         #   frac (= frac_hbm)   HBM-side bytes per launch from the TCC counters / live launch time / 8 TB/s.  FETCH_SIZE counts
         #                       Infinity-Cache hits too (MI355X_MICROARCH.md "HBM"), so this is an UPPER bound on HBM use.
@@ -845,22 +883,24 @@ def main():
         if flags:
             roofline["flags"] = flags
             sys.stderr.write("[bench] roofline flags: %s\n" % "; ".join(flags))
+    if rank == 0:
         out = {
             "metric": "Mray/s", "value": round(rays_total / dt / 1e6, 3), "unit": "Mray/s", "n_gpus": world,
             "steps": args.steps, "warmup": args.warmup, "ms_per_step": round(dt / K * 1e3, 3),
             "higher_is_better": True, "scaling": "strong", "vs_baseline": None, "dtype": "f32", "data": "synthetic",
             "config": {"workload": workload, "resolution": f"{W}x{H}", "bounces": args.depth, "spp": args.spp,
                        "step": f"one frame = one skh_render_subframes({args.spp}) pass: {args.spp} sub-frames of 1 spp traced together, accumulated in order (bit-identical to {args.spp} calls; the "
-                               "reference caller's one-call-per-sub-frame loop is `value_drop_in` / `drop_in`, its moving-camera loop `interactive`)", "tile": args.tile, "world_size": world,
+                               "reference caller's one-call-per-sub-frame loop is `value_drop_in` / `drop_in`, its moving-camera loop `interactive`: --full)", "tile": args.tile, "world_size": world,
                        "parallelism": f"pixel tiles round-robin over {world} GPU(s), 1 gather/frame ({gather_kind})" if world > 1
                        else "single GPU", "rays_per_frame": int(rays_total / K), "bvh_build_ms": round(build_ms, 2), "bvh": bvh_info,
                        "bake_world": {"baked_instances": baked[1], "baked_triangles": baked[2]}, "scene_load_s": round(t_scene, 1)},
             "gather": gather_kind, "rccl_nranks": rccl_nranks,
-            "roofline_replayed": bool(pmc and pmc.get("replayed")) or pmc is None,
             "kernel_ms_per_frame": {k: round(st[k] / K, 3) for k in ("ms_trace_closest", "ms_trace_shadow", "ms_shade",
                                                                      "ms_raygen", "ms_accumulate", "ms_sort")},
-            "roofline": roofline,
         }
+        if full:
+            out["roofline_replayed"] = bool(pmc and pmc.get("replayed")) or pmc is None
+            out["roofline"] = roofline
         if per_rank is not None:
             out["per_rank"] = per_rank
         if gather_error:
@@ -882,7 +922,7 @@ def main():
 
             img = image.cpu().numpy() if world > 1 else ctx.read_accum()
             out["image_crc32"] = zlib.crc32(np.ascontiguousarray(img[..., :3]).tobytes())
-        if not args.no_cpu_baseline and world == 1:
+        if full and not args.no_cpu_baseline and world == 1:
             out["cpu_baseline"] = cpu_baseline(arr, cam, W, H, args.spp, args.depth, args.cpu_budget)
         print(json.dumps(out), flush=True)
         if args.strict and flags and PMC_RESULT:

@@ -190,7 +190,7 @@ def test_limiter_is_derived_from_the_lines_own_fractions():
     assert bench.frac_of_copy(blk, None) is None
     src = open(os.path.join(ROOT, "bench.py")).read()
     assert '"limiter": "' not in src  # no literal limiter left
-    assert 'extra["hair"]' in src  # C5 is a leg of the default line
+    assert 'extra["hair"]' in src  # C5 is a leg of the --full line
 
 
 def test_measured_clock_from_the_counter_pass(tmp_path):
@@ -217,3 +217,29 @@ def test_measured_clock_from_the_counter_pass(tmp_path):
     src = open(os.path.join(ROOT, "bench.py")).read()
     for needle in ('out["value_drop_in"]', 'out["interactive"]', "one skh_render_subframes(", "frac_valu_issue_at_max_clock", 'extra["hair_multi"]'):
         assert needle in src, needle
+
+
+def test_dump_outputs_writes_the_image_or_a_fixed_sample(tmp_path):
+    """--dump-outputs: the whole float32 image when it fits, else the same seeded pixel sample every time, within the size limit."""
+    import numpy as np
+
+    img = np.random.RandomState(3).rand(40, 60, 4).astype(np.float32)
+    assert bench.dump_outputs(str(tmp_path / "a"), img) == ["image.npy"]
+    got = np.load(tmp_path / "a" / "image.npy")
+    assert got.dtype == np.float32 and np.array_equal(got, img)
+    limit = 4096 + 200 * (4 * 4 + 8)  # room for 200 pixels and their indices
+    for d in ("b", "c"):
+        assert bench.dump_outputs(str(tmp_path / d), img, limit=limit) == ["image_sample.npy", "image_sample_index.npy"]
+        assert sum(os.path.getsize(tmp_path / d / f) for f in os.listdir(tmp_path / d)) <= limit
+    px, idx = np.load(tmp_path / "b" / "image_sample.npy"), np.load(tmp_path / "b" / "image_sample_index.npy")
+    assert px.dtype == np.float32 and idx.dtype == np.float64 and px.shape == (200, 4)
+    assert np.array_equal(px, img.reshape(-1, 4)[idx.astype(np.int64)])
+    assert np.array_equal(idx, np.load(tmp_path / "c" / "image_sample_index.npy"))  # the same pixels in every run
+
+
+def test_plain_run_options():
+    """--full and --dump-outputs exist; --steps below 1 is refused before anything is imported or launched."""
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--help"], capture_output=True, text=True, timeout=120)
+    assert r.returncode == 0 and "--full" in r.stdout and "--dump-outputs" in r.stdout
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "0"], capture_output=True, text=True, timeout=120)
+    assert r.returncode == 2 and "--steps" in r.stderr

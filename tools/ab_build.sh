@@ -4,7 +4,7 @@
 name=$1; shift
 defs=""; for d in "$@"; do defs="$defs -D$d"; done
 /opt/rocm/bin/hipcc -O3 --offload-arch=gfx950 -ffp-contract=off -fno-slp-vectorize -mllvm -amdgpu-sched-strategy=max-ilp -fPIC -shared -std=c++17 $defs -o /tmp/lib_$name.so strelka_amd/csrc/strelka_hip.hip || exit 1
-SKH_LIB=/tmp/lib_$name.so python bench.py --steps ${STEPS:-2} --warmup 1 --no-pmc --no-drop-in --no-cpu-baseline ${BENCH_ARGS:-} > /tmp/ab_$name.json 2> /tmp/ab_$name.err
+SKH_LIB=/tmp/lib_$name.so python bench.py --full --steps ${STEPS:-2} --warmup 1 --no-pmc --no-drop-in --no-cpu-baseline ${BENCH_ARGS:-} > /tmp/ab_$name.json 2> /tmp/ab_$name.err
 python - <<PY
 import json
 d=json.load(open('/tmp/ab_$name.json')); k=d['kernel_ms_per_frame']; r=d['roofline']

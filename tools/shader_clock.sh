@@ -7,7 +7,7 @@ export SKH_LIB=/tmp/lib_$name.so
 R=$PWD
 cd /tmp && export TMPDIR=/tmp
 rm -rf /tmp/clk_$name
-rocprofv3 --pmc GRBM_GUI_ACTIVE --output-format csv -d /tmp/clk_$name -- python3 $R/bench.py --steps 1 --warmup 0 --spp 32 --no-pmc --no-drop-in --no-cpu-baseline > /tmp/clk_$name.log 2>&1
+rocprofv3 --pmc GRBM_GUI_ACTIVE --output-format csv -d /tmp/clk_$name -- python3 $R/bench.py --full --steps 1 --warmup 0 --spp 32 --no-pmc --no-drop-in --no-cpu-baseline > /tmp/clk_$name.log 2>&1
 cd $R
 python3 - <<PY
 import csv, glob
