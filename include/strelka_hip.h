@@ -26,7 +26,7 @@
 extern "C" {
 #endif
 
-#define SKH_ABI_VERSION 5 /* 5 (round 6): + skh_refit_accel, skh_build_info.refit / ms_refit; options curve_merge, curve_segnode, curve_strand_major, split_pairs.  4 (round 5): + skh_get_build_info; options reinsert_rounds, reinsert_min_size; wide, tail_park, tail_lag removed.  3 (round 4): + skh_unit_probe, skh_copy_aov */
+#define SKH_ABI_VERSION 5 /* 5 (round 6): + skh_refit_accel, skh_build_info.refit / ms_refit, then skh_update_accel (additive: refit = 2); options curve_merge, curve_segnode, curve_strand_major, split_pairs.  4 (round 5): + skh_get_build_info; options reinsert_rounds, reinsert_min_size; wide, tail_park, tail_lag removed.  3 (round 4): + skh_unit_probe, skh_copy_aov */
 
 /* mirrors oka::Result (include/render/common.h:30-35) */
 typedef enum skh_status
@@ -267,6 +267,30 @@ skh_status skh_build_accel(skh_context* ctx, uint32_t flags);
  * so a refitted tree returns what a rebuilt one returns; after large deformations a rebuild traverses faster.  Kitchen stand-in (23 M world-space triangles,
  * 6.06 M nodes): build 61 ms, refit 2.2 ms. */
 skh_status skh_refit_accel(skh_context* ctx);
+/* After edits that keep every hierarchy's topology -- instance TRANSFORMS, vertices (skh_set_geometry with the built mesh table and index buffer), curve control
+ * points and radii (skh_set_curves with the built curve sets and vertex counts), in any combination, for every scene kind -- update every level of the
+ * acceleration structure in place: the triangle and curve trees (the baked world-space triangles carry their instances' transforms) are refitted when their
+ * primitives moved, the instance records and world boxes recomputed, the TLAS keeps its tree and leaf order and is refitted level by level on the GPU.  The
+ * reference has the edit channel (Scene::updateInstanceTransform / getDirtyInstances, include/scene/scene.h:437-455) and never reads it.
+ *   instances  the instance table of the last build (or update) with any TRANSFORMS -- type, geom_id, material_id, light_id unchanged -- and n_instances its
+ *              count; NULL (n_instances 0) = the table as it is (skh_set_instances may have set it).
+ * skh_build_info.refit = 2 and ms_refit = the wall time when it updated in place.  Otherwise it IS skh_set_instances(instances) + skh_build_accel(flags of the
+ * last build), refit = 0, results as exact; that happens for
+ *   - no build yet, or an option changed since the last one (every option that changes a hierarchy clears it);
+ *   - another instance count, or an instance whose type, geom_id, material_id or light_id changed (what the bake and the TLAS leaves are made of);
+ *   - another mesh table / index buffer, or other curve sets / vertex counts (topology: the refit's own rule);
+ *   - a transform that became singular (invert_affine fails) or stopped being singular: the instance gains or loses its TLAS leaf and its bake;
+ *   - a world-curve entry (a curve tree the world-only kernel enters itself) whose transform left or reached the bit-exact identity: the build orders the
+ *     table by it and lets the kernel skip the identity's matrix (SKH_REF_CURVEROOT_IDENT);
+ *   - members of a merged curve group (option curve_merge) that no longer share one transform: their segments sit in ONE tree, in the group's object space;
+ *   - tlas_open > 1 (experimental): the opened TLAS leaves are BLAS subtrees whose boxes the build made from the transforms;
+ *   - the experimental segment-node curve build (curve_segnode), which has no refit.
+ * Hit records do not depend on the hierarchy, so the updated structure returns what a rebuild returns; the trees keep the shape they were built for, so after
+ * large moves a rebuild traverses faster (kitchen stand-in, one 1080p sub-frame's closest-hit trace: 2.2 ms as built, 2.9 ms after one instance moved by half
+ * the room, 84 ms after every instance moved, 2.8 ms rebuilt).  Drops sub-frames traced ahead, as every scene setter does.  Cost: the shading tables, one
+ * launch per tree level of every tree whose boxes changed, one host inversion per instance -- kitchen stand-in with every instance moved: 2.1 ms baked
+ * (64-69 ms build), 0.6 ms with bake_world 0 (37 ms); 10^5 instances with bake_world 0: 1.3 ms (10.5 ms); docs/LOG.md. */
+skh_status skh_update_accel(skh_context* ctx, const skh_instance* instances, uint32_t n_instances);
 
 /* Which instances skh_build_accel baked to world space (option bake_world; `flags` receives one byte per instance, 1 = baked;
  * either pointer may be NULL).  A baked mesh instance has no IAS entry (OptixRender.cpp:412-441 creates one per instance): its
@@ -481,12 +505,13 @@ typedef struct skh_build_info
     uint32_t reinsert_rounds; /* rounds that ran (a round without a move ends the pass) */
     uint32_t reinsert_moves; /* subtrees moved, all rounds */
     uint32_t reinsert_min_size; /* truncation used: only nodes whose parent holds at least this many primitives moved */
-    uint32_t refit; /* 1: the hierarchy in use came out of skh_refit_accel's refit (topology of the last build, boxes of the current vertices); 0: out of a build */
+    uint32_t refit; /* 1: the hierarchy in use came out of skh_refit_accel's refit (topology of the last build, boxes of the current vertices); 2: out of skh_update_accel's
+                       in-place update, top level included (topology of the last build, boxes of the current transforms, vertices and control points); 0: out of a build */
     double cost_before; /* sum of the internal binary nodes' box half-areas after PLOC ... */
     double cost_after; /* ... and after the reinsertion pass (== cost_before when it did not run) */
     double ms_reinsert; /* wall time of the pass, inside ms_build */
     double ms_build; /* == skh_stats.ms_build */
-    double ms_refit; /* wall time of the last refit (leaf records gathered again + one launch per tree level + the shading tables) */
+    double ms_refit; /* wall time of the last refit or in-place update (leaf records gathered again + one launch per tree level + the shading tables) */
 } skh_build_info;
 skh_status skh_get_build_info(skh_context* ctx, skh_build_info* out);
 skh_status skh_get_stats(skh_context* ctx, skh_stats* out);

@@ -24,6 +24,25 @@
 namespace oka
 {
 
+// the scene's instances as skh_set_instances / skh_update_accel take them
+static std::vector<skh_instance> instanceTable(Scene& sc)
+{
+    std::vector<skh_instance> inst(sc.getInstances().size());
+    for (size_t i = 0; i < inst.size(); ++i)
+    {
+        const Instance& in = sc.getInstances()[i];
+        // glm::float3x4(glm::rowMajor4(transform)) (OptixRender.cpp:438): rows of the affine transform
+        for (int r = 0; r < 3; ++r)
+            for (int c = 0; c < 4; ++c)
+                inst[i].transform[4 * r + c] = in.transform[c][r];
+        inst[i].type = (uint32_t)in.type;
+        inst[i].geom_id = in.mMeshId;
+        inst[i].material_id = in.mMaterialId;
+        inst[i].light_id = in.mLightId;
+    }
+    return inst;
+}
+
 HipBuffer::HipBuffer(skh_context* ctx, void* devicePtr, BufferFormat format, uint32_t width, uint32_t height) : mCtx(ctx), mDeviceData(devicePtr)
 {
     mFormat = format;
@@ -156,23 +175,28 @@ void HipRender::uploadScene()
                              (uint32_t)sc.getCurvesVertexCounts().size(), reinterpret_cast<const skh_curve*>(sc.getCurves().data()),
                              (uint32_t)sc.getCurves().size()),
               "skh_set_curves");
-    std::vector<skh_instance> inst(sc.getInstances().size());
-    for (size_t i = 0; i < inst.size(); ++i)
-    {
-        const Instance& in = sc.getInstances()[i];
-        // glm::float3x4(glm::rowMajor4(transform)) (OptixRender.cpp:438): rows of the affine transform
-        for (int r = 0; r < 3; ++r)
-            for (int c = 0; c < 4; ++c)
-                inst[i].transform[4 * r + c] = in.transform[c][r];
-        inst[i].type = (uint32_t)in.type;
-        inst[i].geom_id = in.mMeshId;
-        inst[i].material_id = in.mMaterialId;
-        inst[i].light_id = in.mLightId;
-    }
+    std::vector<skh_instance> inst = instanceTable(sc);
     check(skh_set_instances(mCtx, inst.data(), (uint32_t)inst.size()), "skh_set_instances");
+    mSentInstances = inst;
     check(skh_set_lights(mCtx, reinterpret_cast<const skh_light*>(sc.getLights().data()), (uint32_t)sc.getLights().size()), "skh_set_lights");
     uploadMaterials();
     check(skh_build_accel(mCtx, SKH_BUILD_LBVH), "skh_build_accel");
+}
+
+bool HipRender::sendMovedInstances()
+{
+    Scene& sc = *mScene;
+    const std::vector<skh_instance> inst = instanceTable(sc);
+    bool moved = false;
+    for (uint32_t id : sc.getDirtyInstances())
+        moved = moved || (id < inst.size() && id < mSentInstances.size() &&
+                          memcmp(inst[id].transform, mSentInstances[id].transform, sizeof(inst[id].transform)) != 0);
+    if (!moved)
+        return false;
+    // (the caller's dirty set is left alone: it belongs to the scene's frame protocol, beginFrame / endFrame)
+    check(skh_update_accel(mCtx, inst.data(), (uint32_t)inst.size()), "skh_update_accel");
+    mSentInstances = inst;
+    return true;
 }
 
 void HipRender::uploadMaterials()
@@ -229,7 +253,9 @@ void HipRender::render(Buffer* output)
 {
     SharedContext& sh = getSharedContext();
     if (sh.mFrameNumber == 0)
-        uploadScene(); // scene is uploaded once; later edits are ignored, like the reference (OptixRender.cpp:876-888)
+        uploadScene(); // scene is uploaded once (OptixRender.cpp:876-888); later edits are ignored, like the reference, except ...
+    else if (!mScene->getDirtyInstances().empty() && sendMovedInstances())
+        sh.mSubframeIndex = 0; // ... moved instances (Scene::updateInstanceTransform): the hierarchy is updated, accumulation restarts as after a camera move
 
     const uint32_t width = output->width();
     const uint32_t height = output->height();

@@ -94,6 +94,10 @@ private:
     std::vector<uint32_t> mAllTileXY; // root: (x0, y0) of every rank's tiles, rank-major, padded to mMaxTiles per rank
     void* mGatherBuf = nullptr; // root: [world][mMaxTiles][tile^2] float4
     void uploadScene(); // mFrameNumber == 0 block: OptixRender.cpp:876-888
+    // instances the scene marks dirty (Scene::updateInstanceTransform) whose transform differs from what was last sent: the whole table goes to
+    // skh_update_accel (in place where it can); true = something was sent
+    bool sendMovedInstances();
+    std::vector<skh_instance> mSentInstances;
     void uploadMaterials(); // MaterialDescription list -> skh_material blocks + textures (OptixRender.cpp:1270-1433)
 };
 

@@ -26,7 +26,8 @@ SYMBOLS = ["skh_create", "skh_destroy", "skh_last_error", "skh_abi_version", "sk
            "skh_render_subframe", "skh_render_subframes", "skh_tonemap", "skh_read_accum", "skh_read_aov",
            "skh_buffer_alloc", "skh_buffer_free", "skh_buffer_download", "skh_copy_accum", "skh_copy_accum_tiles", "skh_scatter_tiles", "skh_trace", "skh_trace_device",
            "skh_set_option", "skh_get_stats", "skh_reset_stats", "skh_synchronize", "skh_get_stream", "skh_bsdf_probe", "skh_get_device_info", "skh_comm_unique_id", "skh_comm_init",
-           "skh_comm_destroy", "skh_gather_tiles", "skh_host_register", "skh_host_unregister", "skh_get_baked", "skh_comm_info", "skh_probe_memory", "skh_unit_probe", "skh_copy_aov", "skh_get_build_info", "skh_refit_accel"]
+           "skh_comm_destroy", "skh_gather_tiles", "skh_host_register", "skh_host_unregister", "skh_get_baked", "skh_comm_info", "skh_probe_memory", "skh_unit_probe", "skh_copy_aov", "skh_get_build_info", "skh_refit_accel",
+           "skh_update_accel"]
 
 BUILD_INFO = np.dtype([("triangles", np.uint32), ("nodes", np.uint32), ("reinsert_rounds", np.uint32), ("reinsert_moves", np.uint32),
                        ("reinsert_min_size", np.uint32), ("refit", np.uint32), ("cost_before", np.float64), ("cost_after", np.float64),
@@ -73,6 +74,7 @@ def load():
         getattr(lib, n).argtypes = [vp, vp, u32]
     lib.skh_build_accel.argtypes = [vp, u32]
     lib.skh_refit_accel.argtypes = [vp]
+    lib.skh_update_accel.argtypes = [vp, vp, u32]
     lib.skh_resize.argtypes = [vp, u32, u32]
     lib.skh_set_tiles.argtypes = [vp, u32, vp, u32]
     lib.skh_render_subframe.argtypes = [vp, vp, vp]
@@ -329,6 +331,21 @@ class Context:
     def refit_accel(self):
         """skh_refit_accel: keep the hierarchy's topology, recompute leaf records and boxes from the current vertices (falls back to a build)"""
         self._ck(self.lib.skh_refit_accel(self.h), "skh_refit_accel")
+
+    def set_instances(self, instances):
+        """skh_set_instances alone (the table update_accel(None) then takes, or the next build)"""
+        inst = np.ascontiguousarray(instances, dtype=S.INSTANCE)
+        self._ck(self.lib.skh_set_instances(self.h, _p(inst), len(inst)), "skh_set_instances")
+
+    def update_accel(self, instances=None):
+        """skh_update_accel: update every level of the hierarchy in place after edited instance transforms (`instances`: the structured S.INSTANCE
+        array of the last build with new transforms; None = the table as it is) and / or vertex and control-point edits (set_geometry / set_curves
+        first).  build_info()["refit"] says 2 when it updated in place, 0 when it fell back to a build."""
+        if instances is None:
+            self._ck(self.lib.skh_update_accel(self.h, None, 0), "skh_update_accel")
+            return
+        inst = np.ascontiguousarray(instances, dtype=S.INSTANCE)
+        self._ck(self.lib.skh_update_accel(self.h, _p(inst), len(inst)), "skh_update_accel")
 
     def build_info(self):
         """what the last skh_build_accel did to the triangle hierarchy (reinsertion rounds / moves, cost before and after)"""

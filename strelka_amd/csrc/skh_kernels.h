@@ -1691,6 +1691,36 @@ __global__ void k_permute_instances(const DevInstance* __restrict__ src, const u
     if (i < n)
         dst[i] = src[order[i]];
 }
+// TLAS refit (skh_update_accel): a TLAS leaf's box is the world box of the instance its traversal record names (pad), as the builders took it
+struct TlasLeaves
+{
+    const DevInstance* __restrict__ tinst;
+    const float4* __restrict__ boxLo;
+    const float4* __restrict__ boxHi;
+    __device__ __forceinline__ void box(uint32_t first, uint32_t count, float4& lo, float4& hi) const
+    {
+        lo = make_float4(INFINITY, INFINITY, INFINITY, 0.0f), hi = make_float4(-INFINITY, -INFINITY, -INFINITY, 0.0f);
+        for (uint32_t k = 0; k < count; ++k)
+        {
+            const uint32_t i = tinst[first + k].pad;
+            const float4 l = boxLo[i], h = boxHi[i];
+            lo = make_float4(fminf(lo.x, l.x), fminf(lo.y, l.y), fminf(lo.z, l.z), 0.0f);
+            hi = make_float4(fmaxf(hi.x, h.x), fmaxf(hi.y, h.y), fmaxf(hi.z, h.z), 0.0f);
+        }
+    }
+};
+// ... and the leaf-ordered traversal records rewritten from the new instance records (leaf order, instance id and BLAS root stay)
+__global__ void k_tlas_records(DevInstance* __restrict__ tinst, uint32_t n, const DevInstance* __restrict__ inst)
+{
+    const uint32_t r = blockIdx.x * blockDim.x + threadIdx.x;
+    if (r >= n)
+        return;
+    const DevInstance old = tinst[r];
+    DevInstance d = inst[old.pad];
+    d.rootRef = old.rootRef;
+    d.pad = old.pad;
+    tinst[r] = d;
+}
 
 // Tight world box of a mesh instance: the box of its transformed VERTICES instead of the box of the eight transformed corners
 // of the object-space box (for a round object turned by 45 degrees the latter has twice the footprint).  One workgroup per

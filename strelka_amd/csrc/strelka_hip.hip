@@ -151,6 +151,16 @@ struct skh_context
     uint64_t curveSig = 0, builtCurveSig = 0;
     bool curvePointsEdited = false, curveRefitReady = false;
     uint32_t nTris = 0, nSegs = 0;
+    // skh_update_accel (edited instance transforms, any scene kind): what the last build leaves behind for it -- the instance table it was built from (kept
+    // up to date by every update), per instance whether its transform had a finite inverse and whether it took a TLAS leaf, the BLASes' group roots and
+    // bounds (k_instance_boxes' inputs), the TLAS's node levels, the merged curve groups -- and the instance boxes' scratch
+    bool updateReady = false; // the last skh_build_accel ran to its end
+    bool vertsEdited = false; // skh_set_geometry since the last build / refit / update
+    std::vector<skh_instance> builtInstances;
+    std::vector<uint8_t> builtInvOk;
+    std::vector<std::vector<uint32_t>> builtMergedGroups;
+    DevBuf dBuiltValid, dW2o, dInstLo, dInstHi, dInstGrp, dTriGroupRoot, dTriGroupBounds, dSegGroupRoot, dSegGroupBounds, dTlasNodeBox;
+    std::vector<uint32_t> tlasLevelStart;
 
     // frame
     uint32_t width = 0, height = 0, tileSize = 32, tileShift = 5, numTiles = 0, numSlots = 0;
@@ -244,7 +254,6 @@ struct skh_context
     uint32_t compactHits = 1;   // option compact_hits: 16-byte hit records in the render passes of world-only triangle scenes that fit (HitQ::primBits)
     uint32_t leafMaxTris = 2; // measured on MI355X: 2 beats 1, 3, 4, 6, 8 (the kernel is ALU bound, wasted triangle tests cost more than extra nodes)
     uint32_t buildQuality = 1; // 0: Karras radix tree (fastest build), 1: PLOC clustering (SAH-class quality)
-    float sceneLo[3] = { 0, 0, 0 }, sceneHi[3] = { 1, 1, 1 };
 
     // timing
     std::vector<TimedSpan> spans;
@@ -889,11 +898,12 @@ static void hb_box_of_ref(int ref, const std::vector<HostBin>& bin, const std::v
     }
 }
 static int tlas_sah_build(const std::vector<HostBox>& boxes, const std::vector<uint32_t>& ids, std::vector<Node4>& nodes,
-                          std::vector<uint32_t>& order)
+                          std::vector<uint32_t>& order, std::vector<uint32_t>& levelStart /* as LbvhOut::levelStart: the nodes of level L = [levelStart[L], levelStart[L + 1]) */)
 {
     const uint32_t n = (uint32_t)ids.size();
     nodes.clear();
     order.clear();
+    levelStart.clear();
     if (n == 0)
         return SKH_REF_INVALID;
     order.assign(ids.begin(), ids.end());
@@ -992,16 +1002,19 @@ static int tlas_sah_build(const std::vector<HostBox>& boxes, const std::vector<u
             bin[t.parent].right = ref;
     }
     // collapse the binary tree into 4-wide nodes (same greedy rule as k_collapse)
+    // (breadth first: node w is work item w, and the children of a level's nodes take the next slots -- levels are contiguous ranges, children behind parents)
     struct Item
     {
-        int bin, out;
+        int bin, out, depth;
     };
     std::vector<Item> work;
     nodes.push_back(Node4{});
-    work.push_back(Item{ rootRef, 0 });
+    work.push_back(Item{ rootRef, 0, 0 });
     for (size_t w = 0; w < work.size(); ++w)
     {
         const Item it = work[w];
+        if (levelStart.size() <= (size_t)it.depth)
+            levelStart.push_back((uint32_t)w);
         int slot[4];
         int cnt = 2;
         slot[0] = bin[it.bin].left;
@@ -1035,7 +1048,7 @@ static int tlas_sah_build(const std::vector<HostBox>& boxes, const std::vector<u
             {
                 refs[k] = (int)nodes.size();
                 nodes.push_back(Node4{});
-                work.push_back(Item{ slot[k], refs[k] });
+                work.push_back(Item{ slot[k], refs[k], it.depth + 1 });
             }
             else
                 refs[k] = slot[k];
@@ -1044,6 +1057,7 @@ static int tlas_sah_build(const std::vector<HostBox>& boxes, const std::vector<u
         encode_node4(nd, bin[it.bin].lo, bin[it.bin].hi, clo, chi, refs, cnt);
         nodes[it.out] = nd;
     }
+    levelStart.push_back((uint32_t)nodes.size());
     return 0; // the root is node 0
 }
 
@@ -1149,7 +1163,8 @@ void skh_destroy(skh_context* c)
                        &c->dCurveSegBase, &c->dSegStartAll, &c->dTriNodes, &c->dTris, &c->dSegNodes, &c->dSegs,
                        &c->dTlasNodes, &c->dTlasInst, &c->dDevInst, &c->dTravInst, &c->dTexels, &c->dTexDesc, &c->dTriOrder, &c->dTriMeshK, &c->dTriLocalK, &c->dWInstK, &c->dWFirstK, &c->dTriNodeBox, &c->dSegOrder, &c->dSegBuildStartK, &c->dSegLocalK, &c->dSegInstOfK, &c->dSegNodeBox, &c->dScatterXY, &c->dRaygenBase, &c->dTileXY, &c->dAccum, &c->dDiffuse, &c->dSpecular, &c->dDiffCnt,
                        &c->dSpecCnt, &c->dSums, &c->dPath, &c->dRayQ[0], &c->dRayQ[1], &c->dHits, &c->dShadowQ, &c->dContrib,
-                       &c->dCounts, &c->dOvf, &c->dOvf2, &c->dStats, &c->dScratchImage, &c->dPathB })
+                       &c->dCounts, &c->dOvf, &c->dOvf2, &c->dStats, &c->dScratchImage, &c->dPathB, &c->dBuiltValid, &c->dW2o, &c->dInstLo, &c->dInstHi, &c->dInstGrp,
+                       &c->dTriGroupRoot, &c->dTriGroupBounds, &c->dSegGroupRoot, &c->dSegGroupBounds, &c->dTlasNodeBox })
         dev_free(*b);
     for (hipEvent_t e : c->eventPool)
         (void)hipEventDestroy(e);
@@ -1205,6 +1220,7 @@ skh_status skh_set_geometry(skh_context* c, const skh_vertex* verts, uint32_t n_
     c->nVerts = n_verts;
     c->nIndices = n_indices;
     c->accelBuilt = false;
+    c->vertsEdited = true;
     {
         // signature of the TOPOLOGY (mesh table + index buffer, FNV-1a over their words): skh_refit_accel keeps the hierarchy only while it is the built one
         uint64_t h = 1469598103934665603ull;
@@ -1279,9 +1295,8 @@ skh_status skh_set_instances(skh_context* c, const skh_instance* instances, uint
         return SKH_INVALID_ARGUMENT;
     spec_drop(c);
     (void)hipSetDevice(c->device);
-    // (the same table again -- a caller that re-sends the whole scene with edited vertices -- keeps a refit possible)
-    if (!(n == c->nInstances && n == c->instances.size() && (n == 0 || memcmp(c->instances.data(), instances, sizeof(skh_instance) * (size_t)n) == 0)))
-        c->refitReady = false;
+    // (skh_refit_accel compares the table with the build's: the same table again -- a caller that re-sends the whole scene with edited vertices -- keeps a refit
+    // possible; skh_update_accel takes edited transforms in place)
     c->instances.assign(instances, instances + n);
     c->nInstances = n;
     c->accelBuilt = false;
@@ -1443,6 +1458,7 @@ skh_status skh_build_accel(skh_context* c, uint32_t flags)
             return SKH_INVALID_ARGUMENT;
         }
     }
+    c->updateReady = false;
     const bool usePloc = (flags & SKH_BUILD_SAH) != 0 || c->buildQuality != 0;
     const auto t0 = std::chrono::steady_clock::now();
     hipStream_t st = c->stream;
@@ -1455,6 +1471,7 @@ skh_status skh_build_accel(skh_context* c, uint32_t flags)
     std::vector<uint8_t> valid(std::max(1u, nInst));
     for (uint32_t i = 0; i < nInst; ++i)
         valid[i] = invert_affine(c->instances[i].transform, &w2o[12 * (size_t)i]) ? 1 : 0;
+    c->builtInvOk = valid;
     std::vector<uint32_t> meshUsers(nMeshes, 0u), meshUsersLeft(nMeshes, 0u); // users: mesh + light instances; left: those that keep their TLAS leaf
     c->baked.assign(std::max(1u, nInst), 0);
     // two world-space groups: [0] mesh instances (every ray), [1] light proxies (radiance rays only: shadow rays do not see lights,
@@ -1621,9 +1638,9 @@ skh_status skh_build_accel(skh_context* c, uint32_t flags)
     const uint32_t nTris = nMeshTris + nBaked;
     c->nTris = nTris;
     LbvhOut triOut, segOut;
-    DevBuf dTriMesh, dTriLocal, dBoxLo, dBoxHi, dGrp, dSegStart, dSegCurve, dSegLocal, dSegBuildStart, dSegInstOf, dW2o, dValid, dWInst, dWFirst;
+    DevBuf dTriMesh, dTriLocal, dBoxLo, dBoxHi, dGrp, dSegStart, dSegCurve, dSegLocal, dSegBuildStart, dSegInstOf, dW2o, dWInst, dWFirst;
     auto cleanup = [&]() {
-        for (DevBuf* b : { &dTriMesh, &dTriLocal, &dBoxLo, &dBoxHi, &dGrp, &dSegStart, &dSegCurve, &dSegLocal, &dSegBuildStart, &dSegInstOf, &dW2o, &dValid, &dWInst, &dWFirst,
+        for (DevBuf* b : { &dTriMesh, &dTriLocal, &dBoxLo, &dBoxHi, &dGrp, &dSegStart, &dSegCurve, &dSegLocal, &dSegBuildStart, &dSegInstOf, &dW2o, &dWInst, &dWFirst,
                            &triOut.sortedVals, &segOut.sortedVals, &triOut.groupRoot, &segOut.groupRoot, &triOut.groupBounds,
                            &segOut.groupBounds })
             dev_free(*b);
@@ -1704,7 +1721,6 @@ skh_status skh_build_accel(skh_context* c, uint32_t flags)
     c->refitReady = true; // (either builder ends in the same collapse)
     c->worldRoot = nGroup0 ? triOut.hostGroupRoot[nMeshes] : SKH_REF_INVALID;
     c->lightRoot = nGroup1 ? triOut.hostGroupRoot[nMeshes + 1u] : SKH_REF_INVALID;
-    float worldBounds[6] = { INFINITY, INFINITY, INFINITY, -INFINITY, -INFINITY, -INFINITY };
     for (int k = 0; k < 3; ++k)
         c->lightBox.lo[k] = -INFINITY, c->lightBox.hi[k] = INFINITY;
     if (nBaked)
@@ -1718,13 +1734,6 @@ skh_status skh_build_accel(skh_context* c, uint32_t flags)
             return SKH_FAIL;
         }
         set_light_box(c, nGroup1 != 0u, gb + 6);
-        for (uint32_t g = 0; g < 2; ++g)
-            if (g == 0 ? nGroup0 : nGroup1)
-                for (int k = 0; k < 3; ++k)
-                {
-                    worldBounds[k] = std::min(worldBounds[k], gb[6 * g + k]);
-                    worldBounds[3 + k] = std::max(worldBounds[3 + k], gb[6 * g + 3 + k]);
-                }
     }
     // ---- curve segments of all curve sets (segment enumeration: OptixRender.cpp:226-245) ----
     const uint32_t nCurves = (uint32_t)c->curves.size();
@@ -1763,6 +1772,7 @@ skh_status skh_build_accel(skh_context* c, uint32_t flags)
     const bool worldCurveKernel = worldCurves && c->worldKernel && !othersInTlas;
     if (!worldCurveKernel)
         mergedGroups.clear(); // (every curve instance keeps its TLAS leaf and its set's own tree)
+    c->builtMergedGroups = mergedGroups;
     // The curve build's primitives, group after group: groups [0, SKH_WORLD_CURVES) = the segments of the MERGED transform groups (object space of the
     // group's transform; the record names the instance), group SKH_WORLD_CURVES + s = curve set s (skipped when every instance of the set was merged).
     std::vector<uint32_t> segStart, segCurve, segLocal, segInstOf;
@@ -1928,10 +1938,10 @@ skh_status skh_build_accel(skh_context* c, uint32_t flags)
     }
     // ---- instances -> TLAS (baked instances were marked invalid above: they get a record for shading, no leaf) ----
     BA(dev_upload(c, dW2o, w2o.data(), sizeof(float) * w2o.size()));
-    BA(dev_upload(c, dValid, valid.data(), valid.size()));
+    BA(dev_upload(c, c->dBuiltValid, valid.data(), valid.size()));
     BA(dev_alloc(c, c->dDevInst, sizeof(DevInstance) * (size_t)std::max(1u, nInst)));
     if (nInst)
-        k_instance_boxes<<<(nInst + B - 1) / B, B, 0, st>>>(c->dInstances.as<HostInstance>(), dW2o.as<float>(), dValid.as<uint8_t>(),
+        k_instance_boxes<<<(nInst + B - 1) / B, B, 0, st>>>(c->dInstances.as<HostInstance>(), dW2o.as<float>(), c->dBuiltValid.as<uint8_t>(),
                                                            triOut.groupBounds.as<float>(), triOut.groupRoot.as<int>(),
                                                            segOut.groupBounds.as<float>() + 6 * SKH_WORLD_CURVES, segOut.groupRoot.as<int>() + SKH_WORLD_CURVES /* curve set s = group SKH_WORLD_CURVES + s */, nMeshes, nCurves,
                                                            nInst, c->dDevInst.as<DevInstance>(), dBoxLo.as<float4>(),
@@ -1959,6 +1969,7 @@ skh_status skh_build_accel(skh_context* c, uint32_t flags)
         c->numTlasLeaves = nLeaves;
         dev_free(c->dTlasNodes);
         dev_free(c->dTlasInst);
+        c->tlasLevelStart.clear();
         if (nLeaves == 0)
         {
             dev_free(c->dTravInst);
@@ -1993,22 +2004,9 @@ skh_status skh_build_accel(skh_context* c, uint32_t flags)
             // traversal records into leaf order (a TLAS leaf ref carries its position: sc.tinst + first)
             k_permute_instances<<<(nLeaves + B - 1) / B, B, 0, st>>>(dTinstTmp.as<DevInstance>(), tlasOut.sortedVals.as<uint32_t>(), nLeaves,
                                                                      c->dTravInst.as<DevInstance>());
-            float gb[6];
-            if (hipMemcpyAsync(gb, tlasOut.groupBounds.p, sizeof(gb), hipMemcpyDeviceToHost, st) != hipSuccess || hipStreamSynchronize(st) != hipSuccess)
-            {
-                cleanupT();
-                dev_free(tlasOut.nodes);
-                cleanup();
-                c->err = "skh_build_accel: TLAS bounds read-back failed";
-                return SKH_FAIL;
-            }
-            for (int k = 0; k < 3; ++k)
-            {
-                c->sceneLo[k] = gb[k];
-                c->sceneHi[k] = gb[3 + k];
-            }
             c->tlasRoot = tlasOut.hostGroupRoot[0];
             c->dTlasNodes = tlasOut.nodes;
+            c->tlasLevelStart = tlasOut.levelStart; // (skh_update_accel refits the TLAS level by level; its leaf order is the one dTravInst holds)
             if (getenv("SKH_DEBUG"))
                 fprintf(stderr, "[skh] TLAS (GPU PLOC): %u instances, %u leaves, %u nodes, root %d\n", nInst, nLeaves, tlasOut.numNodes, c->tlasRoot);
             cleanupT();
@@ -2032,7 +2030,6 @@ skh_status skh_build_accel(skh_context* c, uint32_t flags)
         std::vector<HostBox> hb;
         std::vector<uint32_t> ids;
         std::vector<DevInstance> tinst; // traversal records, one per TLAS leaf; pad = id of the instance it belongs to
-        float slo[3] = { INFINITY, INFINITY, INFINITY }, shi[3] = { -INFINITY, -INFINITY, -INFINITY };
         {
             // ---- TLAS opening (partial re-braiding) ----
             // A TLAS leaf is (instance, BLAS subtree).  Starting from one leaf per instance, the leaf with the largest world
@@ -2138,18 +2135,13 @@ skh_status skh_build_accel(skh_context* c, uint32_t flags)
                 tinst[r] = hinst[done[r].inst];
                 tinst[r].rootRef = done[r].node;
                 tinst[r].pad = done[r].inst;
-                for (int k = 0; k < 3; ++k)
-                {
-                    slo[k] = std::min(slo[k], hb[r].lo[k]);
-                    shi[k] = std::max(shi[k], hb[r].hi[k]);
-                }
             }
             c->numTlasLeaves = (uint32_t)done.size();
         }
         BA(dev_upload(c, c->dTravInst, tinst.data(), sizeof(DevInstance) * tinst.size()));
         std::vector<Node4> hnodes;
         std::vector<uint32_t> horder;
-        c->tlasRoot = tlas_sah_build(hb, ids, hnodes, horder);
+        c->tlasRoot = tlas_sah_build(hb, ids, hnodes, horder, c->tlasLevelStart);
         if (getenv("SKH_DEBUG"))
         {
             fprintf(stderr, "[skh] TLAS: %u instances, %zu leaves, %zu nodes, root %d\n", nInst, ids.size(), hnodes.size(), c->tlasRoot);
@@ -2160,11 +2152,6 @@ skh_status skh_build_accel(skh_context* c, uint32_t flags)
         dev_free(c->dTlasInst);
         BA(dev_upload(c, c->dTlasNodes, hnodes.data(), sizeof(Node4) * hnodes.size()));
         BA(dev_upload(c, c->dTlasInst, horder.data(), sizeof(uint32_t) * horder.size()));
-        for (int k = 0; k < 3; ++k)
-        {
-            c->sceneLo[k] = ids.empty() ? 0.0f : slo[k];
-            c->sceneHi[k] = ids.empty() ? 1.0f : shi[k];
-        }
     }
     else
     {
@@ -2172,17 +2159,16 @@ skh_status skh_build_accel(skh_context* c, uint32_t flags)
         dev_free(c->dTlasInst);
         dev_free(c->dTravInst);
         c->tlasRoot = SKH_REF_INVALID;
+        c->tlasLevelStart.clear();
     }
-    if (nBaked)
-        for (int k = 0; k < 3; ++k)
-        {
-            const bool none = c->tlasRoot == SKH_REF_INVALID;
-            c->sceneLo[k] = none ? worldBounds[k] : std::min(c->sceneLo[k], worldBounds[k]);
-            c->sceneHi[k] = none ? worldBounds[3 + k] : std::max(c->sceneHi[k], worldBounds[3 + k]);
-        }
     if (getenv("SKH_DEBUG"))
         fprintf(stderr, "[skh] bake_world %u: %u of %u instances baked, %u + %u world-space triangles, roots %d %d; %u object-space triangles; TLAS root %d\n", c->bakeWorld,
                 c->nBakedInst, nInst, nBakedG[0], nBakedG[1], c->worldRoot, c->lightRoot, nMeshTris, c->tlasRoot);
+    // k_instance_boxes' inputs for skh_update_accel (this call's cleanup frees the previous build's)
+    std::swap(c->dTriGroupRoot, triOut.groupRoot);
+    std::swap(c->dTriGroupBounds, triOut.groupBounds);
+    std::swap(c->dSegGroupRoot, segOut.groupRoot);
+    std::swap(c->dSegGroupBounds, segOut.groupBounds);
     hipError_t e = hipStreamSynchronize(st);
     cleanup();
     if (e != hipSuccess || (e = hipGetLastError()) != hipSuccess)
@@ -2191,17 +2177,157 @@ skh_status skh_build_accel(skh_context* c, uint32_t flags)
         return SKH_FAIL;
     }
     c->accelBuilt = true;
+    c->builtInstances = c->instances;
+    c->vertsEdited = false;
+    c->updateReady = true;
     c->msBuild = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
     return SKH_OK;
 #undef BA
 }
 
 // ---------------------------------------------------------------------------------------------------------------
-// skh_refit_accel: after a VERTEX edit (skh_set_geometry with the same mesh table and index buffer) -- the triangle hierarchy keeps its topology, its
-// leaf records are gathered again from the new vertices and its boxes are recomputed bottom-up, one launch per level (skh_bvh.h k_node4_refit_level).
-// north_star's "SAH refit".  Offered for what a real bake is: every mesh instance baked to world space (no top level: the world-only kernels); anything
-// else -- a top level, edited instances / curves / options, another topology -- falls back to the full rebuild, and the build info says which happened.
+// In-place updates: skh_refit_accel (round 6: a VERTEX edit of a scene without a top level) and skh_update_accel (instance TRANSFORMS, vertices and curve
+// control points, in any combination, for every scene kind) share ONE routine.  Every hierarchy keeps its topology; the build's own pieces recompute the rest:
+//   - the triangle tree (object-space BLASes + the baked world-space groups, which carry the instance transforms): leaf records gathered again by k_gather_tris,
+//     boxes level by level, deepest first (skh_bvh.h k_node4_refit_level: one launch per level, no atomics); the curve tree likewise;
+//   - the BLASes' root boxes (k_ref_boxes over the group roots) replace the build's group bounds;
+//   - the instance records (w2o by invert_affine, the build's bits) and world boxes: k_instance_boxes (+ k_instance_tight_boxes);
+//   - the TLAS: its traversal records rewritten (k_tlas_records), its boxes refitted level by level from the new instance boxes (TlasLeaves);
+//   - the light box; the shading tables.
+// Hit records do not depend on the hierarchy: the updated trees return what a rebuild returns, only the nodes visited per ray differ
+// (tests/test_gpu_parity.py::test_refit_after_a_vertex_edit_equals_a_rebuild, tests/test_gpu_update.py).
 // ---------------------------------------------------------------------------------------------------------------
+static skh_status update_in_place(skh_context* c, bool verts /* vertices may have changed: the triangle tree is refitted */, bool moved /* instance transforms changed */,
+                                  const std::vector<float>& w2o /* 12 per instance (invert_affine of the current table); may be empty when !moved */, uint32_t kind /* build_info.refit */)
+{
+    const auto t0 = std::chrono::steady_clock::now();
+    hipStream_t st = c->stream;
+    const uint32_t B = 256;
+    const uint32_t nInst = c->nInstances, nMeshes = (uint32_t)c->meshes.size(), nCurves = (uint32_t)c->curves.size();
+    DevBuf dRefs, dOut;
+    auto fail = [&](skh_status s) {
+        dev_free(dRefs), dev_free(dOut);
+        c->accelBuilt = false, c->refitReady = false, c->updateReady = false;
+        return s;
+    };
+    if (nInst != c->builtInstances.size() || c->instances.size() != nInst)
+    {
+        // (the records below -- dDevInst, the validity flags, the TLAS leaves -- are the build's, sized by its instance count; the callers admit nothing else)
+        c->err = std::string(kind == 1 ? "skh_refit_accel" : "skh_update_accel") + ": the instance table does not have the built count";
+        return fail(SKH_INVALID_ARGUMENT);
+    }
+    skh_status s = build_shading_tables(c); // (normals, tangents, uvs may have changed with the positions; the instance copy carries the transforms)
+    if (s != SKH_OK)
+        return fail(s);
+    // ---- bottom level: the triangle tree (baked world-space triangles move with their instances) and the curve tree ----
+    const bool tris = (verts || (moved && c->nBakedTris > 0)) && c->nTriSlots > 0;
+    if (tris)
+    {
+        k_gather_tris<<<(c->nTriSlots + B - 1) / B, B, 0, st>>>(c->dVerts.as<uint8_t>(), c->dIndices.as<uint32_t>(), c->dMeshes.as<uint4>(), c->dTriMeshK.as<uint32_t>(),
+                                                                 c->dTriLocalK.as<uint32_t>(), c->dTriOrder.as<uint32_t>(), c->nTriSlots, c->nMeshTrisBuilt, c->dInstances.as<uint8_t>(),
+                                                                 c->dShadeInst.as<uint8_t>(), c->dWInstK.as<uint32_t>(), c->dWFirstK.as<uint32_t>(), c->nWInstBuilt, c->directRecords,
+                                                                 c->dTris.as<float4>());
+        if ((s = dev_alloc(c, c->dTriNodeBox, sizeof(float4) * 2 * (size_t)std::max(1u, c->triNumNodes))) != SKH_OK)
+            return fail(s);
+        const TriLeaves leaves{ c->dTris.as<float4>() };
+        for (size_t L = c->triLevelStart.size() > 1 ? c->triLevelStart.size() - 1 : 0; L-- > 0;)
+        {
+            const uint32_t first = c->triLevelStart[L], count = c->triLevelStart[L + 1] - first;
+            if (count)
+                k_node4_refit_level<<<(count + B - 1) / B, B, 0, st>>>(c->dTriNodes.as<Node4>(), c->dTriNodeBox.as<float4>(), first, count, leaves);
+        }
+        // the BLASes' root boxes: k_instance_boxes' input from now on
+        k_ref_boxes<<<(nMeshes + 2u + 63u) / 64u, 64, 0, st>>>(c->dTriGroupRoot.as<int>(), nMeshes + 2u, leaves, c->dTriNodeBox.as<float4>(), c->dTriGroupBounds.as<float>());
+    }
+    const bool segs = c->curvePointsEdited && c->nSubBuilt > 0;
+    if (segs)
+    {
+        // leaf records (control points, bounding cylinders) gathered again from the new points, boxes level by level
+        k_gather_segs<<<(c->nSubBuilt + B - 1) / B, B, 0, st>>>(c->dPoints.as<float>(), c->dRadii.as<float>(), c->dSegBuildStartK.as<uint32_t>(), c->dSegLocalK.as<uint32_t>(),
+                                                               c->dSegInstOfK.as<uint32_t>(), c->dSegOrder.as<uint32_t>(), c->nSubBuilt, c->curveSplitBuilt, c->dSegs.as<float4>(), 0u);
+        if ((s = dev_alloc(c, c->dSegNodeBox, sizeof(float4) * 2 * (size_t)std::max(1u, c->segNumNodes))) != SKH_OK)
+            return fail(s);
+        const CurveLeaves leaves{ c->dSegs.as<float4>(), c->curveSplitBuilt };
+        for (size_t L = c->segLevelStart.size() > 1 ? c->segLevelStart.size() - 1 : 0; L-- > 0;)
+        {
+            const uint32_t first = c->segLevelStart[L], count = c->segLevelStart[L + 1] - first;
+            if (count)
+                k_node4_refit_level<<<(count + B - 1) / B, B, 0, st>>>(c->dSegNodes.as<Node4>(), c->dSegNodeBox.as<float4>(), first, count, leaves);
+        }
+        k_ref_boxes<<<(nCurves + SKH_WORLD_CURVES + 63u) / 64u, 64, 0, st>>>(c->dSegGroupRoot.as<int>(), nCurves + SKH_WORLD_CURVES, leaves, c->dSegNodeBox.as<float4>(),
+                                                                             c->dSegGroupBounds.as<float>());
+    }
+    c->curvePointsEdited = false;
+    // ---- instance records and boxes, then the top level ----
+    const bool tlas = c->tlasRoot != SKH_REF_INVALID && nInst > 0 && (moved || tris || segs); // (the instance stage runs, and with it the TLAS refit)
+    if (nInst > 0 && (moved || tlas))
+    {
+        std::vector<float> w2oNow;
+        const std::vector<float>* W = &w2o;
+        if (w2o.size() < 12 * (size_t)nInst)
+        {
+            w2oNow.resize(12 * (size_t)nInst);
+            for (uint32_t i = 0; i < nInst; ++i)
+                (void)invert_affine(c->instances[i].transform, &w2oNow[12 * (size_t)i]);
+            W = &w2oNow;
+        }
+        if ((s = dev_upload(c, c->dW2o, W->data(), sizeof(float) * 12 * (size_t)nInst)) != SKH_OK || (s = dev_alloc(c, c->dInstLo, sizeof(float4) * (size_t)nInst)) != SKH_OK ||
+            (s = dev_alloc(c, c->dInstHi, sizeof(float4) * (size_t)nInst)) != SKH_OK || (s = dev_alloc(c, c->dInstGrp, sizeof(uint32_t) * (size_t)nInst)) != SKH_OK)
+            return fail(s);
+        k_instance_boxes<<<(nInst + B - 1) / B, B, 0, st>>>(c->dInstances.as<HostInstance>(), c->dW2o.as<float>(), c->dBuiltValid.as<uint8_t>(), c->dTriGroupBounds.as<float>(),
+                                                           c->dTriGroupRoot.as<int>(), c->dSegGroupBounds.as<float>() + 6 * SKH_WORLD_CURVES, c->dSegGroupRoot.as<int>() + SKH_WORLD_CURVES,
+                                                           nMeshes, nCurves, nInst, c->dDevInst.as<DevInstance>(), c->dInstLo.as<float4>(), c->dInstHi.as<float4>(), c->dInstGrp.as<uint32_t>());
+        if (c->tightInstanceBoxes)
+            k_instance_tight_boxes<<<nInst, 256, 0, st>>>(c->dInstances.as<HostInstance>(), c->dDevInst.as<DevInstance>(), c->dMeshes.as<uint4>(), c->dVerts.as<uint8_t>(), nMeshes,
+                                                          1u << 22, c->dInstLo.as<float4>(), c->dInstHi.as<float4>());
+        if (tlas)
+        {
+            k_tlas_records<<<(c->numTlasLeaves + B - 1) / B, B, 0, st>>>(c->dTravInst.as<DevInstance>(), c->numTlasLeaves, c->dDevInst.as<DevInstance>());
+            const uint32_t nNodes = c->tlasLevelStart.empty() ? 0u : c->tlasLevelStart.back();
+            if ((s = dev_alloc(c, c->dTlasNodeBox, sizeof(float4) * 2 * (size_t)std::max(1u, nNodes))) != SKH_OK)
+                return fail(s);
+            const TlasLeaves leaves{ c->dTravInst.as<DevInstance>(), c->dInstLo.as<float4>(), c->dInstHi.as<float4>() };
+            for (size_t L = c->tlasLevelStart.size() > 1 ? c->tlasLevelStart.size() - 1 : 0; L-- > 0;)
+            {
+                const uint32_t first = c->tlasLevelStart[L], count = c->tlasLevelStart[L + 1] - first;
+                if (count)
+                    k_node4_refit_level<<<(count + B - 1) / B, B, 0, st>>>(c->dTlasNodes.as<Node4>(), c->dTlasNodeBox.as<float4>(), first, count, leaves);
+            }
+        }
+    }
+    // ---- the box the host keeps: around the baked light proxies (radiance rays that miss it skip their tree) ----
+    float gb[12];
+    hipError_t e = hipSuccess;
+    if (tris)
+    {
+        const int refs[2] = { c->worldRoot, c->lightRoot };
+        if ((s = dev_upload(c, dRefs, refs, sizeof(refs))) != SKH_OK || (s = dev_alloc(c, dOut, sizeof(gb))) != SKH_OK)
+            return fail(s);
+        k_ref_boxes<<<1, 64, 0, st>>>(dRefs.as<int>(), 2u, TriLeaves{ c->dTris.as<float4>() }, c->dTriNodeBox.as<float4>(), dOut.as<float>()); // (INVALID roots give empty boxes)
+        e = hipMemcpyAsync(gb, dOut.p, sizeof(gb), hipMemcpyDeviceToHost, st);
+    }
+    if (e == hipSuccess)
+        e = hipStreamSynchronize(st);
+    if (e != hipSuccess || (e = hipGetLastError()) != hipSuccess)
+    {
+        c->err = std::string(kind == 1 ? "skh_refit_accel: " : "skh_update_accel: ") + hipGetErrorString(e);
+        return fail(SKH_FAIL);
+    }
+    dev_free(dRefs), dev_free(dOut);
+    if (tris)
+        set_light_box(c, c->lightRoot != SKH_REF_INVALID && c->nGroup1Built != 0u, gb + 6);
+    c->builtInstances = c->instances;
+    c->vertsEdited = false;
+    c->accelBuilt = true;
+    c->buildInfo.refit = kind;
+    c->msRefit = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    c->buildInfo.ms_refit = c->msRefit;
+    c->refits++;
+    return SKH_OK;
+}
+
+// skh_refit_accel (round 6): offered for what a real bake is -- every mesh instance baked to world space (no top level: the world-only kernels) and nothing but
+// the vertices / control points changed since the build; anything else falls back to the full rebuild, and the build info says which happened.
 skh_status skh_refit_accel(skh_context* c)
 {
     if (!c)
@@ -2210,77 +2336,87 @@ skh_status skh_refit_accel(skh_context* c)
     (void)hipSetDevice(c->device);
     // (curves: control points and radii may have changed -- skh_set_curves with the built sets' table and vertex counts --; their tree is refitted the same way)
     const bool curvesOk = c->curves.empty() ? c->nSubBuilt == 0 : (c->curveRefitReady && c->curveSig == c->builtCurveSig);
-    const bool can = c->refitReady && c->geomSig == c->builtGeomSig && c->nVerts == c->builtNVerts && c->tlasRoot == SKH_REF_INVALID && curvesOk &&
-                     (c->triNumNodes > 0 || c->segNumNodes > 0);
+    const bool sameInstances = c->instances.size() == c->builtInstances.size() &&
+                               (c->instances.empty() || memcmp(c->instances.data(), c->builtInstances.data(), sizeof(skh_instance) * c->instances.size()) == 0);
+    const bool can = c->refitReady && c->updateReady && c->geomSig == c->builtGeomSig && c->nVerts == c->builtNVerts && c->tlasRoot == SKH_REF_INVALID && curvesOk &&
+                     sameInstances && (c->triNumNodes > 0 || c->segNumNodes > 0);
     c->buildInfo.refit = 0;
     if (!can)
         return skh_build_accel(c, c->lastBuildFlags);
-    const auto t0 = std::chrono::steady_clock::now();
-    hipStream_t st = c->stream;
-    const uint32_t B = 256;
-    skh_status s = build_shading_tables(c); // (normals, tangents, uvs may have changed with the positions)
-    if (s != SKH_OK)
-        return s;
-    if (c->nTriSlots)
-        k_gather_tris<<<(c->nTriSlots + B - 1) / B, B, 0, st>>>(c->dVerts.as<uint8_t>(), c->dIndices.as<uint32_t>(), c->dMeshes.as<uint4>(), c->dTriMeshK.as<uint32_t>(),
-                                                                 c->dTriLocalK.as<uint32_t>(), c->dTriOrder.as<uint32_t>(), c->nTriSlots, c->nMeshTrisBuilt, c->dInstances.as<uint8_t>(),
-                                                                 c->dShadeInst.as<uint8_t>(), c->dWInstK.as<uint32_t>(), c->dWFirstK.as<uint32_t>(), c->nWInstBuilt, c->directRecords,
-                                                                 c->dTris.as<float4>());
-    if ((s = dev_alloc(c, c->dTriNodeBox, sizeof(float4) * 2 * (size_t)std::max(1u, c->triNumNodes))) != SKH_OK)
-        return s;
-    for (size_t L = c->triLevelStart.size() > 1 ? c->triLevelStart.size() - 1 : 0; L-- > 0;)
+    return update_in_place(c, true, false, std::vector<float>(), 1u);
+}
+
+// What keeps skh_update_accel from updating in place (nullptr: nothing).  Fills w2o (invert_affine of the new table) and whether any transform moved.
+static const char* update_blocker(const skh_context* c, const skh_instance* in, uint32_t n, std::vector<float>& w2o, bool& moved)
+{
+    static const float kIdentity[12] = { 1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0 };
+    moved = false;
+    if (!c->refitReady || !c->updateReady)
+        return "no build since the context was created or an option changed";
+    if (c->geomSig != c->builtGeomSig || c->nVerts != c->builtNVerts)
+        return "another mesh table or index buffer";
+    if (!(c->curves.empty() ? c->nSubBuilt == 0 : (c->curveRefitReady && c->curveSig == c->builtCurveSig)))
+        return "another curve-set table or vertex counts, or the segment-node curve build";
+    if (c->tlasOpen > 1)
+        return "tlas_open > 1 (opened TLAS leaves are BLAS subtrees)";
+    if (n != c->builtInstances.size())
+        return "another instance count";
+    w2o.resize(12 * (size_t)std::max(1u, n));
+    for (uint32_t i = 0; i < n; ++i)
     {
-        const uint32_t first = c->triLevelStart[L], count = c->triLevelStart[L + 1] - first;
-        if (count)
-            k_node4_refit_level<<<(count + B - 1) / B, B, 0, st>>>(c->dTriNodes.as<Node4>(), c->dTriNodeBox.as<float4>(), first, count, c->dTris.as<float4>());
+        const skh_instance &a = in[i], &b = c->builtInstances[i];
+        if (a.type != b.type || a.geom_id != b.geom_id || a.material_id != b.material_id || a.light_id != b.light_id)
+            return "an instance's type, geom_id, material_id or light_id";
+        if (invert_affine(a.transform, &w2o[12 * (size_t)i]) != (c->builtInvOk[i] != 0))
+            return "a transform that became singular, or stopped being singular";
+        moved = moved || memcmp(a.transform, b.transform, sizeof(a.transform)) != 0;
     }
-    if (c->curvePointsEdited && c->nSubBuilt)
+    // decisions the build took from the transforms: which world-curve entry sits under a bit-exact identity (SKH_REF_CURVEROOT_IDENT), which curve instances share one
+    for (uint32_t k = 0; k < c->numWorldCurves; ++k)
     {
-        // the curve tree: leaf records (control points, bounding cylinders) gathered again from the new points, boxes level by level
-        k_gather_segs<<<(c->nSubBuilt + B - 1) / B, B, 0, st>>>(c->dPoints.as<float>(), c->dRadii.as<float>(), c->dSegBuildStartK.as<uint32_t>(), c->dSegLocalK.as<uint32_t>(),
-                                                               c->dSegInstOfK.as<uint32_t>(), c->dSegOrder.as<uint32_t>(), c->nSubBuilt, c->curveSplitBuilt, c->dSegs.as<float4>(), 0u);
-        if ((s = dev_alloc(c, c->dSegNodeBox, sizeof(float4) * 2 * (size_t)std::max(1u, c->segNumNodes))) != SKH_OK)
-            return s;
-        for (size_t L = c->segLevelStart.size() > 1 ? c->segLevelStart.size() - 1 : 0; L-- > 0;)
+        const uint32_t i = c->worldCurveInst[k];
+        if ((memcmp(in[i].transform, kIdentity, sizeof(kIdentity)) == 0) != (memcmp(c->builtInstances[i].transform, kIdentity, sizeof(kIdentity)) == 0))
+            return "a world-curve entry that left or reached the identity transform";
+    }
+    for (const std::vector<uint32_t>& grp : c->builtMergedGroups)
+        for (uint32_t i : grp)
+            if (memcmp(in[i].transform, in[grp[0]].transform, sizeof(in[i].transform)) != 0)
+                return "a merged curve group whose members no longer share one transform";
+    return nullptr;
+}
+
+skh_status skh_update_accel(skh_context* c, const skh_instance* instances, uint32_t n_instances)
+{
+    if (!c || (n_instances && !instances))
+        return SKH_INVALID_ARGUMENT;
+    spec_drop(c);
+    (void)hipSetDevice(c->device);
+    const skh_instance* in = instances ? instances : c->instances.data();
+    const uint32_t n = instances ? n_instances : (uint32_t)c->instances.size();
+    std::vector<float> w2o;
+    bool moved = false;
+    const char* why = update_blocker(c, in, n, w2o, moved);
+    c->buildInfo.refit = 0;
+    if (why)
+    {
+        if (getenv("SKH_DEBUG"))
+            fprintf(stderr, "[skh] skh_update_accel: full build (%s)\n", why);
+        skh_status s = instances ? skh_set_instances(c, instances, n_instances) : SKH_OK;
+        return s != SKH_OK ? s : skh_build_accel(c, c->lastBuildFlags);
+    }
+    if (instances)
+    {
+        // (the table replaces whatever skh_set_instances set since the build -- which may have had another count: n is the built count here)
+        c->instances.assign(instances, instances + n);
+        c->nInstances = n;
+        const skh_status s = dev_upload(c, c->dInstances, instances, sizeof(skh_instance) * (size_t)n);
+        if (s != SKH_OK)
         {
-            const uint32_t first = c->segLevelStart[L], count = c->segLevelStart[L + 1] - first;
-            if (count)
-                k_node4_refit_level_curves<<<(count + B - 1) / B, B, 0, st>>>(c->dSegNodes.as<Node4>(), c->dSegNodeBox.as<float4>(), first, count, c->dSegs.as<float4>(), c->curveSplitBuilt);
+            c->accelBuilt = false, c->refitReady = false, c->updateReady = false;
+            return s;
         }
-        c->curvePointsEdited = false;
     }
-    // the two baked groups' bounds: the box around the light proxies (radiance rays that miss it skip their tree), the scene box
-    DevBuf dRefs, dOut;
-    const int refs[2] = { c->worldRoot, c->lightRoot };
-    float gb[12];
-    if ((s = dev_upload(c, dRefs, refs, sizeof(refs))) != SKH_OK || (s = dev_alloc(c, dOut, sizeof(gb))) != SKH_OK)
-    {
-        dev_free(dRefs), dev_free(dOut);
-        return s;
-    }
-    k_ref_boxes<<<1, 64, 0, st>>>(dRefs.as<int>(), 2u, c->dTris.as<float4>(), c->dTriNodeBox.as<float4>(), dOut.as<float>()); // (INVALID roots give empty boxes)
-    hipError_t e = hipMemcpyAsync(gb, dOut.p, sizeof(gb), hipMemcpyDeviceToHost, st);
-    if (e == hipSuccess)
-        e = hipStreamSynchronize(st);
-    dev_free(dRefs), dev_free(dOut);
-    if (e != hipSuccess || (e = hipGetLastError()) != hipSuccess)
-    {
-        c->err = std::string("skh_refit_accel: ") + hipGetErrorString(e);
-        c->accelBuilt = false, c->refitReady = false;
-        return SKH_FAIL;
-    }
-    set_light_box(c, c->lightRoot != SKH_REF_INVALID && c->nGroup1Built != 0u, gb + 6);
-    for (int k = 0; k < 3; ++k)
-    {
-        c->sceneLo[k] = std::min(c->worldRoot != SKH_REF_INVALID ? gb[k] : INFINITY, c->lightRoot != SKH_REF_INVALID ? gb[6 + k] : INFINITY);
-        c->sceneHi[k] = std::max(c->worldRoot != SKH_REF_INVALID ? gb[3 + k] : -INFINITY, c->lightRoot != SKH_REF_INVALID ? gb[9 + k] : -INFINITY);
-    }
-    c->accelBuilt = true;
-    c->buildInfo.refit = 1;
-    c->msRefit = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
-    c->buildInfo.ms_refit = c->msRefit;
-    c->refits++;
-    return SKH_OK;
+    return update_in_place(c, c->vertsEdited, moved, w2o, 2u);
 }
 
 skh_status skh_get_baked(skh_context* c, uint8_t* flags, uint32_t n_instances, uint32_t* out_baked_instances, uint32_t* out_baked_triangles)

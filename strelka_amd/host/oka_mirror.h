@@ -19,6 +19,7 @@
 #include "../../include/strelka_hip.h"
 
 #include <cstdint>
+#include <set>
 #include <string>
 #include <unordered_map>
 #include <vector>
@@ -307,6 +308,25 @@ public:
         return mCameras[index];
     }
     float4x4 getTransform(const UniformLightDesc& desc); // scene.h:331-343
+    // the reference's edit channel (scene.h:437-455, scene.cpp:435-456): updateInstanceTransform records the instance as dirty, beginFrame clears the set
+    std::set<uint32_t> getDirtyInstances()
+    {
+        return mDirtyInstances;
+    }
+    void updateInstanceTransform(uint32_t instId, float4x4 newTransform)
+    {
+        mInstances[instId].transform = newTransform;
+        mDirtyInstances.insert(instId);
+    }
+    void beginFrame()
+    {
+        mFrMod = true;
+        mDirtyInstances.clear();
+    }
+    void endFrame()
+    {
+        mFrMod = false;
+    }
     // flat binary dump of the arrays render() uploads (".skscene"; format in strelka_amd/scene_io.py)
     bool saveDump(const std::string& path) const;
     bool loadDump(const std::string& path); // replaces the scene's content; false (scene untouched) on a malformed file
@@ -370,6 +390,8 @@ private:
     std::vector<MaterialDescription> mMaterialsDescs;
     std::vector<Texture> mTextures;
     std::vector<Camera> mCameras;
+    std::set<uint32_t> mDirtyInstances;
+    bool mFrMod = false;
     int mRectLightMeshId = -1, mSphereLightMeshId = -1, mDiskLightMeshId = -1;
     uint32_t createRectLightMesh();
     uint32_t createSphereLightMesh();
