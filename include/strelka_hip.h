@@ -26,7 +26,7 @@
 extern "C" {
 #endif
 
-#define SKH_ABI_VERSION 5 /* 5 (round 6): + skh_refit_accel, skh_build_info.refit / ms_refit, then skh_update_accel (additive: refit = 2); options curve_merge, curve_segnode, curve_strand_major, split_pairs.  4 (round 5): + skh_get_build_info; options reinsert_rounds, reinsert_min_size; wide, tail_park, tail_lag removed.  3 (round 4): + skh_unit_probe, skh_copy_aov */
+#define SKH_ABI_VERSION 5 /* 5 (round 6): + skh_refit_accel, skh_build_info.refit / ms_refit, then skh_update_accel (additive: refit = 2), then skh_set_environment / _transform / skh_get_environment_info + two unit probes (additive); options curve_merge, curve_segnode, curve_strand_major, split_pairs.  4 (round 5): + skh_get_build_info; options reinsert_rounds, reinsert_min_size; wide, tail_park, tail_lag removed.  3 (round 4): + skh_unit_probe, skh_copy_aov */
 
 /* mirrors oka::Result (include/render/common.h:30-35) */
 typedef enum skh_status
@@ -257,6 +257,37 @@ skh_status skh_set_lights(skh_context* ctx, const skh_light* lights, uint32_t n_
 skh_status skh_set_textures(skh_context* ctx, const skh_texture* textures, uint32_t count);
 skh_status skh_set_materials(skh_context* ctx, const skh_material* materials, uint32_t n_materials);
 
+/* ---- environment (dome) light: new, the reference declares HdPrimTypeTokens->domeLight (src/HdStrelka/RenderPass.cpp:383) and never creates one ----
+ * A lat-long map of linear float RGB that every ray leaving the scene sees, importance-sampled by the light pick ("Environment light").
+ *   map        row 0 = the +Y pole, column 0 at phi = 0 on +X, phi growing towards +Z; 2 <= width <= 8192, 2 <= height <= 4096; finite values >= 0
+ *   look-up    l = world_to_env * d, theta = acos(clamp(l.y)), phi = atan2(l.z, l.x) (+ 2 pi if negative);
+ *              ix = min(int(phi / 2 pi * W), W - 1), iy = min(int(theta / pi * H), H - 1); nearest texel; Le = scale * texel
+ *   sampling   texel weight w = luminance_709(texel) * sin(pi (iy + 1/2) / H); marginal CDF over rows, conditional CDF per row, CDF inversion, uniform inside the
+ *              texel; pdf per solid angle of a direction = w / sum w * W H / (2 pi^2 sin theta), sin theta = sqrt(l.x^2 + l.z^2); an all-black map is legal (pdf 0)
+ *   light pick with an environment the pick has numLights + 1 entries, the last one being the environment (selection pdf 1 / (numLights + 1)); a ray that
+ *              misses adds throughput * Le * weight, weight = 1 at depth 0 or after a specular bounce, else the balance heuristic of the BSDF's pdf against
+ *              pdf / (numLights + 1).  Option env_nee 0: never picked, every miss weighs 1.
+ * skh_set_environment uploads the map and builds the tables on the device (rgb == NULL removes the environment: the context then runs the kernels and produces
+ * the bits of one that never had any).  skh_set_environment_transform changes scale / rotation only -- no rebuild -- and needs an environment.  Both discard
+ * sub-frames traced ahead, as skh_set_lights does; neither touches the acceleration structures.  A failed call leaves the previous environment in place. */
+typedef struct skh_environment
+{
+    const float* rgb; /* width * height * 3; NULL = remove the environment */
+    uint32_t width, height;
+    float scale[3]; /* intensity * colour */
+    float world_to_env[9]; /* row-major rotation */
+} skh_environment;
+skh_status skh_set_environment(skh_context* ctx, const skh_environment* env);
+skh_status skh_set_environment_transform(skh_context* ctx, const float scale[3], const float world_to_env[9]);
+typedef struct skh_environment_info
+{
+    uint32_t width, height; /* 0, 0: no environment */
+    double sum_w; /* sum of the texel weights */
+    double ms_build; /* wall time of the table build (device kernels, without the upload of the map) */
+    uint64_t bytes; /* device memory of the tables: 16 B texels + 4 B conditional CDF per texel + the marginal CDF */
+} skh_environment_info;
+skh_status skh_get_environment_info(skh_context* ctx, skh_environment_info* out);
+
 /* ---- createAccelerationStructure (OptixRender.cpp:388-496): per-mesh / per-curve BLAS + one TLAS ---- */
 skh_status skh_build_accel(skh_context* ctx, uint32_t flags);
 /* After a VERTEX edit -- skh_set_geometry with the mesh table and index buffer of the last build, any vertex data; skh_set_curves with the curve sets and vertex
@@ -425,7 +456,10 @@ skh_status skh_bsdf_probe(skh_context* ctx, const skh_bsdf_query* queries, uint3
  *   SKH_UNIT_TONEMAP        f32 exposure[3]      f32 color[3]                             --                            f32 tonemap[3], inverseTonemap[3]
  *   SKH_UNIT_LIBM           --                   f32 x, y                                 --                            f32 sin x, cos x, acos x, asin x, atan2(y, x), exp x, log x,
  *                                                                                                                       sinh x, pow(x, y), atan2(x, y): strelka_amd/csrc/skh_libm.h,
- *                                                                                                                       the libm stand-ins both sides compile */
+ *                                                                                                                       the libm stand-ins both sides compile
+ *   SKH_UNIT_ENV_SAMPLE     --                   f32 u[2] (row, column)                   --                            f32 dir[3], pdf, Le[3], u32 ix, iy (the texel selected)
+ *   SKH_UNIT_ENV_EVAL       --                   f32 dir[3]                               --                            f32 Le[3], pdf, u32 ix, iy
+ *   (both on the context's current environment, skh_set_environment below; pdf and Le are those of the returned direction) */
 typedef enum skh_unit
 {
     SKH_UNIT_SAMPLER = 0,
@@ -437,7 +471,9 @@ typedef enum skh_unit
     SKH_UNIT_ACCUMULATE = 6,
     SKH_UNIT_TONEMAP = 7,
     SKH_UNIT_LIBM = 8,
-    SKH_UNIT_COUNT = 9
+    SKH_UNIT_ENV_SAMPLE = 9,
+    SKH_UNIT_ENV_EVAL = 10,
+    SKH_UNIT_COUNT = 11
 } skh_unit;
 skh_status skh_unit_probe(skh_context* ctx, uint32_t unit, uint32_t param, const void* consts, const void* in, uint32_t n, void* out);
 
@@ -471,8 +507,11 @@ skh_status skh_unit_probe(skh_context* ctx, uint32_t unit, uint32_t param, const
  *                 within bake_budget_mtris (64) million, else 2; 0 = every instance keeps its TLAS leaf), world_kernel 1|0 (scenes
  *                 with an empty top level run the world-only build of the traversal kernel; curve instances -- at most 16, no unbaked
  *                 mesh or light instance beside them -- do not need a top level either: their trees are walked from the world-only kernel with the
- *                 curve block, each instance's transform applied to the ray as at a TLAS leaf)
- *   build         build_quality 1|0 (PLOC | Karras radix tree), reinsert_rounds (8; 0 = off: rounds of parallel reinsertion over the PLOC tree of the
+ *                 curve block, each instance's transform applied to the ray as at a TLAS leaf),
+ *                 env_nee 1|0 (the second option that is part of a definition, the estimator's: 1 = the environment is an entry of the light pick and a miss is
+ *                 MIS-weighted against it; 0 = the environment is reached by BSDF sampling only, every miss weighs 1.  Two estimators of one integral: the
+ *                 expectation is the same, the bits are not.  Without an environment it changes nothing)
+ *   build        build_quality 1|0 (PLOC | Karras radix tree), reinsert_rounds (8; 0 = off: rounds of parallel reinsertion over the PLOC tree of the
  *                 triangle build -- every subtree looks for the place in the tree where it costs least, the best non-conflicting moves are applied),
  *                 reinsert_curve_rounds (4: the same over the curve sub-segment trees),
  *                 reinsert_min_size (0 = auto: 1 up to 4 M triangles, 32 beyond: only the part of the tree above subtrees of this many primitives is optimised), morton_bits (10 per axis in the sort keys; 4..21), ploc_top (0: clusters left at which the triangle build widens PLOC's neighbour search from 12 to 96), leaf_max_tris (2), leaf_lines 0|1 (triangle leaves padded so that none

@@ -249,9 +249,39 @@ void HipRender::uploadMaterials()
     check(skh_set_materials(mCtx, mats.data(), (uint32_t)mats.size()), "skh_set_materials");
 }
 
+static void environmentRotation(const float* worldToEnv, float out[9])
+{
+    static const float identity[9] = { 1.0f, 0.0f, 0.0f, 0.0f, 1.0f, 0.0f, 0.0f, 0.0f, 1.0f };
+    memcpy(out, worldToEnv ? worldToEnv : identity, sizeof(identity));
+}
+
+bool HipRender::setEnvironment(const float* rgb, uint32_t width, uint32_t height, const float scale[3], const float* worldToEnv)
+{
+    skh_environment e;
+    e.rgb = rgb;
+    e.width = width, e.height = height;
+    memcpy(e.scale, scale, sizeof(e.scale));
+    environmentRotation(worldToEnv, e.world_to_env);
+    mEnvironmentChanged = true;
+    return check(skh_set_environment(mCtx, &e), "skh_set_environment");
+}
+
+bool HipRender::setEnvironmentTransform(const float scale[3], const float* worldToEnv)
+{
+    float m[9];
+    environmentRotation(worldToEnv, m);
+    mEnvironmentChanged = true;
+    return check(skh_set_environment_transform(mCtx, scale, m), "skh_set_environment_transform");
+}
+
 void HipRender::render(Buffer* output)
 {
     SharedContext& sh = getSharedContext();
+    if (mEnvironmentChanged)
+    {
+        sh.mSubframeIndex = 0; // a new sky: the accumulated image is of the old one
+        mEnvironmentChanged = false;
+    }
     if (sh.mFrameNumber == 0)
         uploadScene(); // scene is uploaded once (OptixRender.cpp:876-888); later edits are ignored, like the reference, except ...
     else if (!mScene->getDirtyInstances().empty() && sendMovedInstances())

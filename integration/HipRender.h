@@ -76,6 +76,13 @@ public:
     // buffer then holds the whole frame (the other ranks' buffers hold their own tiles).  commId: 128 bytes from
     // skh_comm_unique_id on rank 0, handed to every rank by whatever launched the processes.  Call after init(), before render().
     bool enableTileSharing(const void* commId, int worldSize, int rank, uint32_t tileSize = 32);
+    // Environment (dome) light (new: the reference lists HdPrimTypeTokens->domeLight and never creates one).  rgb: width x height x 3 linear floats, lat-long,
+    // row 0 = the +Y pole, column 0 at phi = 0 on +X, phi towards +Z; nullptr removes it.  scale = intensity x colour; worldToEnv = row-major 3x3 rotation
+    // (nullptr = identity).  Accumulation restarts at the next render(), as after a camera move.  With tile sharing every rank makes the same call.
+    // Call after init().  INTEGRATION.md says how an HdStrelkaLight of type domeLight feeds it.
+    bool setEnvironment(const float* rgb, uint32_t width, uint32_t height, const float scale[3], const float* worldToEnv = nullptr);
+    // the same map under a new intensity x colour and rotation: no table rebuild (a viewer spinning its dome)
+    bool setEnvironmentTransform(const float scale[3], const float* worldToEnv = nullptr);
 
 private:
     skh_context* mCtx = nullptr;
@@ -88,6 +95,7 @@ private:
     bool mEnableAccumulationPrev = false;
     bool check(skh_status s, const char* what);
     bool applyTiles(uint32_t width, uint32_t height); // this rank's share of the frame -> skh_set_tiles (multi-GPU)
+    bool mEnvironmentChanged = false; // render() restarts the accumulation once
     bool mSharing = false;
     int mWorld = 1, mRank = 0;
     uint32_t mTileSize = 32, mMaxTiles = 0;

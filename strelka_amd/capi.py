@@ -27,13 +27,20 @@ SYMBOLS = ["skh_create", "skh_destroy", "skh_last_error", "skh_abi_version", "sk
            "skh_buffer_alloc", "skh_buffer_free", "skh_buffer_download", "skh_copy_accum", "skh_copy_accum_tiles", "skh_scatter_tiles", "skh_trace", "skh_trace_device",
            "skh_set_option", "skh_get_stats", "skh_reset_stats", "skh_synchronize", "skh_get_stream", "skh_bsdf_probe", "skh_get_device_info", "skh_comm_unique_id", "skh_comm_init",
            "skh_comm_destroy", "skh_gather_tiles", "skh_host_register", "skh_host_unregister", "skh_get_baked", "skh_comm_info", "skh_probe_memory", "skh_unit_probe", "skh_copy_aov", "skh_get_build_info", "skh_refit_accel",
-           "skh_update_accel"]
+           "skh_update_accel", "skh_set_environment", "skh_set_environment_transform", "skh_get_environment_info"]
 
 BUILD_INFO = np.dtype([("triangles", np.uint32), ("nodes", np.uint32), ("reinsert_rounds", np.uint32), ("reinsert_moves", np.uint32),
                        ("reinsert_min_size", np.uint32), ("refit", np.uint32), ("cost_before", np.float64), ("cost_after", np.float64),
                        ("ms_reinsert", np.float64), ("ms_build", np.float64), ("ms_refit", np.float64)])
 DEVICE_INFO = np.dtype([("compute_units", np.uint32), ("simds_per_cu", np.uint32), ("clock_khz", np.uint32), ("memory_clock_khz", np.uint32),
                         ("memory_bus_bits", np.uint32), ("wavefront_size", np.uint32), ("total_memory_bytes", np.uint64), ("name", "S64")])
+
+ENVIRONMENT_INFO = np.dtype([("width", np.uint32), ("height", np.uint32), ("sum_w", np.float64), ("ms_build", np.float64), ("bytes", np.uint64)])
+
+
+class SkhEnvironment(C.Structure):  # skh_environment
+    _fields_ = [("rgb", C.c_void_p), ("width", C.c_uint32), ("height", C.c_uint32), ("scale", C.c_float * 3), ("world_to_env", C.c_float * 9)]
+
 
 BSDF_QUERY = np.dtype([("normal", np.float32, 3), ("geom_normal", np.float32, 3), ("tangent_u", np.float32, 3), ("k1", np.float32, 3),
                        ("k2", np.float32, 3), ("xi", np.float32, 4), ("material", np.uint32), ("inside", np.uint32)])
@@ -75,6 +82,9 @@ def load():
     lib.skh_build_accel.argtypes = [vp, u32]
     lib.skh_refit_accel.argtypes = [vp]
     lib.skh_update_accel.argtypes = [vp, vp, u32]
+    lib.skh_set_environment.argtypes = [vp, C.POINTER(SkhEnvironment)]
+    lib.skh_set_environment_transform.argtypes = [vp, vp, vp]
+    lib.skh_get_environment_info.argtypes = [vp, vp]
     lib.skh_resize.argtypes = [vp, u32, u32]
     lib.skh_set_tiles.argtypes = [vp, u32, vp, u32]
     lib.skh_render_subframe.argtypes = [vp, vp, vp]
@@ -164,6 +174,12 @@ class Context:
         self._ck(L.skh_set_lights(self.h, _p(arr["lights"]), len(arr["lights"])), "skh_set_lights")
         self.set_textures(arr.get("textures") or [])
         self._ck(L.skh_set_materials(self.h, _p(arr["materials"]), len(arr["materials"])), "skh_set_materials")
+        # a scene without an environment removes the one a reused context may still hold (a no-op when it holds none)
+        env = arr.get("environment")
+        if env is None:
+            self.set_environment(None)
+        else:
+            self.set_environment(env["rgb"], env.get("scale", (1, 1, 1)), env.get("world_to_env"))
         if build:
             self.build_accel(flags)
 
@@ -181,6 +197,36 @@ class Context:
         for k, t in enumerate(keep):
             recs[k].rgba8, recs[k].width, recs[k].height = t.ctypes.data, t.shape[1], t.shape[0]
         self._ck(self.lib.skh_set_textures(self.h, C.cast(recs, C.c_void_p), len(keep)), "skh_set_textures")
+
+    @staticmethod
+    def _env_transform(scale, world_to_env):
+        sc = np.ascontiguousarray(scale, np.float32).reshape(3)
+        m = np.eye(3, dtype=np.float32) if world_to_env is None else np.ascontiguousarray(world_to_env, np.float32).reshape(3, 3)
+        return sc, np.ascontiguousarray(m.reshape(9))
+
+    def set_environment(self, rgb, scale=(1, 1, 1), world_to_env=None):
+        """skh_set_environment: `rgb` an (H, W, 3) float array, lat-long, row 0 = the +Y pole, column 0 at phi = 0 on +X (None removes the
+        environment); `scale` = intensity * colour; `world_to_env` a 3x3 rotation (None = identity).  The sampling tables are built on the device."""
+        e = SkhEnvironment()
+        sc, m = self._env_transform(scale, world_to_env)
+        e.scale[:], e.world_to_env[:] = sc.tolist(), m.tolist()
+        keep = None
+        if rgb is not None:
+            keep = np.ascontiguousarray(rgb, np.float32)
+            if keep.ndim != 3 or keep.shape[2] != 3:
+                raise ValueError("the environment map must be an (H, W, 3) array")
+            e.rgb, e.width, e.height = keep.ctypes.data, keep.shape[1], keep.shape[0]
+        self._ck(self.lib.skh_set_environment(self.h, C.byref(e)), "skh_set_environment")
+
+    def set_environment_transform(self, scale=(1, 1, 1), world_to_env=None):
+        """skh_set_environment_transform: new intensity * colour and rotation for the environment in place (no table rebuild)"""
+        sc, m = self._env_transform(scale, world_to_env)
+        self._ck(self.lib.skh_set_environment_transform(self.h, _p(sc), _p(m)), "skh_set_environment_transform")
+
+    def environment_info(self):
+        d = np.zeros((), ENVIRONMENT_INFO)
+        self._ck(self.lib.skh_get_environment_info(self.h, _p(d)), "skh_get_environment_info")
+        return {k: (float(d[k]) if d[k].dtype.kind == "f" else int(d[k])) for k in ENVIRONMENT_INFO.names}
 
     def build_accel(self, flags=0):
         self._ck(self.lib.skh_build_accel(self.h, flags), "skh_build_accel")
@@ -267,7 +313,8 @@ class Context:
 
     # skh_unit: (words in, words out) per record
     UNITS = {"sampler": (0, 5, 3), "sobol": (1, 2, 1), "light_sample": (2, 5, 12), "light_pdf": (3, 6, 1), "light_normal": (4, 3, 4),
-             "mis": (5, 2, 1), "accumulate": (6, 3, 3), "tonemap": (7, 3, 6), "libm": (8, 2, 10)}
+             "mis": (5, 2, 1), "accumulate": (6, 3, 3), "tonemap": (7, 3, 6), "libm": (8, 2, 10),
+             "env_sample": (9, 2, 9), "env_eval": (10, 3, 6)}
 
     def unit_probe(self, unit, records, param=0, consts=None):
         """skh_unit_probe: one device call of the named function per record (include/strelka_hip.h lists the record layouts);

@@ -572,6 +572,89 @@ SKH_DI LightSample sample_sphere_light(const Light& l, float ux, float uy, const
 }
 
 // =================================================================================================
+// Environment (dome) light -- not in the reference; DESIGN.md section 2 "Environment light" is the definition, skh_env.h builds the tables.
+// Lat-long map, row 0 = +Y pole, column 0 at phi = 0 on +X, phi towards +Z; nearest texel; CDF inversion over texel weights
+// luminance * sin(theta of the row centre).
+// =================================================================================================
+struct EnvP // by-value kernel argument; texels == nullptr: no environment
+{
+    const float4* texels; // W x H of {r, g, b, w / sum w}: radiance and pdf in one 16-byte fetch
+    const float* rowCdf; // H: inclusive marginal CDF over rows
+    const float* colCdf; // H x W: inclusive conditional CDF of every row
+    uint32_t width, height;
+    float pdfScale; // W H / (2 pi^2), rounded once
+    uint32_t nee; // option env_nee
+    float scale[3];
+    float w2e[9]; // world -> environment rotation, row-major
+};
+struct EnvEval
+{
+    v3 Le;
+    float pdf; // per solid angle
+    uint32_t ix, iy;
+};
+// radiance and solid-angle pdf of a WORLD direction: the miss branch, the sampler's own pdf and SKH_UNIT_ENV_EVAL are this one function
+SKH_DI EnvEval env_eval(const EnvP& e, const v3& d)
+{
+    const float* m = e.w2e;
+    const v3 l = mk3(m[0] * d.x + m[1] * d.y + m[2] * d.z, m[3] * d.x + m[4] * d.y + m[5] * d.z, m[6] * d.x + m[7] * d.y + m[8] * d.z);
+    const float theta = skm::acosf_(fminf(fmaxf(l.y, -1.0f), 1.0f));
+    float phi = skm::atan2f_(l.z, l.x);
+    if (phi < 0.0f)
+        phi += 2.0f * SKH_PI;
+    EnvEval r;
+    // (float -> uint32 saturates and takes a NaN to 0: the index stays inside the table whatever the direction holds)
+    r.ix = min((uint32_t)(phi * (0.5f / SKH_PI) * (float)e.width), e.width - 1u);
+    r.iy = min((uint32_t)(theta * (1.0f / SKH_PI) * (float)e.height), e.height - 1u);
+    const float4 t = e.texels[(size_t)r.iy * e.width + r.ix];
+    r.Le = mk3(e.scale[0] * t.x, e.scale[1] * t.y, e.scale[2] * t.z);
+    const float sinTheta = sqrtf(l.x * l.x + l.z * l.z); // (sqrt(1 - l.y^2) loses its digits at the poles, where the pdf is largest)
+    r.pdf = (t.w > 0.0f && sinTheta > 0.0f) ? (t.w * e.pdfScale) / sinTheta : 0.0f;
+    return r;
+}
+// smallest i with u < cdf[i], at most n - 1 (inclusive CDF: an entry of weight 0 repeats its predecessor's value and is never selected)
+SKH_DI uint32_t env_cdf_search(const float* __restrict__ cdf, uint32_t n, float u)
+{
+    uint32_t lo = 0u, hi = n - 1u;
+    while (lo < hi)
+    {
+        const uint32_t mid = (lo + hi) >> 1;
+        if (u < cdf[mid])
+            hi = mid;
+        else
+            lo = mid + 1u;
+    }
+    return lo;
+}
+// where u lies between the CDF values on either side of the selected entry, in [0, 1)
+SKH_DI float env_cdf_remap(float u, float c0, float c1)
+{
+    return c1 > c0 ? fminf(fmaxf((u - c0) / (c1 - c0), 0.0f), 0.99999994f) : 0.5f;
+}
+struct EnvSample
+{
+    v3 dir; // world
+    uint32_t ix, iy; // the texel the inversion selected
+    EnvEval ev; // env_eval(dir): Le and pdf AS FUNCTIONS OF THE DIRECTION RETURNED, so that both sides of the MIS see one number for one direction
+};
+SKH_DI EnvSample env_sample(const EnvP& e, float uRow, float uCol)
+{
+    EnvSample s;
+    s.iy = env_cdf_search(e.rowCdf, e.height, uRow);
+    const float* __restrict__ row = e.colCdf + (size_t)s.iy * e.width;
+    s.ix = env_cdf_search(row, e.width, uCol);
+    const float fv = env_cdf_remap(uRow, s.iy ? e.rowCdf[s.iy - 1u] : 0.0f, e.rowCdf[s.iy]);
+    const float fu = env_cdf_remap(uCol, s.ix ? row[s.ix - 1u] : 0.0f, row[s.ix]);
+    const float theta = ((float)s.iy + fv) * (SKH_PI / (float)e.height), phi = ((float)s.ix + fu) * (2.0f * SKH_PI / (float)e.width);
+    const float st = skm::sinf_(theta);
+    const v3 l = mk3(st * skm::cosf_(phi), skm::cosf_(theta), st * skm::sinf_(phi));
+    const float* m = e.w2e; // environment -> world: the rotation's transpose
+    s.dir = mk3(m[0] * l.x + m[3] * l.y + m[6] * l.z, m[1] * l.x + m[4] * l.y + m[7] * l.z, m[2] * l.x + m[5] * l.y + m[8] * l.z);
+    s.ev = env_eval(e, s.dir);
+    return s;
+}
+
+// =================================================================================================
 // Hit reconstruction helpers: src/render/optix/OptixRender_radiance_closest_hit.cu:199-254
 // =================================================================================================
 SKH_DI v3 unpack_normal(uint32_t val) // closest_hit.cu:236-244

@@ -16,6 +16,7 @@
 // per-thread global overflow area only for pathological depths.
 #pragma once
 #include "skh_bvh.h"
+#include "skh_env.h"
 
 namespace skh
 {
@@ -882,12 +883,16 @@ SKH_DI SurfaceHit fill_curve(const DevScene& sc, const HostInstance& hi, const f
 #define SKH_SHADE_BLOCK 256 // 132 VGPRs = 3 waves/SIMD: 256-thread blocks (1 wave per SIMD) fill all three, 512-thread blocks only two
 #endif
 // HAIR: the build with df::chiang_hair_bsdf in it (launched when the material list holds a hair material)
-template <bool HAIR>
+// ENV: the build with the environment light in it (launched when the context has one: skh_set_environment).  ENV = false never reads `env` and is the
+// kernel of before the environment existed, instruction for instruction (tools/kernel_resources.sh: same registers, no scratch).
+template <bool HAIR, bool ENV>
 __global__ void __launch_bounds__(SKH_SHADE_BLOCK) SKH_SHADE_ATTR(HAIR)
     k_shade(DevScene sc, FrameP fp, uint32_t sampleOffset, uint32_t depth /* bounce index */, const uint32_t* __restrict__ tileXY, RayQ rq,
             const uint32_t* __restrict__ countPtr, HitQ hq, PathS ps, RayQ nextQ, uint32_t* __restrict__ nextCount, RayQ shadowQ,
-            float4* __restrict__ contrib, uint32_t* __restrict__ shadowCount)
+            float4* __restrict__ contrib, uint32_t* __restrict__ shadowCount, EnvP env)
 {
+    // entries of the light pick: the lights, and behind them the environment when it is sampled (option env_nee)
+    const uint32_t numPick = ENV ? sc.numLights + (env.nee ? 1u : 0u) : sc.numLights;
     __shared__ uint32_t s_wave[2 * (SKH_COMPACT_MAX_WAVES + 1)];
     __shared__ uint32_t s_sobol[SKH_SOBOL_LUT_WORDS];
 #if SKH_MATERIALS_LDS
@@ -989,12 +994,29 @@ __global__ void __launch_bounds__(SKH_SHADE_BLOCK) SKH_SHADE_ATTR(HAIR)
 
         if (hinst == 0xffffffffu)
         {
-            // __miss__ms: bg_color = 0 (OptixRender.cpp:739)
-            const v3 bg = throughput * mk3(0.0f);
-            if (!(bg.x == 0.0f && bg.y == 0.0f && bg.z == 0.0f))
+            if constexpr (ENV)
             {
+                // the environment seen by a ray that leaves the scene: weighted as __closesthit__light weighs a light it hits
+                const EnvEval ee = env_eval(env, rayD);
                 SKH_RADIANCE_LOAD();
-                radiance = radiance + bg;
+                if (depth == 0 || specularBounce || !env.nee)
+                    radiance = radiance + throughput * ee.Le;
+                else
+                {
+                    const float lightPdf = ee.pdf / (float)numPick;
+                    const float misWeight = mis_weight_balance(lastBsdfPdf, lightPdf);
+                    radiance = radiance + throughput * ee.Le * misWeight;
+                }
+            }
+            else
+            {
+                // __miss__ms: bg_color = 0 (OptixRender.cpp:739)
+                const v3 bg = throughput * mk3(0.0f);
+                if (!(bg.x == 0.0f && bg.y == 0.0f && bg.z == 0.0f))
+                {
+                    SKH_RADIANCE_LOAD();
+                    radiance = radiance + bg;
+                }
             }
             throughput = mk3(0.0f);
             prdDepth = fp.maxDepth;
@@ -1037,7 +1059,7 @@ __global__ void __launch_bounds__(SKH_SHADE_BLOCK) SKH_SHADE_ATTR(HAIR)
                         radiance = radiance + throughput * mk3(l.color) * -dot(rayD, lightNormal);
                     else
                     {
-                        const float lightPdf = get_light_pdf(l, hitPoint, rayO) / (float)sc.numLights;
+                        const float lightPdf = get_light_pdf(l, hitPoint, rayO) / (float)numPick;
                         const float misWeight = mis_weight_balance(lastBsdfPdf, lightPdf);
                         radiance = radiance + throughput * mk3(l.color) * -dot(rayD, lightNormal) * misWeight;
                     }
@@ -1123,11 +1145,32 @@ __global__ void __launch_bounds__(SKH_SHADE_BLOCK) SKH_SHADE_ATTR(HAIR)
                     bool wantShadow = false;
                     float distToLight = 0.0f;
                     auto sampleLight = [&]() {
-                        if (sc.numLights > 0)
+                        if (numPick > 0)
                         {
                             const float u = sampler_random_lut(smp, DIM_LIGHT_ID, s_sobol);
-                            const uint32_t lightId = (uint32_t)((float)sc.numLights * u);
-                            const float lightSelectionPdf = 1.0f / (float)sc.numLights;
+                            const uint32_t lightId = (uint32_t)((float)numPick * u);
+                            const float lightSelectionPdf = 1.0f / (float)numPick;
+                            if constexpr (ENV)
+                            {
+                                if (lightId >= sc.numLights)
+                                {
+                                    // the environment: entry numLights of the pick.  No normal, no area; the shadow ray is a distant light's.
+                                    const float ux = sampler_random_lut(smp, DIM_LIGHT_X, s_sobol), uy = sampler_random_lut(smp, DIM_LIGHT_Y, s_sobol);
+                                    const EnvSample es = env_sample(env, ux, uy);
+                                    toLight = es.dir;
+                                    if (dot(sh.normal, es.dir) > 0.0f && es.ev.pdf > 0.0f)
+                                    {
+                                        wantShadow = true;
+                                        distToLight = 1e9f;
+                                        lightPdf = es.ev.pdf;
+                                        // (no cosine here: bsdf_evaluate's value carries the surface's, as MDL's does.  The reference's light branch below multiplies by
+                                        // a second one -- its lights are cosine emitters through it --; a sky is not, and the closed forms of tests/test_gpu_env.py hold the estimator to that)
+                                        lrad = es.ev.Le;
+                                    }
+                                    lightPdf *= lightSelectionPdf;
+                                    return;
+                                }
+                            }
                             // the whole 112-byte record in one round trip (by reference its fields were fetched in three dependent
                             // steps: type, then the branch's points, then colour / normal)
                             const Light light = sc.lights[lightId];

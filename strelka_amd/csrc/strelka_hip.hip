@@ -101,6 +101,11 @@ struct skh_context
     uint32_t raygenBlocksPerSub = 0, raygenValidPerSub = 0;
     uint32_t nTextures = 0;
     bool hasHairMaterial = false; // selects the k_shade build that carries df::chiang_hair_bsdf
+    // environment light (skh_set_environment): envW != 0 selects the k_shade build that carries it
+    DevBuf dEnvTexels, dEnvColCdf, dEnvRowCdf;
+    uint32_t envW = 0, envH = 0, envNee = 1;
+    float envScale[3] = { 1.0f, 1.0f, 1.0f }, envW2E[9] = { 1.0f, 0.0f, 0.0f, 0.0f, 1.0f, 0.0f, 0.0f, 0.0f, 1.0f };
+    double envSumW = 0.0, envMsBuild = 0.0;
     // Speculative sub-frame batching for the reference's call pattern (one render() per sub-frame, RenderPass.cpp:441-447): once two
     // consecutive calls continue the same frame (same parameters, subframe_index + 1), the next call traces several sub-frames
     // ahead in ONE wavefront pass and the calls after it only apply their accumulation step to the radiances already in the path
@@ -1180,6 +1185,7 @@ void skh_destroy(skh_context* c)
     if (c->hOverflow)
         (void)hipHostFree(c->hOverflow);
     dev_free(c->dTileSend);
+    dev_free(c->dEnvTexels), dev_free(c->dEnvColCdf), dev_free(c->dEnvRowCdf);
     delete c;
 }
 
@@ -1311,6 +1317,155 @@ skh_status skh_set_lights(skh_context* c, const skh_light* lights, uint32_t n)
     (void)hipSetDevice(c->device);
     c->nLights = n;
     return dev_upload(c, c->dLights, lights, sizeof(skh_light) * (size_t)n);
+}
+
+static bool env_transform_ok(const float scale[3], const float w2e[9])
+{
+    for (int k = 0; k < 3; ++k)
+        if (!(scale[k] >= 0.0f) || std::isinf(scale[k]))
+            return false;
+    for (int k = 0; k < 9; ++k)
+        if (!std::isfinite(w2e[k]))
+            return false;
+    return true;
+}
+
+static EnvP make_env(const skh_context* c)
+{
+    EnvP e;
+    memset(&e, 0, sizeof(e));
+    if (c->envW == 0)
+        return e;
+    e.texels = c->dEnvTexels.as<float4>();
+    e.rowCdf = c->dEnvRowCdf.as<float>();
+    e.colCdf = c->dEnvColCdf.as<float>();
+    e.width = c->envW, e.height = c->envH;
+    e.pdfScale = (float)((double)c->envW * (double)c->envH / (2.0 * 3.14159265358979323846 * 3.14159265358979323846));
+    e.nee = c->envNee;
+    memcpy(e.scale, c->envScale, sizeof(e.scale));
+    memcpy(e.w2e, c->envW2E, sizeof(e.w2e));
+    return e;
+}
+
+skh_status skh_set_environment(skh_context* c, const skh_environment* env)
+{
+    if (!c)
+        return SKH_INVALID_ARGUMENT;
+    if (!env)
+    {
+        c->err = "skh_set_environment: null description (rgb = NULL inside it removes the environment)";
+        return SKH_INVALID_ARGUMENT;
+    }
+    (void)hipSetDevice(c->device);
+    if (!env->rgb)
+    {
+        // remove: a no-op on a context that has none (nothing traced ahead is thrown away for it)
+        if (c->envW == 0)
+            return SKH_OK;
+        spec_drop(c);
+        SKH_TRY(c, hipStreamSynchronize(c->stream));
+        dev_free(c->dEnvTexels), dev_free(c->dEnvColCdf), dev_free(c->dEnvRowCdf);
+        c->envW = c->envH = 0;
+        c->envSumW = c->envMsBuild = 0.0;
+        return SKH_OK;
+    }
+    if (env->width < 2 || env->width > SKH_ENV_MAX_WIDTH || env->height < 2 || env->height > SKH_ENV_MAX_HEIGHT)
+    {
+        c->err = "skh_set_environment: the map must be 2..8192 texels wide and 2..4096 high";
+        return SKH_INVALID_ARGUMENT;
+    }
+    if (!env_transform_ok(env->scale, env->world_to_env))
+    {
+        c->err = "skh_set_environment: scale must be finite and >= 0, world_to_env finite";
+        return SKH_INVALID_ARGUMENT;
+    }
+    spec_drop(c);
+    const uint32_t W = env->width, H = env->height;
+    const size_t n = (size_t)W * H;
+    // built beside the tables in use: a map that is refused leaves the previous environment as it was
+    DevBuf dRgb, dTex, dCol, dRow, dTmp; // dTmp: H row sums (double), sum w (double), the bad-value flag
+    skh_status st;
+    auto drop = [&]() { dev_free(dRgb), dev_free(dTex), dev_free(dCol), dev_free(dRow), dev_free(dTmp); };
+    if ((st = dev_upload(c, dRgb, env->rgb, n * 3 * sizeof(float))) != SKH_OK || (st = dev_alloc(c, dTex, n * sizeof(float4))) != SKH_OK ||
+        (st = dev_alloc(c, dCol, n * sizeof(float))) != SKH_OK || (st = dev_alloc(c, dRow, H * sizeof(float))) != SKH_OK ||
+        (st = dev_alloc(c, dTmp, (H + 2) * sizeof(double))) != SKH_OK)
+    {
+        drop();
+        return st;
+    }
+    double* rowSum = dTmp.as<double>();
+    double* sumW = rowSum + H;
+    uint32_t* bad = reinterpret_cast<uint32_t*>(rowSum + H + 1);
+    hipError_t e = hipMemsetAsync(bad, 0, sizeof(double), c->stream);
+    if (e == hipSuccess)
+        e = hipStreamSynchronize(c->stream);
+    const auto t0 = std::chrono::steady_clock::now();
+    if (e == hipSuccess)
+    {
+        k_env_rows<<<H, SKH_ENV_BLOCK, 0, c->stream>>>(dRgb.as<float>(), W, H, dTex.as<float4>(), dCol.as<float>(), rowSum, bad);
+        k_env_marginal<<<1, SKH_ENV_BLOCK, 0, c->stream>>>(rowSum, H, dRow.as<float>(), sumW);
+        const uint32_t blocks = (uint32_t)std::min<size_t>((n + SKH_ENV_BLOCK - 1) / SKH_ENV_BLOCK, (size_t)c->numCUs * 16u);
+        k_env_normalise<<<blocks, SKH_ENV_BLOCK, 0, c->stream>>>(dTex.as<float4>(), n, sumW);
+        e = hipGetLastError();
+    }
+    if (e == hipSuccess)
+        e = hipStreamSynchronize(c->stream);
+    const double ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    double total = 0.0;
+    uint32_t badHost = 0;
+    if (e == hipSuccess)
+        e = hipMemcpy(&total, sumW, sizeof(double), hipMemcpyDeviceToHost);
+    if (e == hipSuccess)
+        e = hipMemcpy(&badHost, bad, sizeof(uint32_t), hipMemcpyDeviceToHost);
+    if (e != hipSuccess)
+    {
+        drop();
+        c->err = std::string("skh_set_environment: ") + hipGetErrorString(e);
+        return e == hipErrorOutOfMemory ? SKH_OUT_OF_MEMORY : SKH_FAIL;
+    }
+    if (badHost)
+    {
+        drop();
+        c->err = "skh_set_environment: the map holds a negative or non-finite value";
+        return SKH_INVALID_ARGUMENT;
+    }
+    dev_free(dRgb), dev_free(dTmp);
+    dev_free(c->dEnvTexels), dev_free(c->dEnvColCdf), dev_free(c->dEnvRowCdf);
+    c->dEnvTexels = dTex, c->dEnvColCdf = dCol, c->dEnvRowCdf = dRow;
+    c->envW = W, c->envH = H;
+    memcpy(c->envScale, env->scale, sizeof(c->envScale));
+    memcpy(c->envW2E, env->world_to_env, sizeof(c->envW2E));
+    c->envSumW = total;
+    c->envMsBuild = ms;
+    return SKH_OK;
+}
+
+skh_status skh_set_environment_transform(skh_context* c, const float scale[3], const float world_to_env[9])
+{
+    if (!c)
+        return SKH_INVALID_ARGUMENT;
+    if (!scale || !world_to_env || c->envW == 0 || !env_transform_ok(scale, world_to_env))
+    {
+        c->err = c->envW == 0 ? "skh_set_environment_transform: the context has no environment" :
+                                "skh_set_environment_transform: scale must be finite and >= 0, world_to_env finite";
+        return SKH_INVALID_ARGUMENT;
+    }
+    spec_drop(c); // sub-frames traced ahead hold radiance of the old sky
+    memcpy(c->envScale, scale, sizeof(c->envScale));
+    memcpy(c->envW2E, world_to_env, sizeof(c->envW2E));
+    return SKH_OK;
+}
+
+skh_status skh_get_environment_info(skh_context* c, skh_environment_info* out)
+{
+    if (!c || !out)
+        return SKH_INVALID_ARGUMENT;
+    memset(out, 0, sizeof(*out));
+    out->width = c->envW, out->height = c->envH;
+    out->sum_w = c->envSumW;
+    out->ms_build = c->envMsBuild;
+    out->bytes = c->envW ? (uint64_t)c->envW * c->envH * (sizeof(float4) + sizeof(float)) + (uint64_t)c->envH * sizeof(float) : 0u;
+    return SKH_OK;
 }
 
 skh_status skh_set_textures(skh_context* c, const skh_texture* textures, uint32_t n)
@@ -2771,6 +2926,7 @@ static skh_status render_one(skh_context* c, const skh_frame_params* p, uint32_t
     fp.finalFirst = std::min(finalFirst, batch);
     fp.finalCount = std::min(finalCount, batch - fp.finalFirst);
     const DevScene sc = make_dev_scene(c);
+    const EnvP envp = make_env(c);
     const uint32_t N = c->numSlots * c->batchCapacity; // plane stride of the path-state buffer
     const uint32_t NQ = SKH_SHARDS * c->queueRegion; // plane stride of every queue (rays, hits, shadow contributions)
     const uint32_t NP = c->numSlots * batch; // paths in this pass
@@ -2861,13 +3017,18 @@ static skh_status render_one(skh_context* c, const skh_frame_params* p, uint32_t
                 // workgroup b on shard b & 7; those past the end of their shard leave at once
                 const uint32_t perShard = (((NP + SKH_SHARDS - 1u) / SKH_SHARDS) + 63u) & ~63u;
                 const dim3 sg(SKH_SHARDS * ((perShard + SKH_SHADE_BLOCK - 1) / SKH_SHADE_BLOCK));
-#define SKH_SHADE_LAUNCH(HAIRB)                                                                                                                      \
-    k_shade<HAIRB><<<sg, SKH_SHADE_BLOCK, 0, st>>>(sc, fp, s, b, tiles, rq[b & 1], counts + 2 * b * QW, hq, ps, rq[(b + 1) & 1], counts + 2 * (b + 1) * QW, \
-                                                   shq, c->dContrib.as<float4>(), counts + (2 * b + 1) * QW)
-                if (c->hasHairMaterial)
-                    SKH_SHADE_LAUNCH(true);
+#define SKH_SHADE_LAUNCH(HAIRB, ENVB)                                                                                                                      \
+    k_shade<HAIRB, ENVB><<<sg, SKH_SHADE_BLOCK, 0, st>>>(sc, fp, s, b, tiles, rq[b & 1], counts + 2 * b * QW, hq, ps, rq[(b + 1) & 1], counts + 2 * (b + 1) * QW, \
+                                                         shq, c->dContrib.as<float4>(), counts + (2 * b + 1) * QW, envp)
+                // (a context without an environment launches the builds it always launched)
+                if (c->hasHairMaterial && c->envW)
+                    SKH_SHADE_LAUNCH(true, true);
+                else if (c->hasHairMaterial)
+                    SKH_SHADE_LAUNCH(true, false);
+                else if (c->envW)
+                    SKH_SHADE_LAUNCH(false, true);
                 else
-                    SKH_SHADE_LAUNCH(false);
+                    SKH_SHADE_LAUNCH(false, false);
 #undef SKH_SHADE_LAUNCH
             }
             {
@@ -3817,8 +3978,8 @@ skh_status skh_bsdf_probe(skh_context* c, const skh_bsdf_query* queries, uint32_
 
 // ---- unit probes (tests): the device functions of the sampler, the light samplers and the accumulator, one call per record, so that
 // GPU tests can hold the HIP code against the reference-generated fixtures of tests/golden/ directly ----
-static const uint32_t kUnitIn[SKH_UNIT_COUNT] = { 20, 8, 20, 24, 12, 8, 12, 12, 8 }, kUnitOut[SKH_UNIT_COUNT] = { 12, 4, 48, 4, 16, 4, 12, 24, 40 };
-static const uint32_t kUnitConst[SKH_UNIT_COUNT] = { 0, 0, 112, 112, 112, 0, 12, 12, 0 };
+static const uint32_t kUnitIn[SKH_UNIT_COUNT] = { 20, 8, 20, 24, 12, 8, 12, 12, 8, 8, 12 }, kUnitOut[SKH_UNIT_COUNT] = { 12, 4, 48, 4, 16, 4, 12, 24, 40, 36, 24 };
+static const uint32_t kUnitConst[SKH_UNIT_COUNT] = { 0, 0, 112, 112, 112, 0, 12, 12, 0, 0, 0 };
 __global__ void __launch_bounds__(256) k_unit_probe(uint32_t unit, uint32_t param, const float* __restrict__ consts, const uint32_t* __restrict__ in, uint32_t n,
                                                     uint32_t* __restrict__ out)
 {
@@ -3922,6 +4083,12 @@ skh_status skh_unit_probe(skh_context* c, uint32_t unit, uint32_t param, const v
             c->err = "skh_unit_probe: unknown unit, or a missing input / output / constants pointer";
         return SKH_INVALID_ARGUMENT;
     }
+    const bool envUnit = unit == SKH_UNIT_ENV_SAMPLE || unit == SKH_UNIT_ENV_EVAL;
+    if (envUnit && c->envW == 0)
+    {
+        c->err = "skh_unit_probe: the context has no environment";
+        return SKH_INVALID_ARGUMENT;
+    }
     (void)hipSetDevice(c->device);
     if (n == 0)
         return SKH_OK;
@@ -3933,7 +4100,10 @@ skh_status skh_unit_probe(skh_context* c, uint32_t unit, uint32_t param, const v
         dev_free(di), dev_free(dc), dev_free(dout);
         return s;
     }
-    k_unit_probe<<<(n + 255) / 256, 256, 0, c->stream>>>(unit, param, dc.as<float>(), di.as<uint32_t>(), n, dout.as<uint32_t>());
+    if (envUnit)
+        k_env_probe<<<(n + 255) / 256, 256, 0, c->stream>>>(make_env(c), unit == SKH_UNIT_ENV_SAMPLE ? 1u : 0u, di.as<float>(), n, dout.as<uint32_t>());
+    else
+        k_unit_probe<<<(n + 255) / 256, 256, 0, c->stream>>>(unit, param, dc.as<float>(), di.as<uint32_t>(), n, dout.as<uint32_t>());
     hipError_t e = hipStreamSynchronize(c->stream);
     if (e == hipSuccess)
         e = hipMemcpy(out, dout.p, (size_t)kUnitOut[unit] * n, hipMemcpyDeviceToHost);
@@ -4119,6 +4289,12 @@ skh_status skh_set_option(skh_context* c, const char* name, int64_t value)
             return SKH_INVALID_ARGUMENT;
         c->bakeSmallTris = (uint32_t)value;
         c->accelBuilt = false, c->refitReady = false;
+    }
+    else if (n == "env_nee")
+    {
+        if (value != 0 && value != 1)
+            return SKH_INVALID_ARGUMENT;
+        c->envNee = (uint32_t)value;
     }
     else if (n == "speculate_grow")
     {

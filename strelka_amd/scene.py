@@ -347,6 +347,18 @@ class Scene:
         self.createInstance(INSTANCE_LIGHT, mesh, NO_ID, transform, light_id)
         return light_id
 
+    # -- environment (dome) light: not in the reference's Scene; what an HdStrelkaLight of type domeLight would hand over
+    def setEnvironment(self, rgb, scale=(1.0, 1.0, 1.0), world_to_env=None):
+        """rgb: (H, W, 3) linear floats, lat-long, row 0 = the +Y pole, column 0 at phi = 0 on +X; None removes it"""
+        if rgb is None:
+            self.mEnvironment = None
+            return
+        rgb = np.ascontiguousarray(rgb, np.float32)
+        if rgb.ndim != 3 or rgb.shape[2] != 3:
+            raise ValueError("the environment map must be an (H, W, 3) array")
+        m = np.eye(3, dtype=np.float32) if world_to_env is None else np.ascontiguousarray(world_to_env, np.float32).reshape(3, 3)
+        self.mEnvironment = {"rgb": rgb, "scale": np.ascontiguousarray(scale, np.float32).reshape(3), "world_to_env": m}
+
     # -- flat getters (scene.h:229-327) in C-ABI layouts
     def arrays(self):
         def cat(lst, dtype, shape=None):
@@ -374,7 +386,7 @@ class Scene:
             mats[i]["metallic"], mats[i]["specular"], mats[i]["ior"] = me, sp, ior
             mats[i]["base_color_texture"], mats[i]["normal_texture"] = bt, nt
             mats[i]["reserved"] = rsv
-        return {
+        out = {
             "vertices": cat(self.mVertices, VERTEX),
             "indices": cat(self.mIndices, np.uint32),
             "meshes": meshes,
@@ -387,6 +399,9 @@ class Scene:
             "materials": mats,
             "textures": list(self.mTextures),
         }
+        if getattr(self, "mEnvironment", None) is not None:  # (only then: a scene without one has the keys it always had)
+            out["environment"] = self.mEnvironment
+        return out
 
 
 def hair_sigma_a_from_color(color, roughness_n=0.3):

@@ -1,10 +1,25 @@
-"""Renders one of the stand-in scenes on the GPU and writes a tonemapped PNG (usage: render_png.py kitchen|cornell|hair W H spp depth [exposure_scale] [out.png])."""
+"""Renders one of the stand-in scenes on the GPU and writes a tonemapped PNG (usage: render_png.py kitchen|cornell|hair W H spp depth [exposure_scale] [out.png] [--env FILE.hdr [--env-rotate DEG]]:
+--env lights the scene with a lat-long Radiance map as its dome light, --env-rotate turns the dome about +Y)."""
 import sys, numpy as np
 sys.path.insert(0, ".")
+import math
 import torch
-from strelka_amd import capi, scene as S, scenes, png
+from strelka_amd import capi, hdr, scene as S, scenes, png
+env_file = env_deg = None
+for flag in ("--env-rotate", "--env"):
+    if flag in sys.argv:
+        k = sys.argv.index(flag)
+        val = sys.argv[k + 1]
+        del sys.argv[k:k + 2]
+        if flag == "--env":
+            env_file = val
+        else:
+            env_deg = float(val)
 name = sys.argv[1]; W, H, spp, depth = int(sys.argv[2]), int(sys.argv[3]), int(sys.argv[4]), int(sys.argv[5])
 sc = {"kitchen": scenes.kitchen_standin, "cornell": scenes.cornell_box, "hair": scenes.hair_standin}[name]()
+if env_file:
+    a = math.radians(env_deg or 0.0)  # world -> environment: a turn of the dome by +a about Y is a turn of the directions by -a
+    sc.setEnvironment(hdr.load_hdr(env_file), world_to_env=[[math.cos(a), 0, math.sin(a)], [0, 1, 0], [-math.sin(a), 0, math.cos(a)]])
 ctx = capi.Context(0); ctx.set_scene(sc.arrays()); ctx.resize(W, H)
 p = S.frame_params(sc.getCamera(), W, H, subframe_index=0, spp_total=spp, max_depth=depth)
 ctx.render_subframes(p, spp, None)
