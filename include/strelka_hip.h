@@ -26,7 +26,7 @@
 extern "C" {
 #endif
 
-#define SKH_ABI_VERSION 5 /* 5 (round 6): + skh_refit_accel, skh_build_info.refit / ms_refit, then skh_update_accel (additive: refit = 2), then skh_set_environment / _transform / skh_get_environment_info + two unit probes (additive); options curve_merge, curve_segnode, curve_strand_major, split_pairs.  4 (round 5): + skh_get_build_info; options reinsert_rounds, reinsert_min_size; wide, tail_park, tail_lag removed.  3 (round 4): + skh_unit_probe, skh_copy_aov */
+#define SKH_ABI_VERSION 5 /* 5 (round 6): + skh_refit_accel, skh_build_info.refit / ms_refit, then skh_update_accel (additive: refit = 2), then skh_set_environment / _transform / skh_get_environment_info + two unit probes (additive), then skh_set_emission / skh_get_emitter_info / skh_emitter_probe (additive); options curve_merge, curve_segnode, curve_strand_major, split_pairs.  4 (round 5): + skh_get_build_info; options reinsert_rounds, reinsert_min_size; wide, tail_park, tail_lag removed.  3 (round 4): + skh_unit_probe, skh_copy_aov */
 
 /* mirrors oka::Result (include/render/common.h:30-35) */
 typedef enum skh_status
@@ -288,6 +288,39 @@ typedef struct skh_environment_info
 } skh_environment_info;
 skh_status skh_get_environment_info(skh_context* ctx, skh_environment_info* out);
 
+/* ---- emissive meshes: new, the reference generates mdl_edf_emission_* for every material (src/materialmanager/mdlPtxCodeGen.cpp:14-15,140-159) and no hit program calls them ----
+ * One linear RGB radiance Le per material, indexed as the material list is ("Emissive meshes").  Hits on mesh instances only; a triangle emits from
+ * its front side, the one its world-space geometric normal points to, and still reflects.
+ *   emitter table  one entry per (mesh instance whose material emits, triangle of its mesh), world space, built on the device: weight w_k = world area * luminance_709(Le),
+ *                  sum w in double, an inclusive CDF of floats (each one rounding away from the exact CDF of the stored weights) and a guide table over it.
+ *                  64 B per entry (three world-space vertices, Le, ids) + 4 B CDF + at most 8 B guide; at most SKH_EMIT_MAX_ENTRIES = 2^24 entries -- a scene
+ *                  with more is refused with SKH_INVALID_ARGUMENT by the call that builds the table (render, probe, info)
+ *   light pick     the whole emitter set is ONE more entry of the pick, behind the lights and the environment; the triangle by CDF inversion of the fraction of the pick's own
+ *                  draw, the point uniform on it; pdf per solid angle = luminance_709(Le) / sum w * dist^2 / cos at the emitter; no second surface cosine (as the environment)
+ *   hit            radiance += throughput * Le * weight, weight = 1 at depth 0, after a specular bounce or with option emit_nee 0, else the balance heuristic of the
+ *                  BSDF's pdf against pdf / entries of the pick
+ * skh_set_emission: rgb = 3 * n_materials floats, finite and >= 0, n_materials <= the material count; materials beyond n do not emit.  NULL or 0 removes all emission: the
+ * context then runs the kernels and produces the bits of one that never had any.  Discards sub-frames traced ahead, as skh_set_lights does; never touches the acceleration
+ * structures; a failed call leaves the previous emission in place.  The table is derived data: stale after skh_set_geometry / _instances / _materials / _emission and after
+ * skh_update_accel with a new instance table, rebuilt on the device before the next render, probe or info call; it needs no acceleration structure. */
+#define SKH_EMIT_MAX_ENTRIES (1u << 24)
+skh_status skh_set_emission(skh_context* ctx, const float* rgb, uint32_t n_materials);
+typedef struct skh_emitter_info
+{
+    uint32_t triangles, instances; /* entries of the table and the mesh instances they come from; 0, 0: nothing emits */
+    double sum_w; /* sum of the entry weights */
+    double ms_build; /* wall time of the last table build (device kernels and the small uploads) */
+    uint64_t bytes; /* device memory of the table */
+} skh_emitter_info;
+skh_status skh_get_emitter_info(skh_context* ctx, skh_emitter_info* out);
+/* The device functions k_shade calls, on host arrays of packed 32-bit words (n records):
+ *   SKH_EMIT_PROBE_SAMPLE  in  f32 u' (the selection draw), ux, uy, P[3] (the shaded point)
+ *                          out f32 point[3], normal[3], Le[3], pdf per solid angle (without the pick's 1 / entries), dist, u32 instance, prim
+ *   SKH_EMIT_PROBE_PDF     in  u32 instance, prim, f32 hitPoint[3], origin[3]      out f32 pdf, Le[3]   (0s for a triangle that is not in the table) */
+#define SKH_EMIT_PROBE_SAMPLE 0u
+#define SKH_EMIT_PROBE_PDF 1u
+skh_status skh_emitter_probe(skh_context* ctx, uint32_t kind, const void* in, uint32_t n, void* out);
+
 /* ---- createAccelerationStructure (OptixRender.cpp:388-496): per-mesh / per-curve BLAS + one TLAS ---- */
 skh_status skh_build_accel(skh_context* ctx, uint32_t flags);
 /* After a VERTEX edit -- skh_set_geometry with the mesh table and index buffer of the last build, any vertex data; skh_set_curves with the curve sets and vertex
@@ -510,7 +543,9 @@ skh_status skh_unit_probe(skh_context* ctx, uint32_t unit, uint32_t param, const
  *                 curve block, each instance's transform applied to the ray as at a TLAS leaf),
  *                 env_nee 1|0 (the second option that is part of a definition, the estimator's: 1 = the environment is an entry of the light pick and a miss is
  *                 MIS-weighted against it; 0 = the environment is reached by BSDF sampling only, every miss weighs 1.  Two estimators of one integral: the
- *                 expectation is the same, the bits are not.  Without an environment it changes nothing)
+ *                 expectation is the same, the bits are not.  Without an environment it changes nothing),
+ *                 emit_nee 1|0 (the same for emissive meshes: 1 = the emitter set is an entry of the light pick and a hit on an emitter is MIS-weighted against it; 0 = never
+ *                 picked, every emitter hit weighs 1.  Same expectation, other bits; with no emissive material it changes nothing)
  *   build        build_quality 1|0 (PLOC | Karras radix tree), reinsert_rounds (8; 0 = off: rounds of parallel reinsertion over the PLOC tree of the
  *                 triangle build -- every subtree looks for the place in the tree where it costs least, the best non-conflicting moves are applied),
  *                 reinsert_curve_rounds (4: the same over the curve sub-segment trees),

@@ -203,6 +203,7 @@ void HipRender::uploadMaterials()
 {
     Scene& sc = *mScene;
     std::vector<skh_material> mats;
+    std::vector<float> emission; // 3 per material: skh_set_emission, after the materials
 #ifdef SKH_WITH_STRELKA_HEADERS
     // every eTexture parameter becomes one RGBA8 texture (OptixRender.cpp:1346-1377: resolved against resource/searchPath, stbi_load
     // with STBI_rgb_alpha); a file that cannot be read is reported and the material keeps its constant colour (:1195-1199)
@@ -228,6 +229,9 @@ void HipRender::uploadMaterials()
     {
         const uint32_t diffuseId = load(skhmat::texturePath(d, "diffuse_texture")), normalId = load(skhmat::texturePath(d, "normalmap_texture"));
         mats.push_back(skhmat::translate(d, diffuseId, normalId));
+        float le[3];
+        skhmat::emission(d, le);
+        emission.insert(emission.end(), le, le + 3);
     }
     for (size_t k = 0; k < tex.size(); ++k)
         tex[k].rgba8 = pixels[k].data();
@@ -247,6 +251,9 @@ void HipRender::uploadMaterials()
         mats.push_back(m);
     }
     check(skh_set_materials(mCtx, mats.data(), (uint32_t)mats.size()), "skh_set_materials");
+    // emissive meshes: a lamp shade, a screen (all zeros = none: the context then runs the kernels it always ran)
+    const bool emits = std::any_of(emission.begin(), emission.end(), [](float v) { return v > 0.0f; });
+    check(skh_set_emission(mCtx, emits ? emission.data() : nullptr, emits ? (uint32_t)(emission.size() / 3) : 0u), "skh_set_emission");
 }
 
 static void environmentRotation(const float* worldToEnv, float out[9])

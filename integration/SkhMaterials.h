@@ -160,5 +160,28 @@ inline skh_material translate(const Desc& d, uint32_t diffuseTextureId = 0, uint
     }
     return m;
 }
+
+// The radiance Le the description's surfaces emit (skh_set_emission's entry for the material; 0 0 0 = none) -- the C++ statement of
+// strelka_amd/scene_io.py::emission_from_description: UsdPreviewSurface emissiveColor; OmniPBR enable_emission ? emissive_color * emissive_intensity : 0.
+template <class Desc>
+inline void emission(const Desc& d, float out[3])
+{
+    out[0] = out[1] = out[2] = 0.0f;
+    std::string low = d.name + " " + d.file;
+    std::transform(low.begin(), low.end(), low.begin(), [](unsigned char c) { return (char)tolower(c); });
+    const bool preview = find(d, "diffuseColor") || find(d, "useSpecularWorkflow") || find(d, "specularColor") || find(d, "clearcoat") ||
+                         find(d, "emissiveColor");
+    if (preview)
+        color(d, "emissiveColor", out, 0.0f, 0.0f, 0.0f);
+    else if (low.find("glass") == std::string::npos && low.find("pbr") != std::string::npos && scalar(d, "enable_emission", 0.0f) != 0.0f)
+    {
+        color(d, "emissive_color", out, 1.0f, 1.0f, 1.0f);
+        const float k = scalar(d, "emissive_intensity", 1.0f);
+        for (int c = 0; c < 3; ++c)
+            out[c] *= k;
+    }
+    for (int c = 0; c < 3; ++c)
+        out[c] = out[c] > 0.0f ? out[c] : 0.0f; // (a negative value, or a NaN, does not emit)
+}
 } // namespace skhmat
 } // namespace oka

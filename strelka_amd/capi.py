@@ -27,7 +27,8 @@ SYMBOLS = ["skh_create", "skh_destroy", "skh_last_error", "skh_abi_version", "sk
            "skh_buffer_alloc", "skh_buffer_free", "skh_buffer_download", "skh_copy_accum", "skh_copy_accum_tiles", "skh_scatter_tiles", "skh_trace", "skh_trace_device",
            "skh_set_option", "skh_get_stats", "skh_reset_stats", "skh_synchronize", "skh_get_stream", "skh_bsdf_probe", "skh_get_device_info", "skh_comm_unique_id", "skh_comm_init",
            "skh_comm_destroy", "skh_gather_tiles", "skh_host_register", "skh_host_unregister", "skh_get_baked", "skh_comm_info", "skh_probe_memory", "skh_unit_probe", "skh_copy_aov", "skh_get_build_info", "skh_refit_accel",
-           "skh_update_accel", "skh_set_environment", "skh_set_environment_transform", "skh_get_environment_info"]
+           "skh_update_accel", "skh_set_environment", "skh_set_environment_transform", "skh_get_environment_info",
+           "skh_set_emission", "skh_get_emitter_info", "skh_emitter_probe"]
 
 BUILD_INFO = np.dtype([("triangles", np.uint32), ("nodes", np.uint32), ("reinsert_rounds", np.uint32), ("reinsert_moves", np.uint32),
                        ("reinsert_min_size", np.uint32), ("refit", np.uint32), ("cost_before", np.float64), ("cost_after", np.float64),
@@ -36,6 +37,9 @@ DEVICE_INFO = np.dtype([("compute_units", np.uint32), ("simds_per_cu", np.uint32
                         ("memory_bus_bits", np.uint32), ("wavefront_size", np.uint32), ("total_memory_bytes", np.uint64), ("name", "S64")])
 
 ENVIRONMENT_INFO = np.dtype([("width", np.uint32), ("height", np.uint32), ("sum_w", np.float64), ("ms_build", np.float64), ("bytes", np.uint64)])
+EMITTER_INFO = np.dtype([("triangles", np.uint32), ("instances", np.uint32), ("sum_w", np.float64), ("ms_build", np.float64), ("bytes", np.uint64)])
+# skh_emitter_probe: kind -> (number, words in, words out) per record
+EMIT_PROBES = {"sample": (0, 6, 13), "pdf": (1, 8, 4)}
 
 
 class SkhEnvironment(C.Structure):  # skh_environment
@@ -85,6 +89,9 @@ def load():
     lib.skh_set_environment.argtypes = [vp, C.POINTER(SkhEnvironment)]
     lib.skh_set_environment_transform.argtypes = [vp, vp, vp]
     lib.skh_get_environment_info.argtypes = [vp, vp]
+    lib.skh_set_emission.argtypes = [vp, vp, u32]
+    lib.skh_get_emitter_info.argtypes = [vp, vp]
+    lib.skh_emitter_probe.argtypes = [vp, u32, vp, u32, vp]
     lib.skh_resize.argtypes = [vp, u32, u32]
     lib.skh_set_tiles.argtypes = [vp, u32, vp, u32]
     lib.skh_render_subframe.argtypes = [vp, vp, vp]
@@ -180,6 +187,7 @@ class Context:
             self.set_environment(None)
         else:
             self.set_environment(env["rgb"], env.get("scale", (1, 1, 1)), env.get("world_to_env"))
+        self.set_emission(arr.get("emission"))  # (likewise: a scene without emissive materials removes what a reused context holds)
         if build:
             self.build_accel(flags)
 
@@ -227,6 +235,33 @@ class Context:
         d = np.zeros((), ENVIRONMENT_INFO)
         self._ck(self.lib.skh_get_environment_info(self.h, _p(d)), "skh_get_environment_info")
         return {k: (float(d[k]) if d[k].dtype.kind == "f" else int(d[k])) for k in ENVIRONMENT_INFO.names}
+
+    def set_emission(self, rgb):
+        """skh_set_emission: `rgb` an (n, 3) float array, the radiance Le of the first n materials (None or empty removes all emission)"""
+        if rgb is None or len(rgb) == 0:
+            self._ck(self.lib.skh_set_emission(self.h, None, 0), "skh_set_emission")
+            return
+        keep = np.ascontiguousarray(rgb, np.float32)
+        if keep.ndim != 2 or keep.shape[1] != 3:
+            raise ValueError("the emission must be an (n_materials, 3) array")
+        self._ck(self.lib.skh_set_emission(self.h, _p(keep), keep.shape[0]), "skh_set_emission")
+
+    def emitter_info(self):
+        """skh_get_emitter_info (builds the emitter table when it is stale)"""
+        d = np.zeros((), EMITTER_INFO)
+        self._ck(self.lib.skh_get_emitter_info(self.h, _p(d)), "skh_get_emitter_info")
+        return {k: (float(d[k]) if d[k].dtype.kind == "f" else int(d[k])) for k in EMITTER_INFO.names}
+
+    def emitter_probe(self, kind, records):
+        """skh_emitter_probe: `kind` "sample" ({u', ux, uy, P[3]} -> 13 words) or "pdf" ({instance, prim, hitPoint[3], origin[3]} -> 4 words);
+        `records` an (n, words in) array of 32-bit words; returns (n, words out) uint32 (view as float32 where the header says f32)."""
+        num, win, wout = EMIT_PROBES[kind]
+        rec = np.ascontiguousarray(records)
+        if rec.dtype.itemsize != 4 or rec.ndim != 2 or rec.shape[1] != win:
+            raise ValueError(f"{kind}: records must be (n, {win}) 32-bit words")
+        out = np.zeros((rec.shape[0], wout), np.uint32)
+        self._ck(self.lib.skh_emitter_probe(self.h, num, _p(rec), rec.shape[0], _p(out)), "skh_emitter_probe")
+        return out
 
     def build_accel(self, flags=0):
         self._ck(self.lib.skh_build_accel(self.h, flags), "skh_build_accel")

@@ -655,6 +655,89 @@ SKH_DI EnvSample env_sample(const EnvP& e, float uRow, float uCol)
 }
 
 // =================================================================================================
+// Emissive meshes -- not in the reference's hit programs; DESIGN.md section 2 "Emissive meshes" is the definition, skh_emit.h builds the table.
+// One entry per (emitting mesh instance, triangle), world space; the whole set is ONE entry of the light pick, the triangle by CDF inversion.
+// =================================================================================================
+struct EmitP // by-value kernel argument; count == 0: nothing emits
+{
+    const float4* entries; // 4 per entry: {v0, Le.r} {v1, Le.g} {v2, Le.b} {luminance_709(Le), instance, prim | flip << 31, -}: all a sample needs in one round trip
+    const float* cdf; // inclusive CDF over the entry weights
+    const uint32_t* guide; // (1 << guideBits) + 1 words: guide[b] = the entry the search returns for u = b / 2^guideBits
+    const float4* Le; // per material: {r, g, b, luminance_709}
+    const uint32_t* instOffset; // per instance: its first entry, ~0 = not an emitter (the PDF probe only)
+    uint32_t count, guideBits, numMaterials;
+    uint32_t nee; // option emit_nee
+    float invSumW; // 1 / sum w, rounded once
+};
+// A pick costs: guide[b], guide[b + 1] (one round trip), the binary search between them (log2 of the bucket's entries + 1 dependent round trips: 0 ... 2 where
+// the weights are of one magnitude, since the guide has at least as many buckets as the table entries), the entry (one).  Same result as the plain search over
+// all entries -- smallest i with u < cdf[i], at most count - 1 --: b / 2^bits <= u < (b + 1) / 2^bits are exact floats and the search is monotone in u.
+SKH_DI uint32_t emit_select(const EmitP& e, float u)
+{
+    const uint32_t G = 1u << e.guideBits;
+    const uint32_t b = min((uint32_t)(u * (float)G), G - 1u); // (saturating, NaN -> 0)
+    uint32_t lo = e.guide[b], hi = e.guide[b + 1u];
+    while (lo < hi)
+    {
+        const uint32_t mid = (lo + hi) >> 1;
+        if (u < e.cdf[mid])
+            hi = mid;
+        else
+            lo = mid + 1u;
+    }
+    return lo;
+}
+// the emitting side: the object-space winding's normal carried to world space (the side normalize(M^-T cross(p1 - p0, p2 - p0)) points to, fill_triangle's
+// geometric normal) = the world-space winding's, turned round under a mirroring transform
+SKH_DI v3 emit_normal(const v3& v0, const v3& v1, const v3& v2, bool flip)
+{
+    const v3 n = normalize(cross(v1 - v0, v2 - v0));
+    return flip ? -n : n;
+}
+// pdf per solid angle, seen from `origin`, of the point `hitPoint` on an emitter of normal n_e; pdfArea = luminance_709(Le) / sum w, the density per area every
+// point of every emitter of that Le has.  0 from behind.  k_shade's hit branch, the sampler and SKH_EMIT_PROBE_PDF are this one function.
+SKH_DI float emit_pdf(const v3& n_e, float pdfArea, const v3& hitPoint, const v3& origin)
+{
+    const v3 d = hitPoint - origin;
+    const float dist = length(d);
+    const float cosE = -dot(d / dist, n_e);
+    return (cosE > 0.0f && pdfArea > 0.0f) ? pdfArea * (dist * dist) / cosE : 0.0f; // (dist = 0: NaN fails the test)
+}
+struct EmitSample
+{
+    v3 point, normal, Le, L; // L: unit, from P to the point
+    float pdf, dist; // pdf per solid angle, without the pick's 1 / numPick
+    uint32_t instance, prim;
+};
+SKH_DI EmitSample emit_sample(const EmitP& e, float uSel, float ux, float uy, const v3& P)
+{
+    const uint32_t k = emit_select(e, uSel);
+    const float4* __restrict__ p = e.entries + 4 * (size_t)k;
+    const float4 a = p[0], b = p[1], c = p[2], d = p[3];
+    const v3 v0 = mk3(a), v1 = mk3(b), v2 = mk3(c);
+    const uint32_t pw = __float_as_uint(d.z);
+    EmitSample s;
+    const float su = sqrtf(ux);
+    s.point = v0 * (1.0f - su) + v1 * (su * (1.0f - uy)) + v2 * (su * uy);
+    s.normal = emit_normal(v0, v1, v2, (pw >> 31) != 0u);
+    s.Le = mk3(a.w, b.w, c.w);
+    const v3 toP = s.point - P;
+    s.dist = length(toP);
+    s.L = toP / s.dist;
+    s.pdf = emit_pdf(s.normal, d.x * e.invSumW, s.point, P);
+    s.instance = __float_as_uint(d.y), s.prim = pw & 0x7fffffffu;
+    return s;
+}
+// The shadow ray of an emitter sample must end short of the sampled point: emitters are geometry and any-hit rays see them.  Its origin is offset_ray's -- moved off
+// the surface by delta <= 2^-15 |P| (256 ulps per component; 2^-16 absolute near the origin) --, the point X carries 3 roundings of the barycentric sum (<= 2^-22 |X|),
+// and the intersector's t is one fp32 evaluation inside its envelope (a few ulps, 2^-21 t, up to 10^3 thinnest extents between origin and target).
+// Along the ray the emitter's own plane therefore lies at t = dist - (delta n_s.n_e + eps_X) / cos_e +- 2^-21 dist: a relative margin m keeps the ray clear of it while
+// cos_e >= (2^-15 |P| + 2^-22 |X|) / (m dist).  m = 2^-10: cos_e >= 2^-5 |P| / dist -- a sample more grazing than that may shadow itself, and its contribution carries
+// the factor cos_e (pdf ~ 1 / cos_e), so what is lost is of the order (2^-5 |P| / dist)^2 of the emitter's light; what is gained wrongly is an occluder nearer to the
+// emitter than dist / 1024, which the ray no longer sees.
+#define SKH_EMIT_SHADOW_MARGIN (1.0f / 1024.0f)
+
+// =================================================================================================
 // Hit reconstruction helpers: src/render/optix/OptixRender_radiance_closest_hit.cu:199-254
 // =================================================================================================
 SKH_DI v3 unpack_normal(uint32_t val) // closest_hit.cu:236-244

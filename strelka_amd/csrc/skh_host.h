@@ -112,6 +112,13 @@ struct skh_context
     uint32_t envW = 0, envH = 0, envNee = 1;
     float envScale[3] = { 1.0f, 1.0f, 1.0f }, envW2E[9] = { 1.0f, 0.0f, 0.0f, 0.0f, 1.0f, 0.0f, 0.0f, 0.0f, 1.0f };
     double envSumW = 0.0, envMsBuild = 0.0;
+    // emissive meshes (skh_set_emission): the per-material radiances as the caller gave them, and the emitter table derived from them, the geometry, the
+    // instances and the material count (emit_ensure builds it when stale).  emitSumW > 0 selects the k_shade build that carries it.
+    std::vector<float> emission; // 3 per material; empty: nothing emits
+    bool emitStale = false;
+    DevBuf dEmitEntries, dEmitCdf, dEmitGuide, dEmitLe, dEmitInstOffset;
+    uint32_t emitCount = 0, emitInstances = 0, emitGuideBits = 0, emitNee = 1;
+    double emitSumW = 0.0, emitMsBuild = 0.0;
     // Speculative sub-frame batching for the reference's call pattern (one render() per sub-frame, RenderPass.cpp:441-447): once two
     // consecutive calls continue the same frame (same parameters, subframe_index + 1), the next call traces several sub-frames
     // ahead in ONE wavefront pass and the calls after it only apply their accumulation step to the radiances already in the path

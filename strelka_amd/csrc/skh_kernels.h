@@ -17,6 +17,7 @@
 #pragma once
 #include "skh_bvh.h"
 #include "skh_env.h"
+#include "skh_emit.h"
 
 namespace skh
 {
@@ -885,14 +886,16 @@ SKH_DI SurfaceHit fill_curve(const DevScene& sc, const HostInstance& hi, const f
 // HAIR: the build with df::chiang_hair_bsdf in it (launched when the material list holds a hair material)
 // ENV: the build with the environment light in it (launched when the context has one: skh_set_environment).  ENV = false never reads `env` and is the
 // kernel of before the environment existed, instruction for instruction (tools/kernel_resources.sh: same registers, no scratch).
-template <bool HAIR, bool ENV>
+// EMIT: the build with emissive meshes in it (launched when the emitter table has sum w > 0: skh_set_emission).  EMIT = false never reads `emit`: the four
+// builds without it are the kernels they were (profiles/: tools/kernel_resources.sh before and after).
+template <bool HAIR, bool ENV, bool EMIT>
 __global__ void __launch_bounds__(SKH_SHADE_BLOCK) SKH_SHADE_ATTR(HAIR)
     k_shade(DevScene sc, FrameP fp, uint32_t sampleOffset, uint32_t depth /* bounce index */, const uint32_t* __restrict__ tileXY, RayQ rq,
             const uint32_t* __restrict__ countPtr, HitQ hq, PathS ps, RayQ nextQ, uint32_t* __restrict__ nextCount, RayQ shadowQ,
-            float4* __restrict__ contrib, uint32_t* __restrict__ shadowCount, EnvP env)
+            float4* __restrict__ contrib, uint32_t* __restrict__ shadowCount, EnvP env, EmitP emit)
 {
-    // entries of the light pick: the lights, and behind them the environment when it is sampled (option env_nee)
-    const uint32_t numPick = ENV ? sc.numLights + (env.nee ? 1u : 0u) : sc.numLights;
+    // entries of the light pick: the lights, behind them the environment when it is sampled (option env_nee), behind that the emitter set (option emit_nee)
+    const uint32_t numPick = (ENV ? sc.numLights + (env.nee ? 1u : 0u) : sc.numLights) + (EMIT ? (emit.nee ? 1u : 0u) : 0u);
     __shared__ uint32_t s_wave[2 * (SKH_COMPACT_MAX_WAVES + 1)];
     __shared__ uint32_t s_sobol[SKH_SOBOL_LUT_WORDS];
 #if SKH_MATERIALS_LDS
@@ -1070,6 +1073,9 @@ __global__ void __launch_bounds__(SKH_SHADE_BLOCK) SKH_SHADE_ATTR(HAIR)
             {
                 // __closesthit__radiance
                 const uint32_t mid = hi.material == 0xffffffffu ? 0u : hi.material; // OptixRender.cpp:768
+                float4 matLe = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+                if constexpr (EMIT) // (beside the material's record: one round trip for both)
+                    matLe = emit.Le[mid < emit.numMaterials ? mid : 0u];
 #if SKH_MATERIALS_LDS
                 const uint32_t midc = mid < sc.numMaterials ? mid : 0u;
                 Material mat;
@@ -1130,6 +1136,28 @@ __global__ void __launch_bounds__(SKH_SHADE_BLOCK) SKH_SHADE_ATTR(HAIR)
                     radiance = (sh.normal + mk3(1.0f)) * 0.5f, radianceDirty = true;
                 else
                 {
+                    if constexpr (EMIT)
+                    {
+                        // an emissive mesh seen from its front side (the geometric normal before the `inside` flip): weighted as __closesthit__light weighs a
+                        // light it hits, WITHOUT that branch's cosine (a Lambertian surface, as the sky); the path goes on below, the surface reflects too
+                        if (hi.type == 0u && matLe.w > 0.0f)
+                        {
+                            const v3 ne = inside ? -sh.geom_normal : sh.geom_normal;
+                            if (-dot(rayD, ne) > 0.0f)
+                            {
+                                const v3 Le = mk3(matLe.x, matLe.y, matLe.z);
+                                SKH_RADIANCE_LOAD();
+                                if (depth == 0 || specularBounce || !emit.nee)
+                                    radiance = radiance + throughput * Le;
+                                else
+                                {
+                                    const float lightPdf = emit_pdf(ne, matLe.w * emit.invSumW, sh.position, rayO) / (float)numPick;
+                                    const float misWeight = mis_weight_balance(lastBsdfPdf, lightPdf);
+                                    radiance = radiance + throughput * Le * misWeight;
+                                }
+                            }
+                        }
+                    }
                     const float xi0 = sampler_random_lut(smp, DIM_BSDF0, s_sobol), xi1 = sampler_random_lut(smp, DIM_BSDF1, s_sobol),
                                 xi2 = sampler_random_lut(smp, DIM_BSDF2, s_sobol);
                     const float xi3 = HAIR ? sampler_random_lut(smp, DIM_BSDF3, s_sobol) : 0.0f; // (only the hair BSDF consumes xi.w)
@@ -1150,6 +1178,26 @@ __global__ void __launch_bounds__(SKH_SHADE_BLOCK) SKH_SHADE_ATTR(HAIR)
                             const float u = sampler_random_lut(smp, DIM_LIGHT_ID, s_sobol);
                             const uint32_t lightId = (uint32_t)((float)numPick * u);
                             const float lightSelectionPdf = 1.0f / (float)numPick;
+                            if constexpr (EMIT)
+                            {
+                                if (emit.nee && lightId + 1u >= numPick)
+                                {
+                                    // the emitter set: the last entry of the pick.  The triangle from the fraction of the pick's own draw (no new dimension, its stratification survives)
+                                    const float uSel = fminf(fmaxf((float)numPick * u - (float)(numPick - 1u), 0.0f), 0.99999994f);
+                                    const float ux = sampler_random_lut(smp, DIM_LIGHT_X, s_sobol), uy = sampler_random_lut(smp, DIM_LIGHT_Y, s_sobol);
+                                    const EmitSample es = emit_sample(emit, uSel, ux, uy, sh.position);
+                                    toLight = es.L;
+                                    if (dot(sh.normal, es.L) > 0.0f && -dot(es.L, es.normal) > 0.0f && es.pdf > 0.0f)
+                                    {
+                                        wantShadow = true;
+                                        distToLight = es.dist * (1.0f - SKH_EMIT_SHADOW_MARGIN); // (ends short of the emitter itself: skh_device.h)
+                                        lightPdf = es.pdf;
+                                        lrad = es.Le; // (no second cosine, as for the environment: bsdf_evaluate carries the surface's)
+                                    }
+                                    lightPdf *= lightSelectionPdf;
+                                    return;
+                                }
+                            }
                             if constexpr (ENV)
                             {
                                 if (lightId >= sc.numLights)

@@ -215,6 +215,7 @@ skh_status skh_set_geometry(skh_context* c, const skh_vertex* verts, uint32_t n_
     c->nIndices = n_indices;
     c->accelBuilt = false;
     c->vertsEdited = true;
+    c->emitStale = true;
     {
         // signature of the TOPOLOGY (mesh table + index buffer, FNV-1a over their words): skh_refit_accel keeps the hierarchy only while it is the built one
         uint64_t h = 1469598103934665603ull;
@@ -294,6 +295,7 @@ skh_status skh_set_instances(skh_context* c, const skh_instance* instances, uint
     c->instances.assign(instances, instances + n);
     c->nInstances = n;
     c->accelBuilt = false;
+    c->emitStale = true;
     return dev_upload(c, c->dInstances, instances, sizeof(skh_instance) * (size_t)n);
 }
 
@@ -487,6 +489,7 @@ skh_status skh_set_materials(skh_context* c, const skh_material* materials, uint
     spec_drop(c);
     (void)hipSetDevice(c->device);
     c->nMaterials = n;
+    c->emitStale = true;
     c->hasHairMaterial = false;
     for (uint32_t k = 0; k < n; ++k)
         c->hasHairMaterial = c->hasHairMaterial || materials[k].type == SKH_MAT_HAIR;
@@ -746,6 +749,210 @@ static DevScene make_dev_scene(const skh_context* c)
     return sc;
 }
 
+// ---- emissive meshes: skh_set_emission, the emitter table (skh_emit.h) ----
+static void emit_clear(skh_context* c)
+{
+    dev_free(c->dEmitEntries), dev_free(c->dEmitCdf), dev_free(c->dEmitGuide), dev_free(c->dEmitLe), dev_free(c->dEmitInstOffset);
+    c->emitCount = c->emitInstances = c->emitGuideBits = 0;
+    c->emitSumW = 0.0;
+}
+
+static float lum709(const float* rgb)
+{
+    return (float)(0.2126 * (double)rgb[0] + 0.7152 * (double)rgb[1] + 0.0722 * (double)rgb[2]);
+}
+
+// Builds the table when it is stale.  Needs the geometry, the instances and the material count, no acceleration structure.
+static skh_status emit_ensure(skh_context* c)
+{
+    if (!c->emitStale)
+        return SKH_OK;
+    if (c->emission.empty())
+    {
+        // (nothing emits: no device work, no synchronisation -- a context that was never told pays one test per call)
+        if (c->emitCount || c->dEmitLe.p)
+        {
+            SKH_TRY(c, hipStreamSynchronize(c->stream));
+            emit_clear(c);
+        }
+        c->emitMsBuild = 0.0;
+        c->emitStale = false;
+        return SKH_OK;
+    }
+    const auto t0 = std::chrono::steady_clock::now();
+    SKH_TRY(c, hipStreamSynchronize(c->stream)); // (the tables are about to be replaced)
+    const uint32_t nMat = std::max(1u, c->nMaterials), nMeshes = (uint32_t)c->meshes.size(), nInst = (uint32_t)c->instances.size();
+    std::vector<float> le(4 * (size_t)nMat, 0.0f); // {r, g, b, luminance}; materials beyond the emission list do not emit
+    for (uint32_t m = 0; m < nMat && 3 * (size_t)m + 2 < c->emission.size(); ++m)
+    {
+        memcpy(&le[4 * (size_t)m], &c->emission[3 * (size_t)m], 3 * sizeof(float));
+        le[4 * (size_t)m + 3] = lum709(&c->emission[3 * (size_t)m]);
+    }
+    std::vector<uint32_t> emitInst, emitBase, instOffset(std::max(1u, nInst), 0xffffffffu);
+    uint64_t total = 0;
+    for (uint32_t i = 0; i < nInst; ++i)
+    {
+        const skh_instance& in = c->instances[i];
+        if (in.type != SKH_INSTANCE_MESH || in.geom_id >= nMeshes)
+            continue;
+        const uint32_t mid0 = in.material_id == 0xffffffffu ? 0u : in.material_id, mid = mid0 < c->nMaterials ? mid0 : 0u; // (as k_shade reads it)
+        float w2o[12];
+        const uint32_t tris = c->meshes[in.geom_id].index_count / 3u;
+        if (!(le[4 * (size_t)mid + 3] > 0.0f) || tris == 0 || !invert_affine(in.transform, w2o)) // (a singular instance is disabled: no ray reaches it)
+            continue;
+        emitInst.push_back(i);
+        emitBase.push_back((uint32_t)total);
+        instOffset[i] = (uint32_t)total;
+        total += tris;
+        if (total > SKH_EMIT_MAX_ENTRIES)
+        {
+            c->err = "emitter table: more than 2^24 emissive triangles (SKH_EMIT_MAX_ENTRIES)";
+            return SKH_INVALID_ARGUMENT;
+        }
+    }
+    const uint32_t n = (uint32_t)total, nEmit = (uint32_t)emitInst.size();
+    if (n == 0)
+    {
+        emit_clear(c);
+        c->emitMsBuild = 0.0;
+        c->emitStale = false;
+        return SKH_OK;
+    }
+    emitBase.push_back(n);
+    uint32_t bits = 0;
+    while ((1u << bits) < n)
+        ++bits;
+    const uint32_t G = 1u << bits, nTiles = (n + SKH_EMIT_TILE - 1u) / SKH_EMIT_TILE;
+    DevBuf dEntries, dCdf, dGuide, dLe, dOff, dInst, dBase, dWeight, dTmp; // dTmp: the tile sums, sum w
+    SKH_CHECK(dev_alloc(c, dEntries, (size_t)n * 4 * sizeof(float4)));
+    SKH_CHECK(dev_alloc(c, dCdf, (size_t)n * sizeof(float)));
+    SKH_CHECK(dev_alloc(c, dWeight, (size_t)n * sizeof(float)));
+    SKH_CHECK(dev_alloc(c, dGuide, ((size_t)G + 1u) * sizeof(uint32_t)));
+    SKH_CHECK(dev_alloc(c, dTmp, ((size_t)nTiles + 1u) * sizeof(double)));
+    SKH_CHECK(dev_upload(c, dLe, le.data(), le.size() * sizeof(float)));
+    SKH_CHECK(dev_upload(c, dOff, instOffset.data(), instOffset.size() * sizeof(uint32_t)));
+    SKH_CHECK(dev_upload(c, dInst, emitInst.data(), emitInst.size() * sizeof(uint32_t)));
+    SKH_CHECK(dev_upload(c, dBase, emitBase.data(), emitBase.size() * sizeof(uint32_t)));
+    double* tileSum = dTmp.as<double>();
+    double* sumW = tileSum + nTiles;
+    hipStream_t st = c->stream;
+    k_emit_gather<<<(n + SKH_EMIT_BLOCK - 1u) / SKH_EMIT_BLOCK, SKH_EMIT_BLOCK, 0, st>>>(c->dVerts.as<uint8_t>(), c->dIndices.as<uint32_t>(), c->dMeshes.as<uint4>(),
+                                                                                       c->dInstances.as<uint32_t>(), dLe.as<float4>(), nMat, dInst.as<uint32_t>(),
+                                                                                       dBase.as<uint32_t>(), nEmit, n, dEntries.as<float4>(), dWeight.as<float>());
+    k_emit_tile_sums<<<nTiles, SKH_EMIT_BLOCK, 0, st>>>(dWeight.as<float>(), n, tileSum);
+    k_emit_scan_tiles<<<1, SKH_EMIT_BLOCK, 0, st>>>(tileSum, nTiles, sumW);
+    k_emit_cdf<<<nTiles, SKH_EMIT_BLOCK, 0, st>>>(dWeight.as<float>(), n, tileSum, sumW, dCdf.as<float>());
+    k_emit_guide<<<(G + 1u + SKH_EMIT_BLOCK - 1u) / SKH_EMIT_BLOCK, SKH_EMIT_BLOCK, 0, st>>>(dCdf.as<float>(), n, bits, dGuide.as<uint32_t>());
+    SKH_TRY(c, hipGetLastError());
+    double totalW = 0.0;
+    SKH_TRY(c, hipMemcpyAsync(&totalW, sumW, sizeof(double), hipMemcpyDeviceToHost, st));
+    SKH_TRY(c, hipStreamSynchronize(st));
+    c->dEmitEntries = std::move(dEntries), c->dEmitCdf = std::move(dCdf), c->dEmitGuide = std::move(dGuide), c->dEmitLe = std::move(dLe), c->dEmitInstOffset = std::move(dOff);
+    c->emitCount = n, c->emitInstances = nEmit, c->emitGuideBits = bits;
+    c->emitSumW = totalW;
+    c->emitMsBuild = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    c->emitStale = false;
+    return SKH_OK;
+}
+
+static EmitP make_emit(const skh_context* c)
+{
+    EmitP e;
+    memset(&e, 0, sizeof(e));
+    if (!(c->emitSumW > 0.0))
+        return e;
+    e.entries = c->dEmitEntries.as<float4>();
+    e.cdf = c->dEmitCdf.as<float>();
+    e.guide = c->dEmitGuide.as<uint32_t>();
+    e.Le = c->dEmitLe.as<float4>();
+    e.instOffset = c->dEmitInstOffset.as<uint32_t>();
+    e.count = c->emitCount, e.guideBits = c->emitGuideBits, e.numMaterials = std::max(1u, c->nMaterials);
+    e.nee = c->emitNee;
+    e.invSumW = (float)(1.0 / c->emitSumW);
+    return e;
+}
+
+skh_status skh_set_emission(skh_context* c, const float* rgb, uint32_t n)
+{
+    if (!c)
+        return SKH_INVALID_ARGUMENT;
+    (void)hipSetDevice(c->device);
+    if (!rgb || n == 0)
+    {
+        // remove: a no-op on a context that has none (nothing traced ahead is thrown away for it)
+        if (c->emission.empty())
+            return SKH_OK;
+        spec_drop(c);
+        c->emission.clear();
+        c->emitStale = true;
+        return SKH_OK;
+    }
+    if (n > c->nMaterials)
+    {
+        c->err = "skh_set_emission: " + std::to_string(n) + " radiances for " + std::to_string(c->nMaterials) + " materials (call skh_set_materials first)";
+        return SKH_INVALID_ARGUMENT;
+    }
+    for (size_t k = 0; k < 3 * (size_t)n; ++k)
+        if (!(rgb[k] >= 0.0f) || std::isinf(rgb[k])) // (a NaN fails >=)
+        {
+            c->err = "skh_set_emission: the radiances must be finite and >= 0";
+            return SKH_INVALID_ARGUMENT;
+        }
+    spec_drop(c);
+    bool any = false;
+    for (size_t k = 0; k < 3 * (size_t)n; ++k)
+        any = any || rgb[k] > 0.0f;
+    if (any)
+        c->emission.assign(rgb, rgb + 3 * (size_t)n);
+    else
+        c->emission.clear(); // (all black: the context of one that was never told)
+    c->emitStale = true;
+    return SKH_OK;
+}
+
+skh_status skh_get_emitter_info(skh_context* c, skh_emitter_info* out)
+{
+    if (!c || !out)
+        return SKH_INVALID_ARGUMENT;
+    memset(out, 0, sizeof(*out));
+    (void)hipSetDevice(c->device);
+    SKH_CHECK(emit_ensure(c));
+    out->triangles = c->emitCount, out->instances = c->emitInstances;
+    out->sum_w = c->emitSumW;
+    out->ms_build = c->emitMsBuild;
+    out->bytes = c->emitCount ? c->dEmitEntries.bytes + c->dEmitCdf.bytes + c->dEmitGuide.bytes + c->dEmitLe.bytes + c->dEmitInstOffset.bytes : 0u;
+    return SKH_OK;
+}
+
+skh_status skh_emitter_probe(skh_context* c, uint32_t kind, const void* in, uint32_t n, void* out)
+{
+    if (!c)
+        return SKH_INVALID_ARGUMENT;
+    if (kind > SKH_EMIT_PROBE_PDF || (n && (!in || !out)))
+    {
+        c->err = "skh_emitter_probe: unknown kind, or a missing input / output pointer";
+        return SKH_INVALID_ARGUMENT;
+    }
+    (void)hipSetDevice(c->device);
+    SKH_CHECK(emit_ensure(c));
+    if (!(c->emitSumW > 0.0))
+    {
+        c->err = "skh_emitter_probe: the context has no emitter (no emissive material on a mesh instance)";
+        return SKH_INVALID_ARGUMENT;
+    }
+    if (n == 0)
+        return SKH_OK;
+    const size_t inBytes = (kind == SKH_EMIT_PROBE_SAMPLE ? 6u : 8u) * sizeof(uint32_t), outBytes = (kind == SKH_EMIT_PROBE_SAMPLE ? 13u : 4u) * sizeof(uint32_t);
+    DevBuf di, dout;
+    SKH_CHECK(dev_upload(c, di, in, inBytes * n));
+    SKH_CHECK(dev_alloc(c, dout, outBytes * n));
+    k_emit_probe<<<(n + 255) / 256, 256, 0, c->stream>>>(make_emit(c), (uint32_t)c->instances.size(), kind, di.as<uint32_t>(), n, dout.as<uint32_t>());
+    SKH_TRY(c, hipGetLastError());
+    SKH_TRY(c, hipStreamSynchronize(c->stream));
+    SKH_TRY(c, hipMemcpy(out, dout.p, outBytes * n, hipMemcpyDeviceToHost));
+    return SKH_OK;
+}
+
 static skh_status ensure_ready(skh_context* c)
 {
     if (!c->accelBuilt)
@@ -765,7 +972,7 @@ static skh_status ensure_ready(skh_context* c)
         if (s != SKH_OK)
             return s;
     }
-    return SKH_OK;
+    return emit_ensure(c);
 }
 
 // one launch of the persistent trace kernel over a sharded queue: picks the build (world-only / two-level / two-level + curves) and the grid
@@ -867,6 +1074,7 @@ static skh_status render_one(skh_context* c, const skh_frame_params* p, uint32_t
     fp.finalCount = std::min(finalCount, batch - fp.finalFirst);
     const DevScene sc = make_dev_scene(c);
     const EnvP envp = make_env(c);
+    const EmitP emitp = make_emit(c);
     const uint32_t N = c->numSlots * c->batchCapacity; // plane stride of the path-state buffer
     const uint32_t NQ = SKH_SHARDS * c->queueRegion; // plane stride of every queue (rays, hits, shadow contributions)
     const uint32_t NP = c->numSlots * batch; // paths in this pass
@@ -957,18 +1165,32 @@ static skh_status render_one(skh_context* c, const skh_frame_params* p, uint32_t
                 // workgroup b on shard b & 7; those past the end of their shard leave at once
                 const uint32_t perShard = (((NP + SKH_SHARDS - 1u) / SKH_SHARDS) + 63u) & ~63u;
                 const dim3 sg(SKH_SHARDS * ((perShard + SKH_SHADE_BLOCK - 1) / SKH_SHADE_BLOCK));
-#define SKH_SHADE_LAUNCH(HAIRB, ENVB)                                                                                                                      \
-    k_shade<HAIRB, ENVB><<<sg, SKH_SHADE_BLOCK, 0, st>>>(sc, fp, s, b, tiles, rq[b & 1], counts + 2 * b * QW, hq, ps, rq[(b + 1) & 1], counts + 2 * (b + 1) * QW, \
-                                                         shq, c->dContrib.as<float4>(), counts + (2 * b + 1) * QW, envp)
-                // (a context without an environment launches the builds it always launched)
+#define SKH_SHADE_LAUNCH(HAIRB, ENVB, EMITB)                                                                                                                      \
+    k_shade<HAIRB, ENVB, EMITB><<<sg, SKH_SHADE_BLOCK, 0, st>>>(sc, fp, s, b, tiles, rq[b & 1], counts + 2 * b * QW, hq, ps, rq[(b + 1) & 1], counts + 2 * (b + 1) * QW, \
+                                                                shq, c->dContrib.as<float4>(), counts + (2 * b + 1) * QW, envp, emitp)
+#define SKH_SHADE_LAUNCH_EMIT(HAIRB, ENVB) \
+    if (emitp.count)                       \
+        SKH_SHADE_LAUNCH(HAIRB, ENVB, true); \
+    else                                   \
+        SKH_SHADE_LAUNCH(HAIRB, ENVB, false)
+                // (a context without an environment and without emitters launches the builds it always launched)
                 if (c->hasHairMaterial && c->envW)
-                    SKH_SHADE_LAUNCH(true, true);
+                {
+                    SKH_SHADE_LAUNCH_EMIT(true, true);
+                }
                 else if (c->hasHairMaterial)
-                    SKH_SHADE_LAUNCH(true, false);
+                {
+                    SKH_SHADE_LAUNCH_EMIT(true, false);
+                }
                 else if (c->envW)
-                    SKH_SHADE_LAUNCH(false, true);
+                {
+                    SKH_SHADE_LAUNCH_EMIT(false, true);
+                }
                 else
-                    SKH_SHADE_LAUNCH(false, false);
+                {
+                    SKH_SHADE_LAUNCH_EMIT(false, false);
+                }
+#undef SKH_SHADE_LAUNCH_EMIT
 #undef SKH_SHADE_LAUNCH
             }
             {
@@ -2064,6 +2286,7 @@ static const OptRow kOptions[] = {
     { "small_waves_closest", 0, 64, OPT_NONE, OPT_U32(smallWavesClosest) },
     { "small_waves_shadow", 0, 64, OPT_NONE, OPT_U32(smallWavesShadow) },
     { "env_nee", 0, 1, OPT_NONE, OPT_U32(envNee) },
+    { "emit_nee", 0, 1, OPT_NONE, OPT_U32(emitNee) },
     { "speculate", 0, 64, OPT_NONE, OPT_U32(speculateMax) },
     { "speculate_grow", 2, 64, OPT_NONE, OPT_U32(speculateGrow) },
     { "speculate_async", 0, 1, OPT_NONE, [](skh_context* c, int64_t v) { spec_drop(c), c->speculateAsync = (uint32_t)v; } },

@@ -168,10 +168,16 @@ class GltfScene(S.Scene):
                     elif p["name"] == "normalmap_texture":
                         mats[k]["normal_texture"] = self.texture_ids[p["value"]]
         arr["materials"] = mats
+        em = scene_io.emission_from_descriptions(self.material_descriptions)
+        if em is not None:
+            arr["emission"] = em
         return arr
 
 
 def _load_materials(doc, sc):
+    """glTF materials -> the reference loader's OmniPBR / OmniGlass descriptions (gltfloader.cpp:304-406).  New here: emissiveFactor times the
+    KHR_materials_emissive_strength extension's emissiveStrength, when not zero, becomes OmniPBR's enable_emission / emissive_color /
+    emissive_intensity (a zero factor leaves the description as the reference writes it).  emissiveTexture is not read: out of scope."""
     images, textures = doc.get("images", []), doc.get("textures", [])
 
     def tex_uri(info):
@@ -196,6 +202,11 @@ def _load_materials(doc, sc):
                 uri = tex_uri(info)
                 if uri is not None:
                     params.append({"name": key, "type": "texture", "value": uri})
+            ef = [float(v) for v in m.get("emissiveFactor", (0.0, 0.0, 0.0))]
+            strength = float(m.get("extensions", {}).get("KHR_materials_emissive_strength", {}).get("emissiveStrength", 1.0))
+            if any(v * strength != 0.0 for v in ef):
+                params += [{"name": "enable_emission", "type": "bool", "value": True}, {"name": "emissive_color", "type": "float3", "value": ef},
+                           {"name": "emissive_intensity", "type": "float", "value": strength}]
             sc.material_descriptions.append({"file": "OmniPBR.mdl", "name": "OmniPBR", "params": params})
         else:
             sc.material_descriptions.append({"file": "OmniGlass.mdl", "name": "OmniGlass", "params": [

@@ -188,24 +188,31 @@ class Scene:
 
     # -- scene.cpp:89-95.  `material` is a dict of the fixed-layout argument block (skh_material)
     def addMaterial(self, type=MAT_DIFFUSE, base_color=(0.8, 0.8, 0.8), roughness=None, metallic=0.0, specular=0.5, ior=1.5,
-                    base_color_texture=0, normal_texture=0, reserved=(0.0,) * 6):
-        """MAT_GLASS: `roughness` is OmniGlass' frosting_roughness (default 0 = clear glass: gltfloader.cpp:354-406 sets it from the
+                    base_color_texture=0, normal_texture=0, reserved=(0.0,) * 6, emission=None):
+        """`emission`: linear RGB radiance Le the material's mesh surfaces emit from their front side (None = none; include/strelka_hip.h, skh_set_emission).
+        MAT_GLASS: `roughness` is OmniGlass' frosting_roughness (default 0 = clear glass: gltfloader.cpp:354-406 sets it from the
         file's roughnessFactor, OmniGlass.mdl's own default is clear).  Other types: default 0.5.  MAT_HAIR: use addHairMaterial."""
         if roughness is None:
             roughness = 0.0 if type == MAT_GLASS else 0.5
         self.mMaterials.append((type, tuple(base_color), roughness, metallic, specular, ior, base_color_texture, normal_texture,
                                 tuple(reserved)))
+        if emission is not None and any(float(v) != 0.0 for v in emission):
+            e = tuple(float(v) for v in emission)
+            if len(e) != 3 or not all(math.isfinite(v) and v >= 0.0 for v in e):
+                raise ValueError("emission must be three finite values >= 0")
+            self.__dict__.setdefault("mEmission", {})[len(self.mMaterials) - 1] = e  # (kept beside the list: its tuples are the argument blocks)
         return len(self.mMaterials) - 1
 
     def addHairMaterial(self, color=(0.35, 0.2, 0.1), roughness_r=0.3, roughness_n=0.3, roughness_tt=0.0, roughness_trt=0.0,
-                        cuticle_angle=math.radians(2.0), ior=1.55, absorption=None, diffuse_weight=0.0, diffuse_tint=(1.0, 1.0, 1.0)):
+                        cuticle_angle=math.radians(2.0), ior=1.55, absorption=None, diffuse_weight=0.0, diffuse_tint=(1.0, 1.0, 1.0),
+                        emission=None):
         """The arguments of df::chiang_hair_bsdf in the fixed-layout block (include/strelka_hip.h, SKH_MAT_HAIR).  `color` is the
         fibre's multiple-scattering albedo; the absorption coefficient follows from it by Chiang et al. 2016, eq. 9 -- what a hair
         material's MDL code does in front of the distribution function -- unless `absorption` gives sigma_a directly."""
         if absorption is None:
             absorption = hair_sigma_a_from_color(color, roughness_n)
         return self.addMaterial(MAT_HAIR, diffuse_tint, roughness=roughness_r, metallic=roughness_tt, specular=roughness_trt, ior=ior,
-                                reserved=(absorption[0], absorption[1], absorption[2], roughness_n, cuticle_angle, diffuse_weight))
+                                reserved=(absorption[0], absorption[1], absorption[2], roughness_n, cuticle_angle, diffuse_weight), emission=emission)
 
     def addTexture(self, rgba8):
         """RGBA8 image, rows top to bottom as stbi_load returns them (OptixRender.cpp:1191-1264).  Returns the texture ID
@@ -401,6 +408,11 @@ class Scene:
         }
         if getattr(self, "mEnvironment", None) is not None:  # (only then: a scene without one has the keys it always had)
             out["environment"] = self.mEnvironment
+        if getattr(self, "mEmission", None):  # (likewise only when some material emits; the CPU oracle does not read it)
+            em = np.zeros((len(mats), 3), np.float32)
+            for i, e in self.mEmission.items():
+                em[i] = e
+            out["emission"] = em
         return out
 
 

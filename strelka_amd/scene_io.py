@@ -163,6 +163,9 @@ def load_scene(path):
         arrays["textures"].append(texels[int(d["offset"]):int(d["offset"]) + n].view(np.uint8).reshape(int(d["height"]), int(d["width"]), 4).copy())
     if len(arrays["materials"]) == 0:
         arrays["materials"] = materials_from_descriptions(descs or [])
+        em = emission_from_descriptions(descs or [])  # (the format is unchanged: emission travels as material parameters)
+        if em is not None:
+            arrays["emission"] = em
     if not cameras:
         cameras.append(S.Camera())
     validate(arrays)
@@ -256,6 +259,29 @@ def material_from_description(desc):
         m["type"] = S.MAT_DIFFUSE
         m["base_color"] = _param(desc, "diffuse_color", (0.8, 0.8, 0.8))
     return m
+
+
+def emission_from_description(desc):
+    """The radiance Le (linear RGB, three floats) the description's surfaces emit -- skh_set_emission's entry for the material; (0, 0, 0) = none.
+    UsdPreviewSurface: emissiveColor.  OmniPBR: enable_emission ? emissive_color * emissive_intensity : 0 (the defaults of absent parameters: the
+    white colour and intensity 1 a glTF factor is written with here, strelka_amd/gltf.py).  Other materials do not emit."""
+    low = ((desc.get("name") or "") + " " + (desc.get("file") or "")).lower()
+    pnames = {p.get("name") for p in desc.get("params", [])}
+    if pnames & {"diffuseColor", "useSpecularWorkflow", "specularColor", "clearcoat", "emissiveColor"}:
+        e = np.asarray(_param(desc, "emissiveColor", (0.0, 0.0, 0.0)), np.float32)
+    elif "glass" not in low and "pbr" in low and _param(desc, "enable_emission", False):
+        e = np.asarray(_param(desc, "emissive_color", (1.0, 1.0, 1.0)), np.float32) * np.float32(_param(desc, "emissive_intensity", 1.0))
+    else:
+        e = np.zeros(3, np.float32)
+    return np.maximum(e.reshape(3), np.float32(0.0))  # (a negative value does not emit)
+
+
+def emission_from_descriptions(descs):
+    """(n, 3) float32 for skh_set_emission, or None when no description emits"""
+    em = np.zeros((max(1, len(descs)), 3), np.float32)
+    for k, d in enumerate(descs):
+        em[k] = emission_from_description(d)
+    return em if em.any() else None
 
 
 def materials_from_descriptions(descs):

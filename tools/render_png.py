@@ -1,5 +1,6 @@
 """Renders one of the stand-in scenes on the GPU and writes a tonemapped PNG (usage: render_png.py kitchen|cornell|hair W H spp depth [exposure_scale] [out.png] [--env FILE.hdr [--env-rotate DEG]]:
---env lights the scene with a lat-long Radiance map as its dome light, --env-rotate turns the dome about +Y)."""
+--env lights the scene with a lat-long Radiance map as its dome light, --env-rotate turns the dome about +Y).  A scene whose materials emit
+(Scene.addMaterial(emission=...), a glTF emissiveFactor) needs no flag: its arrays carry "emission" and Context.set_scene forwards it."""
 import sys, numpy as np
 sys.path.insert(0, ".")
 import math
