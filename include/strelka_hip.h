@@ -135,7 +135,8 @@ typedef struct skh_material
     float ior;
     /* Texture ids (1-based index into skh_set_textures' list, 0 = none -- MDL numbers its resources from 1, 0 being the
      * invalid texture: texture_support_cuda.h:300-304).  OmniPBR "diffuse_texture" / "normalmap_texture"
-     * (gltfloader.cpp:336-350): a valid diffuse texture replaces base_color, a valid normal map perturbs state.normal. */
+     * (gltfloader.cpp:336-350): a valid diffuse texture replaces base_color, a valid normal map perturbs state.normal.
+     * Roughness, metallic and emission maps travel beside this record: skh_set_material_textures. */
     uint32_t base_color_texture;
     uint32_t normal_texture;
     float reserved[6];
@@ -316,10 +317,41 @@ skh_status skh_get_emitter_info(skh_context* ctx, skh_emitter_info* out);
 /* The device functions k_shade calls, on host arrays of packed 32-bit words (n records):
  *   SKH_EMIT_PROBE_SAMPLE  in  f32 u' (the selection draw), ux, uy, P[3] (the shaded point)
  *                          out f32 point[3], normal[3], Le[3], pdf per solid angle (without the pick's 1 / entries), dist, u32 instance, prim
+ *                          (Le at the sampled point: times the emission map's texel when skh_set_material_textures bound one; this kind then needs the build's shading records)
  *   SKH_EMIT_PROBE_PDF     in  u32 instance, prim, f32 hitPoint[3], origin[3]      out f32 pdf, Le[3]   (0s for a triangle that is not in the table) */
 #define SKH_EMIT_PROBE_SAMPLE 0u
 #define SKH_EMIT_PROBE_PDF 1u
 skh_status skh_emitter_probe(skh_context* ctx, uint32_t kind, const void* in, uint32_t n, void* out);
+
+/* ---- Material textures: roughness, metallic / ORM and emission maps (DESIGN.md section 2 "Material textures") ----
+ * What OmniPBR's reflectionroughness_texture, metallic_texture, ORM_texture, emissive_color_texture and emissive_mask_texture and glTF's metallicRoughnessTexture and
+ * emissiveTexture do, as one table beside the material list.  The look-up is base colour's: bilinear, wrap, 1.8 fixed-point weights, the raw 8-bit values / 255 with
+ * no sRGB decode, at the hit's interpolated text_coords[0]; triangle hits only.
+ *   roughness, metallic   SKH_MAT_PBR materials: value = clamp01(scale * texel + bias), the product and the sum rounded separately (no fma).  OmniPBR's
+ *                         mix(constant, texel, influence): scale = influence, bias = constant * (1 - influence); glTF's factor * texel: scale = factor, bias = 0.
+ *                         Two slots that name the same texture id share ONE look-up (ORM: roughness = g, metallic = b).
+ *   emission              every material skh_set_emission gave an Le: Le(x) = Le_material * texel (rgb, or one channel for all three), at an emitter hit and at an
+ *                         emitter sample (the uv there from the triangle's vertices at the sample's barycentrics).  The emitter table keeps its material-level weights
+ *                         area * luminance(Le_material) and the pdfs do not change: the estimator stays unbiased, a dark part of a map only wastes picks.  A material
+ *                         whose Le is 0 does not emit, whatever its map.
+ * One entry per material, indexed as the material list; 48 B.  Texture ids as skh_material's: 1-based into skh_set_textures' list, 0 = none, an id beyond the list = none. */
+typedef struct skh_material_textures
+{
+    uint32_t roughness_texture, metallic_texture, emission_texture;
+    uint32_t roughness_channel, metallic_channel; /* 0..3 = r, g, b, a */
+    uint32_t emission_channel; /* 0..3 = that channel for all three, 4 = rgb */
+    float roughness_scale, roughness_bias; /* roughness = clamp01(scale * texel + bias) */
+    float metallic_scale, metallic_bias;
+    uint32_t reserved[2]; /* must be 0 */
+} skh_material_textures;
+/* n_materials <= the material count; materials beyond n bind nothing.  NULL or 0 removes the table: the context then runs the kernels and produces the bits of one that
+ * never had any -- as does a table in which no entry binds a texture that exists.  A channel out of range, a scale or bias that is not finite or a non-zero reserved word
+ * is refused with SKH_INVALID_ARGUMENT and leaves the previous table in place.  Discards sub-frames traced ahead; never touches the acceleration structures or the
+ * emitter table. */
+skh_status skh_set_material_textures(skh_context* ctx, const skh_material_textures* entries, uint32_t n_materials);
+/* The device function k_shade calls for a triangle hit of `material[i]` at uv[2 i], uv[2 i + 1]: out[8 i ...] = base_color[3], roughness, metallic, Le[3] (all of it
+ * after the textures; a context without a table answers with base_color_texture alone). */
+skh_status skh_material_probe(skh_context* ctx, uint32_t n, const uint32_t* material, const float* uv, float* out);
 
 /* ---- createAccelerationStructure (OptixRender.cpp:388-496): per-mesh / per-curve BLAS + one TLAS ---- */
 skh_status skh_build_accel(skh_context* ctx, uint32_t flags);

@@ -204,6 +204,7 @@ void HipRender::uploadMaterials()
     Scene& sc = *mScene;
     std::vector<skh_material> mats;
     std::vector<float> emission; // 3 per material: skh_set_emission, after the materials
+    std::vector<skh_material_textures> mtex; // one per material: skh_set_material_textures, after the materials
 #ifdef SKH_WITH_STRELKA_HEADERS
     // every eTexture parameter becomes one RGBA8 texture (OptixRender.cpp:1346-1377: resolved against resource/searchPath, stbi_load
     // with STBI_rgb_alpha); a file that cannot be read is reported and the material keeps its constant colour (:1195-1199)
@@ -232,6 +233,8 @@ void HipRender::uploadMaterials()
         float le[3];
         skhmat::emission(d, le);
         emission.insert(emission.end(), le, le + 3);
+        // roughness / metallic / ORM / emissive maps: loaded through the same path as diffuse_texture
+        mtex.push_back(skhmat::materialTextures(d, load));
     }
     for (size_t k = 0; k < tex.size(); ++k)
         tex[k].rgba8 = pixels[k].data();
@@ -254,6 +257,9 @@ void HipRender::uploadMaterials()
     // emissive meshes: a lamp shade, a screen (all zeros = none: the context then runs the kernels it always ran)
     const bool emits = std::any_of(emission.begin(), emission.end(), [](float v) { return v > 0.0f; });
     check(skh_set_emission(mCtx, emits ? emission.data() : nullptr, emits ? (uint32_t)(emission.size() / 3) : 0u), "skh_set_emission");
+    // material textures (no entry binds one = none: likewise)
+    const bool maps = std::any_of(mtex.begin(), mtex.end(), [](const skh_material_textures& e) { return e.roughness_texture || e.metallic_texture || e.emission_texture; });
+    check(skh_set_material_textures(mCtx, maps ? mtex.data() : nullptr, maps ? (uint32_t)mtex.size() : 0u), "skh_set_material_textures");
 }
 
 static void environmentRotation(const float* worldToEnv, float out[9])

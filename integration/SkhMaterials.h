@@ -7,6 +7,7 @@
 //   default.mdl::default_material.diffuse_color          (OptixRender.cpp:1090-1097, HdStrelka/RenderPass.cpp:222-245)  -> SKH_MAT_DIFFUSE
 //   OmniPBR.{diffuse_color_constant, reflection_roughness_constant, metallic_constant, diffuse_texture, normalmap_texture}
 //                                                         (sceneloader/gltfloader.cpp:304-352)                            -> SKH_MAT_PBR
+//           its roughness / metallic / ORM / emissive maps                                                               -> skh_material_textures (materialTextures below)
 //   OmniGlass.{glass_color, glass_ior, frosting_roughness} (gltfloader.cpp:354-406)                                      -> SKH_MAT_GLASS
 //   UsdPreviewSurface parameter sets (HdStrelka's eMaterialX descriptions, HdStrelka/Material.cpp:52-150)                -> PBR | GLASS
 //   names containing "hair" (the `hair` sub-expression, materialmanager/mdlPtxCodeGen.cpp:143-155)                       -> SKH_MAT_HAIR
@@ -182,6 +183,65 @@ inline void emission(const Desc& d, float out[3])
     }
     for (int c = 0; c < 3; ++c)
         out[c] = out[c] > 0.0f ? out[c] : 0.0f; // (a negative value, or a NaN, does not emit)
+}
+
+// The description's roughness / metallic / emission maps (skh_set_material_textures' entry for the material) -- the C++ statement of
+// strelka_amd/scene_io.py::material_textures_from_description, OmniPBR only:
+//   reflectionroughness_texture + reflection_roughness_texture_influence (default 0)  -> roughness, channel r, scale = influence,
+//                                                                                         bias = reflection_roughness_constant * (1 - influence)
+//   metallic_texture + metallic_texture_influence                                      -> metallic, likewise
+//   enable_ORM_texture + ORM_texture [ORM_roughness_scale, ORM_metallic_scale]         -> roughness = g, metallic = b of one texture (r, occlusion, is ignored)
+//   enable_emission + emissive_color_texture | emissive_mask_texture                   -> emission, rgb | channel r (the mask only without a colour texture)
+// `textureId(path)` loads the named texture the way the caller loads diffuse_texture and returns its 1-based id (0: not available -> the slot binds nothing).
+template <class Desc, class TextureId>
+inline skh_material_textures materialTextures(const Desc& d, TextureId&& textureId)
+{
+    skh_material_textures e;
+    memset(&e, 0, sizeof(e));
+    e.emission_channel = 4u;
+    e.roughness_scale = e.metallic_scale = 1.0f;
+    std::string low = d.name + " " + d.file;
+    std::transform(low.begin(), low.end(), low.begin(), [](unsigned char c) { return (char)tolower(c); });
+    const bool preview = find(d, "diffuseColor") || find(d, "useSpecularWorkflow") || find(d, "specularColor") || find(d, "clearcoat") ||
+                         find(d, "emissiveColor");
+    if (preview || low.find("glass") != std::string::npos || low.find("pbr") == std::string::npos)
+        return e;
+    auto id = [&](const char* name) -> uint32_t {
+        const std::string path = texturePath(d, name);
+        return path.empty() ? 0u : (uint32_t)textureId(path);
+    };
+    const uint32_t orm = scalar(d, "enable_ORM_texture", 0.0f) != 0.0f ? id("ORM_texture") : 0u;
+    if (orm)
+    {
+        e.roughness_texture = e.metallic_texture = orm;
+        e.roughness_channel = 1u, e.metallic_channel = 2u;
+        e.roughness_scale = scalar(d, "ORM_roughness_scale", 1.0f);
+        e.metallic_scale = scalar(d, "ORM_metallic_scale", 1.0f);
+    }
+    else
+    {
+        const float wr = scalar(d, "reflection_roughness_texture_influence", 0.0f), wm = scalar(d, "metallic_texture_influence", 0.0f);
+        const uint32_t tr = wr != 0.0f ? id("reflectionroughness_texture") : 0u, tm = wm != 0.0f ? id("metallic_texture") : 0u;
+        if (tr)
+        {
+            const float rest = 1.0f - wr;
+            e.roughness_texture = tr, e.roughness_scale = wr, e.roughness_bias = scalar(d, "reflection_roughness_constant", 0.5f) * rest;
+        }
+        if (tm)
+        {
+            const float rest = 1.0f - wm;
+            e.metallic_texture = tm, e.metallic_scale = wm, e.metallic_bias = scalar(d, "metallic_constant", 0.0f) * rest;
+        }
+    }
+    if (scalar(d, "enable_emission", 0.0f) != 0.0f)
+    {
+        const uint32_t col = id("emissive_color_texture"), mask = col ? 0u : id("emissive_mask_texture");
+        if (col)
+            e.emission_texture = col, e.emission_channel = 4u;
+        else if (mask)
+            e.emission_texture = mask, e.emission_channel = 0u;
+    }
+    return e;
 }
 } // namespace skhmat
 } // namespace oka

@@ -28,7 +28,8 @@ SYMBOLS = ["skh_create", "skh_destroy", "skh_last_error", "skh_abi_version", "sk
            "skh_set_option", "skh_get_stats", "skh_reset_stats", "skh_synchronize", "skh_get_stream", "skh_bsdf_probe", "skh_get_device_info", "skh_comm_unique_id", "skh_comm_init",
            "skh_comm_destroy", "skh_gather_tiles", "skh_host_register", "skh_host_unregister", "skh_get_baked", "skh_comm_info", "skh_probe_memory", "skh_unit_probe", "skh_copy_aov", "skh_get_build_info", "skh_refit_accel",
            "skh_update_accel", "skh_set_environment", "skh_set_environment_transform", "skh_get_environment_info",
-           "skh_set_emission", "skh_get_emitter_info", "skh_emitter_probe"]
+           "skh_set_emission", "skh_get_emitter_info", "skh_emitter_probe",
+           "skh_set_material_textures", "skh_material_probe"]
 
 BUILD_INFO = np.dtype([("triangles", np.uint32), ("nodes", np.uint32), ("reinsert_rounds", np.uint32), ("reinsert_moves", np.uint32),
                        ("reinsert_min_size", np.uint32), ("refit", np.uint32), ("cost_before", np.float64), ("cost_after", np.float64),
@@ -92,6 +93,8 @@ def load():
     lib.skh_set_emission.argtypes = [vp, vp, u32]
     lib.skh_get_emitter_info.argtypes = [vp, vp]
     lib.skh_emitter_probe.argtypes = [vp, u32, vp, u32, vp]
+    lib.skh_set_material_textures.argtypes = [vp, vp, u32]
+    lib.skh_material_probe.argtypes = [vp, u32, vp, vp, vp]
     lib.skh_resize.argtypes = [vp, u32, u32]
     lib.skh_set_tiles.argtypes = [vp, u32, vp, u32]
     lib.skh_render_subframe.argtypes = [vp, vp, vp]
@@ -188,6 +191,7 @@ class Context:
         else:
             self.set_environment(env["rgb"], env.get("scale", (1, 1, 1)), env.get("world_to_env"))
         self.set_emission(arr.get("emission"))  # (likewise: a scene without emissive materials removes what a reused context holds)
+        self.set_material_textures(arr.get("material_textures"))  # (likewise)
         if build:
             self.build_accel(flags)
 
@@ -261,6 +265,25 @@ class Context:
             raise ValueError(f"{kind}: records must be (n, {win}) 32-bit words")
         out = np.zeros((rec.shape[0], wout), np.uint32)
         self._ck(self.lib.skh_emitter_probe(self.h, num, _p(rec), rec.shape[0], _p(out)), "skh_emitter_probe")
+        return out
+
+    def set_material_textures(self, table):
+        """skh_set_material_textures: `table` an S.MATERIAL_TEXTURES array, one entry per material (None or empty removes the table)"""
+        if table is None or len(table) == 0:
+            self._ck(self.lib.skh_set_material_textures(self.h, None, 0), "skh_set_material_textures")
+            return
+        t = np.ascontiguousarray(table, S.MATERIAL_TEXTURES).reshape(-1)
+        self._ck(self.lib.skh_set_material_textures(self.h, _p(t), len(t)), "skh_set_material_textures")
+
+    def material_probe(self, material, uv):
+        """skh_material_probe: the device function k_shade calls for a triangle hit of material[i] at uv[i] -> (n, 8) float32:
+        base_color[3], roughness, metallic, Le[3]"""
+        m = np.ascontiguousarray(material, np.uint32).reshape(-1)
+        t = np.ascontiguousarray(uv, np.float32).reshape(-1, 2)
+        if len(m) != len(t):
+            raise ValueError("one uv pair per material id")
+        out = np.zeros((len(m), 8), np.float32)
+        self._ck(self.lib.skh_material_probe(self.h, len(m), _p(m), _p(t), _p(out)), "skh_material_probe")
         return out
 
     def build_accel(self, flags=0):

@@ -119,6 +119,10 @@ struct skh_context
     DevBuf dEmitEntries, dEmitCdf, dEmitGuide, dEmitLe, dEmitInstOffset;
     uint32_t emitCount = 0, emitInstances = 0, emitGuideBits = 0, emitNee = 1;
     double emitSumW = 0.0, emitMsBuild = 0.0;
+    // material textures (skh_set_material_textures): the table as the caller gave it and its device copy.  mtex_active() -- an entry binds a texture that
+    // exists -- selects the k_shade build that carries it.
+    std::vector<skh_material_textures> mtex;
+    DevBuf dMtex;
     // Speculative sub-frame batching for the reference's call pattern (one render() per sub-frame, RenderPass.cpp:441-447): once two
     // consecutive calls continue the same frame (same parameters, subframe_index + 1), the next call traces several sub-frames
     // ahead in ONE wavefront pass and the calls after it only apply their accumulation step to the radiances already in the path

@@ -870,6 +870,141 @@ SKH_DI SurfaceHit fill_curve(const DevScene& sc, const HostInstance& hi, const f
     return s;
 }
 
+// =================================================================================================
+// Material textures -- skh_set_material_textures; DESIGN.md section 2 "Material textures" is the definition.  One 48-byte entry per material beside the
+// material's record: roughness and metallic of SKH_MAT_PBR materials as clamp01(scale * texel + bias) (two roundings), the emitted radiance of every
+// emissive material as Le_material * texel.  The look-up is tex_lookup_rgba8 at text_coords[0], as base colour; triangle hits only.
+// =================================================================================================
+struct MtexEntry // == skh_material_textures
+{
+    uint32_t roughness_texture, metallic_texture, emission_texture;
+    uint32_t roughness_channel, metallic_channel, emission_channel;
+    float roughness_scale, roughness_bias, metallic_scale, metallic_bias;
+    uint32_t reserved[2];
+};
+static_assert(sizeof(MtexEntry) == 48, "skh_material_textures");
+struct MtexP // by-value kernel argument; count == 0: no table
+{
+    const uint4* table; // 3 per material
+    uint32_t count;
+};
+SKH_DI MtexEntry mtex_entry(const MtexP& m, uint32_t mid) // (materials beyond the table bind nothing)
+{
+    MtexEntry e;
+    uint4 a = make_uint4(0u, 0u, 0u, 0u), b = a, c = a;
+    if (mid < m.count)
+    {
+        const uint4* __restrict__ p = m.table + 3 * (size_t)mid;
+        a = p[0], b = p[1], c = p[2];
+    }
+    e.roughness_texture = a.x, e.metallic_texture = a.y, e.emission_texture = a.z, e.roughness_channel = a.w;
+    e.metallic_channel = b.x, e.emission_channel = b.y, e.roughness_scale = __uint_as_float(b.z), e.roughness_bias = __uint_as_float(b.w);
+    e.metallic_scale = __uint_as_float(c.x), e.metallic_bias = __uint_as_float(c.y), e.reserved[0] = c.z, e.reserved[1] = c.w;
+    return e;
+}
+SKH_DI bool mtex_valid(uint32_t id, uint32_t numTextures) // (0 = none, an id beyond the list = none: what base_color_texture does)
+{
+    return id != 0u && id <= numTextures;
+}
+SKH_DI float mtex_channel(const v4& c, uint32_t ch)
+{
+    return ch == 0u ? c.x : (ch == 1u ? c.y : (ch == 2u ? c.z : c.w));
+}
+SKH_DI v3 mtex_emission_texel(const v4& c, uint32_t ch) // 4 = rgb, 0..3 = that channel for all three
+{
+    if (ch >= 4u)
+        return mk3(c.x, c.y, c.z);
+    const float t = mtex_channel(c, ch);
+    return mk3(t, t, t);
+}
+// does a triangle hit of this material look anything up through the table?  (`emits`: the material has an Le > 0)
+SKH_DI bool mtex_wanted(const Material& mat, const MtexEntry& e, uint32_t numTextures, bool emits)
+{
+    return (mat.type == 1u && (mtex_valid(e.roughness_texture, numTextures) || mtex_valid(e.metallic_texture, numTextures))) ||
+           (emits && mtex_valid(e.emission_texture, numTextures));
+}
+// mdlcode_init's texture reads for a triangle hit at (u, v), the normal map apart: base colour (every material type), roughness / metallic (SKH_MAT_PBR),
+// Le (materials that emit).  One look-up serves roughness and metallic when they name the same texture.  k_shade<..., MTEX = true> and skh_material_probe
+// are this one function.
+SKH_DI void resolve_material(const uint32_t* __restrict__ texels, const uint4* __restrict__ texDesc, uint32_t numTextures, Material& mat, const MtexEntry& e,
+                             v3& Le, float u, float v)
+{
+    if (mtex_valid(mat.base_color_texture, numTextures))
+    {
+        const v4 c = tex_lookup_rgba8(texels, texDesc[mat.base_color_texture - 1u], u, v);
+        mat.base_color[0] = c.x, mat.base_color[1] = c.y, mat.base_color[2] = c.z;
+    }
+    if (mat.type == 1u)
+    {
+        const bool useR = mtex_valid(e.roughness_texture, numTextures), useM = mtex_valid(e.metallic_texture, numTextures);
+        v4 cr = mk4(0.0f, 0.0f, 0.0f, 0.0f);
+        if (useR)
+        {
+            cr = tex_lookup_rgba8(texels, texDesc[e.roughness_texture - 1u], u, v);
+            mat.roughness = saturatef(e.roughness_scale * mtex_channel(cr, e.roughness_channel) + e.roughness_bias);
+        }
+        if (useM)
+        {
+            const v4 cm = (useR && e.metallic_texture == e.roughness_texture) ? cr : tex_lookup_rgba8(texels, texDesc[e.metallic_texture - 1u], u, v);
+            mat.metallic = saturatef(e.metallic_scale * mtex_channel(cm, e.metallic_channel) + e.metallic_bias);
+        }
+    }
+    if (mtex_valid(e.emission_texture, numTextures) && (Le.x > 0.0f || Le.y > 0.0f || Le.z > 0.0f))
+        Le = Le * mtex_emission_texel(tex_lookup_rgba8(texels, texDesc[e.emission_texture - 1u], u, v), e.emission_channel);
+}
+// the emission map's texel at an emitter sample: the uv from the triangle's shading record through the entry's ids, at emit_sample's barycentrics
+// (1 - sqrt(ux), sqrt(ux) (1 - uy), sqrt(ux) uy).  (1, 1, 1) for a material without a map.
+SKH_DI v3 emit_sample_texel(const MtexP& m, const DevScene& sc, uint32_t instance, uint32_t prim, float ux, float uy)
+{
+    const HostInstance* __restrict__ hi = sc.instances + instance;
+    const uint32_t mid0 = hi->material == 0xffffffffu ? 0u : hi->material, mid = mid0 < sc.numMaterials ? mid0 : 0u;
+    const MtexEntry e = mtex_entry(m, mid);
+    if (!mtex_valid(e.emission_texture, sc.numTextures))
+        return mk3(1.0f);
+    const float4* __restrict__ tp = sc.shadeTris + 6 * (size_t)(hi->light + prim);
+    const float4 t3 = tp[3], t4 = tp[4];
+    float u0, v0, u1, v1, u2, v2;
+    unpack_uv(__float_as_uint(t3.w), u0, v0);
+    unpack_uv(__float_as_uint(t4.x), u1, v1);
+    unpack_uv(__float_as_uint(t4.y), u2, v2);
+    const float su = sqrtf(ux);
+    const float b0 = 1.0f - su, b1 = su * (1.0f - uy), b2 = su * uy;
+    return mtex_emission_texel(tex_lookup_rgba8(sc.texels, sc.texDesc[e.emission_texture - 1u], (u0 * b0 + u1 * b1) + u2 * b2, (v0 * b0 + v1 * b1) + v2 * b2),
+                               e.emission_channel);
+}
+// skh_material_probe: resolve_material for n (material, uv) pairs -> base_color[3], roughness, metallic, Le[3]
+__global__ void __launch_bounds__(256) k_material_probe(MtexP mt, const Material* __restrict__ materials, uint32_t numMaterials, const float4* __restrict__ Le,
+                                                        const uint32_t* __restrict__ texels, const uint4* __restrict__ texDesc, uint32_t numTextures,
+                                                        const uint32_t* __restrict__ material, const float* __restrict__ uv, uint32_t n, float* __restrict__ out)
+{
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n)
+        return;
+    const uint32_t mid0 = material[i] == 0xffffffffu ? 0u : material[i], mid = mid0 < numMaterials ? mid0 : 0u;
+    Material mat = materials[mid];
+    const float4 l = Le[mid];
+    v3 le = mk3(l.x, l.y, l.z);
+    resolve_material(texels, texDesc, numTextures, mat, mtex_entry(mt, mid), le, uv[2 * (size_t)i], uv[2 * (size_t)i + 1]);
+    float* o = out + 8 * (size_t)i;
+    o[0] = mat.base_color[0], o[1] = mat.base_color[1], o[2] = mat.base_color[2], o[3] = mat.roughness, o[4] = mat.metallic;
+    o[5] = le.x, o[6] = le.y, o[7] = le.z;
+}
+// SKH_EMIT_PROBE_SAMPLE of a context with material textures: k_emit_probe's record, Le times the emission map's texel at the sampled point
+__global__ void __launch_bounds__(256) k_emit_probe_mtex(EmitP em, MtexP mt, DevScene sc, const float* __restrict__ in, uint32_t n, uint32_t* __restrict__ out)
+{
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n)
+        return;
+    const float* q = in + 6 * (size_t)i;
+    const EmitSample s = emit_sample(em, q[0], q[1], q[2], mk3(q[3], q[4], q[5]));
+    const v3 Le = s.Le * emit_sample_texel(mt, sc, s.instance, s.prim, q[1], q[2]);
+    uint32_t* o = out + 13 * (size_t)i;
+    o[0] = __float_as_uint(s.point.x), o[1] = __float_as_uint(s.point.y), o[2] = __float_as_uint(s.point.z);
+    o[3] = __float_as_uint(s.normal.x), o[4] = __float_as_uint(s.normal.y), o[5] = __float_as_uint(s.normal.z);
+    o[6] = __float_as_uint(Le.x), o[7] = __float_as_uint(Le.y), o[8] = __float_as_uint(Le.z);
+    o[9] = __float_as_uint(s.pdf), o[10] = __float_as_uint(s.dist), o[11] = s.instance, o[12] = s.prim;
+}
+
 // ------------------------------------------------------------------------------------------------------------
 // k_shade: __miss__ms (OptixRender.cu:250-257), __closesthit__light (:315-341), __closesthit__radiance
 // (closest_hit.cu:456-606) and the tail of the raygen bounce loop (OptixRender.cu:131-153) for one bounce.
@@ -888,11 +1023,13 @@ SKH_DI SurfaceHit fill_curve(const DevScene& sc, const HostInstance& hi, const f
 // kernel of before the environment existed, instruction for instruction (tools/kernel_resources.sh: same registers, no scratch).
 // EMIT: the build with emissive meshes in it (launched when the emitter table has sum w > 0: skh_set_emission).  EMIT = false never reads `emit`: the four
 // builds without it are the kernels they were (profiles/: tools/kernel_resources.sh before and after).
-template <bool HAIR, bool ENV, bool EMIT>
+// MTEX: the build with material textures in it (launched when an entry of skh_set_material_textures' table binds a texture that exists).  MTEX = false never
+// reads `mtex`: the eight builds without it are the kernels they were (profiles/mtex_kernel_resources*.txt).
+template <bool HAIR, bool ENV, bool EMIT, bool MTEX>
 __global__ void __launch_bounds__(SKH_SHADE_BLOCK) SKH_SHADE_ATTR(HAIR)
     k_shade(DevScene sc, FrameP fp, uint32_t sampleOffset, uint32_t depth /* bounce index */, const uint32_t* __restrict__ tileXY, RayQ rq,
             const uint32_t* __restrict__ countPtr, HitQ hq, PathS ps, RayQ nextQ, uint32_t* __restrict__ nextCount, RayQ shadowQ,
-            float4* __restrict__ contrib, uint32_t* __restrict__ shadowCount, EnvP env, EmitP emit)
+            float4* __restrict__ contrib, uint32_t* __restrict__ shadowCount, EnvP env, EmitP emit, MtexP mtex)
 {
     // entries of the light pick: the lights, behind them the environment when it is sampled (option env_nee), behind that the emitter set (option emit_nee)
     const uint32_t numPick = (ENV ? sc.numLights + (env.nee ? 1u : 0u) : sc.numLights) + (EMIT ? (emit.nee ? 1u : 0u) : 0u);
@@ -1076,6 +1213,9 @@ __global__ void __launch_bounds__(SKH_SHADE_BLOCK) SKH_SHADE_ATTR(HAIR)
                 float4 matLe = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
                 if constexpr (EMIT) // (beside the material's record: one round trip for both)
                     matLe = emit.Le[mid < emit.numMaterials ? mid : 0u];
+                MtexEntry mte;
+                if constexpr (MTEX) // (likewise)
+                    mte = mtex_entry(mtex, mid < sc.numMaterials ? mid : 0u);
 #if SKH_MATERIALS_LDS
                 const uint32_t midc = mid < sc.numMaterials ? mid : 0u;
                 Material mat;
@@ -1109,7 +1249,10 @@ __global__ void __launch_bounds__(SKH_SHADE_BLOCK) SKH_SHADE_ATTR(HAIR)
                 // normalize(tu x + tv y + n z), (x, y, z) = 2 rgb - 1 (base::tangent_space_normal_texture, factor 1)
                 const bool useBase = mat.base_color_texture != 0u && mat.base_color_texture <= sc.numTextures;
                 const bool useNormal = mat.normal_texture != 0u && mat.normal_texture <= sc.numTextures;
-                const bool textured = hi.type != 2 && (useBase || useNormal);
+                bool mtexWanted = false;
+                if constexpr (MTEX)
+                    mtexWanted = mtex_wanted(mat, mte, sc.numTextures, matLe.w > 0.0f);
+                const bool textured = hi.type != 2 && (useBase || useNormal || mtexWanted);
                 SurfaceTex st;
                 v3 stT = mk3(0.0f);
                 // (a hair material on a triangle mesh reads state.tangent_u too: the vertex tangent, closest_hit.cu:399-400)
@@ -1120,7 +1263,14 @@ __global__ void __launch_bounds__(SKH_SHADE_BLOCK) SKH_SHADE_ATTR(HAIR)
                     stT = st.tangent_u;
                 if (textured)
                 {
-                    if (useBase)
+                    if constexpr (MTEX)
+                    {
+                        // base colour, roughness / metallic, Le: skh_material_probe's function
+                        v3 Le = mk3(matLe.x, matLe.y, matLe.z);
+                        resolve_material(sc.texels, sc.texDesc, sc.numTextures, mat, mte, Le, st.u, st.v);
+                        matLe.x = Le.x, matLe.y = Le.y, matLe.z = Le.z; // (.w stays the material's luminance: the pdf is the table's)
+                    }
+                    else if (useBase)
                     {
                         const v4 c = tex_lookup_rgba8(sc.texels, sc.texDesc[mat.base_color_texture - 1u], st.u, st.v);
                         mat.base_color[0] = c.x, mat.base_color[1] = c.y, mat.base_color[2] = c.z;
@@ -1193,6 +1343,8 @@ __global__ void __launch_bounds__(SKH_SHADE_BLOCK) SKH_SHADE_ATTR(HAIR)
                                         distToLight = es.dist * (1.0f - SKH_EMIT_SHADOW_MARGIN); // (ends short of the emitter itself: skh_device.h)
                                         lightPdf = es.pdf;
                                         lrad = es.Le; // (no second cosine, as for the environment: bsdf_evaluate carries the surface's)
+                                        if constexpr (MTEX)
+                                            lrad = lrad * emit_sample_texel(mtex, sc, es.instance, es.prim, ux, uy);
                                     }
                                     lightPdf *= lightSelectionPdf;
                                     return;

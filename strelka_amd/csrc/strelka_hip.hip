@@ -749,6 +749,102 @@ static DevScene make_dev_scene(const skh_context* c)
     return sc;
 }
 
+// ---- material textures: skh_set_material_textures ----
+// an entry binds a texture that exists: the k_shade builds with MTEX in them run (anything else -- no table, all ids 0 or beyond the list -- runs the others)
+static bool mtex_active(const skh_context* c)
+{
+    for (const skh_material_textures& e : c->mtex)
+        for (uint32_t id : { e.roughness_texture, e.metallic_texture, e.emission_texture })
+            if (id != 0u && id <= c->nTextures)
+                return true;
+    return false;
+}
+
+static MtexP make_mtex(const skh_context* c)
+{
+    MtexP m;
+    m.table = nullptr, m.count = 0;
+    if (mtex_active(c))
+        m.table = c->dMtex.as<uint4>(), m.count = (uint32_t)c->mtex.size();
+    return m;
+}
+
+skh_status skh_set_material_textures(skh_context* c, const skh_material_textures* entries, uint32_t n)
+{
+    if (!c)
+        return SKH_INVALID_ARGUMENT;
+    (void)hipSetDevice(c->device);
+    if (!entries || n == 0)
+    {
+        // remove: a no-op on a context that has none (nothing traced ahead is thrown away for it)
+        if (c->mtex.empty())
+            return SKH_OK;
+        spec_drop(c);
+        SKH_TRY(c, hipStreamSynchronize(c->stream));
+        c->mtex.clear();
+        dev_free(c->dMtex);
+        return SKH_OK;
+    }
+    if (n > c->nMaterials)
+    {
+        c->err = "skh_set_material_textures: " + std::to_string(n) + " entries for " + std::to_string(c->nMaterials) + " materials (call skh_set_materials first)";
+        return SKH_INVALID_ARGUMENT;
+    }
+    for (uint32_t k = 0; k < n; ++k)
+    {
+        const skh_material_textures& e = entries[k];
+        if (e.roughness_channel > 3u || e.metallic_channel > 3u || e.emission_channel > 4u || !std::isfinite(e.roughness_scale) || !std::isfinite(e.roughness_bias) ||
+            !std::isfinite(e.metallic_scale) || !std::isfinite(e.metallic_bias) || e.reserved[0] != 0u || e.reserved[1] != 0u)
+        {
+            c->err = "skh_set_material_textures: entry " + std::to_string(k) + ": a channel out of range (0..3, emission 0..4), a scale or bias that is not finite, or a non-zero reserved word";
+            return SKH_INVALID_ARGUMENT;
+        }
+    }
+    spec_drop(c);
+    static_assert(sizeof(skh_material_textures) == 48 && sizeof(skh_material_textures) == sizeof(MtexEntry), "skh_material_textures");
+    SKH_TRY(c, hipStreamSynchronize(c->stream)); // (the table is about to be replaced)
+    DevBuf d;
+    SKH_CHECK(dev_upload(c, d, entries, sizeof(skh_material_textures) * (size_t)n));
+    c->dMtex = std::move(d);
+    c->mtex.assign(entries, entries + n);
+    return SKH_OK;
+}
+
+skh_status skh_material_probe(skh_context* c, uint32_t n, const uint32_t* material, const float* uv, float* out)
+{
+    if (!c)
+        return SKH_INVALID_ARGUMENT;
+    if (n && (!material || !uv || !out))
+    {
+        c->err = "skh_material_probe: a missing input / output pointer";
+        return SKH_INVALID_ARGUMENT;
+    }
+    if (c->nMaterials == 0)
+    {
+        c->err = "skh_material_probe: the context has no materials (call skh_set_materials first)";
+        return SKH_INVALID_ARGUMENT;
+    }
+    if (n == 0)
+        return SKH_OK;
+    (void)hipSetDevice(c->device);
+    std::vector<float> le(4 * (size_t)c->nMaterials, 0.0f); // (materials beyond the emission list do not emit)
+    for (uint32_t m = 0; m < c->nMaterials && 3 * (size_t)m + 2 < c->emission.size(); ++m)
+        memcpy(&le[4 * (size_t)m], &c->emission[3 * (size_t)m], 3 * sizeof(float));
+    DevBuf dLe, dMat, dUv, dOut;
+    SKH_CHECK(dev_upload(c, dLe, le.data(), le.size() * sizeof(float)));
+    SKH_CHECK(dev_upload(c, dMat, material, sizeof(uint32_t) * (size_t)n));
+    SKH_CHECK(dev_upload(c, dUv, uv, 2 * sizeof(float) * (size_t)n));
+    SKH_CHECK(dev_alloc(c, dOut, 8 * sizeof(float) * (size_t)n));
+    k_material_probe<<<(n + 255) / 256, 256, 0, c->stream>>>(make_mtex(c), c->dMaterials.as<Material>(), c->nMaterials, dLe.as<float4>(), c->dTexels.as<uint32_t>(),
+                                                             c->dTexDesc.as<uint4>(), c->nTextures, dMat.as<uint32_t>(), dUv.as<float>(), n, dOut.as<float>());
+    SKH_TRY(c, hipGetLastError());
+    SKH_TRY(c, hipStreamSynchronize(c->stream));
+    SKH_TRY(c, hipMemcpy(out, dOut.p, 8 * sizeof(float) * (size_t)n, hipMemcpyDeviceToHost));
+    return SKH_OK;
+}
+
+static skh_status ensure_ready(skh_context* c);
+
 // ---- emissive meshes: skh_set_emission, the emitter table (skh_emit.h) ----
 static void emit_clear(skh_context* c)
 {
@@ -946,7 +1042,14 @@ skh_status skh_emitter_probe(skh_context* c, uint32_t kind, const void* in, uint
     DevBuf di, dout;
     SKH_CHECK(dev_upload(c, di, in, inBytes * n));
     SKH_CHECK(dev_alloc(c, dout, outBytes * n));
-    k_emit_probe<<<(n + 255) / 256, 256, 0, c->stream>>>(make_emit(c), (uint32_t)c->instances.size(), kind, di.as<uint32_t>(), n, dout.as<uint32_t>());
+    if (kind == SKH_EMIT_PROBE_SAMPLE && mtex_active(c))
+    {
+        // (Le at the sampled point carries the emission map: the uv comes from the shading records, which the build makes)
+        SKH_CHECK(ensure_ready(c));
+        k_emit_probe_mtex<<<(n + 255) / 256, 256, 0, c->stream>>>(make_emit(c), make_mtex(c), make_dev_scene(c), di.as<float>(), n, dout.as<uint32_t>());
+    }
+    else
+        k_emit_probe<<<(n + 255) / 256, 256, 0, c->stream>>>(make_emit(c), (uint32_t)c->instances.size(), kind, di.as<uint32_t>(), n, dout.as<uint32_t>());
     SKH_TRY(c, hipGetLastError());
     SKH_TRY(c, hipStreamSynchronize(c->stream));
     SKH_TRY(c, hipMemcpy(out, dout.p, outBytes * n, hipMemcpyDeviceToHost));
@@ -1075,6 +1178,7 @@ static skh_status render_one(skh_context* c, const skh_frame_params* p, uint32_t
     const DevScene sc = make_dev_scene(c);
     const EnvP envp = make_env(c);
     const EmitP emitp = make_emit(c);
+    const MtexP mtexp = make_mtex(c);
     const uint32_t N = c->numSlots * c->batchCapacity; // plane stride of the path-state buffer
     const uint32_t NQ = SKH_SHARDS * c->queueRegion; // plane stride of every queue (rays, hits, shadow contributions)
     const uint32_t NP = c->numSlots * batch; // paths in this pass
@@ -1165,15 +1269,24 @@ static skh_status render_one(skh_context* c, const skh_frame_params* p, uint32_t
                 // workgroup b on shard b & 7; those past the end of their shard leave at once
                 const uint32_t perShard = (((NP + SKH_SHARDS - 1u) / SKH_SHARDS) + 63u) & ~63u;
                 const dim3 sg(SKH_SHARDS * ((perShard + SKH_SHADE_BLOCK - 1) / SKH_SHADE_BLOCK));
-#define SKH_SHADE_LAUNCH(HAIRB, ENVB, EMITB)                                                                                                                      \
-    k_shade<HAIRB, ENVB, EMITB><<<sg, SKH_SHADE_BLOCK, 0, st>>>(sc, fp, s, b, tiles, rq[b & 1], counts + 2 * b * QW, hq, ps, rq[(b + 1) & 1], counts + 2 * (b + 1) * QW, \
-                                                                shq, c->dContrib.as<float4>(), counts + (2 * b + 1) * QW, envp, emitp)
-#define SKH_SHADE_LAUNCH_EMIT(HAIRB, ENVB) \
-    if (emitp.count)                       \
-        SKH_SHADE_LAUNCH(HAIRB, ENVB, true); \
-    else                                   \
-        SKH_SHADE_LAUNCH(HAIRB, ENVB, false)
-                // (a context without an environment and without emitters launches the builds it always launched)
+#define SKH_SHADE_LAUNCH_MTEX(HAIRB, ENVB, EMITB, MTEXB)                                                                                                                  \
+    k_shade<HAIRB, ENVB, EMITB, MTEXB><<<sg, SKH_SHADE_BLOCK, 0, st>>>(sc, fp, s, b, tiles, rq[b & 1], counts + 2 * b * QW, hq, ps, rq[(b + 1) & 1], counts + 2 * (b + 1) * QW, \
+                                                                       shq, c->dContrib.as<float4>(), counts + (2 * b + 1) * QW, envp, emitp, mtexp)
+#define SKH_SHADE_LAUNCH(HAIRB, ENVB, EMITB)             \
+    if (mtexp.count)                                     \
+        SKH_SHADE_LAUNCH_MTEX(HAIRB, ENVB, EMITB, true); \
+    else                                                 \
+        SKH_SHADE_LAUNCH_MTEX(HAIRB, ENVB, EMITB, false)
+#define SKH_SHADE_LAUNCH_EMIT(HAIRB, ENVB)     \
+    if (emitp.count)                           \
+    {                                          \
+        SKH_SHADE_LAUNCH(HAIRB, ENVB, true);   \
+    }                                          \
+    else                                       \
+    {                                          \
+        SKH_SHADE_LAUNCH(HAIRB, ENVB, false);  \
+    }
+                // (a context without an environment, without emitters and without material textures launches the builds it always launched)
                 if (c->hasHairMaterial && c->envW)
                 {
                     SKH_SHADE_LAUNCH_EMIT(true, true);
@@ -1192,6 +1305,7 @@ static skh_status render_one(skh_context* c, const skh_frame_params* p, uint32_t
                 }
 #undef SKH_SHADE_LAUNCH_EMIT
 #undef SKH_SHADE_LAUNCH
+#undef SKH_SHADE_LAUNCH_MTEX
             }
             {
                 hipStream_t sst = useOverlap ? c->stream2 : st;

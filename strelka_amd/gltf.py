@@ -6,7 +6,8 @@ from external files, data: URIs or the GLB binary chunk.  What the reference doe
 * `loadMaterials` (:407-420): alphaMode "OPAQUE" -> OmniPBR {diffuse_color_constant = baseColorFactor.rgb,
   reflection_roughness_constant, metallic_constant; diffuse_texture / normalmap_texture uris} (:304-352), anything else ->
   OmniGlass {enable_opacity, thin_walled = false, frosting_roughness = roughnessFactor} (:354-406).  The scene's material
-  list is model.materials in order; a primitive without a material uses index 0 (:134-138).
+  list is model.materials in order; a primitive without a material uses index 0 (:134-138).  Beyond the reference, opt-in
+  (`load_gltf(path, material_textures=True)`): metallicRoughnessTexture and emissiveTexture of OPAQUE materials.
 * lights: `<model>_light.json` next to the file -> rect lights {position, orientation (Euler degrees), width, height, color,
   intensity} (:597-641); otherwise ONE default distant light: orientation (-45, 15, 0), half angle 5 deg, intensity 100000,
   white (:664-678).
@@ -171,13 +172,19 @@ class GltfScene(S.Scene):
         em = scene_io.emission_from_descriptions(self.material_descriptions)
         if em is not None:
             arr["emission"] = em
+        mt = scene_io.material_textures_from_descriptions(self.material_descriptions, self.texture_ids)
+        if mt is not None:
+            arr["material_textures"] = mt
         return arr
 
 
-def _load_materials(doc, sc):
+def _load_materials(doc, sc, material_textures=False):
     """glTF materials -> the reference loader's OmniPBR / OmniGlass descriptions (gltfloader.cpp:304-406).  New here: emissiveFactor times the
     KHR_materials_emissive_strength extension's emissiveStrength, when not zero, becomes OmniPBR's enable_emission / emissive_color /
-    emissive_intensity (a zero factor leaves the description as the reference writes it).  emissiveTexture is not read: out of scope."""
+    emissive_intensity (a zero factor leaves the description as the reference writes it).  With `material_textures` (the reference's loader
+    reads neither): pbrMetallicRoughness.metallicRoughnessTexture becomes enable_ORM_texture / ORM_texture (glTF's layout is OmniPBR's: roughness
+    in g, metallic in b) with ORM_roughness_scale / ORM_metallic_scale = roughnessFactor / metallicFactor (value = factor * texel, the glTF
+    definition; scene_io.material_textures_from_description), and emissiveTexture, under a non-zero factor, becomes emissive_color_texture."""
     images, textures = doc.get("images", []), doc.get("textures", [])
 
     def tex_uri(info):
@@ -202,11 +209,18 @@ def _load_materials(doc, sc):
                 uri = tex_uri(info)
                 if uri is not None:
                     params.append({"name": key, "type": "texture", "value": uri})
+            orm = tex_uri(pbr.get("metallicRoughnessTexture")) if material_textures else None
+            if orm is not None:
+                params += [{"name": "enable_ORM_texture", "type": "bool", "value": True}, {"name": "ORM_texture", "type": "texture", "value": orm},
+                           {"name": "ORM_roughness_scale", "type": "float", "value": rough}, {"name": "ORM_metallic_scale", "type": "float", "value": metal}]
             ef = [float(v) for v in m.get("emissiveFactor", (0.0, 0.0, 0.0))]
             strength = float(m.get("extensions", {}).get("KHR_materials_emissive_strength", {}).get("emissiveStrength", 1.0))
             if any(v * strength != 0.0 for v in ef):
                 params += [{"name": "enable_emission", "type": "bool", "value": True}, {"name": "emissive_color", "type": "float3", "value": ef},
                            {"name": "emissive_intensity", "type": "float", "value": strength}]
+                etex = tex_uri(m.get("emissiveTexture")) if material_textures else None
+                if etex is not None:
+                    params.append({"name": "emissive_color_texture", "type": "texture", "value": etex})
             sc.material_descriptions.append({"file": "OmniPBR.mdl", "name": "OmniPBR", "params": params})
         else:
             sc.material_descriptions.append({"file": "OmniGlass.mdl", "name": "OmniGlass", "params": [
@@ -325,11 +339,13 @@ def _process_node(doc, buffers, sc, index, base):
         _process_node(doc, buffers, sc, child, glob)
 
 
-def load_gltf(path):
-    """GltfLoader::loadGltf (gltfloader.cpp:643-689).  Returns a Scene (strelka_amd.scene API + material_descriptions)."""
+def load_gltf(path, material_textures=False):
+    """GltfLoader::loadGltf (gltfloader.cpp:643-689).  Returns a Scene (strelka_amd.scene API + material_descriptions).
+    `material_textures`: also read metallicRoughnessTexture and emissiveTexture (_load_materials); off, a file gives the descriptions
+    the reference's loader gives."""
     doc, buffers = _read_model(path)
     sc = GltfScene()
-    _load_materials(doc, sc)
+    _load_materials(doc, sc, material_textures)
     _load_textures(path, sc, doc, buffers)
     _load_lights(path, sc)
     _load_cameras(doc, sc)

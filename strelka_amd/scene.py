@@ -24,6 +24,11 @@ MATERIAL = np.dtype([("type", np.uint32), ("base_color", np.float32, 3), ("rough
                      ("metallic", np.float32), ("specular", np.float32), ("ior", np.float32),
                      ("base_color_texture", np.uint32), ("normal_texture", np.uint32),  # texture ids: 1-based, 0 = none
                      ("reserved", np.float32, 6)])  # 64 B
+MATERIAL_TEXTURES = np.dtype([("roughness_texture", np.uint32), ("metallic_texture", np.uint32), ("emission_texture", np.uint32),
+                              ("roughness_channel", np.uint32), ("metallic_channel", np.uint32), ("emission_channel", np.uint32),
+                              ("roughness_scale", np.float32), ("roughness_bias", np.float32), ("metallic_scale", np.float32),
+                              ("metallic_bias", np.float32), ("reserved", np.uint32, 2)])  # skh_material_textures, 48 B
+EMISSION_RGB = 4  # emission_channel: the texel's rgb (0..3: that channel for all three)
 TEXTURE_DESC = np.dtype([("offset", np.uint32), ("width", np.uint32), ("height", np.uint32), ("pad", np.uint32)])
 FRAME_PARAMS = np.dtype([("view_to_world", np.float32, 16), ("clip_to_view", np.float32, 16),
                          ("subframe_index", np.uint32), ("samples_this_launch", np.uint32), ("spp_total", np.uint32),
@@ -34,6 +39,7 @@ RAY = np.dtype([("origin", np.float32, 3), ("tmin", np.float32), ("dir", np.floa
 HIT = np.dtype([("t", np.float32), ("instance_id", np.uint32), ("prim_id", np.uint32), ("u", np.float32),
                 ("v", np.float32)])
 assert VERTEX.itemsize == 32 and INSTANCE.itemsize == 64 and LIGHT.itemsize == 112
+assert MATERIAL_TEXTURES.itemsize == 48
 assert MATERIAL.itemsize == 64 and FRAME_PARAMS.itemsize == 176 and RAY.itemsize == 32 and HIT.itemsize == 20
 
 INSTANCE_MESH, INSTANCE_LIGHT, INSTANCE_CURVE = 0, 1, 2  # oka::Instance::Type
@@ -188,8 +194,12 @@ class Scene:
 
     # -- scene.cpp:89-95.  `material` is a dict of the fixed-layout argument block (skh_material)
     def addMaterial(self, type=MAT_DIFFUSE, base_color=(0.8, 0.8, 0.8), roughness=None, metallic=0.0, specular=0.5, ior=1.5,
-                    base_color_texture=0, normal_texture=0, reserved=(0.0,) * 6, emission=None):
-        """`emission`: linear RGB radiance Le the material's mesh surfaces emit from their front side (None = none; include/strelka_hip.h, skh_set_emission).
+                    base_color_texture=0, normal_texture=0, reserved=(0.0,) * 6, emission=None,
+                    roughness_texture=0, metallic_texture=0, emission_texture=0, roughness_channel=0, metallic_channel=0,
+                    emission_channel=EMISSION_RGB, roughness_scale=1.0, roughness_bias=0.0, metallic_scale=1.0, metallic_bias=0.0):
+        """`roughness_texture` / `metallic_texture` (MAT_PBR): value = clamp01(scale * texel[channel] + bias); `emission_texture`: Le = emission * texel
+        (rgb, or one channel for all three) -- texture ids as base_color_texture's (include/strelka_hip.h, skh_set_material_textures).
+        `emission`: linear RGB radiance Le the material's mesh surfaces emit from their front side (None = none; include/strelka_hip.h, skh_set_emission).
         MAT_GLASS: `roughness` is OmniGlass' frosting_roughness (default 0 = clear glass: gltfloader.cpp:354-406 sets it from the
         file's roughnessFactor, OmniGlass.mdl's own default is clear).  Other types: default 0.5.  MAT_HAIR: use addHairMaterial."""
         if roughness is None:
@@ -201,6 +211,10 @@ class Scene:
             if len(e) != 3 or not all(math.isfinite(v) and v >= 0.0 for v in e):
                 raise ValueError("emission must be three finite values >= 0")
             self.__dict__.setdefault("mEmission", {})[len(self.mMaterials) - 1] = e  # (kept beside the list: its tuples are the argument blocks)
+        if roughness_texture or metallic_texture or emission_texture:
+            self.__dict__.setdefault("mMaterialTextures", {})[len(self.mMaterials) - 1] = (
+                int(roughness_texture), int(metallic_texture), int(emission_texture), int(roughness_channel), int(metallic_channel), int(emission_channel),
+                float(roughness_scale), float(roughness_bias), float(metallic_scale), float(metallic_bias), (0, 0))
         return len(self.mMaterials) - 1
 
     def addHairMaterial(self, color=(0.35, 0.2, 0.1), roughness_r=0.3, roughness_n=0.3, roughness_tt=0.0, roughness_trt=0.0,
@@ -413,6 +427,13 @@ class Scene:
             for i, e in self.mEmission.items():
                 em[i] = e
             out["emission"] = em
+        if getattr(self, "mMaterialTextures", None):  # (likewise only when some material binds one)
+            mt = np.zeros(len(mats), MATERIAL_TEXTURES)
+            mt["emission_channel"] = EMISSION_RGB
+            mt["roughness_scale"] = mt["metallic_scale"] = 1.0
+            for i, e in self.mMaterialTextures.items():
+                mt[i] = e
+            out["material_textures"] = mt
         return out
 
 

@@ -166,6 +166,9 @@ def load_scene(path):
         em = emission_from_descriptions(descs or [])  # (the format is unchanged: emission travels as material parameters)
         if em is not None:
             arrays["emission"] = em
+    mt = material_textures_from_descriptions(descs or [])  # (likewise; the parameters name TXDS entries, 1-based -- with or without MATL, which has no room for them)
+    if mt is not None and len(mt) <= len(arrays["materials"]):
+        arrays["material_textures"] = mt
     if not cameras:
         cameras.append(S.Camera())
     validate(arrays)
@@ -194,6 +197,9 @@ def validate(arrays):
     for k, m in enumerate(arrays["materials"]):
         if int(m["base_color_texture"]) > nt or int(m["normal_texture"]) > nt:
             raise ValueError(f"material {k} refers to a texture that does not exist")
+    for k, e in enumerate(arrays.get("material_textures", [])):
+        if max(int(e["roughness_texture"]), int(e["metallic_texture"]), int(e["emission_texture"])) > nt:
+            raise ValueError(f"material {k}: a roughness / metallic / emission map refers to a texture that does not exist")
     for k, c in enumerate(arrays["curves"]):
         if (int(c["points_start"]) + int(c["points_count"]) > npts or int(c["widths_start"]) + int(c["widths_count"]) > nw or
                 int(c["vertex_counts_start"]) + int(c["vertex_counts_count"]) > nvc):
@@ -282,6 +288,80 @@ def emission_from_descriptions(descs):
     for k, d in enumerate(descs):
         em[k] = emission_from_description(d)
     return em if em.any() else None
+
+
+def _texture_id(desc, name, texture_ids=None):
+    """a texture parameter's value: the 1-based id into the scene's texture list, or a uri that `texture_ids` maps to one; anything else = none"""
+    v = _param(desc, name, 0)
+    if isinstance(v, str):
+        return int((texture_ids or {}).get(v, 0))
+    return int(v) if isinstance(v, (int, float)) and not isinstance(v, bool) and v > 0 else 0
+
+
+def _is_omnipbr(desc):
+    low = ((desc.get("name") or "") + " " + (desc.get("file") or "")).lower()
+    pnames = {p.get("name") for p in desc.get("params", [])}
+    if pnames & {"diffuseColor", "useSpecularWorkflow", "specularColor", "clearcoat", "emissiveColor"}:
+        return False
+    return "glass" not in low and "pbr" in low  # (material_from_description's OmniPBR branch)
+
+
+def _mix_affine(constant, influence):
+    """OmniPBR's mix(constant, texel, influence) = constant (1 - influence) + texel influence as scale * texel + bias, in float32:
+    scale = influence, bias = fl(constant * fl(1 - influence))"""
+    w = np.float32(influence)
+    return w, np.float32(np.float32(constant) * np.float32(np.float32(1.0) - w))
+
+
+def material_textures_from_description(desc, texture_ids=None):
+    """One MaterialDescription -> one S.MATERIAL_TEXTURES record (skh_set_material_textures' entry).  OmniPBR only; a texture parameter carries a 1-based
+    texture id, or a uri that `texture_ids` (uri -> id, the glTF loader's) resolves; an unresolved one binds nothing.
+      reflectionroughness_texture + reflection_roughness_texture_influence (default 0, OmniPBR.mdl) -> the roughness slot, channel r,
+          scale = influence, bias = reflection_roughness_constant * (1 - influence); an influence of 0 binds nothing (the map has no say)
+      metallic_texture + metallic_texture_influence -> the metallic slot, likewise
+      enable_ORM_texture + ORM_texture -> roughness = g, metallic = b of ONE texture, both influences 1; r (occlusion) is ignored: the
+          renderer has no ambient term it could scale.  Optional ORM_roughness_scale / ORM_metallic_scale (default 1; glTF's
+          roughnessFactor / metallicFactor, strelka_amd/gltf.py) multiply the texel.  ORM wins over the standalone maps, as in OmniPBR.
+      emissive_color_texture -> emission, rgb;  emissive_mask_texture -> emission, channel r, only without a colour texture
+          (both only with enable_emission: emission_from_description gives the Le they scale)
+    A standalone roughness / metallic map is read through channel r: an 8-bit grey image decodes to r = g = b here, so grey maps give
+    MDL's value; for a coloured map MDL's mono look-up averages the three channels and this does not."""
+    e = np.zeros(1, S.MATERIAL_TEXTURES)[0]
+    e["emission_channel"] = S.EMISSION_RGB
+    e["roughness_scale"] = e["metallic_scale"] = 1.0
+    if not _is_omnipbr(desc):
+        return e
+    orm = _texture_id(desc, "ORM_texture", texture_ids) if _param(desc, "enable_ORM_texture", False) else 0
+    if orm:
+        e["roughness_texture"] = e["metallic_texture"] = orm
+        e["roughness_channel"], e["metallic_channel"] = 1, 2
+        e["roughness_scale"] = np.float32(_param(desc, "ORM_roughness_scale", 1.0))
+        e["metallic_scale"] = np.float32(_param(desc, "ORM_metallic_scale", 1.0))
+    else:
+        for slot, tex, infl, const, cdef in (("roughness", "reflectionroughness_texture", "reflection_roughness_texture_influence", "reflection_roughness_constant", 0.5),
+                                             ("metallic", "metallic_texture", "metallic_texture_influence", "metallic_constant", 0.0)):
+            t, w = _texture_id(desc, tex, texture_ids), float(_param(desc, infl, 0.0))
+            if t and w != 0.0:
+                e[slot + "_texture"] = t
+                e[slot + "_scale"], e[slot + "_bias"] = _mix_affine(float(_param(desc, const, cdef)), w)
+    if _param(desc, "enable_emission", False):
+        col, mask = _texture_id(desc, "emissive_color_texture", texture_ids), _texture_id(desc, "emissive_mask_texture", texture_ids)
+        if col:
+            e["emission_texture"], e["emission_channel"] = col, S.EMISSION_RGB
+        elif mask:
+            e["emission_texture"], e["emission_channel"] = mask, 0
+    return e
+
+
+def material_textures_from_descriptions(descs, texture_ids=None):
+    """S.MATERIAL_TEXTURES array for skh_set_material_textures, or None when no description binds a map"""
+    out = np.zeros(max(1, len(descs)), S.MATERIAL_TEXTURES)
+    out["emission_channel"] = S.EMISSION_RGB
+    out["roughness_scale"] = out["metallic_scale"] = 1.0
+    for k, d in enumerate(descs):
+        out[k] = material_textures_from_description(d, texture_ids)
+    any_bound = (out["roughness_texture"] | out["metallic_texture"] | out["emission_texture"]).any()
+    return out if any_bound else None
 
 
 def materials_from_descriptions(descs):

@@ -1,11 +1,12 @@
-"""Renders one of the stand-in scenes on the GPU and writes a tonemapped PNG (usage: render_png.py kitchen|cornell|hair W H spp depth [exposure_scale] [out.png] [--env FILE.hdr [--env-rotate DEG]]:
+"""Renders one of the stand-in scenes, or a glTF file, on the GPU and writes a tonemapped PNG (usage: render_png.py kitchen|cornell|hair|FILE.gltf|FILE.glb W H spp depth [exposure_scale] [out.png] [--env FILE.hdr [--env-rotate DEG]]:
 --env lights the scene with a lat-long Radiance map as its dome light, --env-rotate turns the dome about +Y).  A scene whose materials emit
-(Scene.addMaterial(emission=...), a glTF emissiveFactor) needs no flag: its arrays carry "emission" and Context.set_scene forwards it."""
+(Scene.addMaterial(emission=...), a glTF emissiveFactor) needs no flag: its arrays carry "emission" and Context.set_scene forwards it.  A glTF file is
+loaded with material_textures=True: its metallicRoughnessTexture and emissiveTexture are rendered (arrays()["material_textures"])."""
 import sys, numpy as np
 sys.path.insert(0, ".")
 import math
 import torch
-from strelka_amd import capi, hdr, scene as S, scenes, png
+from strelka_amd import capi, gltf, hdr, scene as S, scenes, png
 env_file = env_deg = None
 for flag in ("--env-rotate", "--env"):
     if flag in sys.argv:
@@ -17,7 +18,10 @@ for flag in ("--env-rotate", "--env"):
         else:
             env_deg = float(val)
 name = sys.argv[1]; W, H, spp, depth = int(sys.argv[2]), int(sys.argv[3]), int(sys.argv[4]), int(sys.argv[5])
-sc = {"kitchen": scenes.kitchen_standin, "cornell": scenes.cornell_box, "hair": scenes.hair_standin}[name]()
+if name.lower().endswith((".gltf", ".glb")):
+    sc, name = gltf.load_gltf(name, material_textures=True), name.replace("/", "_")
+else:
+    sc = {"kitchen": scenes.kitchen_standin, "cornell": scenes.cornell_box, "hair": scenes.hair_standin}[name]()
 if env_file:
     a = math.radians(env_deg or 0.0)  # world -> environment: a turn of the dome by +a about Y is a turn of the directions by -a
     sc.setEnvironment(hdr.load_hdr(env_file), world_to_env=[[math.cos(a), 0, math.sin(a)], [0, 1, 0], [-math.sin(a), 0, math.cos(a)]])
