@@ -353,6 +353,51 @@ skh_status skh_set_material_textures(skh_context* ctx, const skh_material_textur
  * after the textures; a context without a table answers with base_color_texture alone). */
 skh_status skh_material_probe(skh_context* ctx, uint32_t n, const uint32_t* material, const float* uv, float* out);
 
+/* ---- Cutouts: opacity maps tested between trace and shade (DESIGN.md section 2 "Cutouts") ----
+ * What glTF's alphaMode MASK / alphaCutoff, OmniPBR's enable_opacity / opacity_texture / opacity_threshold and UsdPreviewSurface's opacityThreshold do: a hit whose
+ * opacity is below the threshold is no hit, for radiance rays and for shadow rays.  It changes which hit a ray has, so it sits at the traversal level -- not inside the
+ * trace kernels: a stage of its own (k_cutout) looks at the hit records of a trace launch and re-queues the rays whose hit is cut away.
+ * One entry per material, indexed as the material list is; 32 B.
+ *   look-up       tex_lookup_rgba8, unchanged: bilinear, wrap, 1.8 fixed-point weights, raw 8-bit value / 255; at the hit's interpolated text_coords[0], computed as
+ *                 k_shade computes it for the base colour.  Hits on mesh instances only (SKH_INSTANCE_MESH): curve instances and light proxies are never cut.
+ *   closest hit   a ray's hit is the nearest ACCEPTED one.  When the hit at t is rejected the ray goes on with the same origin, the same direction, tmin = t and the
+ *                 same tmax.  The intersectors accept tmin < t' <= tmax, so the rejected primitive cannot come back -- and neither can anything else at exactly that
+ *                 t: a second surface at bit-exactly the rejected distance is skipped with it (part of the definition).  Path depth, sampler dimensions, lastBsdfPdf,
+ *                 the MIS distance of an emitter hit and the offset_ray of the next bounce are those of the ray that produced the accepted hit from the start: an
+ *                 image with a cut-away triangle equals, bit for bit, the image of the scene without that triangle.
+ *   shadow rays   occluded iff an accepted hit lies in (tmin, tmax].  Hits on instances the shadow mask excludes (light proxies, baked hidden ones too) pass through.
+ *   round limit   option cutout_rounds (default 8, 1..32): the number of rejected hits per ray.  After that many the next hit is accepted whatever its opacity (for a
+ *                 shadow ray it occludes; a light proxy met there still does not).  Deterministic, no host round trip.  A light proxy a shadow ray passes through
+ *                 uses up a round like a rejected hit.
+ *   emission      a material that both emits (skh_set_emission gave it an Le != 0) and has an active cutout is refused with SKH_INVALID_ARGUMENT, the message naming
+ *                 the material, by the call that would use it: render, trace or info.
+ * Not part of it: fractional or stochastic opacity (threshold 0 with opacity < 1, glTF BLEND), cutouts on curves, coloured transmission, an alpha test inside the
+ * traversal loop. */
+typedef struct skh_material_cutout
+{
+    uint32_t opacity_texture;   /* 1-based into skh_set_textures' list; 0 or beyond the list = no texture: texel = 1 */
+    uint32_t opacity_channel;   /* 0..3 = r, g, b, a */
+    float opacity_scale, opacity_bias; /* opacity = clamp01(scale * texel + bias), product and sum rounded separately */
+    float threshold;            /* 0 = entry inactive (opaque); else in (0, 1]: the hit counts iff opacity >= threshold */
+    uint32_t reserved[3];       /* must be 0 */
+} skh_material_cutout;
+/* n_materials <= the material count; materials beyond n are opaque.  NULL or 0 removes the table; a table in which no entry is active, or whose active materials no mesh
+ * instance uses, equals no table: the context then launches the kernels (the any-hit shadow kernel among them) and produces the bits of one that never had any.  A channel
+ * above 3, a scale or bias that is not finite, a threshold outside [0, 1] or a non-zero reserved word is refused with SKH_INVALID_ARGUMENT and leaves the previous table in
+ * place.  Discards sub-frames traced ahead; never touches the acceleration structures or the emitter table.  Whether a cutout is in use is derived data: recomputed after
+ * skh_set_materials / _textures / _instances / _material_cutouts / _emission and after skh_update_accel with a new instance table.  skh_trace and skh_trace_device honour
+ * the table in both modes. */
+skh_status skh_set_material_cutouts(skh_context* ctx, const skh_material_cutout* entries, uint32_t n_materials);
+typedef struct skh_cutout_info
+{
+    uint32_t active_materials; /* entries with threshold > 0 (inside the material list) */
+    uint32_t instances; /* mesh instances that use one of them; 0: the cutout stage does not run */
+    uint64_t continued_closest, continued_shadow; /* rays re-queued because their hit was cut away, since the last skh_reset_stats (not part of rays_radiance / rays_shadow) */
+    uint64_t accepted_by_cap; /* hits that are cut away and were accepted by the round limit */
+    uint64_t bytes; /* device memory of the continuation queues and the extra hit buffers */
+} skh_cutout_info;
+skh_status skh_get_cutout_info(skh_context* ctx, skh_cutout_info* out);
+
 /* ---- createAccelerationStructure (OptixRender.cpp:388-496): per-mesh / per-curve BLAS + one TLAS ---- */
 skh_status skh_build_accel(skh_context* ctx, uint32_t flags);
 /* After a VERTEX edit -- skh_set_geometry with the mesh table and index buffer of the last build, any vertex data; skh_set_curves with the curve sets and vertex
@@ -577,7 +622,9 @@ skh_status skh_unit_probe(skh_context* ctx, uint32_t unit, uint32_t param, const
  *                 MIS-weighted against it; 0 = the environment is reached by BSDF sampling only, every miss weighs 1.  Two estimators of one integral: the
  *                 expectation is the same, the bits are not.  Without an environment it changes nothing),
  *                 emit_nee 1|0 (the same for emissive meshes: 1 = the emitter set is an entry of the light pick and a hit on an emitter is MIS-weighted against it; 0 = never
- *                 picked, every emitter hit weighs 1.  Same expectation, other bits; with no emissive material it changes nothing)
+ *                 picked, every emitter hit weighs 1.  Same expectation, other bits; with no emissive material it changes nothing),
+ *                 cutout_rounds (8; 1..32: rejected hits per ray before the next hit is accepted whatever its opacity -- skh_set_material_cutouts; values outside the range
+ *                 are refused.  Without a cutout in use it changes nothing)
  *   build        build_quality 1|0 (PLOC | Karras radix tree), reinsert_rounds (8; 0 = off: rounds of parallel reinsertion over the PLOC tree of the
  *                 triangle build -- every subtree looks for the place in the tree where it costs least, the best non-conflicting moves are applied),
  *                 reinsert_curve_rounds (4: the same over the curve sub-segment trees),

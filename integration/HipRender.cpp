@@ -205,6 +205,7 @@ void HipRender::uploadMaterials()
     std::vector<skh_material> mats;
     std::vector<float> emission; // 3 per material: skh_set_emission, after the materials
     std::vector<skh_material_textures> mtex; // one per material: skh_set_material_textures, after the materials
+    std::vector<skh_material_cutout> cutouts; // one per material: skh_set_material_cutouts, after the materials
 #ifdef SKH_WITH_STRELKA_HEADERS
     // every eTexture parameter becomes one RGBA8 texture (OptixRender.cpp:1346-1377: resolved against resource/searchPath, stbi_load
     // with STBI_rgb_alpha); a file that cannot be read is reported and the material keeps its constant colour (:1195-1199)
@@ -235,6 +236,8 @@ void HipRender::uploadMaterials()
         emission.insert(emission.end(), le, le + 3);
         // roughness / metallic / ORM / emissive maps: loaded through the same path as diffuse_texture
         mtex.push_back(skhmat::materialTextures(d, load));
+        // cutout opacity (OmniPBR enable_opacity / opacity_threshold, UsdPreviewSurface opacityThreshold): its map likewise
+        cutouts.push_back(skhmat::materialCutout(d, load));
     }
     for (size_t k = 0; k < tex.size(); ++k)
         tex[k].rgba8 = pixels[k].data();
@@ -260,6 +263,9 @@ void HipRender::uploadMaterials()
     // material textures (no entry binds one = none: likewise)
     const bool maps = std::any_of(mtex.begin(), mtex.end(), [](const skh_material_textures& e) { return e.roughness_texture || e.metallic_texture || e.emission_texture; });
     check(skh_set_material_textures(mCtx, maps ? mtex.data() : nullptr, maps ? (uint32_t)mtex.size() : 0u), "skh_set_material_textures");
+    // cutouts (no entry is active = none: likewise)
+    const bool cut = std::any_of(cutouts.begin(), cutouts.end(), [](const skh_material_cutout& e) { return e.threshold > 0.0f; });
+    check(skh_set_material_cutouts(mCtx, cut ? cutouts.data() : nullptr, cut ? (uint32_t)cutouts.size() : 0u), "skh_set_material_cutouts");
 }
 
 static void environmentRotation(const float* worldToEnv, float out[9])

@@ -8,6 +8,7 @@
 //   OmniPBR.{diffuse_color_constant, reflection_roughness_constant, metallic_constant, diffuse_texture, normalmap_texture}
 //                                                         (sceneloader/gltfloader.cpp:304-352)                            -> SKH_MAT_PBR
 //           its roughness / metallic / ORM / emissive maps                                                               -> skh_material_textures (materialTextures below)
+//           enable_opacity + opacity_threshold [opacity_texture]; UsdPreviewSurface opacityThreshold                       -> skh_material_cutout (materialCutout below)
 //   OmniGlass.{glass_color, glass_ior, frosting_roughness} (gltfloader.cpp:354-406)                                      -> SKH_MAT_GLASS
 //   UsdPreviewSurface parameter sets (HdStrelka's eMaterialX descriptions, HdStrelka/Material.cpp:52-150)                -> PBR | GLASS
 //   names containing "hair" (the `hair` sub-expression, materialmanager/mdlPtxCodeGen.cpp:143-155)                       -> SKH_MAT_HAIR
@@ -103,8 +104,9 @@ inline skh_material translate(const Desc& d, uint32_t diffuseTextureId = 0, uint
                          find(d, "emissiveColor");
     if (preview)
     {
-        // UsdPreviewSurface spec defaults: diffuseColor 0.18, roughness 0.5, metallic 0, ior 1.5, opacity 1 (< 0.5 is treated as glass)
-        m.type = scalar(d, "opacity", 1.0f) < 0.5f ? SKH_MAT_GLASS : SKH_MAT_PBR;
+        // UsdPreviewSurface spec defaults: diffuseColor 0.18, roughness 0.5, metallic 0, ior 1.5, opacity 1 (< 0.5 is treated as glass -- unless an
+        // opacityThreshold > 0 makes the opacity a cutout's: materialCutout)
+        m.type = (scalar(d, "opacity", 1.0f) < 0.5f && !(scalar(d, "opacityThreshold", 0.0f) > 0.0f)) ? SKH_MAT_GLASS : SKH_MAT_PBR;
         color(d, "diffuseColor", m.base_color, 0.18f, 0.18f, 0.18f);
         m.roughness = scalar(d, "roughness", 0.5f);
         m.metallic = scalar(d, "metallic", 0.0f);
@@ -241,6 +243,53 @@ inline skh_material_textures materialTextures(const Desc& d, TextureId&& texture
         else if (mask)
             e.emission_texture = mask, e.emission_channel = 0u;
     }
+    return e;
+}
+
+// The description's cutout (skh_set_material_cutouts' entry for the material; threshold 0 = none) -- the C++ statement of
+// strelka_amd/scene_io.py::material_cutout_from_description:
+//   OmniPBR, enable_opacity and opacity_threshold > 0   -> threshold = opacity_threshold; with enable_opacity_texture and an opacity_texture that loads: that texture,
+//                                                          channel a for opacity_mode 0, else r (a simplification: the other mono modes agree on grey maps only),
+//                                                          scale = opacity_scale (default 1), bias 0; without one: no look-up, scale 0, bias = opacity_constant (default 1)
+//   UsdPreviewSurface, opacityThreshold > 0             -> no texture, scale 0, bias = opacity (default 1), threshold = opacityThreshold
+// Thresholds above 1 are clamped to 1.  `textureId(path)` as for materialTextures.
+template <class Desc, class TextureId>
+inline skh_material_cutout materialCutout(const Desc& d, TextureId&& textureId)
+{
+    skh_material_cutout e;
+    memset(&e, 0, sizeof(e));
+    e.opacity_channel = 3u;
+    e.opacity_scale = 1.0f;
+    std::string low = d.name + " " + d.file;
+    std::transform(low.begin(), low.end(), low.begin(), [](unsigned char c) { return (char)tolower(c); });
+    const bool preview = find(d, "diffuseColor") || find(d, "useSpecularWorkflow") || find(d, "specularColor") || find(d, "clearcoat") ||
+                         find(d, "emissiveColor");
+    if (preview)
+    {
+        const float th = scalar(d, "opacityThreshold", 0.0f);
+        if (th > 0.0f)
+            e.opacity_scale = 0.0f, e.opacity_bias = scalar(d, "opacity", 1.0f), e.threshold = std::min(th, 1.0f);
+        return e;
+    }
+    if (low.find("glass") != std::string::npos || low.find("pbr") == std::string::npos || scalar(d, "enable_opacity", 0.0f) == 0.0f)
+        return e;
+    const float th = scalar(d, "opacity_threshold", 0.0f);
+    if (!(th > 0.0f))
+        return e;
+    e.threshold = std::min(th, 1.0f);
+    uint32_t t = 0u;
+    if (scalar(d, "enable_opacity_texture", 0.0f) != 0.0f)
+    {
+        const std::string path = texturePath(d, "opacity_texture");
+        t = path.empty() ? 0u : (uint32_t)textureId(path);
+    }
+    if (t)
+    {
+        e.opacity_texture = t, e.opacity_channel = scalar(d, "opacity_mode", 0.0f) == 0.0f ? 3u : 0u;
+        e.opacity_scale = scalar(d, "opacity_scale", 1.0f);
+    }
+    else
+        e.opacity_scale = 0.0f, e.opacity_bias = scalar(d, "opacity_constant", 1.0f);
     return e;
 }
 } // namespace skhmat

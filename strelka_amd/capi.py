@@ -29,7 +29,7 @@ SYMBOLS = ["skh_create", "skh_destroy", "skh_last_error", "skh_abi_version", "sk
            "skh_comm_destroy", "skh_gather_tiles", "skh_host_register", "skh_host_unregister", "skh_get_baked", "skh_comm_info", "skh_probe_memory", "skh_unit_probe", "skh_copy_aov", "skh_get_build_info", "skh_refit_accel",
            "skh_update_accel", "skh_set_environment", "skh_set_environment_transform", "skh_get_environment_info",
            "skh_set_emission", "skh_get_emitter_info", "skh_emitter_probe",
-           "skh_set_material_textures", "skh_material_probe"]
+           "skh_set_material_textures", "skh_material_probe", "skh_set_material_cutouts", "skh_get_cutout_info"]
 
 BUILD_INFO = np.dtype([("triangles", np.uint32), ("nodes", np.uint32), ("reinsert_rounds", np.uint32), ("reinsert_moves", np.uint32),
                        ("reinsert_min_size", np.uint32), ("refit", np.uint32), ("cost_before", np.float64), ("cost_after", np.float64),
@@ -38,6 +38,8 @@ DEVICE_INFO = np.dtype([("compute_units", np.uint32), ("simds_per_cu", np.uint32
                         ("memory_bus_bits", np.uint32), ("wavefront_size", np.uint32), ("total_memory_bytes", np.uint64), ("name", "S64")])
 
 ENVIRONMENT_INFO = np.dtype([("width", np.uint32), ("height", np.uint32), ("sum_w", np.float64), ("ms_build", np.float64), ("bytes", np.uint64)])
+CUTOUT_INFO = np.dtype([("active_materials", np.uint32), ("instances", np.uint32), ("continued_closest", np.uint64), ("continued_shadow", np.uint64),
+                        ("accepted_by_cap", np.uint64), ("bytes", np.uint64)])
 EMITTER_INFO = np.dtype([("triangles", np.uint32), ("instances", np.uint32), ("sum_w", np.float64), ("ms_build", np.float64), ("bytes", np.uint64)])
 # skh_emitter_probe: kind -> (number, words in, words out) per record
 EMIT_PROBES = {"sample": (0, 6, 13), "pdf": (1, 8, 4)}
@@ -95,6 +97,8 @@ def load():
     lib.skh_emitter_probe.argtypes = [vp, u32, vp, u32, vp]
     lib.skh_set_material_textures.argtypes = [vp, vp, u32]
     lib.skh_material_probe.argtypes = [vp, u32, vp, vp, vp]
+    lib.skh_set_material_cutouts.argtypes = [vp, vp, u32]
+    lib.skh_get_cutout_info.argtypes = [vp, vp]
     lib.skh_resize.argtypes = [vp, u32, u32]
     lib.skh_set_tiles.argtypes = [vp, u32, vp, u32]
     lib.skh_render_subframe.argtypes = [vp, vp, vp]
@@ -192,6 +196,7 @@ class Context:
             self.set_environment(env["rgb"], env.get("scale", (1, 1, 1)), env.get("world_to_env"))
         self.set_emission(arr.get("emission"))  # (likewise: a scene without emissive materials removes what a reused context holds)
         self.set_material_textures(arr.get("material_textures"))  # (likewise)
+        self.set_material_cutouts(arr.get("material_cutouts"))  # (likewise)
         if build:
             self.build_accel(flags)
 
@@ -274,6 +279,20 @@ class Context:
             return
         t = np.ascontiguousarray(table, S.MATERIAL_TEXTURES).reshape(-1)
         self._ck(self.lib.skh_set_material_textures(self.h, _p(t), len(t)), "skh_set_material_textures")
+
+    def set_material_cutouts(self, table):
+        """skh_set_material_cutouts: `table` an S.MATERIAL_CUTOUT array, one entry per material (None or empty removes the table)"""
+        if table is None or len(table) == 0:
+            self._ck(self.lib.skh_set_material_cutouts(self.h, None, 0), "skh_set_material_cutouts")
+            return
+        t = np.ascontiguousarray(table, S.MATERIAL_CUTOUT).reshape(-1)
+        self._ck(self.lib.skh_set_material_cutouts(self.h, _p(t), len(t)), "skh_set_material_cutouts")
+
+    def cutout_info(self):
+        """skh_get_cutout_info: materials with an active cutout, mesh instances using them, rays continued / accepted by the round limit since the last reset_stats"""
+        d = np.zeros((), CUTOUT_INFO)
+        self._ck(self.lib.skh_get_cutout_info(self.h, _p(d)), "skh_get_cutout_info")
+        return {k: int(d[k]) for k in CUTOUT_INFO.names}
 
     def material_probe(self, material, uv):
         """skh_material_probe: the device function k_shade calls for a triangle hit of material[i] at uv[i] -> (n, 8) float32:

@@ -1755,6 +1755,7 @@ skh_status skh_update_accel(skh_context* c, const skh_instance* instances, uint3
     if (instances)
     {
         c->emitStale = true; // (the emitter table is in world space: it moves with the instances)
+        c->cutStale = true;
         // (the table replaces whatever skh_set_instances set since the build -- which may have had another count: n is the built count here)
         c->instances.assign(instances, instances + n);
         c->nInstances = n;

@@ -123,6 +123,14 @@ struct skh_context
     // exists -- selects the k_shade build that carries it.
     std::vector<skh_material_textures> mtex;
     DevBuf dMtex;
+    // cutouts (skh_set_material_cutouts): the table as the caller gave it and its device copy.  Whether a cutout is IN USE -- an active entry on a material that a mesh
+    // instance uses -- is derived (cut_ensure, when cutStale): only then does the cutout stage run, and only then do its buffers exist: two continuation queues and a
+    // second hit buffer for the closest-hit side, the same plus the first-round hit buffer for the shadow side (the two sides run on two streams when `overlap` is on)
+    std::vector<skh_material_cutout> cutouts;
+    DevBuf dCutouts, dCutStats, dCutQ[2], dCutHits, dCutShadowQ[2], dCutShadowHits[2];
+    bool cutStale = false;
+    uint32_t cutActiveMaterials = 0, cutInstances = 0; // cutInstances != 0: a cutout is in use
+    uint32_t cutoutRounds = 8; // option cutout_rounds
     // Speculative sub-frame batching for the reference's call pattern (one render() per sub-frame, RenderPass.cpp:441-447): once two
     // consecutive calls continue the same frame (same parameters, subframe_index + 1), the next call traces several sub-frames
     // ahead in ONE wavefront pass and the calls after it only apply their accumulation step to the radiances already in the path

@@ -1578,6 +1578,171 @@ __global__ void __launch_bounds__(SKH_SHADE_BLOCK) SKH_SHADE_ATTR(HAIR)
 #undef SKH_SP
 }
 
+// =================================================================================================
+// Cutouts -- skh_set_material_cutouts; DESIGN.md section 2 "Cutouts" is the definition.  One 32-byte entry per material: a hit on a mesh instance of a material
+// with an active entry counts iff clamp01(scale * texel + bias) >= threshold (two roundings), the texel through tex_lookup_rgba8 at text_coords[0].  The test is a
+// STAGE of its own between a trace launch and whatever reads its results: k_cutout looks at every hit record of a queue, leaves the accepted ones (and the misses)
+// as the final result and appends the rays whose hit is cut away to a continuation queue -- same origin, same direction, tmin = the rejected t, the same tmax, the
+// ORIGINAL queue position in the id plane --, which the host traces and tests again.  k_trace and k_shade do not know about it.
+// =================================================================================================
+struct CutoutP // by-value kernel argument
+{
+    const uint4* table; // 2 per material: {texture, channel, scale, bias} {threshold, 0, 0, 0}
+    uint32_t count;
+};
+struct CutStatsDev // rays continued (their hit was cut away) and rays whose hit the last round accepted although it is cut away: [0] closest, [1] shadow
+{
+    unsigned long long continued[2], capped[2];
+};
+#define SKH_CUTOUT_LDS 128 // entries k_cutout stages in LDS (4 KB); materials beyond them read global memory
+#define SKH_CUTOUT_BLOCK 256
+// SHADOW = false: `hq` holds the closest hits of the rays of `rq`.  A final record (accepted hit, miss, curve or light-proxy hit) of a CONTINUED ray is copied to
+//   outHq at the ray's original position, where k_shade (or the raw query's output kernel) reads it; a first-round ray's record already lies there.
+// SHADOW = true: the same records for shadow rays.  A miss adds the light sample's contribution to the path's radiance -- the any-hit kernel's statement -- or, in raw
+//   query mode (rawOut), answers -1; an accepted hit answers 1 there and is nothing otherwise; a hit on a light proxy passes through like a rejected one.
+// first: rq is the queue the frame (or the query) filled: a ray's original position is its own.  last: the round limit is reached: every hit is accepted
+// (a light proxy in a shadow ray's way still does not occlude).
+template <bool SHADOW>
+__global__ void __launch_bounds__(SKH_CUTOUT_BLOCK) k_cutout(DevScene sc, CutoutP cut, RayQ rq, const uint32_t* __restrict__ countPtr, HitQ hq, uint32_t first, uint32_t last,
+                                                             HitQ outHq, float* __restrict__ rawOut, PathS ps, const float4* __restrict__ contrib, RayQ nextQ,
+                                                             uint32_t* __restrict__ nextCount, CutStatsDev* __restrict__ stats)
+{
+    __shared__ uint4 s_cut[2 * SKH_CUTOUT_LDS];
+    const uint32_t shard = blockIdx.x & (SKH_SHARDS - 1u), lb = blockIdx.x / SKH_SHARDS;
+    const uint32_t n = min(countPtr[shard * SKH_COUNT_STRIDE], rq.region); // rays in this shard
+    if (lb * blockDim.x >= n)
+        return; // whole block past the end of its shard (an empty round: every block)
+    static_assert(2 * SKH_CUTOUT_LDS <= SKH_CUTOUT_BLOCK, "one uint4 of the cutout table per thread");
+    if (threadIdx.x < 2u * min(cut.count, (uint32_t)SKH_CUTOUT_LDS))
+        s_cut[threadIdx.x] = cut.table[threadIdx.x];
+    __syncthreads();
+    const uint32_t il = lb * blockDim.x + threadIdx.x;
+    const uint32_t i = shard * rq.region + il;
+    const bool valid = il < n;
+    bool requeue = false, cutAway = false, capped = false;
+    float ht = 0.0f;
+    uint32_t orig = 0;
+    if (valid)
+    {
+        orig = first ? i : rq.ids()[i];
+        float4 r0, r1 = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+        uint32_t hinst, hprim;
+        if (hq.primBits != 0u)
+        {
+            // (the 16-byte record, decoded as k_shade decodes it)
+            r0 = *hq.rec16(i);
+            const uint32_t w = __float_as_uint(r0.w);
+            hinst = w == 0xffffffffu ? w : w >> hq.primBits;
+            hprim = w == 0xffffffffu ? w : ((w & ((1u << hq.primBits) - 1u)) | (hq.direct ? SKH_PRIM_DIRECT : 0u));
+        }
+        else
+        {
+            r0 = hq.rec(i)[0], r1 = hq.rec(i)[1];
+            hinst = __float_as_uint(r1.x), hprim = __float_as_uint(r1.y);
+        }
+        ht = r0.x;
+        const bool miss = hinst == 0xffffffffu;
+        bool reject = false, proxy = false;
+        if (!miss)
+        {
+            const HostInstance* __restrict__ hip = sc.instances + hinst;
+            const uint32_t type = hip->type, material = hip->material, recBase = hip->light;
+            if (type == 1u)
+                proxy = SHADOW; // (shadow rays do not see lights: the any-hit kernel's mask)
+            else if (type == 0u)
+            {
+                const uint32_t mid0 = material == 0xffffffffu ? 0u : material, mid = mid0 < sc.numMaterials ? mid0 : 0u; // (as k_shade reads it)
+                uint4 a = make_uint4(0u, 0u, 0u, 0u), b = a;
+                if (mid < cut.count)
+                {
+                    if (mid < (uint32_t)SKH_CUTOUT_LDS)
+                        a = s_cut[2u * mid], b = s_cut[2u * mid + 1u];
+                    else
+                        a = cut.table[2 * (size_t)mid], b = cut.table[2 * (size_t)mid + 1];
+                }
+                const float threshold = __uint_as_float(b.x);
+                if (threshold > 0.0f)
+                {
+                    float texel = 1.0f;
+                    if (mtex_valid(a.x, sc.numTextures))
+                    {
+                        // text_coords[0] as fill_triangle computes it, from the triangle's shading record
+                        const uint32_t recIdx = (hprim & SKH_PRIM_DIRECT) ? (hprim & ~SKH_PRIM_DIRECT) : recBase + hprim;
+                        const float4* __restrict__ tp = sc.shadeTris + 6 * (size_t)recIdx;
+                        const float4 t3 = tp[3], t4 = tp[4];
+                        float u0, v0, u1, v1, u2, v2;
+                        unpack_uv(__float_as_uint(t3.w), u0, v0);
+                        unpack_uv(__float_as_uint(t4.x), u1, v1);
+                        unpack_uv(__float_as_uint(t4.y), u2, v2);
+                        const float bu = r0.y, bv = r0.z, bw = 1.0f - bu - bv;
+                        const v4 c = tex_lookup_rgba8(sc.texels, sc.texDesc[a.x - 1u], (u0 * bw + u1 * bu) + u2 * bv, (v0 * bw + v1 * bu) + v2 * bv);
+                        texel = mtex_channel(c, a.y);
+                    }
+                    const float opacity = saturatef(__fadd_rn(__fmul_rn(__uint_as_float(a.z), texel), __uint_as_float(a.w)));
+                    reject = !(opacity >= threshold);
+                }
+            }
+        }
+        cutAway = reject && !last;
+        capped = reject && last;
+        requeue = (reject || proxy) && !last;
+        const bool unoccluded = miss || (proxy && last);
+        if constexpr (SHADOW)
+        {
+            if (rawOut)
+            {
+                if (!requeue)
+                    rawOut[orig] = unoccluded ? -1.0f : 1.0f;
+            }
+            else if (unoccluded)
+            {
+                const float4 cw = contrib[orig];
+                float4* rad = ps.rad() + __float_as_uint(cw.w);
+                float4 r = *rad;
+                r.x += cw.x;
+                r.y += cw.y;
+                r.z += cw.z;
+                *rad = r;
+            }
+        }
+        else if (!requeue && !first)
+        {
+            if (outHq.primBits != 0u)
+                *outHq.rec16(orig) = r0;
+            else
+                outHq.rec(orig)[0] = r0, outHq.rec(orig)[1] = r1;
+        }
+    }
+    // wave-aggregated append: ballot, rank, one atomic per wave on the shard's length word (the output of a shard never outgrows its region: at most one ray per input ray)
+    const unsigned long long m = __ballot(requeue);
+    if (m != 0ull)
+    {
+        const uint32_t lane = threadIdx.x & 63u;
+        uint32_t base = 0;
+        if (lane == 0u)
+            base = atomicAdd(nextCount + shard * SKH_COUNT_STRIDE, (uint32_t)__popcll(m));
+        base = __shfl(base, 0) + rank_below(m);
+        if (requeue && base < nextQ.region)
+        {
+            const uint32_t j = shard * nextQ.region + base;
+#pragma unroll
+            for (int k = 0; k < 6; ++k)
+                nextQ.plane(k)[j] = rq.plane(k)[i];
+            nextQ.plane(6)[j] = ht;
+            nextQ.plane(7)[j] = rq.plane(7)[i];
+            nextQ.ids()[j] = orig;
+        }
+    }
+    const unsigned long long mc = __ballot(cutAway), mk = __ballot(capped);
+    if ((threadIdx.x & 63u) == 0u)
+    {
+        if (mc != 0ull)
+            atomicAdd(&stats->continued[SHADOW ? 1 : 0], (unsigned long long)__popcll(mc));
+        if (mk != 0ull)
+            atomicAdd(&stats->capped[SHADOW ? 1 : 0], (unsigned long long)__popcll(mk));
+    }
+}
+
 // a constant plane of a ray queue (tmin / tmax of the radiance queues, tmin of the shadow queue): written when the queues are allocated or the
 // value changes, instead of once per ray per bounce by k_raygen / k_shade
 __global__ void __launch_bounds__(256) k_fill_f32(float* __restrict__ p, size_t n, float v)

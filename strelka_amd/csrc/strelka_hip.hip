@@ -141,6 +141,7 @@ skh_status skh_create(int device_ordinal, skh_context** out_ctx)
         return SKH_FAIL;
     }
     if (dev_alloc(c, c->dStats, sizeof(StatsDev)) != SKH_OK || hipMemset(c->dStats.p, 0, sizeof(StatsDev)) != hipSuccess ||
+        dev_alloc(c, c->dCutStats, sizeof(CutStatsDev)) != SKH_OK || hipMemset(c->dCutStats.p, 0, sizeof(CutStatsDev)) != hipSuccess ||
         hipHostMalloc(reinterpret_cast<void**>(&c->hOverflow), 64, hipHostMallocMapped) != hipSuccess)
     {
         delete c;
@@ -296,6 +297,7 @@ skh_status skh_set_instances(skh_context* c, const skh_instance* instances, uint
     c->nInstances = n;
     c->accelBuilt = false;
     c->emitStale = true;
+    c->cutStale = true;
     return dev_upload(c, c->dInstances, instances, sizeof(skh_instance) * (size_t)n);
 }
 
@@ -480,6 +482,7 @@ skh_status skh_set_textures(skh_context* c, const skh_texture* textures, uint32_
     if (s == SKH_OK)
         s = dev_upload(c, c->dTexDesc, desc.data(), sizeof(uint4) * desc.size());
     c->nTextures = s == SKH_OK ? n : 0;
+    c->cutStale = true;
     return s;
 }
 skh_status skh_set_materials(skh_context* c, const skh_material* materials, uint32_t n)
@@ -490,6 +493,7 @@ skh_status skh_set_materials(skh_context* c, const skh_material* materials, uint
     (void)hipSetDevice(c->device);
     c->nMaterials = n;
     c->emitStale = true;
+    c->cutStale = true;
     c->hasHairMaterial = false;
     for (uint32_t k = 0; k < n; ++k)
         c->hasHairMaterial = c->hasHairMaterial || materials[k].type == SKH_MAT_HAIR;
@@ -542,6 +546,8 @@ static skh_status build_shading_tables(skh_context* c)
 
 #include "skh_accel.inc"
 
+
+static size_t frame_count_words(const skh_context* c);
 
 static skh_status alloc_frame(skh_context* c)
 {
@@ -612,7 +618,7 @@ static skh_status alloc_frame(skh_context* c)
     SKH_CHECK(dev_alloc(c, c->dShadowQ, sizeof(float) * 9 * NQ));
     SKH_CHECK(dev_alloc(c, c->dContrib, sizeof(float4) * NQ));
     c->queueConstFilled = false;
-    SKH_CHECK(dev_alloc(c, c->dCounts, sizeof(uint32_t) * (SKH_COUNT_STRIDE * SKH_SHARDS * 2 * SKH_MAX_LAUNCH_ROUNDS + 16 * SKH_FETCH_STRIDE * SKH_MAX_LAUNCH_ROUNDS)));
+    SKH_CHECK(dev_alloc(c, c->dCounts, sizeof(uint32_t) * frame_count_words(c)));
     c->traceBlocks = (uint32_t)c->numCUs * c->wavesPerCU;
     SKH_CHECK(dev_alloc(c, c->dOvf, sizeof(int) * (size_t)(SKH_STACK_OVF + SKH_TAIL_EXTRA) * (uint32_t)c->numCUs * std::max(std::max(c->wavesPerCU, c->wavesPerCUWorld), std::max(c->wavesPerCUShadow, c->wavesPerCUShadowWorld)) * SKH_TRACE_BLOCK));
     SKH_CHECK(dev_alloc(c, c->dOvf2, sizeof(int) * (size_t)(SKH_STACK_OVF + SKH_TAIL_EXTRA) * (uint32_t)c->numCUs * std::max(std::max(c->wavesPerCU, c->wavesPerCUWorld), std::max(c->wavesPerCUShadow, c->wavesPerCUShadowWorld)) * SKH_TRACE_BLOCK));
@@ -843,6 +849,147 @@ skh_status skh_material_probe(skh_context* c, uint32_t n, const uint32_t* materi
     return SKH_OK;
 }
 
+// ---- cutouts: skh_set_material_cutouts, the k_cutout stage between trace and shade (skh_kernels.h) ----
+static_assert(sizeof(skh_material_cutout) == 32, "skh_material_cutout");
+#define SKH_CUT_WORDS (SKH_COUNT_STRIDE * SKH_SHARDS + 8 * SKH_FETCH_STRIDE) // per continuation round: the queue's length words, the trace launch's fetch cursors
+
+skh_status skh_set_material_cutouts(skh_context* c, const skh_material_cutout* entries, uint32_t n)
+{
+    if (!c)
+        return SKH_INVALID_ARGUMENT;
+    (void)hipSetDevice(c->device);
+    if (!entries || n == 0)
+    {
+        // remove: a no-op on a context that has none (nothing traced ahead is thrown away for it)
+        if (c->cutouts.empty())
+            return SKH_OK;
+        spec_drop(c);
+        SKH_TRY(c, hipStreamSynchronize(c->stream));
+        c->cutouts.clear();
+        dev_free(c->dCutouts);
+        c->cutStale = true;
+        return SKH_OK;
+    }
+    if (n > c->nMaterials)
+    {
+        c->err = "skh_set_material_cutouts: " + std::to_string(n) + " entries for " + std::to_string(c->nMaterials) + " materials (call skh_set_materials first)";
+        return SKH_INVALID_ARGUMENT;
+    }
+    for (uint32_t k = 0; k < n; ++k)
+    {
+        const skh_material_cutout& e = entries[k];
+        if (e.opacity_channel > 3u || !std::isfinite(e.opacity_scale) || !std::isfinite(e.opacity_bias) || !(e.threshold >= 0.0f && e.threshold <= 1.0f) ||
+            e.reserved[0] != 0u || e.reserved[1] != 0u || e.reserved[2] != 0u)
+        {
+            c->err = "skh_set_material_cutouts: entry " + std::to_string(k) + ": a channel above 3, a scale or bias that is not finite, a threshold outside [0, 1] or a non-zero reserved word";
+            return SKH_INVALID_ARGUMENT;
+        }
+    }
+    spec_drop(c);
+    SKH_TRY(c, hipStreamSynchronize(c->stream)); // (the table is about to be replaced)
+    DevBuf d;
+    SKH_CHECK(dev_upload(c, d, entries, sizeof(skh_material_cutout) * (size_t)n));
+    c->dCutouts = std::move(d);
+    c->cutouts.assign(entries, entries + n);
+    c->cutStale = true;
+    return SKH_OK;
+}
+
+// Is a cutout in use (derived: an active entry on a material that a mesh instance uses)?  And the one combination that is refused: a material that emits and is cut.
+static skh_status cut_ensure(skh_context* c)
+{
+    if (c->cutStale)
+    {
+        const uint32_t nTab = (uint32_t)std::min<size_t>(c->cutouts.size(), c->nMaterials);
+        uint32_t active = 0, users = 0;
+        for (uint32_t k = 0; k < nTab; ++k)
+            active += c->cutouts[k].threshold > 0.0f ? 1u : 0u;
+        if (active)
+            for (const skh_instance& in : c->instances)
+            {
+                if (in.type != SKH_INSTANCE_MESH)
+                    continue;
+                const uint32_t mid0 = in.material_id == 0xffffffffu ? 0u : in.material_id, mid = mid0 < c->nMaterials ? mid0 : 0u; // (as k_shade reads it)
+                users += (mid < nTab && c->cutouts[mid].threshold > 0.0f) ? 1u : 0u;
+            }
+        c->cutActiveMaterials = active, c->cutInstances = users;
+        c->cutStale = false;
+    }
+    if (c->cutActiveMaterials && !c->emission.empty())
+        for (uint32_t k = 0; k < c->cutouts.size() && k < c->nMaterials && 3 * (size_t)k + 2 < c->emission.size(); ++k)
+            if (c->cutouts[k].threshold > 0.0f && (c->emission[3 * (size_t)k] > 0.0f || c->emission[3 * (size_t)k + 1] > 0.0f || c->emission[3 * (size_t)k + 2] > 0.0f))
+            {
+                c->err = "material " + std::to_string(k) + " both emits (skh_set_emission) and has an active cutout (skh_set_material_cutouts): cut-away emitters are not supported";
+                return SKH_INVALID_ARGUMENT;
+            }
+    return SKH_OK;
+}
+
+static CutoutP make_cutout(const skh_context* c)
+{
+    CutoutP p;
+    p.table = c->dCutouts.as<uint4>();
+    p.count = (uint32_t)std::min<size_t>(c->cutouts.size(), c->nMaterials);
+    return p;
+}
+
+static size_t frame_count_words(const skh_context* c)
+{
+    const size_t base = (size_t)SKH_COUNT_STRIDE * SKH_SHARDS * 2 * SKH_MAX_LAUNCH_ROUNDS + (size_t)16 * SKH_FETCH_STRIDE * SKH_MAX_LAUNCH_ROUNDS;
+    // behind them, in a context with a cutout in use: per bounce and side (closest, shadow) cutout_rounds x {length words, fetch cursors}
+    return base + (c->cutInstances ? (size_t)SKH_MAX_LAUNCH_ROUNDS * 2 * c->cutoutRounds * SKH_CUT_WORDS : 0u);
+}
+
+// the cutout stage's frame buffers: allocated when a cutout is in use (and only then), freed when none is any more
+static skh_status cut_alloc_frame(skh_context* c)
+{
+    if (!c->cutInstances)
+    {
+        if (c->dCutQ[0].p)
+        {
+            SKH_TRY(c, hipStreamSynchronize(c->stream));
+            for (int k = 0; k < 2; ++k)
+                dev_free(c->dCutQ[k]), dev_free(c->dCutShadowQ[k]), dev_free(c->dCutShadowHits[k]);
+            dev_free(c->dCutHits);
+        }
+        return SKH_OK;
+    }
+    if (!c->width)
+        return SKH_OK;
+    const size_t NQ = (size_t)SKH_SHARDS * c->queueRegion;
+    const size_t qBytes = sizeof(float) * 9 * NQ, hBytes = sizeof(float) * 8 * NQ, cBytes = sizeof(uint32_t) * frame_count_words(c);
+    if (c->dCutQ[0].bytes >= qBytes && c->dCutQ[0].bytes <= 2 * qBytes + 4096 && c->dCounts.bytes >= cBytes)
+        return SKH_OK;
+    SKH_TRY(c, hipStreamSynchronize(c->stream));
+    for (int k = 0; k < 2; ++k)
+    {
+        SKH_CHECK(dev_alloc(c, c->dCutQ[k], qBytes));
+        SKH_CHECK(dev_alloc(c, c->dCutShadowQ[k], qBytes));
+        SKH_CHECK(dev_alloc(c, c->dCutShadowHits[k], hBytes));
+    }
+    SKH_CHECK(dev_alloc(c, c->dCutHits, hBytes));
+    if (c->dCounts.bytes < cBytes)
+        SKH_CHECK(dev_alloc(c, c->dCounts, cBytes));
+    return SKH_OK;
+}
+
+skh_status skh_get_cutout_info(skh_context* c, skh_cutout_info* out)
+{
+    if (!c || !out)
+        return SKH_INVALID_ARGUMENT;
+    memset(out, 0, sizeof(*out));
+    (void)hipSetDevice(c->device);
+    SKH_CHECK(cut_ensure(c));
+    CutStatsDev sd;
+    SKH_TRY(c, hipStreamSynchronize(c->stream));
+    SKH_TRY(c, hipMemcpy(&sd, c->dCutStats.p, sizeof(sd), hipMemcpyDeviceToHost));
+    out->active_materials = c->cutActiveMaterials, out->instances = c->cutInstances;
+    out->continued_closest = sd.continued[0], out->continued_shadow = sd.continued[1];
+    out->accepted_by_cap = sd.capped[0] + sd.capped[1];
+    out->bytes = c->dCutQ[0].bytes + c->dCutQ[1].bytes + c->dCutHits.bytes + c->dCutShadowQ[0].bytes + c->dCutShadowQ[1].bytes + c->dCutShadowHits[0].bytes + c->dCutShadowHits[1].bytes;
+    return SKH_OK;
+}
+
 static skh_status ensure_ready(skh_context* c);
 
 // ---- emissive meshes: skh_set_emission, the emitter table (skh_emit.h) ----
@@ -981,6 +1128,7 @@ skh_status skh_set_emission(skh_context* c, const float* rgb, uint32_t n)
         spec_drop(c);
         c->emission.clear();
         c->emitStale = true;
+        c->cutStale = true;
         return SKH_OK;
     }
     if (n > c->nMaterials)
@@ -1003,6 +1151,7 @@ skh_status skh_set_emission(skh_context* c, const float* rgb, uint32_t n)
     else
         c->emission.clear(); // (all black: the context of one that was never told)
     c->emitStale = true;
+    c->cutStale = true;
     return SKH_OK;
 }
 
@@ -1075,7 +1224,9 @@ static skh_status ensure_ready(skh_context* c)
         if (s != SKH_OK)
             return s;
     }
-    return emit_ensure(c);
+    SKH_CHECK(emit_ensure(c));
+    SKH_CHECK(cut_ensure(c));
+    return cut_alloc_frame(c);
 }
 
 // one launch of the persistent trace kernel over a sharded queue: picks the build (world-only / two-level / two-level + curves) and the grid
@@ -1127,6 +1278,29 @@ static void launch_trace(skh_context* c, const DevScene& sc, RayQ rq, const uint
         k_trace<ANY, COUNT, true><<<blocks, SKH_TRACE_BLOCK, 0, st>>>(sc, rq, countPtr, fetch, fm, hq, ps, contrib, ovf, sd, c->lightBox, chunk);
     else
         k_trace<ANY, COUNT, false><<<blocks, SKH_TRACE_BLOCK, 0, st>>>(sc, rq, countPtr, fetch, fm, hq, ps, contrib, ovf, sd, c->lightBox, chunk);
+}
+
+// The continuation rounds behind a trace launch whose hit records lie in h0 (rays: q0, lengths: count0): k_cutout on them, then cutout_rounds x {trace the continuation
+// queue into h2, k_cutout}.  `words`: cutout_rounds x SKH_CUT_WORDS zeroed words.  A round whose queue is empty costs two launches that return at once.
+template <bool SHADOW, bool COUNT>
+static void run_cutout_chain(skh_context* c, const DevScene& sc, const DevScene& scTrace, RayQ q0, const uint32_t* count0, HitQ h0, HitQ outH, float* rawOut, PathS ps,
+                             const float4* contrib, RayQ cq0, RayQ cq1, HitQ h2, uint32_t* words, uint32_t rays, hipStream_t st)
+{
+    const CutoutP cutp = make_cutout(c);
+    CutStatsDev* cst = c->dCutStats.as<CutStatsDev>();
+    const uint32_t perShard = (((rays + SKH_SHARDS - 1u) / SKH_SHARDS) + 63u) & ~63u;
+    const dim3 grid(SKH_SHARDS * ((std::min(perShard, q0.region) + SKH_CUTOUT_BLOCK - 1) / SKH_CUTOUT_BLOCK));
+    const uint32_t R = c->cutoutRounds, QW = SKH_COUNT_STRIDE * SKH_SHARDS;
+    const RayQ cq[2] = { cq0, cq1 };
+    k_cutout<SHADOW><<<grid, SKH_CUTOUT_BLOCK, 0, st>>>(sc, cutp, q0, count0, h0, 1u, 0u, outH, rawOut, ps, contrib, cq[0], words, cst);
+    for (uint32_t r = 0; r < R; ++r)
+    {
+        uint32_t* lens = words + (size_t)r * SKH_CUT_WORDS;
+        launch_trace<false, COUNT>(c, scTrace, cq[r & 1], lens, lens + QW, h2, ps, nullptr, st);
+        const bool last = r + 1 == R;
+        k_cutout<SHADOW><<<grid, SKH_CUTOUT_BLOCK, 0, st>>>(sc, cutp, cq[r & 1], lens, h2, 0u, last ? 1u : 0u, outH, rawOut, ps, contrib, cq[(r + 1) & 1],
+                                                            last ? lens : lens + SKH_CUT_WORDS, cst);
+    }
 }
 
 // After a synchronisation: did any traversal of the calls since the last check drop a stack entry (its result may miss hits)?
@@ -1239,13 +1413,26 @@ static skh_status render_one(skh_context* c, const skh_frame_params* p, uint32_t
     const bool smallPass = NP <= (1u << 23) || c->overlap == 2;
     const bool useOverlap = (c->overlap == 2 || (c->overlap == 1 && NP <= (1u << 25))) && fp.debug != 1;
     const uint32_t rounds = fp.maxDepth;
+    // Cutouts (skh_set_material_cutouts), only in a context where one is in use: k_cutout and its continuation rounds between a bounce's closest-hit launch and k_shade, and
+    // a closest-hit launch with the same rounds behind it in the any-hit launch's place.  Per bounce and side cutout_rounds x SKH_CUT_WORDS words, behind the fetch cursors.
+    const bool cutOn = c->cutInstances != 0u;
+    const uint32_t cutBounceWords = 2u * c->cutoutRounds * SKH_CUT_WORDS;
+    uint32_t* cutWords = fetch + 16 * SKH_FETCH_STRIDE * (rounds + 1);
+    const RayQ cutQ[2] = { RayQ{ c->dCutQ[0].as<float>(), NQ, c->queueRegion }, RayQ{ c->dCutQ[1].as<float>(), NQ, c->queueRegion } };
+    const RayQ cutSQ[2] = { RayQ{ c->dCutShadowQ[0].as<float>(), NQ, c->queueRegion }, RayQ{ c->dCutShadowQ[1].as<float>(), NQ, c->queueRegion } };
+    HitQ cutH = hq, cutSH0 = hq, cutSH1 = hq; // (records as the closest-hit launches of this pass write them)
+    cutH.base = c->dCutHits.as<float>(), cutSH0.base = c->dCutShadowHits[0].as<float>(), cutSH1.base = c->dCutShadowHits[1].as<float>();
+    DevScene scShadow = sc; // what the closest-hit launches of SHADOW rays walk: not the baked light proxies' tree (shadow rays do not see lights)
+    if (c->worldRoot != SKH_REF_INVALID || c->tlasRoot != SKH_REF_INVALID)
+        scShadow.lightRoot = SKH_REF_INVALID;
     c->splitNow = c->tailSplit < 0 && smallPass && NP >= (1u << 17);
     // One sub-frame of one sample, accumulated in this call (the reference caller's pattern): its sums ARE the path's radiance and event word -- the batch kernel reads
     // them where they lie (0.0f + radiance, / 1.0f: the same operations), and the k_collect launch and its 11 planes of sums are not needed.
     const bool oneSampleDirect = batch == 1 && fp.samplesThisLaunch == 1 && finalize && fp.finalFirst == 0 && fp.finalCount == 1;
     for (uint32_t s = 0; trace && s < fp.samplesThisLaunch; ++s)
     {
-        SKH_TRY(c, hipMemsetAsync(counts, 0, sizeof(uint32_t) * (QW * 2 * SKH_MAX_LAUNCH_ROUNDS + 16 * SKH_FETCH_STRIDE * (rounds + 1)), st));
+        // (a cutout in use: the words of its continuation rounds lie behind the fetch cursors this sample uses -- one memset for all of them)
+        SKH_TRY(c, hipMemsetAsync(counts, 0, sizeof(uint32_t) * (QW * 2 * SKH_MAX_LAUNCH_ROUNDS + 16 * SKH_FETCH_STRIDE * (rounds + 1) + (size_t)(cutOn ? rounds : 0u) * cutBounceWords), st));
         {
             SpanGuard g(c, KC_RAYGEN);
             k_raygen<<<c->raygenBlocksPerSub * fp.batch, 512, 0, st>>>(fp, tiles, s, rq[0], counts, ps, c->dRaygenBase.as<uint32_t>(),
@@ -1260,6 +1447,13 @@ static skh_status render_one(skh_context* c, const skh_frame_params* p, uint32_t
                     launch_trace<false, true>(c, sc, rq[b & 1], counts + 2 * b * QW, fetch + 16 * b * SKH_FETCH_STRIDE, hq, ps, nullptr);
                 else
                     launch_trace<false, false>(c, sc, rq[b & 1], counts + 2 * b * QW, fetch + 16 * b * SKH_FETCH_STRIDE, hq, ps, nullptr);
+                if (cutOn)
+                {
+                    if (c->countTraversal)
+                        run_cutout_chain<false, true>(c, sc, sc, rq[b & 1], counts + 2 * b * QW, hq, hq, nullptr, ps, nullptr, cutQ[0], cutQ[1], cutH, cutWords + (size_t)b * cutBounceWords, NP, st);
+                    else
+                        run_cutout_chain<false, false>(c, sc, sc, rq[b & 1], counts + 2 * b * QW, hq, hq, nullptr, ps, nullptr, cutQ[0], cutQ[1], cutH, cutWords + (size_t)b * cutBounceWords, NP, st);
+                }
             }
             if (useOverlap && b > 0)
                 (void)hipStreamWaitEvent(st, c->evShadow, 0); // shade[b] reads the radiance shadow[b-1] adds to and reuses its queue
@@ -1317,7 +1511,22 @@ static skh_status render_one(skh_context* c, const skh_frame_params* p, uint32_t
                 {
                     SpanGuard g(c, KC_TRACE_SHADOW, sst);
                     c->gridOverride = (useOverlap && smallPass) ? ((b + 1 == rounds && (c->smallWavesLast || (!c->smallWavesShadow && !c->nSegs))) ? (c->smallWavesLast ? c->smallWavesLast : 20u) : c->smallWavesShadow ? c->smallWavesShadow : (c->nSegs ? 16u : 12u)) * (uint32_t)c->numCUs : 0u;
-                    if (c->countTraversal)
+                    if (cutOn)
+                    {
+                        // the shadow rays' NEAREST hits, tested and continued like the radiance rays'; a ray that ends in a miss adds its contribution (k_cutout)
+                        uint32_t* w = cutWords + (size_t)b * cutBounceWords + c->cutoutRounds * SKH_CUT_WORDS;
+                        if (c->countTraversal)
+                        {
+                            launch_trace<false, true>(c, scShadow, shq, counts + (2 * b + 1) * QW, fetch + (16 * b + 8) * SKH_FETCH_STRIDE, cutSH0, ps, nullptr, sst);
+                            run_cutout_chain<true, true>(c, sc, scShadow, shq, counts + (2 * b + 1) * QW, cutSH0, cutSH0, nullptr, ps, c->dContrib.as<float4>(), cutSQ[0], cutSQ[1], cutSH1, w, NP, sst);
+                        }
+                        else
+                        {
+                            launch_trace<false, false>(c, scShadow, shq, counts + (2 * b + 1) * QW, fetch + (16 * b + 8) * SKH_FETCH_STRIDE, cutSH0, ps, nullptr, sst);
+                            run_cutout_chain<true, false>(c, sc, scShadow, shq, counts + (2 * b + 1) * QW, cutSH0, cutSH0, nullptr, ps, c->dContrib.as<float4>(), cutSQ[0], cutSQ[1], cutSH1, w, NP, sst);
+                        }
+                    }
+                    else if (c->countTraversal)
                         launch_trace<true, true>(c, sc, shq, counts + (2 * b + 1) * QW, fetch + (16 * b + 8) * SKH_FETCH_STRIDE, nohq, ps, c->dContrib.as<float4>(), sst);
                     else
                         launch_trace<true, false>(c, sc, shq, counts + (2 * b + 1) * QW, fetch + (16 * b + 8) * SKH_FETCH_STRIDE, nohq, ps, c->dContrib.as<float4>(), sst);
@@ -2094,7 +2303,19 @@ skh_status skh_trace_device(skh_context* c, const void* d_rays, uint32_t n_rays,
     const size_t NQ = (size_t)SKH_SHARDS * per;
     SKH_CHECK(dev_alloc(c, q, sizeof(float) * 9 * NQ));
     SKH_CHECK(dev_alloc(c, h, sizeof(float) * 8 * NQ));
-    SKH_CHECK(dev_alloc(c, cnt, sizeof(uint32_t) * (SKH_SHARDS * SKH_COUNT_STRIDE + 8 * SKH_FETCH_STRIDE)));
+    // a cutout in use (skh_set_material_cutouts): the continuation rounds run on the internal records, before k_hits_soa_to_aos; their words lie behind the fetch cursors
+    const bool cutOn = c->cutInstances != 0u;
+    const size_t cutWordCount = cutOn ? (size_t)c->cutoutRounds * SKH_CUT_WORDS : 0u;
+    DevBuf cq0, cq1, h2, h0;
+    SKH_CHECK(dev_alloc(c, cnt, sizeof(uint32_t) * (SKH_SHARDS * SKH_COUNT_STRIDE + 8 * SKH_FETCH_STRIDE + cutWordCount)));
+    if (cutOn)
+    {
+        SKH_CHECK(dev_alloc(c, cq0, sizeof(float) * 9 * NQ));
+        SKH_CHECK(dev_alloc(c, cq1, sizeof(float) * 9 * NQ));
+        SKH_CHECK(dev_alloc(c, h2, sizeof(float) * 8 * NQ));
+        if (mode == SKH_TRACE_SHADOW)
+            SKH_CHECK(dev_alloc(c, h0, sizeof(float) * 8 * NQ));
+    }
     if (!c->traceBlocks)
         c->traceBlocks = (uint32_t)c->numCUs * c->wavesPerCU;
     SKH_CHECK(dev_alloc(c, c->dOvf, sizeof(int) * (size_t)(SKH_STACK_OVF + SKH_TAIL_EXTRA) * (uint32_t)c->numCUs * std::max(std::max(c->wavesPerCU, c->wavesPerCUWorld), std::max(c->wavesPerCUShadow, c->wavesPerCUShadowWorld)) * SKH_TRACE_BLOCK));
@@ -2112,9 +2333,38 @@ skh_status skh_trace_device(skh_context* c, const void* d_rays, uint32_t n_rays,
     k_rays_aos_to_soa<<<(n_rays + 255) / 256, 256, 0, c->stream>>>(reinterpret_cast<const skh_ray*>(d_rays), n_rays, per, rq);
     for (uint32_t r = 0; r < std::max(1u, repeat); ++r)
     {
-        (void)hipMemsetAsync(dfetch, 0, sizeof(uint32_t) * 8 * SKH_FETCH_STRIDE, c->stream);
+        (void)hipMemsetAsync(dfetch, 0, sizeof(uint32_t) * (8 * SKH_FETCH_STRIDE + cutWordCount), c->stream);
         SpanGuard g(c, mode == SKH_TRACE_SHADOW ? KC_TRACE_SHADOW : KC_TRACE_CLOSEST);
-        if (mode == SKH_TRACE_SHADOW)
+        if (cutOn)
+        {
+            const RayQ q0{ cq0.as<float>(), (uint32_t)NQ, per }, q1{ cq1.as<float>(), (uint32_t)NQ, per };
+            const HitQ hq2{ h2.as<float>(), (uint32_t)NQ }, hq0{ h0.as<float>(), (uint32_t)NQ };
+            uint32_t* words = dfetch + 8 * SKH_FETCH_STRIDE;
+            DevScene scShadow = sc; // (shadow rays do not see lights: their closest-hit launches leave the baked light proxies' tree out)
+            if (c->worldRoot != SKH_REF_INVALID || c->tlasRoot != SKH_REF_INVALID)
+                scShadow.lightRoot = SKH_REF_INVALID;
+            if (mode == SKH_TRACE_SHADOW && c->countTraversal)
+            {
+                launch_trace<false, true>(c, scShadow, rq, dcount, dfetch, hq0, ps, nullptr);
+                run_cutout_chain<true, true>(c, sc, scShadow, rq, dcount, hq0, hq0, hq.base, ps, nullptr, q0, q1, hq2, words, n_rays, c->stream);
+            }
+            else if (mode == SKH_TRACE_SHADOW)
+            {
+                launch_trace<false, false>(c, scShadow, rq, dcount, dfetch, hq0, ps, nullptr);
+                run_cutout_chain<true, false>(c, sc, scShadow, rq, dcount, hq0, hq0, hq.base, ps, nullptr, q0, q1, hq2, words, n_rays, c->stream);
+            }
+            else if (c->countTraversal)
+            {
+                launch_trace<false, true>(c, sc, rq, dcount, dfetch, hq, ps, nullptr);
+                run_cutout_chain<false, true>(c, sc, sc, rq, dcount, hq, hq, nullptr, ps, nullptr, q0, q1, hq2, words, n_rays, c->stream);
+            }
+            else
+            {
+                launch_trace<false, false>(c, sc, rq, dcount, dfetch, hq, ps, nullptr);
+                run_cutout_chain<false, false>(c, sc, sc, rq, dcount, hq, hq, nullptr, ps, nullptr, q0, q1, hq2, words, n_rays, c->stream);
+            }
+        }
+        else if (mode == SKH_TRACE_SHADOW)
         {
             if (c->countTraversal)
                 launch_trace<true, true>(c, sc, rq, dcount, dfetch, hq, ps, nullptr);
@@ -2401,6 +2651,7 @@ static const OptRow kOptions[] = {
     { "small_waves_shadow", 0, 64, OPT_NONE, OPT_U32(smallWavesShadow) },
     { "env_nee", 0, 1, OPT_NONE, OPT_U32(envNee) },
     { "emit_nee", 0, 1, OPT_NONE, OPT_U32(emitNee) },
+    { "cutout_rounds", 1, 32, OPT_NONE, OPT_U32(cutoutRounds) }, // (the frame's counter words are sized by it: cut_alloc_frame before the next render)
     { "speculate", 0, 64, OPT_NONE, OPT_U32(speculateMax) },
     { "speculate_grow", 2, 64, OPT_NONE, OPT_U32(speculateGrow) },
     { "speculate_async", 0, 1, OPT_NONE, [](skh_context* c, int64_t v) { spec_drop(c), c->speculateAsync = (uint32_t)v; } },
@@ -2611,6 +2862,7 @@ skh_status skh_reset_stats(skh_context* c)
     spec_drop(c, true); // (what was traced ahead belongs to the counters being cleared)
     SKH_TRY(c, hipStreamSynchronize(c->stream));
     SKH_TRY(c, hipMemset(c->dStats.p, 0, sizeof(StatsDev)));
+    SKH_TRY(c, hipMemset(c->dCutStats.p, 0, sizeof(CutStatsDev)));
     c->stackOverflows = 0;
     c->discardedRadiance = c->discardedShadow = 0;
     c->discardedSubframes = 0;

@@ -175,16 +175,23 @@ class GltfScene(S.Scene):
         mt = scene_io.material_textures_from_descriptions(self.material_descriptions, self.texture_ids)
         if mt is not None:
             arr["material_textures"] = mt
+        ct = scene_io.material_cutouts_from_descriptions(self.material_descriptions, self.texture_ids)
+        if ct is not None:
+            arr["material_cutouts"] = ct
         return arr
 
 
-def _load_materials(doc, sc, material_textures=False):
+def _load_materials(doc, sc, material_textures=False, alpha_mask=False):
     """glTF materials -> the reference loader's OmniPBR / OmniGlass descriptions (gltfloader.cpp:304-406).  New here: emissiveFactor times the
     KHR_materials_emissive_strength extension's emissiveStrength, when not zero, becomes OmniPBR's enable_emission / emissive_color /
     emissive_intensity (a zero factor leaves the description as the reference writes it).  With `material_textures` (the reference's loader
     reads neither): pbrMetallicRoughness.metallicRoughnessTexture becomes enable_ORM_texture / ORM_texture (glTF's layout is OmniPBR's: roughness
     in g, metallic in b) with ORM_roughness_scale / ORM_metallic_scale = roughnessFactor / metallicFactor (value = factor * texel, the glTF
-    definition; scene_io.material_textures_from_description), and emissiveTexture, under a non-zero factor, becomes emissive_color_texture."""
+    definition; scene_io.material_textures_from_description), and emissiveTexture, under a non-zero factor, becomes emissive_color_texture.
+    With `alpha_mask` (the reference's loader turns every non-OPAQUE material into OmniGlass): alphaMode MASK becomes the OmniPBR description of the
+    OPAQUE branch plus a cutout (scene_io.material_cutout_from_description): enable_opacity, opacity_threshold = alphaCutoff (default 0.5, the glTF
+    specification's), opacity_constant = baseColorFactor[3]; with a baseColorTexture also enable_opacity_texture, opacity_texture = that texture,
+    opacity_mode 0 (its alpha channel) and opacity_scale = baseColorFactor[3] (opacity = factor * texel alpha, the glTF definition)."""
     images, textures = doc.get("images", []), doc.get("textures", [])
 
     def tex_uri(info):
@@ -201,7 +208,8 @@ def _load_materials(doc, sc, material_textures=False):
         pbr = m.get("pbrMetallicRoughness", {})
         base = pbr.get("baseColorFactor", [1.0, 1.0, 1.0, 1.0])
         rough, metal = float(pbr.get("roughnessFactor", 1.0)), float(pbr.get("metallicFactor", 1.0))
-        if m.get("alphaMode", "OPAQUE") == "OPAQUE":
+        masked = alpha_mask and m.get("alphaMode", "OPAQUE") == "MASK"
+        if m.get("alphaMode", "OPAQUE") == "OPAQUE" or masked:
             params = [{"name": "diffuse_color_constant", "type": "float3", "value": [float(base[0]), float(base[1]), float(base[2])]},
                       {"name": "reflection_roughness_constant", "type": "float", "value": rough},
                       {"name": "metallic_constant", "type": "float", "value": metal}]
@@ -221,6 +229,14 @@ def _load_materials(doc, sc, material_textures=False):
                 etex = tex_uri(m.get("emissiveTexture")) if material_textures else None
                 if etex is not None:
                     params.append({"name": "emissive_color_texture", "type": "texture", "value": etex})
+            if masked:
+                alpha = float(base[3]) if len(base) > 3 else 1.0
+                params += [{"name": "enable_opacity", "type": "bool", "value": True}, {"name": "opacity_constant", "type": "float", "value": alpha},
+                           {"name": "opacity_threshold", "type": "float", "value": float(m.get("alphaCutoff", 0.5))}]
+                auri = tex_uri(pbr.get("baseColorTexture"))
+                if auri is not None:
+                    params += [{"name": "enable_opacity_texture", "type": "bool", "value": True}, {"name": "opacity_texture", "type": "texture", "value": auri},
+                               {"name": "opacity_mode", "type": "int", "value": 0}, {"name": "opacity_scale", "type": "float", "value": alpha}]
             sc.material_descriptions.append({"file": "OmniPBR.mdl", "name": "OmniPBR", "params": params})
         else:
             sc.material_descriptions.append({"file": "OmniGlass.mdl", "name": "OmniGlass", "params": [
@@ -339,13 +355,13 @@ def _process_node(doc, buffers, sc, index, base):
         _process_node(doc, buffers, sc, child, glob)
 
 
-def load_gltf(path, material_textures=False):
+def load_gltf(path, material_textures=False, alpha_mask=False):
     """GltfLoader::loadGltf (gltfloader.cpp:643-689).  Returns a Scene (strelka_amd.scene API + material_descriptions).
     `material_textures`: also read metallicRoughnessTexture and emissiveTexture (_load_materials); off, a file gives the descriptions
-    the reference's loader gives."""
+    the reference's loader gives.  `alpha_mask`: alphaMode MASK becomes an OmniPBR material with a cutout (_load_materials) instead of OmniGlass."""
     doc, buffers = _read_model(path)
     sc = GltfScene()
-    _load_materials(doc, sc, material_textures)
+    _load_materials(doc, sc, material_textures, alpha_mask)
     _load_textures(path, sc, doc, buffers)
     _load_lights(path, sc)
     _load_cameras(doc, sc)

@@ -28,6 +28,8 @@ MATERIAL_TEXTURES = np.dtype([("roughness_texture", np.uint32), ("metallic_textu
                               ("roughness_channel", np.uint32), ("metallic_channel", np.uint32), ("emission_channel", np.uint32),
                               ("roughness_scale", np.float32), ("roughness_bias", np.float32), ("metallic_scale", np.float32),
                               ("metallic_bias", np.float32), ("reserved", np.uint32, 2)])  # skh_material_textures, 48 B
+MATERIAL_CUTOUT = np.dtype([("opacity_texture", np.uint32), ("opacity_channel", np.uint32), ("opacity_scale", np.float32), ("opacity_bias", np.float32),
+                            ("threshold", np.float32), ("reserved", np.uint32, 3)])  # skh_material_cutout, 32 B
 EMISSION_RGB = 4  # emission_channel: the texel's rgb (0..3: that channel for all three)
 TEXTURE_DESC = np.dtype([("offset", np.uint32), ("width", np.uint32), ("height", np.uint32), ("pad", np.uint32)])
 FRAME_PARAMS = np.dtype([("view_to_world", np.float32, 16), ("clip_to_view", np.float32, 16),
@@ -39,7 +41,7 @@ RAY = np.dtype([("origin", np.float32, 3), ("tmin", np.float32), ("dir", np.floa
 HIT = np.dtype([("t", np.float32), ("instance_id", np.uint32), ("prim_id", np.uint32), ("u", np.float32),
                 ("v", np.float32)])
 assert VERTEX.itemsize == 32 and INSTANCE.itemsize == 64 and LIGHT.itemsize == 112
-assert MATERIAL_TEXTURES.itemsize == 48
+assert MATERIAL_TEXTURES.itemsize == 48 and MATERIAL_CUTOUT.itemsize == 32
 assert MATERIAL.itemsize == 64 and FRAME_PARAMS.itemsize == 176 and RAY.itemsize == 32 and HIT.itemsize == 20
 
 INSTANCE_MESH, INSTANCE_LIGHT, INSTANCE_CURVE = 0, 1, 2  # oka::Instance::Type
@@ -196,8 +198,11 @@ class Scene:
     def addMaterial(self, type=MAT_DIFFUSE, base_color=(0.8, 0.8, 0.8), roughness=None, metallic=0.0, specular=0.5, ior=1.5,
                     base_color_texture=0, normal_texture=0, reserved=(0.0,) * 6, emission=None,
                     roughness_texture=0, metallic_texture=0, emission_texture=0, roughness_channel=0, metallic_channel=0,
-                    emission_channel=EMISSION_RGB, roughness_scale=1.0, roughness_bias=0.0, metallic_scale=1.0, metallic_bias=0.0):
-        """`roughness_texture` / `metallic_texture` (MAT_PBR): value = clamp01(scale * texel[channel] + bias); `emission_texture`: Le = emission * texel
+                    emission_channel=EMISSION_RGB, roughness_scale=1.0, roughness_bias=0.0, metallic_scale=1.0, metallic_bias=0.0,
+                    opacity_texture=None, opacity_channel=3, opacity_scale=1.0, opacity_bias=0.0, opacity_threshold=0.0):
+        """`opacity_threshold` > 0 makes the material a CUTOUT (include/strelka_hip.h, skh_set_material_cutouts): a hit on one of its mesh surfaces counts iff
+        clamp01(opacity_scale * texel[opacity_channel] + opacity_bias) >= opacity_threshold; `opacity_texture` None or 0 = no texture (texel = 1).
+        `roughness_texture` / `metallic_texture` (MAT_PBR): value = clamp01(scale * texel[channel] + bias); `emission_texture`: Le = emission * texel
         (rgb, or one channel for all three) -- texture ids as base_color_texture's (include/strelka_hip.h, skh_set_material_textures).
         `emission`: linear RGB radiance Le the material's mesh surfaces emit from their front side (None = none; include/strelka_hip.h, skh_set_emission).
         MAT_GLASS: `roughness` is OmniGlass' frosting_roughness (default 0 = clear glass: gltfloader.cpp:354-406 sets it from the
@@ -215,6 +220,11 @@ class Scene:
             self.__dict__.setdefault("mMaterialTextures", {})[len(self.mMaterials) - 1] = (
                 int(roughness_texture), int(metallic_texture), int(emission_texture), int(roughness_channel), int(metallic_channel), int(emission_channel),
                 float(roughness_scale), float(roughness_bias), float(metallic_scale), float(metallic_bias), (0, 0))
+        if float(opacity_threshold) != 0.0:
+            if not 0.0 < float(opacity_threshold) <= 1.0 or int(opacity_channel) not in (0, 1, 2, 3):
+                raise ValueError("opacity_threshold must lie in (0, 1] and opacity_channel in 0..3")
+            self.__dict__.setdefault("mMaterialCutouts", {})[len(self.mMaterials) - 1] = (
+                int(opacity_texture or 0), int(opacity_channel), float(opacity_scale), float(opacity_bias), float(opacity_threshold), (0, 0, 0))
         return len(self.mMaterials) - 1
 
     def addHairMaterial(self, color=(0.35, 0.2, 0.1), roughness_r=0.3, roughness_n=0.3, roughness_tt=0.0, roughness_trt=0.0,
@@ -434,6 +444,12 @@ class Scene:
             for i, e in self.mMaterialTextures.items():
                 mt[i] = e
             out["material_textures"] = mt
+        if getattr(self, "mMaterialCutouts", None):  # (likewise only when some material is a cutout)
+            ct = np.zeros(len(mats), MATERIAL_CUTOUT)
+            ct["opacity_channel"], ct["opacity_scale"] = 3, 1.0
+            for i, e in self.mMaterialCutouts.items():
+                ct[i] = e
+            out["material_cutouts"] = ct
         return out
 
 

@@ -169,6 +169,9 @@ def load_scene(path):
     mt = material_textures_from_descriptions(descs or [])  # (likewise; the parameters name TXDS entries, 1-based -- with or without MATL, which has no room for them)
     if mt is not None and len(mt) <= len(arrays["materials"]):
         arrays["material_textures"] = mt
+    ct = material_cutouts_from_descriptions(descs or [])  # (likewise)
+    if ct is not None and len(ct) <= len(arrays["materials"]):
+        arrays["material_cutouts"] = ct
     if not cameras:
         cameras.append(S.Camera())
     validate(arrays)
@@ -200,6 +203,9 @@ def validate(arrays):
     for k, e in enumerate(arrays.get("material_textures", [])):
         if max(int(e["roughness_texture"]), int(e["metallic_texture"]), int(e["emission_texture"])) > nt:
             raise ValueError(f"material {k}: a roughness / metallic / emission map refers to a texture that does not exist")
+    for k, e in enumerate(arrays.get("material_cutouts", [])):
+        if int(e["opacity_texture"]) > nt:
+            raise ValueError(f"material {k}: the opacity map refers to a texture that does not exist")
     for k, c in enumerate(arrays["curves"]):
         if (int(c["points_start"]) + int(c["points_count"]) > npts or int(c["widths_start"]) + int(c["widths_count"]) > nw or
                 int(c["vertex_counts_start"]) + int(c["vertex_counts_count"]) > nvc):
@@ -230,8 +236,9 @@ def material_from_description(desc):
         # UsdPreviewSurface: HdStrelkaMaterial copies the node's parameters under their USD names (Material.cpp:52-150) and hands
         # the network to MaterialX -> MDL (RenderPass.cpp:164-172, type eMaterialX).  Spec defaults: diffuseColor 0.18,
         # roughness 0.5, metallic 0, ior 1.5, opacity 1; an opacity below 0.5 is treated as glass.
+        # With an opacityThreshold > 0 the opacity is a CUTOUT's (material_cutout_from_description), never glass.
         opacity = float(_param(desc, "opacity", 1.0))
-        m["type"] = S.MAT_GLASS if opacity < 0.5 else S.MAT_PBR
+        m["type"] = S.MAT_GLASS if opacity < 0.5 and not float(_param(desc, "opacityThreshold", 0.0)) > 0.0 else S.MAT_PBR
         m["base_color"] = _param(desc, "diffuseColor", (0.18, 0.18, 0.18))
         m["roughness"] = float(_param(desc, "roughness", 0.5))
         m["metallic"] = float(_param(desc, "metallic", 0.0))
@@ -362,6 +369,46 @@ def material_textures_from_descriptions(descs, texture_ids=None):
         out[k] = material_textures_from_description(d, texture_ids)
     any_bound = (out["roughness_texture"] | out["metallic_texture"] | out["emission_texture"]).any()
     return out if any_bound else None
+
+
+def material_cutout_from_description(desc, texture_ids=None):
+    """One MaterialDescription -> one S.MATERIAL_CUTOUT record (skh_set_material_cutouts' entry); threshold 0 = the material is no cutout.
+      OmniPBR, enable_opacity and opacity_threshold > 0: threshold = opacity_threshold.  With enable_opacity_texture and an opacity_texture that resolves:
+          that texture, channel a for opacity_mode 0 (mono_alpha), else r -- a simplification: MDL's mono_average / mono_luminance / mono_maximum modes
+          read a grey map's r = g = b identically and differ for coloured ones --, scale = the optional opacity_scale (default 1; glTF's baseColorFactor[3],
+          strelka_amd/gltf.py), bias 0.  Without a texture: no look-up (texel = 1), scale 0, bias = opacity_constant (default 1, OmniPBR.mdl).
+      UsdPreviewSurface, opacityThreshold > 0: no texture, scale 0, bias = opacity (default 1), threshold = opacityThreshold.
+    Thresholds above 1 are clamped to 1."""
+    e = np.zeros(1, S.MATERIAL_CUTOUT)[0]
+    e["opacity_channel"], e["opacity_scale"] = 3, 1.0
+    pnames = {p.get("name") for p in desc.get("params", [])}
+    if pnames & {"diffuseColor", "useSpecularWorkflow", "specularColor", "clearcoat", "emissiveColor"}:
+        th = float(_param(desc, "opacityThreshold", 0.0))
+        if th > 0.0:
+            e["opacity_scale"], e["opacity_bias"], e["threshold"] = 0.0, np.float32(_param(desc, "opacity", 1.0)), min(th, 1.0)
+        return e
+    if not _is_omnipbr(desc) or not _param(desc, "enable_opacity", False):
+        return e
+    th = float(_param(desc, "opacity_threshold", 0.0))
+    if not th > 0.0:
+        return e
+    e["threshold"] = min(th, 1.0)
+    t = _texture_id(desc, "opacity_texture", texture_ids) if _param(desc, "enable_opacity_texture", False) else 0
+    if t:
+        e["opacity_texture"], e["opacity_channel"] = t, 3 if int(_param(desc, "opacity_mode", 0)) == 0 else 0
+        e["opacity_scale"] = np.float32(_param(desc, "opacity_scale", 1.0))
+    else:
+        e["opacity_scale"], e["opacity_bias"] = 0.0, np.float32(_param(desc, "opacity_constant", 1.0))
+    return e
+
+
+def material_cutouts_from_descriptions(descs, texture_ids=None):
+    """S.MATERIAL_CUTOUT array for skh_set_material_cutouts, or None when no description is a cutout"""
+    out = np.zeros(max(1, len(descs)), S.MATERIAL_CUTOUT)
+    out["opacity_channel"], out["opacity_scale"] = 3, 1.0
+    for k, d in enumerate(descs):
+        out[k] = material_cutout_from_description(d, texture_ids)
+    return out if (out["threshold"] > 0).any() else None
 
 
 def materials_from_descriptions(descs):
