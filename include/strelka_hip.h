@@ -26,7 +26,7 @@
 extern "C" {
 #endif
 
-#define SKH_ABI_VERSION 5 /* 5 (round 6): + skh_refit_accel, skh_build_info.refit / ms_refit, then skh_update_accel (additive: refit = 2), then skh_set_environment / _transform / skh_get_environment_info + two unit probes (additive), then skh_set_emission / skh_get_emitter_info / skh_emitter_probe (additive); options curve_merge, curve_segnode, curve_strand_major, split_pairs.  4 (round 5): + skh_get_build_info; options reinsert_rounds, reinsert_min_size; wide, tail_park, tail_lag removed.  3 (round 4): + skh_unit_probe, skh_copy_aov */
+#define SKH_ABI_VERSION 5 /* 5 (round 6): + skh_refit_accel, skh_build_info.refit / ms_refit, then skh_update_accel (additive: refit = 2), then skh_set_environment / _transform / skh_get_environment_info + two unit probes (additive), then skh_set_emission / skh_get_emitter_info / skh_emitter_probe (additive), then skh_set_material_blend / skh_get_blend_info / skh_blend_probe (additive); options curve_merge, curve_segnode, curve_strand_major, split_pairs.  4 (round 5): + skh_get_build_info; options reinsert_rounds, reinsert_min_size; wide, tail_park, tail_lag removed.  3 (round 4): + skh_unit_probe, skh_copy_aov */
 
 /* mirrors oka::Result (include/render/common.h:30-35) */
 typedef enum skh_status
@@ -371,8 +371,8 @@ skh_status skh_material_probe(skh_context* ctx, uint32_t n, const uint32_t* mate
  *                 uses up a round like a rejected hit.
  *   emission      a material that both emits (skh_set_emission gave it an Le != 0) and has an active cutout is refused with SKH_INVALID_ARGUMENT, the message naming
  *                 the material, by the call that would use it: render, trace or info.
- * Not part of it: fractional or stochastic opacity (threshold 0 with opacity < 1, glTF BLEND), cutouts on curves, coloured transmission, an alpha test inside the
- * traversal loop. */
+ * Not part of it: cutouts on curves, coloured transmission, an alpha test inside the traversal loop.  (Fractional opacity -- threshold 0 with opacity < 1, glTF BLEND --
+ * is a table of its own: skh_set_material_blend, below.) */
 typedef struct skh_material_cutout
 {
     uint32_t opacity_texture;   /* 1-based into skh_set_textures' list; 0 or beyond the list = no texture: texel = 1 */
@@ -397,6 +397,55 @@ typedef struct skh_cutout_info
     uint64_t bytes; /* device memory of the continuation queues and the extra hit buffers */
 } skh_cutout_info;
 skh_status skh_get_cutout_info(skh_context* ctx, skh_cutout_info* out);
+
+/* ---- Fractional opacity: stochastic pass-through for radiance rays, transmittance for shadow rays (DESIGN.md section 2 "Fractional opacity") ----
+ * What glTF's alphaMode BLEND, OmniPBR's enable_opacity without a threshold and UsdPreviewSurface's opacity < 1 without an opacityThreshold ask for: smoke cards, decals,
+ * soft-edged leaf and hair cards, gauze.  Not refraction: the ray goes straight on.  The same stage as the cutouts (k_cutout, its BLEND build), the same continuation
+ * rounds, the same round limit; one entry per material, indexed as the material list is; 32 B.
+ *   opacity       a = clamp01(scale * texel + bias), product and sum rounded separately; the texel as the cutouts look it up (tex_lookup_rgba8 at the hit's interpolated
+ *                 text_coords[0]); no texture: texel = 1.  Hits on mesh instances only (SKH_INSTANCE_MESH): curves and light proxies are never blended.
+ *   radiance rays take the hit iff xi < a (a = 1 always, a = 0 never).  A ray that does not goes on as a cut-away ray does: same origin and direction, tmin = t, same
+ *                 tmax, its queue position kept; depth, sampler dimensions, lastBsdfPdf, the MIS distance of an emitter hit and the next bounce's offset_ray are
+ *                 those of the ray that produced the accepted hit.  An accepted hit is shaded at full weight (no factor a): E = a * shade + (1 - a) * behind.
+ *   the draw      xi = (h >> 8) * 2^-24, h = hash_murmur(hash_combine(hash_combine(hash_murmur(sampleIdx ^ 0xb5297a4d), depth), round)); sampleIdx is the sampler's
+ *                 (encode_morton2(px, py) * spp_total + pixel sample index), depth the bounce whose trace launch produced the record, round the number of hits this
+ *                 ray has already passed.  A pure function of the path and the ray's progress: it does not depend on scheduling, sub-frame batching, speculation or
+ *                 tile ownership.  White noise, not a Sobol dimension.  (strelka_amd/csrc/skh_blend.h, which a host program compiles too; skh_blend_probe evaluates it on the device.)
+ *   shadow rays   attenuated, not gambled: occluded iff an opaque hit lies in (tmin, tmax] -- a material without a blend entry, a blend hit with a >= 1, a cutout that
+ *                 accepts.  Otherwise the light sample's contribution is multiplied, per blend hit crossed and in order of increasing t, by w = 1 - a: one rounded
+ *                 subtraction, one rounded product per channel.  a = 0 leaves its bits unchanged.
+ *   round limit   cutout_rounds, shared with the cutouts: every passed hit -- cut away, blended, or a light proxy in a shadow ray's way -- uses up a round.  After that
+ *                 many the next hit is accepted whatever its opacity, and a shadow ray is occluded by it (a light proxy still does not occlude).
+ *   raw queries   skh_trace / skh_trace_device have no sample: a blend hit counts iff a > 0, in both modes.
+ *   refused       with SKH_INVALID_ARGUMENT, the message naming the material, by the call that would use it (render, trace, info): a material with both an active
+ *                 cutout and an active blend entry; a material that emits and has an active blend entry.
+ * Not part of it: coloured transmission, blending on curves, stratified draws. */
+typedef struct skh_material_blend
+{
+    uint32_t opacity_texture;   /* 1-based into skh_set_textures' list; 0 or beyond the list = no texture: texel = 1 */
+    uint32_t opacity_channel;   /* 0..3 = r, g, b, a */
+    float opacity_scale, opacity_bias; /* a = clamp01(scale * texel + bias), product and sum rounded separately */
+    uint32_t active;            /* 0 = opaque (the entry is ignored), 1 = blended */
+    uint32_t reserved[3];       /* must be 0 */
+} skh_material_blend;
+/* n_materials <= the material count; materials beyond n are opaque.  NULL or 0 removes the table; a table in which no entry is active, or whose active materials no mesh
+ * instance uses, equals no table: the context launches the kernels and produces the bits of one that never had any (with threshold cutouts alone in use: the stage of
+ * before, k_cutout's build without BLEND).  A channel above 3, a scale or bias that is not finite, active > 1 or a non-zero reserved word is refused with
+ * SKH_INVALID_ARGUMENT and leaves the previous table in place.  Discards sub-frames traced ahead; never touches the acceleration structures or the emitter table.
+ * Whether blending is in use is derived data, recomputed after the calls that make the cutouts' stale. */
+skh_status skh_set_material_blend(skh_context* ctx, const skh_material_blend* entries, uint32_t n_materials);
+typedef struct skh_blend_info
+{
+    uint32_t active_materials; /* entries with active = 1 (inside the material list) */
+    uint32_t instances; /* mesh instances that use one of them; 0: blending is not in use */
+    uint64_t passed_radiance; /* radiance rays that went on through a blend hit (xi >= a), since the last skh_reset_stats */
+    uint64_t crossed_shadow; /* blend hits shadow rays crossed (each scaled the contribution by 1 - a) */
+    uint64_t accepted_by_cap; /* blend hits the draw (or, for a shadow ray, a < 1) would have passed and the round limit accepted */
+    uint64_t bytes; /* device memory of the stage's buffers: the continuation queues and extra hit buffers it shares with the cutouts (skh_cutout_info.bytes counts the same ones) */
+} skh_blend_info;
+skh_status skh_get_blend_info(skh_context* ctx, skh_blend_info* out);
+/* The draw, evaluated on the device by the function k_cutout calls: in = n x {px, py, pixel sample index, spp_total, depth, round}, xi = n floats in [0, 1). */
+skh_status skh_blend_probe(skh_context* ctx, uint32_t n, const uint32_t* in, float* xi);
 
 /* ---- createAccelerationStructure (OptixRender.cpp:388-496): per-mesh / per-curve BLAS + one TLAS ---- */
 skh_status skh_build_accel(skh_context* ctx, uint32_t flags);

@@ -206,6 +206,7 @@ void HipRender::uploadMaterials()
     std::vector<float> emission; // 3 per material: skh_set_emission, after the materials
     std::vector<skh_material_textures> mtex; // one per material: skh_set_material_textures, after the materials
     std::vector<skh_material_cutout> cutouts; // one per material: skh_set_material_cutouts, after the materials
+    std::vector<skh_material_blend> blends; // one per material, with setAlphaBlend(true) only: skh_set_material_blend, after the materials
 #ifdef SKH_WITH_STRELKA_HEADERS
     // every eTexture parameter becomes one RGBA8 texture (OptixRender.cpp:1346-1377: resolved against resource/searchPath, stbi_load
     // with STBI_rgb_alpha); a file that cannot be read is reported and the material keeps its constant colour (:1195-1199)
@@ -230,7 +231,7 @@ void HipRender::uploadMaterials()
     for (const Scene::MaterialDescription& d : sc.getMaterials())
     {
         const uint32_t diffuseId = load(skhmat::texturePath(d, "diffuse_texture")), normalId = load(skhmat::texturePath(d, "normalmap_texture"));
-        mats.push_back(skhmat::translate(d, diffuseId, normalId));
+        mats.push_back(skhmat::translate(d, diffuseId, normalId, mAlphaBlend));
         float le[3];
         skhmat::emission(d, le);
         emission.insert(emission.end(), le, le + 3);
@@ -238,6 +239,13 @@ void HipRender::uploadMaterials()
         mtex.push_back(skhmat::materialTextures(d, load));
         // cutout opacity (OmniPBR enable_opacity / opacity_threshold, UsdPreviewSurface opacityThreshold): its map likewise
         cutouts.push_back(skhmat::materialCutout(d, load));
+        // fractional opacity (an opacity without a threshold), behind the switch: its map likewise; a blended material does not emit
+        if (mAlphaBlend)
+        {
+            blends.push_back(skhmat::materialBlend(d, load));
+            if (blends.back().active)
+                std::fill(emission.end() - 3, emission.end(), 0.0f);
+        }
     }
     for (size_t k = 0; k < tex.size(); ++k)
         tex[k].rgba8 = pixels[k].data();
@@ -266,6 +274,9 @@ void HipRender::uploadMaterials()
     // cutouts (no entry is active = none: likewise)
     const bool cut = std::any_of(cutouts.begin(), cutouts.end(), [](const skh_material_cutout& e) { return e.threshold > 0.0f; });
     check(skh_set_material_cutouts(mCtx, cut ? cutouts.data() : nullptr, cut ? (uint32_t)cutouts.size() : 0u), "skh_set_material_cutouts");
+    // fractional opacity (the switch is off, or no entry is active = none: likewise)
+    const bool blend = std::any_of(blends.begin(), blends.end(), [](const skh_material_blend& e) { return e.active != 0u; });
+    check(skh_set_material_blend(mCtx, blend ? blends.data() : nullptr, blend ? (uint32_t)blends.size() : 0u), "skh_set_material_blend");
 }
 
 static void environmentRotation(const float* worldToEnv, float out[9])

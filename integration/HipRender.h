@@ -83,6 +83,13 @@ public:
     bool setEnvironment(const float* rgb, uint32_t width, uint32_t height, const float scale[3], const float* worldToEnv = nullptr);
     // the same map under a new intensity x colour and rotation: no table rebuild (a viewer spinning its dome)
     bool setEnvironmentTransform(const float scale[3], const float* worldToEnv = nullptr);
+    // Fractional opacity (skh_set_material_blend), OFF by default: with it, a material description whose opacity has no threshold -- OmniPBR enable_opacity without
+    // opacity_threshold, UsdPreviewSurface opacity < 1 without opacityThreshold -- is uploaded as a PBR material with a blend entry (skhmat::materialBlend), not as
+    // glass or opaque.  Call before init() / before the materials are uploaded.
+    void setAlphaBlend(bool on)
+    {
+        mAlphaBlend = on;
+    }
 
 private:
     skh_context* mCtx = nullptr;
@@ -106,6 +113,7 @@ private:
     // skh_update_accel (in place where it can); true = something was sent
     bool sendMovedInstances();
     std::vector<skh_instance> mSentInstances;
+    bool mAlphaBlend = false;
     void uploadMaterials(); // MaterialDescription list -> skh_material blocks + textures (OptixRender.cpp:1270-1433)
 };
 

@@ -9,6 +9,7 @@
 //                                                         (sceneloader/gltfloader.cpp:304-352)                            -> SKH_MAT_PBR
 //           its roughness / metallic / ORM / emissive maps                                                               -> skh_material_textures (materialTextures below)
 //           enable_opacity + opacity_threshold [opacity_texture]; UsdPreviewSurface opacityThreshold                       -> skh_material_cutout (materialCutout below)
+//           enable_opacity without a threshold; UsdPreviewSurface opacity < 1 without one (behind HipRender::setAlphaBlend)   -> skh_material_blend (materialBlend below)
 //   OmniGlass.{glass_color, glass_ior, frosting_roughness} (gltfloader.cpp:354-406)                                      -> SKH_MAT_GLASS
 //   UsdPreviewSurface parameter sets (HdStrelka's eMaterialX descriptions, HdStrelka/Material.cpp:52-150)                -> PBR | GLASS
 //   names containing "hair" (the `hair` sub-expression, materialmanager/mdlPtxCodeGen.cpp:143-155)                       -> SKH_MAT_HAIR
@@ -92,7 +93,8 @@ inline std::string texturePath(const Desc& d, const char* name)
 }
 
 template <class Desc>
-inline skh_material translate(const Desc& d, uint32_t diffuseTextureId = 0, uint32_t normalTextureId = 0)
+// `alphaBlend` (HipRender::setAlphaBlend, off by default): a UsdPreviewSurface whose opacity is a blend entry's (materialBlend below) is PBR, not glass.
+inline skh_material translate(const Desc& d, uint32_t diffuseTextureId = 0, uint32_t normalTextureId = 0, bool alphaBlend = false)
 {
     skh_material m;
     memset(&m, 0, sizeof(m));
@@ -106,7 +108,7 @@ inline skh_material translate(const Desc& d, uint32_t diffuseTextureId = 0, uint
     {
         // UsdPreviewSurface spec defaults: diffuseColor 0.18, roughness 0.5, metallic 0, ior 1.5, opacity 1 (< 0.5 is treated as glass -- unless an
         // opacityThreshold > 0 makes the opacity a cutout's: materialCutout)
-        m.type = (scalar(d, "opacity", 1.0f) < 0.5f && !(scalar(d, "opacityThreshold", 0.0f) > 0.0f)) ? SKH_MAT_GLASS : SKH_MAT_PBR;
+        m.type = (scalar(d, "opacity", 1.0f) < 0.5f && !(scalar(d, "opacityThreshold", 0.0f) > 0.0f) && !alphaBlend) ? SKH_MAT_GLASS : SKH_MAT_PBR;
         color(d, "diffuseColor", m.base_color, 0.18f, 0.18f, 0.18f);
         m.roughness = scalar(d, "roughness", 0.5f);
         m.metallic = scalar(d, "metallic", 0.0f);
@@ -290,6 +292,54 @@ inline skh_material_cutout materialCutout(const Desc& d, TextureId&& textureId)
     }
     else
         e.opacity_scale = 0.0f, e.opacity_bias = scalar(d, "opacity_constant", 1.0f);
+    return e;
+}
+
+// The description's blend entry (skh_set_material_blend's entry for the material; active 0 = none) -- the C++ statement of
+// strelka_amd/scene_io.py::material_blend_from_description: the cases materialCutout leaves, an opacity WITHOUT a threshold.
+//   OmniPBR, enable_opacity and no opacity_threshold > 0   -> with enable_opacity_texture and an opacity_texture that loads: that texture, channel a for opacity_mode 0,
+//                                                             else r, scale = opacity_scale (default 1), bias 0; without one: scale 0, bias = opacity_constant
+//                                                             (default 1) -- inactive when that constant is 1 or more
+//   UsdPreviewSurface, opacity < 1, no opacityThreshold > 0 -> no texture, scale 0, bias = opacity
+template <class Desc, class TextureId>
+inline skh_material_blend materialBlend(const Desc& d, TextureId&& textureId)
+{
+    skh_material_blend e;
+    memset(&e, 0, sizeof(e));
+    e.opacity_channel = 3u;
+    e.opacity_scale = 1.0f;
+    std::string low = d.name + " " + d.file;
+    std::transform(low.begin(), low.end(), low.begin(), [](unsigned char c) { return (char)tolower(c); });
+    const bool preview = find(d, "diffuseColor") || find(d, "useSpecularWorkflow") || find(d, "specularColor") || find(d, "clearcoat") ||
+                         find(d, "emissiveColor");
+    if (preview)
+    {
+        const float opacity = scalar(d, "opacity", 1.0f);
+        if (opacity < 1.0f && !(scalar(d, "opacityThreshold", 0.0f) > 0.0f))
+            e.opacity_scale = 0.0f, e.opacity_bias = opacity, e.active = 1u;
+        return e;
+    }
+    if (low.find("glass") != std::string::npos || low.find("pbr") == std::string::npos || scalar(d, "enable_opacity", 0.0f) == 0.0f ||
+        scalar(d, "opacity_threshold", 0.0f) > 0.0f)
+        return e;
+    uint32_t t = 0u;
+    if (scalar(d, "enable_opacity_texture", 0.0f) != 0.0f)
+    {
+        const std::string path = texturePath(d, "opacity_texture");
+        t = path.empty() ? 0u : (uint32_t)textureId(path);
+    }
+    if (t)
+    {
+        e.opacity_texture = t, e.opacity_channel = scalar(d, "opacity_mode", 0.0f) == 0.0f ? 3u : 0u;
+        e.opacity_scale = scalar(d, "opacity_scale", 1.0f);
+        e.active = 1u;
+    }
+    else
+    {
+        const float c = scalar(d, "opacity_constant", 1.0f);
+        if (c < 1.0f)
+            e.opacity_scale = 0.0f, e.opacity_bias = c, e.active = 1u;
+    }
     return e;
 }
 } // namespace skhmat

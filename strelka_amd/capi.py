@@ -29,7 +29,8 @@ SYMBOLS = ["skh_create", "skh_destroy", "skh_last_error", "skh_abi_version", "sk
            "skh_comm_destroy", "skh_gather_tiles", "skh_host_register", "skh_host_unregister", "skh_get_baked", "skh_comm_info", "skh_probe_memory", "skh_unit_probe", "skh_copy_aov", "skh_get_build_info", "skh_refit_accel",
            "skh_update_accel", "skh_set_environment", "skh_set_environment_transform", "skh_get_environment_info",
            "skh_set_emission", "skh_get_emitter_info", "skh_emitter_probe",
-           "skh_set_material_textures", "skh_material_probe", "skh_set_material_cutouts", "skh_get_cutout_info"]
+           "skh_set_material_textures", "skh_material_probe", "skh_set_material_cutouts", "skh_get_cutout_info",
+           "skh_set_material_blend", "skh_get_blend_info", "skh_blend_probe"]
 
 BUILD_INFO = np.dtype([("triangles", np.uint32), ("nodes", np.uint32), ("reinsert_rounds", np.uint32), ("reinsert_moves", np.uint32),
                        ("reinsert_min_size", np.uint32), ("refit", np.uint32), ("cost_before", np.float64), ("cost_after", np.float64),
@@ -40,6 +41,8 @@ DEVICE_INFO = np.dtype([("compute_units", np.uint32), ("simds_per_cu", np.uint32
 ENVIRONMENT_INFO = np.dtype([("width", np.uint32), ("height", np.uint32), ("sum_w", np.float64), ("ms_build", np.float64), ("bytes", np.uint64)])
 CUTOUT_INFO = np.dtype([("active_materials", np.uint32), ("instances", np.uint32), ("continued_closest", np.uint64), ("continued_shadow", np.uint64),
                         ("accepted_by_cap", np.uint64), ("bytes", np.uint64)])
+BLEND_INFO = np.dtype([("active_materials", np.uint32), ("instances", np.uint32), ("passed_radiance", np.uint64), ("crossed_shadow", np.uint64),
+                       ("accepted_by_cap", np.uint64), ("bytes", np.uint64)])
 EMITTER_INFO = np.dtype([("triangles", np.uint32), ("instances", np.uint32), ("sum_w", np.float64), ("ms_build", np.float64), ("bytes", np.uint64)])
 # skh_emitter_probe: kind -> (number, words in, words out) per record
 EMIT_PROBES = {"sample": (0, 6, 13), "pdf": (1, 8, 4)}
@@ -99,6 +102,9 @@ def load():
     lib.skh_material_probe.argtypes = [vp, u32, vp, vp, vp]
     lib.skh_set_material_cutouts.argtypes = [vp, vp, u32]
     lib.skh_get_cutout_info.argtypes = [vp, vp]
+    lib.skh_set_material_blend.argtypes = [vp, vp, u32]
+    lib.skh_get_blend_info.argtypes = [vp, vp]
+    lib.skh_blend_probe.argtypes = [vp, u32, vp, vp]
     lib.skh_resize.argtypes = [vp, u32, u32]
     lib.skh_set_tiles.argtypes = [vp, u32, vp, u32]
     lib.skh_render_subframe.argtypes = [vp, vp, vp]
@@ -197,6 +203,7 @@ class Context:
         self.set_emission(arr.get("emission"))  # (likewise: a scene without emissive materials removes what a reused context holds)
         self.set_material_textures(arr.get("material_textures"))  # (likewise)
         self.set_material_cutouts(arr.get("material_cutouts"))  # (likewise)
+        self.set_material_blend(arr.get("material_blend"))  # (likewise)
         if build:
             self.build_accel(flags)
 
@@ -293,6 +300,28 @@ class Context:
         d = np.zeros((), CUTOUT_INFO)
         self._ck(self.lib.skh_get_cutout_info(self.h, _p(d)), "skh_get_cutout_info")
         return {k: int(d[k]) for k in CUTOUT_INFO.names}
+
+    def set_material_blend(self, table):
+        """skh_set_material_blend: `table` an S.MATERIAL_BLEND array, one entry per material (None or empty removes the table)"""
+        if table is None or len(table) == 0:
+            self._ck(self.lib.skh_set_material_blend(self.h, None, 0), "skh_set_material_blend")
+            return
+        t = np.ascontiguousarray(table, S.MATERIAL_BLEND).reshape(-1)
+        self._ck(self.lib.skh_set_material_blend(self.h, _p(t), len(t)), "skh_set_material_blend")
+
+    def blend_info(self):
+        """skh_get_blend_info: materials with an active blend entry, mesh instances using them, radiance rays passed / shadow crossings / hits accepted by
+        the round limit since the last reset_stats"""
+        d = np.zeros((), BLEND_INFO)
+        self._ck(self.lib.skh_get_blend_info(self.h, _p(d)), "skh_get_blend_info")
+        return {k: int(d[k]) for k in BLEND_INFO.names}
+
+    def blend_probe(self, tuples):
+        """skh_blend_probe: the draw on the device for (n, 6) uint32 {px, py, pixel sample index, spp_total, depth, round} -> (n,) float32 xi"""
+        t = np.ascontiguousarray(tuples, np.uint32).reshape(-1, 6)
+        out = np.zeros(len(t), np.float32)
+        self._ck(self.lib.skh_blend_probe(self.h, len(t), _p(t), _p(out)), "skh_blend_probe")
+        return out
 
     def material_probe(self, material, uv):
         """skh_material_probe: the device function k_shade calls for a triangle hit of material[i] at uv[i] -> (n, 8) float32:

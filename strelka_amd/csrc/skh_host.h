@@ -131,6 +131,12 @@ struct skh_context
     bool cutStale = false;
     uint32_t cutActiveMaterials = 0, cutInstances = 0; // cutInstances != 0: a cutout is in use
     uint32_t cutoutRounds = 8; // option cutout_rounds
+    // fractional opacity (skh_set_material_blend): the table as the caller gave it and its device copy, one packed uint4 per material (BlendP).  Whether blending is IN
+    // USE is derived with the cutouts' (cut_ensure): the stage runs -- and its buffers exist -- when a cutout OR a blend entry is in use (cut_stage_on); its BLEND build
+    // is launched only when a blend entry is
+    std::vector<skh_material_blend> blends;
+    DevBuf dBlend;
+    uint32_t blendActiveMaterials = 0, blendInstances = 0; // blendInstances != 0: blending is in use
     // Speculative sub-frame batching for the reference's call pattern (one render() per sub-frame, RenderPass.cpp:441-447): once two
     // consecutive calls continue the same frame (same parameters, subframe_index + 1), the next call traces several sub-frames
     // ahead in ONE wavefront pass and the calls after it only apply their accumulation step to the radiances already in the path

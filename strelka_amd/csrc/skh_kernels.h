@@ -18,6 +18,7 @@
 #include "skh_bvh.h"
 #include "skh_env.h"
 #include "skh_emit.h"
+#include "skh_blend.h"
 
 namespace skh
 {
@@ -1593,7 +1594,38 @@ struct CutoutP // by-value kernel argument
 struct CutStatsDev // rays continued (their hit was cut away) and rays whose hit the last round accepted although it is cut away: [0] closest, [1] shadow
 {
     unsigned long long continued[2], capped[2];
+    // behind them, fractional opacity (the BLEND build): radiance rays that went on through a blend hit, blend hits shadow rays crossed, blend hits the round limit accepted
+    unsigned long long blendPassed, blendCrossed, blendCapped;
 };
+// Fractional opacity -- skh_set_material_blend; DESIGN.md section 2 "Fractional opacity" is the definition.  k_cutout's BLEND build reads this next to the cutout table:
+// a hit on a mesh instance of a material with an active entry has an opacity a = clamp01(scale * texel + bias).  A radiance ray takes it iff blend_xi(path, depth,
+// round) < a (skh_blend.h) and goes on like a cut-away ray otherwise; a shadow ray crosses it when a < 1, its contribution record scaled by 1 - a.
+struct BlendP // by-value kernel argument; all zero in a launch of the build without BLEND
+{
+    const uint4* table; // 1 per material: {texture, channel | active << 31, scale, bias}
+    uint32_t count;
+    uint32_t raw; // a raw query (skh_trace): no sample -- a blend hit counts iff a > 0, in both modes
+    uint32_t depth, round; // the bounce whose trace launch produced the records; hits the rays of this launch have already passed
+    // the path's identity, as k_shade derives it: the path id at the ray's original position -> sub-frame and slot -> pixel -> the sampler's sampleIdx
+    const uint32_t* pathIds; // the id plane of the queue the frame filled
+    const uint32_t* tileXY;
+    uint32_t sampleBase, sppTotal, numSlots, tileShift; // sampleBase = subframeIndex + sampleOffset
+    float4* contrib; // (shadow side) the contribution records, writable: rewritten by the lane that owns the ray
+};
+// text_coords[0] of a triangle hit and the texel's channel there, as the cutout test above reads it
+SKH_DI float blend_texel(const DevScene& sc, uint32_t texture, uint32_t channel, uint32_t hprim, uint32_t recBase, float bu, float bv)
+{
+    const uint32_t recIdx = (hprim & SKH_PRIM_DIRECT) ? (hprim & ~SKH_PRIM_DIRECT) : recBase + hprim;
+    const float4* __restrict__ tp = sc.shadeTris + 6 * (size_t)recIdx;
+    const float4 t3 = tp[3], t4 = tp[4];
+    float u0, v0, u1, v1, u2, v2;
+    unpack_uv(__float_as_uint(t3.w), u0, v0);
+    unpack_uv(__float_as_uint(t4.x), u1, v1);
+    unpack_uv(__float_as_uint(t4.y), u2, v2);
+    const float bw = 1.0f - bu - bv;
+    const v4 c = tex_lookup_rgba8(sc.texels, sc.texDesc[texture - 1u], (u0 * bw + u1 * bu) + u2 * bv, (v0 * bw + v1 * bu) + v2 * bv);
+    return mtex_channel(c, channel);
+}
 #define SKH_CUTOUT_LDS 128 // entries k_cutout stages in LDS (4 KB); materials beyond them read global memory
 #define SKH_CUTOUT_BLOCK 256
 // SHADOW = false: `hq` holds the closest hits of the rays of `rq`.  A final record (accepted hit, miss, curve or light-proxy hit) of a CONTINUED ray is copied to
@@ -1602,12 +1634,15 @@ struct CutStatsDev // rays continued (their hit was cut away) and rays whose hit
 //   query mode (rawOut), answers -1; an accepted hit answers 1 there and is nothing otherwise; a hit on a light proxy passes through like a rejected one.
 // first: rq is the queue the frame (or the query) filled: a ray's original position is its own.  last: the round limit is reached: every hit is accepted
 // (a light proxy in a shadow ray's way still does not occlude).
-template <bool SHADOW>
+// BLEND = false is the stage of a context with threshold cutouts alone: none of the `if constexpr (BLEND)` blocks exists in it and `bl` is not looked at.
+// BLEND = true also reads the blend table (1 uint4 per material, staged beside the cutout table: 2 KB more LDS) -- see BlendP.
+template <bool SHADOW, bool BLEND>
 __global__ void __launch_bounds__(SKH_CUTOUT_BLOCK) k_cutout(DevScene sc, CutoutP cut, RayQ rq, const uint32_t* __restrict__ countPtr, HitQ hq, uint32_t first, uint32_t last,
                                                              HitQ outHq, float* __restrict__ rawOut, PathS ps, const float4* __restrict__ contrib, RayQ nextQ,
-                                                             uint32_t* __restrict__ nextCount, CutStatsDev* __restrict__ stats)
+                                                             uint32_t* __restrict__ nextCount, CutStatsDev* __restrict__ stats, BlendP bl)
 {
     __shared__ uint4 s_cut[2 * SKH_CUTOUT_LDS];
+    __shared__ uint4 s_blend[BLEND ? SKH_CUTOUT_LDS : 1];
     const uint32_t shard = blockIdx.x & (SKH_SHARDS - 1u), lb = blockIdx.x / SKH_SHARDS;
     const uint32_t n = min(countPtr[shard * SKH_COUNT_STRIDE], rq.region); // rays in this shard
     if (lb * blockDim.x >= n)
@@ -1615,11 +1650,17 @@ __global__ void __launch_bounds__(SKH_CUTOUT_BLOCK) k_cutout(DevScene sc, Cutout
     static_assert(2 * SKH_CUTOUT_LDS <= SKH_CUTOUT_BLOCK, "one uint4 of the cutout table per thread");
     if (threadIdx.x < 2u * min(cut.count, (uint32_t)SKH_CUTOUT_LDS))
         s_cut[threadIdx.x] = cut.table[threadIdx.x];
+    if constexpr (BLEND)
+    {
+        if (threadIdx.x < min(bl.count, (uint32_t)SKH_CUTOUT_LDS))
+            s_blend[threadIdx.x] = bl.table[threadIdx.x];
+    }
     __syncthreads();
     const uint32_t il = lb * blockDim.x + threadIdx.x;
     const uint32_t i = shard * rq.region + il;
     const bool valid = il < n;
     bool requeue = false, cutAway = false, capped = false;
+    bool blendPass = false, blendCap = false; // (BLEND) the hit is a blend hit this ray does not take: it goes on / the round limit accepts it
     float ht = 0.0f;
     uint32_t orig = 0;
     if (valid)
@@ -1681,11 +1722,55 @@ __global__ void __launch_bounds__(SKH_CUTOUT_BLOCK) k_cutout(DevScene sc, Cutout
                     const float opacity = saturatef(__fadd_rn(__fmul_rn(__uint_as_float(a.z), texel), __uint_as_float(a.w)));
                     reject = !(opacity >= threshold);
                 }
+                if constexpr (BLEND)
+                {
+                    // (a material has an active cutout or an active blend entry, never both: refused by the host)
+                    uint4 e = make_uint4(0u, 0u, 0u, 0u);
+                    if (mid < bl.count)
+                        e = mid < (uint32_t)SKH_CUTOUT_LDS ? s_blend[mid] : bl.table[mid];
+                    if ((e.y >> 31) != 0u)
+                    {
+                        const float texel = mtex_valid(e.x, sc.numTextures) ? blend_texel(sc, e.x, e.y & 3u, hprim, recBase, r0.y, r0.z) : 1.0f;
+                        const float a = saturatef(__fadd_rn(__fmul_rn(__uint_as_float(e.z), texel), __uint_as_float(e.w)));
+                        bool pass;
+                        if (bl.raw)
+                            pass = !(a > 0.0f);
+                        else if constexpr (SHADOW)
+                        {
+                            pass = a < 1.0f;
+                            if (pass && !last)
+                            {
+                                // transmittance: one rounded subtraction, one rounded product per channel; the record is this ray's own
+                                const float w = __fsub_rn(1.0f, a);
+                                float4 cw = bl.contrib[orig];
+                                cw.x = __fmul_rn(cw.x, w), cw.y = __fmul_rn(cw.y, w), cw.z = __fmul_rn(cw.z, w);
+                                bl.contrib[orig] = cw;
+                            }
+                        }
+                        else
+                        {
+                            const uint32_t pid = bl.pathIds[orig];
+                            const uint32_t sub = pid / bl.numSlots, slot = pid - sub * bl.numSlots;
+                            // (slot_to_pixel)
+                            const uint32_t tile = slot >> (2 * bl.tileShift), m = slot & ((1u << (2 * bl.tileShift)) - 1u);
+                            const uint32_t px = bl.tileXY[2 * tile] + compact1by1(m), py = bl.tileXY[2 * tile + 1] + compact1by1(m >> 1);
+                            const Sampler smp = init_sampler(px, py, bl.sampleBase + sub, bl.sppTotal, 52u);
+                            pass = !(blend_xi(smp.sampleIdx, bl.depth, bl.round) < a);
+                        }
+                        reject = pass;
+                        blendPass = pass && !last, blendCap = pass && last;
+                    }
+                }
             }
         }
         cutAway = reject && !last;
         capped = reject && last;
         requeue = (reject || proxy) && !last;
+        if constexpr (BLEND)
+        {
+            if (blendPass || blendCap)
+                cutAway = capped = false; // (counted on their own, below)
+        }
         const bool unoccluded = miss || (proxy && last);
         if constexpr (SHADOW)
         {
@@ -1741,6 +1826,28 @@ __global__ void __launch_bounds__(SKH_CUTOUT_BLOCK) k_cutout(DevScene sc, Cutout
         if (mk != 0ull)
             atomicAdd(&stats->capped[SHADOW ? 1 : 0], (unsigned long long)__popcll(mk));
     }
+    if constexpr (BLEND)
+    {
+        const unsigned long long mp = __ballot(blendPass), mb = __ballot(blendCap);
+        if ((threadIdx.x & 63u) == 0u)
+        {
+            if (mp != 0ull)
+                atomicAdd(SHADOW ? &stats->blendCrossed : &stats->blendPassed, (unsigned long long)__popcll(mp));
+            if (mb != 0ull)
+                atomicAdd(&stats->blendCapped, (unsigned long long)__popcll(mb));
+        }
+    }
+}
+
+// skh_blend_probe: the draw as k_cutout evaluates it, for n x {px, py, pixel sample index, sppTotal, depth, round}
+__global__ void __launch_bounds__(256) k_blend_probe(uint32_t n, const uint32_t* __restrict__ in, float* __restrict__ xi)
+{
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n)
+        return;
+    const uint32_t* r = in + 6 * (size_t)i;
+    const Sampler smp = init_sampler(r[0], r[1], r[2], r[3], 52u);
+    xi[i] = blend_xi(smp.sampleIdx, r[4], r[5]);
 }
 
 // a constant plane of a ray queue (tmin / tmax of the radiance queues, tmin of the shadow queue): written when the queues are allocated or the

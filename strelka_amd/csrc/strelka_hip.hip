@@ -895,6 +895,56 @@ skh_status skh_set_material_cutouts(skh_context* c, const skh_material_cutout* e
     return SKH_OK;
 }
 
+// ---- fractional opacity: skh_set_material_blend, the BLEND build of k_cutout (skh_kernels.h) ----
+static_assert(sizeof(skh_material_blend) == 32, "skh_material_blend");
+
+skh_status skh_set_material_blend(skh_context* c, const skh_material_blend* entries, uint32_t n)
+{
+    if (!c)
+        return SKH_INVALID_ARGUMENT;
+    (void)hipSetDevice(c->device);
+    if (!entries || n == 0)
+    {
+        // remove: a no-op on a context that has none (nothing traced ahead is thrown away for it)
+        if (c->blends.empty())
+            return SKH_OK;
+        spec_drop(c);
+        SKH_TRY(c, hipStreamSynchronize(c->stream));
+        c->blends.clear();
+        dev_free(c->dBlend);
+        c->cutStale = true;
+        return SKH_OK;
+    }
+    if (n > c->nMaterials)
+    {
+        c->err = "skh_set_material_blend: " + std::to_string(n) + " entries for " + std::to_string(c->nMaterials) + " materials (call skh_set_materials first)";
+        return SKH_INVALID_ARGUMENT;
+    }
+    std::vector<uint4> packed(n);
+    for (uint32_t k = 0; k < n; ++k)
+    {
+        const skh_material_blend& e = entries[k];
+        if (e.opacity_channel > 3u || !std::isfinite(e.opacity_scale) || !std::isfinite(e.opacity_bias) || e.active > 1u || e.reserved[0] != 0u || e.reserved[1] != 0u ||
+            e.reserved[2] != 0u)
+        {
+            c->err = "skh_set_material_blend: material " + std::to_string(k) + ": a channel above 3, a scale or bias that is not finite, active above 1 or a non-zero reserved word";
+            return SKH_INVALID_ARGUMENT;
+        }
+        uint32_t sb, bb;
+        memcpy(&sb, &e.opacity_scale, 4);
+        memcpy(&bb, &e.opacity_bias, 4);
+        packed[k] = make_uint4(e.opacity_texture, e.opacity_channel | (e.active << 31), sb, bb);
+    }
+    spec_drop(c);
+    SKH_TRY(c, hipStreamSynchronize(c->stream)); // (the table is about to be replaced)
+    DevBuf d;
+    SKH_CHECK(dev_upload(c, d, packed.data(), sizeof(uint4) * (size_t)n));
+    c->dBlend = std::move(d);
+    c->blends.assign(entries, entries + n);
+    c->cutStale = true;
+    return SKH_OK;
+}
+
 // Is a cutout in use (derived: an active entry on a material that a mesh instance uses)?  And the one combination that is refused: a material that emits and is cut.
 static skh_status cut_ensure(skh_context* c)
 {
@@ -913,8 +963,38 @@ static skh_status cut_ensure(skh_context* c)
                 users += (mid < nTab && c->cutouts[mid].threshold > 0.0f) ? 1u : 0u;
             }
         c->cutActiveMaterials = active, c->cutInstances = users;
+        // fractional opacity: the same derivation over the blend table
+        const uint32_t nBl = (uint32_t)std::min<size_t>(c->blends.size(), c->nMaterials);
+        uint32_t bActive = 0, bUsers = 0;
+        for (uint32_t k = 0; k < nBl; ++k)
+            bActive += c->blends[k].active ? 1u : 0u;
+        if (bActive)
+            for (const skh_instance& in : c->instances)
+            {
+                if (in.type != SKH_INSTANCE_MESH)
+                    continue;
+                const uint32_t mid0 = in.material_id == 0xffffffffu ? 0u : in.material_id, mid = mid0 < c->nMaterials ? mid0 : 0u;
+                bUsers += (mid < nBl && c->blends[mid].active) ? 1u : 0u;
+            }
+        c->blendActiveMaterials = bActive, c->blendInstances = bUsers;
         c->cutStale = false;
     }
+    if (c->blendActiveMaterials)
+        for (uint32_t k = 0; k < c->blends.size() && k < c->nMaterials; ++k)
+        {
+            if (!c->blends[k].active)
+                continue;
+            if (k < c->cutouts.size() && c->cutouts[k].threshold > 0.0f)
+            {
+                c->err = "material " + std::to_string(k) + " has both an active cutout (skh_set_material_cutouts) and an active blend entry (skh_set_material_blend): one opacity rule per material";
+                return SKH_INVALID_ARGUMENT;
+            }
+            if (3 * (size_t)k + 2 < c->emission.size() && (c->emission[3 * (size_t)k] > 0.0f || c->emission[3 * (size_t)k + 1] > 0.0f || c->emission[3 * (size_t)k + 2] > 0.0f))
+            {
+                c->err = "material " + std::to_string(k) + " both emits (skh_set_emission) and has an active blend entry (skh_set_material_blend): blended emitters are not supported";
+                return SKH_INVALID_ARGUMENT;
+            }
+        }
     if (c->cutActiveMaterials && !c->emission.empty())
         for (uint32_t k = 0; k < c->cutouts.size() && k < c->nMaterials && 3 * (size_t)k + 2 < c->emission.size(); ++k)
             if (c->cutouts[k].threshold > 0.0f && (c->emission[3 * (size_t)k] > 0.0f || c->emission[3 * (size_t)k + 1] > 0.0f || c->emission[3 * (size_t)k + 2] > 0.0f))
@@ -925,6 +1005,12 @@ static skh_status cut_ensure(skh_context* c)
     return SKH_OK;
 }
 
+// does the stage between trace and shade run: is a cutout or a blend entry in use?
+static inline bool cut_stage_on(const skh_context* c)
+{
+    return c->cutInstances != 0u || c->blendInstances != 0u;
+}
+
 static CutoutP make_cutout(const skh_context* c)
 {
     CutoutP p;
@@ -933,17 +1019,30 @@ static CutoutP make_cutout(const skh_context* c)
     return p;
 }
 
+// the part of BlendP a context fixes; the caller adds what the launch fixes (raw or depth and the frame's constants, the contribution records), the chain the round
+static BlendP make_blend(const skh_context* c)
+{
+    BlendP p;
+    memset(&p, 0, sizeof(p));
+    if (c->blendInstances)
+    {
+        p.table = c->dBlend.as<uint4>();
+        p.count = (uint32_t)std::min<size_t>(c->blends.size(), c->nMaterials);
+    }
+    return p;
+}
+
 static size_t frame_count_words(const skh_context* c)
 {
     const size_t base = (size_t)SKH_COUNT_STRIDE * SKH_SHARDS * 2 * SKH_MAX_LAUNCH_ROUNDS + (size_t)16 * SKH_FETCH_STRIDE * SKH_MAX_LAUNCH_ROUNDS;
     // behind them, in a context with a cutout in use: per bounce and side (closest, shadow) cutout_rounds x {length words, fetch cursors}
-    return base + (c->cutInstances ? (size_t)SKH_MAX_LAUNCH_ROUNDS * 2 * c->cutoutRounds * SKH_CUT_WORDS : 0u);
+    return base + (cut_stage_on(c) ? (size_t)SKH_MAX_LAUNCH_ROUNDS * 2 * c->cutoutRounds * SKH_CUT_WORDS : 0u);
 }
 
 // the cutout stage's frame buffers: allocated when a cutout is in use (and only then), freed when none is any more
 static skh_status cut_alloc_frame(skh_context* c)
 {
-    if (!c->cutInstances)
+    if (!cut_stage_on(c))
     {
         if (c->dCutQ[0].p)
         {
@@ -987,6 +1086,40 @@ skh_status skh_get_cutout_info(skh_context* c, skh_cutout_info* out)
     out->continued_closest = sd.continued[0], out->continued_shadow = sd.continued[1];
     out->accepted_by_cap = sd.capped[0] + sd.capped[1];
     out->bytes = c->dCutQ[0].bytes + c->dCutQ[1].bytes + c->dCutHits.bytes + c->dCutShadowQ[0].bytes + c->dCutShadowQ[1].bytes + c->dCutShadowHits[0].bytes + c->dCutShadowHits[1].bytes;
+    return SKH_OK;
+}
+
+skh_status skh_get_blend_info(skh_context* c, skh_blend_info* out)
+{
+    if (!c || !out)
+        return SKH_INVALID_ARGUMENT;
+    memset(out, 0, sizeof(*out));
+    (void)hipSetDevice(c->device);
+    SKH_CHECK(cut_ensure(c));
+    CutStatsDev sd;
+    SKH_TRY(c, hipStreamSynchronize(c->stream));
+    SKH_TRY(c, hipMemcpy(&sd, c->dCutStats.p, sizeof(sd), hipMemcpyDeviceToHost));
+    out->active_materials = c->blendActiveMaterials, out->instances = c->blendInstances;
+    out->passed_radiance = sd.blendPassed, out->crossed_shadow = sd.blendCrossed, out->accepted_by_cap = sd.blendCapped;
+    out->bytes = c->dCutQ[0].bytes + c->dCutQ[1].bytes + c->dCutHits.bytes + c->dCutShadowQ[0].bytes + c->dCutShadowQ[1].bytes + c->dCutShadowHits[0].bytes +
+                 c->dCutShadowHits[1].bytes;
+    return SKH_OK;
+}
+
+skh_status skh_blend_probe(skh_context* c, uint32_t n, const uint32_t* in, float* xi)
+{
+    if (!c || (n && (!in || !xi)))
+        return SKH_INVALID_ARGUMENT;
+    if (!n)
+        return SKH_OK;
+    (void)hipSetDevice(c->device);
+    DevBuf dIn, dOut;
+    SKH_CHECK(dev_upload(c, dIn, in, sizeof(uint32_t) * 6 * (size_t)n));
+    SKH_CHECK(dev_alloc(c, dOut, sizeof(float) * (size_t)n));
+    k_blend_probe<<<(n + 255) / 256, 256, 0, c->stream>>>(n, dIn.as<uint32_t>(), dOut.as<float>());
+    SKH_TRY(c, hipGetLastError());
+    SKH_TRY(c, hipStreamSynchronize(c->stream));
+    SKH_TRY(c, hipMemcpy(xi, dOut.p, sizeof(float) * (size_t)n, hipMemcpyDeviceToHost));
     return SKH_OK;
 }
 
@@ -1284,22 +1417,34 @@ static void launch_trace(skh_context* c, const DevScene& sc, RayQ rq, const uint
 // queue into h2, k_cutout}.  `words`: cutout_rounds x SKH_CUT_WORDS zeroed words.  A round whose queue is empty costs two launches that return at once.
 template <bool SHADOW, bool COUNT>
 static void run_cutout_chain(skh_context* c, const DevScene& sc, const DevScene& scTrace, RayQ q0, const uint32_t* count0, HitQ h0, HitQ outH, float* rawOut, PathS ps,
-                             const float4* contrib, RayQ cq0, RayQ cq1, HitQ h2, uint32_t* words, uint32_t rays, hipStream_t st)
+                             const float4* contrib, RayQ cq0, RayQ cq1, HitQ h2, uint32_t* words, uint32_t rays, hipStream_t st, BlendP bl)
 {
     const CutoutP cutp = make_cutout(c);
+    // the BLEND build only where blending is in use (bl.count != 0: make_blend); round = hits the rays of a launch have already passed; the path ids lie in the first queue
+    const bool blend = bl.count != 0u;
+    bl.pathIds = reinterpret_cast<const uint32_t*>(q0.base + (size_t)8 * q0.stride);
     CutStatsDev* cst = c->dCutStats.as<CutStatsDev>();
     const uint32_t perShard = (((rays + SKH_SHARDS - 1u) / SKH_SHARDS) + 63u) & ~63u;
     const dim3 grid(SKH_SHARDS * ((std::min(perShard, q0.region) + SKH_CUTOUT_BLOCK - 1) / SKH_CUTOUT_BLOCK));
     const uint32_t R = c->cutoutRounds, QW = SKH_COUNT_STRIDE * SKH_SHARDS;
     const RayQ cq[2] = { cq0, cq1 };
-    k_cutout<SHADOW><<<grid, SKH_CUTOUT_BLOCK, 0, st>>>(sc, cutp, q0, count0, h0, 1u, 0u, outH, rawOut, ps, contrib, cq[0], words, cst);
+    bl.round = 0u;
+    if (blend)
+        k_cutout<SHADOW, true><<<grid, SKH_CUTOUT_BLOCK, 0, st>>>(sc, cutp, q0, count0, h0, 1u, 0u, outH, rawOut, ps, contrib, cq[0], words, cst, bl);
+    else
+        k_cutout<SHADOW, false><<<grid, SKH_CUTOUT_BLOCK, 0, st>>>(sc, cutp, q0, count0, h0, 1u, 0u, outH, rawOut, ps, contrib, cq[0], words, cst, bl);
     for (uint32_t r = 0; r < R; ++r)
     {
         uint32_t* lens = words + (size_t)r * SKH_CUT_WORDS;
         launch_trace<false, COUNT>(c, scTrace, cq[r & 1], lens, lens + QW, h2, ps, nullptr, st);
         const bool last = r + 1 == R;
-        k_cutout<SHADOW><<<grid, SKH_CUTOUT_BLOCK, 0, st>>>(sc, cutp, cq[r & 1], lens, h2, 0u, last ? 1u : 0u, outH, rawOut, ps, contrib, cq[(r + 1) & 1],
-                                                            last ? lens : lens + SKH_CUT_WORDS, cst);
+        bl.round = r + 1u;
+        if (blend)
+            k_cutout<SHADOW, true><<<grid, SKH_CUTOUT_BLOCK, 0, st>>>(sc, cutp, cq[r & 1], lens, h2, 0u, last ? 1u : 0u, outH, rawOut, ps, contrib, cq[(r + 1) & 1],
+                                                                      last ? lens : lens + SKH_CUT_WORDS, cst, bl);
+        else
+            k_cutout<SHADOW, false><<<grid, SKH_CUTOUT_BLOCK, 0, st>>>(sc, cutp, cq[r & 1], lens, h2, 0u, last ? 1u : 0u, outH, rawOut, ps, contrib, cq[(r + 1) & 1],
+                                                                       last ? lens : lens + SKH_CUT_WORDS, cst, bl);
     }
 }
 
@@ -1415,7 +1560,7 @@ static skh_status render_one(skh_context* c, const skh_frame_params* p, uint32_t
     const uint32_t rounds = fp.maxDepth;
     // Cutouts (skh_set_material_cutouts), only in a context where one is in use: k_cutout and its continuation rounds between a bounce's closest-hit launch and k_shade, and
     // a closest-hit launch with the same rounds behind it in the any-hit launch's place.  Per bounce and side cutout_rounds x SKH_CUT_WORDS words, behind the fetch cursors.
-    const bool cutOn = c->cutInstances != 0u;
+    const bool cutOn = cut_stage_on(c);
     const uint32_t cutBounceWords = 2u * c->cutoutRounds * SKH_CUT_WORDS;
     uint32_t* cutWords = fetch + 16 * SKH_FETCH_STRIDE * (rounds + 1);
     const RayQ cutQ[2] = { RayQ{ c->dCutQ[0].as<float>(), NQ, c->queueRegion }, RayQ{ c->dCutQ[1].as<float>(), NQ, c->queueRegion } };
@@ -1425,6 +1570,10 @@ static skh_status render_one(skh_context* c, const skh_frame_params* p, uint32_t
     DevScene scShadow = sc; // what the closest-hit launches of SHADOW rays walk: not the baked light proxies' tree (shadow rays do not see lights)
     if (c->worldRoot != SKH_REF_INVALID || c->tlasRoot != SKH_REF_INVALID)
         scShadow.lightRoot = SKH_REF_INVALID;
+    // fractional opacity (skh_set_material_blend), where it is in use: what the draw's path identity needs of the frame, and the contribution records, writable
+    BlendP blp = make_blend(c);
+    blp.tileXY = tiles, blp.sppTotal = fp.sppTotal, blp.numSlots = fp.numSlots, blp.tileShift = fp.tileShift;
+    blp.contrib = c->dContrib.as<float4>();
     c->splitNow = c->tailSplit < 0 && smallPass && NP >= (1u << 17);
     // One sub-frame of one sample, accumulated in this call (the reference caller's pattern): its sums ARE the path's radiance and event word -- the batch kernel reads
     // them where they lie (0.0f + radiance, / 1.0f: the same operations), and the k_collect launch and its 11 planes of sums are not needed.
@@ -1433,6 +1582,7 @@ static skh_status render_one(skh_context* c, const skh_frame_params* p, uint32_t
     {
         // (a cutout in use: the words of its continuation rounds lie behind the fetch cursors this sample uses -- one memset for all of them)
         SKH_TRY(c, hipMemsetAsync(counts, 0, sizeof(uint32_t) * (QW * 2 * SKH_MAX_LAUNCH_ROUNDS + 16 * SKH_FETCH_STRIDE * (rounds + 1) + (size_t)(cutOn ? rounds : 0u) * cutBounceWords), st));
+        blp.sampleBase = fp.subframeIndex + s;
         {
             SpanGuard g(c, KC_RAYGEN);
             k_raygen<<<c->raygenBlocksPerSub * fp.batch, 512, 0, st>>>(fp, tiles, s, rq[0], counts, ps, c->dRaygenBase.as<uint32_t>(),
@@ -1449,10 +1599,11 @@ static skh_status render_one(skh_context* c, const skh_frame_params* p, uint32_t
                     launch_trace<false, false>(c, sc, rq[b & 1], counts + 2 * b * QW, fetch + 16 * b * SKH_FETCH_STRIDE, hq, ps, nullptr);
                 if (cutOn)
                 {
+                    blp.depth = b;
                     if (c->countTraversal)
-                        run_cutout_chain<false, true>(c, sc, sc, rq[b & 1], counts + 2 * b * QW, hq, hq, nullptr, ps, nullptr, cutQ[0], cutQ[1], cutH, cutWords + (size_t)b * cutBounceWords, NP, st);
+                        run_cutout_chain<false, true>(c, sc, sc, rq[b & 1], counts + 2 * b * QW, hq, hq, nullptr, ps, nullptr, cutQ[0], cutQ[1], cutH, cutWords + (size_t)b * cutBounceWords, NP, st, blp);
                     else
-                        run_cutout_chain<false, false>(c, sc, sc, rq[b & 1], counts + 2 * b * QW, hq, hq, nullptr, ps, nullptr, cutQ[0], cutQ[1], cutH, cutWords + (size_t)b * cutBounceWords, NP, st);
+                        run_cutout_chain<false, false>(c, sc, sc, rq[b & 1], counts + 2 * b * QW, hq, hq, nullptr, ps, nullptr, cutQ[0], cutQ[1], cutH, cutWords + (size_t)b * cutBounceWords, NP, st, blp);
                 }
             }
             if (useOverlap && b > 0)
@@ -1518,12 +1669,12 @@ static skh_status render_one(skh_context* c, const skh_frame_params* p, uint32_t
                         if (c->countTraversal)
                         {
                             launch_trace<false, true>(c, scShadow, shq, counts + (2 * b + 1) * QW, fetch + (16 * b + 8) * SKH_FETCH_STRIDE, cutSH0, ps, nullptr, sst);
-                            run_cutout_chain<true, true>(c, sc, scShadow, shq, counts + (2 * b + 1) * QW, cutSH0, cutSH0, nullptr, ps, c->dContrib.as<float4>(), cutSQ[0], cutSQ[1], cutSH1, w, NP, sst);
+                            run_cutout_chain<true, true>(c, sc, scShadow, shq, counts + (2 * b + 1) * QW, cutSH0, cutSH0, nullptr, ps, c->dContrib.as<float4>(), cutSQ[0], cutSQ[1], cutSH1, w, NP, sst, blp);
                         }
                         else
                         {
                             launch_trace<false, false>(c, scShadow, shq, counts + (2 * b + 1) * QW, fetch + (16 * b + 8) * SKH_FETCH_STRIDE, cutSH0, ps, nullptr, sst);
-                            run_cutout_chain<true, false>(c, sc, scShadow, shq, counts + (2 * b + 1) * QW, cutSH0, cutSH0, nullptr, ps, c->dContrib.as<float4>(), cutSQ[0], cutSQ[1], cutSH1, w, NP, sst);
+                            run_cutout_chain<true, false>(c, sc, scShadow, shq, counts + (2 * b + 1) * QW, cutSH0, cutSH0, nullptr, ps, c->dContrib.as<float4>(), cutSQ[0], cutSQ[1], cutSH1, w, NP, sst, blp);
                         }
                     }
                     else if (c->countTraversal)
@@ -2304,7 +2455,7 @@ skh_status skh_trace_device(skh_context* c, const void* d_rays, uint32_t n_rays,
     SKH_CHECK(dev_alloc(c, q, sizeof(float) * 9 * NQ));
     SKH_CHECK(dev_alloc(c, h, sizeof(float) * 8 * NQ));
     // a cutout in use (skh_set_material_cutouts): the continuation rounds run on the internal records, before k_hits_soa_to_aos; their words lie behind the fetch cursors
-    const bool cutOn = c->cutInstances != 0u;
+    const bool cutOn = cut_stage_on(c);
     const size_t cutWordCount = cutOn ? (size_t)c->cutoutRounds * SKH_CUT_WORDS : 0u;
     DevBuf cq0, cq1, h2, h0;
     SKH_CHECK(dev_alloc(c, cnt, sizeof(uint32_t) * (SKH_SHARDS * SKH_COUNT_STRIDE + 8 * SKH_FETCH_STRIDE + cutWordCount)));
@@ -2343,25 +2494,27 @@ skh_status skh_trace_device(skh_context* c, const void* d_rays, uint32_t n_rays,
             DevScene scShadow = sc; // (shadow rays do not see lights: their closest-hit launches leave the baked light proxies' tree out)
             if (c->worldRoot != SKH_REF_INVALID || c->tlasRoot != SKH_REF_INVALID)
                 scShadow.lightRoot = SKH_REF_INVALID;
+            BlendP blp = make_blend(c);
+            blp.raw = 1u; // (no sample: a blend hit counts iff a > 0)
             if (mode == SKH_TRACE_SHADOW && c->countTraversal)
             {
                 launch_trace<false, true>(c, scShadow, rq, dcount, dfetch, hq0, ps, nullptr);
-                run_cutout_chain<true, true>(c, sc, scShadow, rq, dcount, hq0, hq0, hq.base, ps, nullptr, q0, q1, hq2, words, n_rays, c->stream);
+                run_cutout_chain<true, true>(c, sc, scShadow, rq, dcount, hq0, hq0, hq.base, ps, nullptr, q0, q1, hq2, words, n_rays, c->stream, blp);
             }
             else if (mode == SKH_TRACE_SHADOW)
             {
                 launch_trace<false, false>(c, scShadow, rq, dcount, dfetch, hq0, ps, nullptr);
-                run_cutout_chain<true, false>(c, sc, scShadow, rq, dcount, hq0, hq0, hq.base, ps, nullptr, q0, q1, hq2, words, n_rays, c->stream);
+                run_cutout_chain<true, false>(c, sc, scShadow, rq, dcount, hq0, hq0, hq.base, ps, nullptr, q0, q1, hq2, words, n_rays, c->stream, blp);
             }
             else if (c->countTraversal)
             {
                 launch_trace<false, true>(c, sc, rq, dcount, dfetch, hq, ps, nullptr);
-                run_cutout_chain<false, true>(c, sc, sc, rq, dcount, hq, hq, nullptr, ps, nullptr, q0, q1, hq2, words, n_rays, c->stream);
+                run_cutout_chain<false, true>(c, sc, sc, rq, dcount, hq, hq, nullptr, ps, nullptr, q0, q1, hq2, words, n_rays, c->stream, blp);
             }
             else
             {
                 launch_trace<false, false>(c, sc, rq, dcount, dfetch, hq, ps, nullptr);
-                run_cutout_chain<false, false>(c, sc, sc, rq, dcount, hq, hq, nullptr, ps, nullptr, q0, q1, hq2, words, n_rays, c->stream);
+                run_cutout_chain<false, false>(c, sc, sc, rq, dcount, hq, hq, nullptr, ps, nullptr, q0, q1, hq2, words, n_rays, c->stream, blp);
             }
         }
         else if (mode == SKH_TRACE_SHADOW)

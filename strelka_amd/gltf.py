@@ -178,10 +178,14 @@ class GltfScene(S.Scene):
         ct = scene_io.material_cutouts_from_descriptions(self.material_descriptions, self.texture_ids)
         if ct is not None:
             arr["material_cutouts"] = ct
+        if getattr(self, "alpha_blend", False):  # (load_gltf(alpha_blend=True) only: without it no description asks for a blend)
+            bt = scene_io.material_blends_from_descriptions(self.material_descriptions, self.texture_ids)
+            if bt is not None:
+                arr["material_blend"] = bt
         return arr
 
 
-def _load_materials(doc, sc, material_textures=False, alpha_mask=False):
+def _load_materials(doc, sc, material_textures=False, alpha_mask=False, alpha_blend=False):
     """glTF materials -> the reference loader's OmniPBR / OmniGlass descriptions (gltfloader.cpp:304-406).  New here: emissiveFactor times the
     KHR_materials_emissive_strength extension's emissiveStrength, when not zero, becomes OmniPBR's enable_emission / emissive_color /
     emissive_intensity (a zero factor leaves the description as the reference writes it).  With `material_textures` (the reference's loader
@@ -191,7 +195,10 @@ def _load_materials(doc, sc, material_textures=False, alpha_mask=False):
     With `alpha_mask` (the reference's loader turns every non-OPAQUE material into OmniGlass): alphaMode MASK becomes the OmniPBR description of the
     OPAQUE branch plus a cutout (scene_io.material_cutout_from_description): enable_opacity, opacity_threshold = alphaCutoff (default 0.5, the glTF
     specification's), opacity_constant = baseColorFactor[3]; with a baseColorTexture also enable_opacity_texture, opacity_texture = that texture,
-    opacity_mode 0 (its alpha channel) and opacity_scale = baseColorFactor[3] (opacity = factor * texel alpha, the glTF definition)."""
+    opacity_mode 0 (its alpha channel) and opacity_scale = baseColorFactor[3] (opacity = factor * texel alpha, the glTF definition).
+    With `alpha_blend`: alphaMode BLEND becomes the same OmniPBR description WITHOUT a threshold -- a blend entry (scene_io.material_blend_from_description):
+    fractional opacity factor * texel alpha, not glass.  A blended material does not emit (skh_set_material_blend refuses the combination): its
+    emissiveFactor is left out."""
     images, textures = doc.get("images", []), doc.get("textures", [])
 
     def tex_uri(info):
@@ -209,7 +216,8 @@ def _load_materials(doc, sc, material_textures=False, alpha_mask=False):
         base = pbr.get("baseColorFactor", [1.0, 1.0, 1.0, 1.0])
         rough, metal = float(pbr.get("roughnessFactor", 1.0)), float(pbr.get("metallicFactor", 1.0))
         masked = alpha_mask and m.get("alphaMode", "OPAQUE") == "MASK"
-        if m.get("alphaMode", "OPAQUE") == "OPAQUE" or masked:
+        blended = alpha_blend and m.get("alphaMode", "OPAQUE") == "BLEND"
+        if m.get("alphaMode", "OPAQUE") == "OPAQUE" or masked or blended:
             params = [{"name": "diffuse_color_constant", "type": "float3", "value": [float(base[0]), float(base[1]), float(base[2])]},
                       {"name": "reflection_roughness_constant", "type": "float", "value": rough},
                       {"name": "metallic_constant", "type": "float", "value": metal}]
@@ -223,16 +231,17 @@ def _load_materials(doc, sc, material_textures=False, alpha_mask=False):
                            {"name": "ORM_roughness_scale", "type": "float", "value": rough}, {"name": "ORM_metallic_scale", "type": "float", "value": metal}]
             ef = [float(v) for v in m.get("emissiveFactor", (0.0, 0.0, 0.0))]
             strength = float(m.get("extensions", {}).get("KHR_materials_emissive_strength", {}).get("emissiveStrength", 1.0))
-            if any(v * strength != 0.0 for v in ef):
+            if any(v * strength != 0.0 for v in ef) and not blended:
                 params += [{"name": "enable_emission", "type": "bool", "value": True}, {"name": "emissive_color", "type": "float3", "value": ef},
                            {"name": "emissive_intensity", "type": "float", "value": strength}]
                 etex = tex_uri(m.get("emissiveTexture")) if material_textures else None
                 if etex is not None:
                     params.append({"name": "emissive_color_texture", "type": "texture", "value": etex})
-            if masked:
+            if masked or blended:
                 alpha = float(base[3]) if len(base) > 3 else 1.0
-                params += [{"name": "enable_opacity", "type": "bool", "value": True}, {"name": "opacity_constant", "type": "float", "value": alpha},
-                           {"name": "opacity_threshold", "type": "float", "value": float(m.get("alphaCutoff", 0.5))}]
+                params += [{"name": "enable_opacity", "type": "bool", "value": True}, {"name": "opacity_constant", "type": "float", "value": alpha}]
+                if masked:
+                    params.append({"name": "opacity_threshold", "type": "float", "value": float(m.get("alphaCutoff", 0.5))})
                 auri = tex_uri(pbr.get("baseColorTexture"))
                 if auri is not None:
                     params += [{"name": "enable_opacity_texture", "type": "bool", "value": True}, {"name": "opacity_texture", "type": "texture", "value": auri},
@@ -355,13 +364,15 @@ def _process_node(doc, buffers, sc, index, base):
         _process_node(doc, buffers, sc, child, glob)
 
 
-def load_gltf(path, material_textures=False, alpha_mask=False):
+def load_gltf(path, material_textures=False, alpha_mask=False, alpha_blend=False):
     """GltfLoader::loadGltf (gltfloader.cpp:643-689).  Returns a Scene (strelka_amd.scene API + material_descriptions).
     `material_textures`: also read metallicRoughnessTexture and emissiveTexture (_load_materials); off, a file gives the descriptions
-    the reference's loader gives.  `alpha_mask`: alphaMode MASK becomes an OmniPBR material with a cutout (_load_materials) instead of OmniGlass."""
+    the reference's loader gives.  `alpha_mask`: alphaMode MASK becomes an OmniPBR material with a cutout (_load_materials) instead of OmniGlass.
+    `alpha_blend`: alphaMode BLEND becomes an OmniPBR material with a blend entry (fractional opacity; arrays()["material_blend"]) instead of OmniGlass."""
     doc, buffers = _read_model(path)
     sc = GltfScene()
-    _load_materials(doc, sc, material_textures, alpha_mask)
+    sc.alpha_blend = bool(alpha_blend)
+    _load_materials(doc, sc, material_textures, alpha_mask, alpha_blend)
     _load_textures(path, sc, doc, buffers)
     _load_lights(path, sc)
     _load_cameras(doc, sc)

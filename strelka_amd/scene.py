@@ -42,6 +42,9 @@ HIT = np.dtype([("t", np.float32), ("instance_id", np.uint32), ("prim_id", np.ui
                 ("v", np.float32)])
 assert VERTEX.itemsize == 32 and INSTANCE.itemsize == 64 and LIGHT.itemsize == 112
 assert MATERIAL_TEXTURES.itemsize == 48 and MATERIAL_CUTOUT.itemsize == 32
+MATERIAL_BLEND = np.dtype([("opacity_texture", np.uint32), ("opacity_channel", np.uint32), ("opacity_scale", np.float32), ("opacity_bias", np.float32),
+                           ("active", np.uint32), ("reserved", np.uint32, 3)])  # skh_material_blend, 32 B
+assert MATERIAL_BLEND.itemsize == 32
 assert MATERIAL.itemsize == 64 and FRAME_PARAMS.itemsize == 176 and RAY.itemsize == 32 and HIT.itemsize == 20
 
 INSTANCE_MESH, INSTANCE_LIGHT, INSTANCE_CURVE = 0, 1, 2  # oka::Instance::Type
@@ -199,8 +202,12 @@ class Scene:
                     base_color_texture=0, normal_texture=0, reserved=(0.0,) * 6, emission=None,
                     roughness_texture=0, metallic_texture=0, emission_texture=0, roughness_channel=0, metallic_channel=0,
                     emission_channel=EMISSION_RGB, roughness_scale=1.0, roughness_bias=0.0, metallic_scale=1.0, metallic_bias=0.0,
-                    opacity_texture=None, opacity_channel=3, opacity_scale=1.0, opacity_bias=0.0, opacity_threshold=0.0):
-        """`opacity_threshold` > 0 makes the material a CUTOUT (include/strelka_hip.h, skh_set_material_cutouts): a hit on one of its mesh surfaces counts iff
+                    opacity_texture=None, opacity_channel=3, opacity_scale=1.0, opacity_bias=0.0, opacity_threshold=0.0,
+                    opacity_blend=False):
+        """`opacity_blend` makes the material BLENDED (include/strelka_hip.h, skh_set_material_blend): fractional opacity a = clamp01(opacity_scale *
+        texel[opacity_channel] + opacity_bias) from the same `opacity_*` arguments -- a radiance ray takes a hit with probability a, a shadow ray's light is
+        scaled by 1 - a.  Not together with `opacity_threshold`, not on an emitting material.
+        `opacity_threshold` > 0 makes the material a CUTOUT (include/strelka_hip.h, skh_set_material_cutouts): a hit on one of its mesh surfaces counts iff
         clamp01(opacity_scale * texel[opacity_channel] + opacity_bias) >= opacity_threshold; `opacity_texture` None or 0 = no texture (texel = 1).
         `roughness_texture` / `metallic_texture` (MAT_PBR): value = clamp01(scale * texel[channel] + bias); `emission_texture`: Le = emission * texel
         (rgb, or one channel for all three) -- texture ids as base_color_texture's (include/strelka_hip.h, skh_set_material_textures).
@@ -225,6 +232,15 @@ class Scene:
                 raise ValueError("opacity_threshold must lie in (0, 1] and opacity_channel in 0..3")
             self.__dict__.setdefault("mMaterialCutouts", {})[len(self.mMaterials) - 1] = (
                 int(opacity_texture or 0), int(opacity_channel), float(opacity_scale), float(opacity_bias), float(opacity_threshold), (0, 0, 0))
+        if opacity_blend:
+            if float(opacity_threshold) != 0.0:
+                raise ValueError("a material is a cutout (opacity_threshold) or blended (opacity_blend), not both")
+            if emission is not None and any(float(v) != 0.0 for v in emission):
+                raise ValueError("a blended material (opacity_blend) cannot emit")
+            if int(opacity_channel) not in (0, 1, 2, 3) or not (math.isfinite(float(opacity_scale)) and math.isfinite(float(opacity_bias))):
+                raise ValueError("opacity_channel must lie in 0..3, opacity_scale and opacity_bias must be finite")
+            self.__dict__.setdefault("mMaterialBlend", {})[len(self.mMaterials) - 1] = (
+                int(opacity_texture or 0), int(opacity_channel), float(opacity_scale), float(opacity_bias), 1, (0, 0, 0))
         return len(self.mMaterials) - 1
 
     def addHairMaterial(self, color=(0.35, 0.2, 0.1), roughness_r=0.3, roughness_n=0.3, roughness_tt=0.0, roughness_trt=0.0,
@@ -450,6 +466,12 @@ class Scene:
             for i, e in self.mMaterialCutouts.items():
                 ct[i] = e
             out["material_cutouts"] = ct
+        if getattr(self, "mMaterialBlend", None):  # (likewise only when some material is blended)
+            bt = np.zeros(len(mats), MATERIAL_BLEND)
+            bt["opacity_channel"], bt["opacity_scale"] = 3, 1.0
+            for i, e in self.mMaterialBlend.items():
+                bt[i] = e
+            out["material_blend"] = bt
         return out
 
 

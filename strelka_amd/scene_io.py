@@ -77,6 +77,10 @@ def save_scene(path, arrays, camera=None, material_descriptions=None):
         desc, texels = S.pack_textures(arrays["textures"])
         sections.append((b"TXDS", S.TEXTURE_DESC.itemsize, len(desc), desc.tobytes()))
         sections.append((b"TXEL", 4, len(texels), texels.tobytes()))
+    if arrays.get("material_blend") is not None and len(arrays["material_blend"]):
+        # fractional opacity (skh_set_material_blend): a section of its own -- a reader that does not know the tag skips it, a file without it has no blend
+        bt = np.ascontiguousarray(arrays["material_blend"], S.MATERIAL_BLEND).reshape(-1)
+        sections.append((b"MBLD", S.MATERIAL_BLEND.itemsize, len(bt), bt.tobytes()))
     if material_descriptions is not None:
         text = json.dumps(material_descriptions).encode()
         sections.append((b"MDSC", 1, len(text), text))
@@ -115,7 +119,9 @@ class LoadedScene:
         return self.mCameras[index]
 
 
-def load_scene(path):
+def load_scene(path, alpha_blend=False):
+    """`alpha_blend`: a file WITHOUT a blend section whose material descriptions ask for fractional opacity (material_blend_from_description) gets a blend table
+    from them, and such a UsdPreviewSurface is PBR, not glass.  Off (the default): the translations of before.  A file's own blend section is always honoured."""
     with open(path, "rb") as f:
         blob = f.read()
     if blob[:8] != MAGIC:
@@ -127,6 +133,7 @@ def load_scene(path):
     arrays = {key: np.zeros((0,) + dt.shape, dt.base if dt.shape else dt) for _, key, dt in _SECTIONS}
     cameras, descs = [], None
     tex_desc, texels = np.zeros(0, S.TEXTURE_DESC), np.zeros(0, np.uint32)
+    blend = None
     off = 16
     for _ in range(nsec):
         if off + 16 > len(blob):
@@ -152,6 +159,8 @@ def load_scene(path):
             descs = json.loads(bytes(data).decode())
         elif tag == b"TXDS" and esz == S.TEXTURE_DESC.itemsize:
             tex_desc = np.frombuffer(data, dtype=S.TEXTURE_DESC).copy()
+        elif tag == b"MBLD" and esz == S.MATERIAL_BLEND.itemsize:
+            blend = np.frombuffer(data, dtype=S.MATERIAL_BLEND).copy()
         elif tag == b"TXEL" and esz == 4:
             texels = np.frombuffer(data, dtype=np.uint32).copy()
         # unknown tags: skipped
@@ -162,7 +171,7 @@ def load_scene(path):
             raise ValueError(f"{path}: texture {k} reaches outside the texel section")
         arrays["textures"].append(texels[int(d["offset"]):int(d["offset"]) + n].view(np.uint8).reshape(int(d["height"]), int(d["width"]), 4).copy())
     if len(arrays["materials"]) == 0:
-        arrays["materials"] = materials_from_descriptions(descs or [])
+        arrays["materials"] = materials_from_descriptions(descs or [], alpha_blend and blend is None)
         em = emission_from_descriptions(descs or [])  # (the format is unchanged: emission travels as material parameters)
         if em is not None:
             arrays["emission"] = em
@@ -172,6 +181,10 @@ def load_scene(path):
     ct = material_cutouts_from_descriptions(descs or [])  # (likewise)
     if ct is not None and len(ct) <= len(arrays["materials"]):
         arrays["material_cutouts"] = ct
+    if blend is None and alpha_blend:
+        blend = material_blends_from_descriptions(descs or [])
+    if blend is not None and len(blend) <= len(arrays["materials"]):
+        arrays["material_blend"] = blend
     if not cameras:
         cameras.append(S.Camera())
     validate(arrays)
@@ -206,6 +219,9 @@ def validate(arrays):
     for k, e in enumerate(arrays.get("material_cutouts", [])):
         if int(e["opacity_texture"]) > nt:
             raise ValueError(f"material {k}: the opacity map refers to a texture that does not exist")
+    for k, e in enumerate(arrays.get("material_blend", [])):
+        if int(e["opacity_texture"]) > nt:
+            raise ValueError(f"material {k}: the blend entry's opacity map refers to a texture that does not exist")
     for k, c in enumerate(arrays["curves"]):
         if (int(c["points_start"]) + int(c["points_count"]) > npts or int(c["widths_start"]) + int(c["widths_count"]) > nw or
                 int(c["vertex_counts_start"]) + int(c["vertex_counts_count"]) > nvc):
@@ -220,8 +236,9 @@ def _param(desc, name, default=None):
     return default
 
 
-def material_from_description(desc):
-    """One reference MaterialDescription {file, name, params[{name, type, value}]} -> one MATERIAL record.
+def material_from_description(desc, alpha_blend=False):
+    """`alpha_blend`: a UsdPreviewSurface whose opacity is a blend entry's (material_blend_from_description) is PBR, not glass.
+    One reference MaterialDescription {file, name, params[{name, type, value}]} -> one MATERIAL record.
     default.mdl::default_material.diffuse_color (OptixRender.cpp:1090-1097, RenderPass.cpp:222-245) -> diffuse;
     OmniPBR.{diffuse_color_constant, reflection_roughness_constant, metallic_constant} (gltfloader.cpp:304-352) -> PBR;
     OmniGlass (gltfloader.cpp:354-406: enable_opacity, thin_walled, frosting_roughness; glass_ior when present) -> glass;
@@ -238,7 +255,7 @@ def material_from_description(desc):
         # roughness 0.5, metallic 0, ior 1.5, opacity 1; an opacity below 0.5 is treated as glass.
         # With an opacityThreshold > 0 the opacity is a CUTOUT's (material_cutout_from_description), never glass.
         opacity = float(_param(desc, "opacity", 1.0))
-        m["type"] = S.MAT_GLASS if opacity < 0.5 and not float(_param(desc, "opacityThreshold", 0.0)) > 0.0 else S.MAT_PBR
+        m["type"] = S.MAT_GLASS if opacity < 0.5 and not float(_param(desc, "opacityThreshold", 0.0)) > 0.0 and not alpha_blend else S.MAT_PBR
         m["base_color"] = _param(desc, "diffuseColor", (0.18, 0.18, 0.18))
         m["roughness"] = float(_param(desc, "roughness", 0.5))
         m["metallic"] = float(_param(desc, "metallic", 0.0))
@@ -411,10 +428,47 @@ def material_cutouts_from_descriptions(descs, texture_ids=None):
     return out if (out["threshold"] > 0).any() else None
 
 
-def materials_from_descriptions(descs):
+def material_blend_from_description(desc, texture_ids=None):
+    """One MaterialDescription -> one S.MATERIAL_BLEND record (skh_set_material_blend's entry); active 0 = the material is not blended.  The cases
+    material_cutout_from_description leaves: an opacity WITHOUT a threshold.
+      OmniPBR, enable_opacity and no opacity_threshold > 0: with enable_opacity_texture and an opacity_texture that resolves: that texture, channel a for
+          opacity_mode 0, else r, scale = the optional opacity_scale (default 1), bias 0.  Without a texture: scale 0, bias = opacity_constant (default 1) --
+          and inactive when that constant is 1 or more (opaque either way).
+      UsdPreviewSurface, opacity < 1 and no opacityThreshold > 0: no texture, scale 0, bias = opacity."""
+    e = np.zeros(1, S.MATERIAL_BLEND)[0]
+    e["opacity_channel"], e["opacity_scale"] = 3, 1.0
+    pnames = {p.get("name") for p in desc.get("params", [])}
+    if pnames & {"diffuseColor", "useSpecularWorkflow", "specularColor", "clearcoat", "emissiveColor"}:
+        opacity = float(_param(desc, "opacity", 1.0))
+        if opacity < 1.0 and not float(_param(desc, "opacityThreshold", 0.0)) > 0.0:
+            e["opacity_scale"], e["opacity_bias"], e["active"] = 0.0, np.float32(opacity), 1
+        return e
+    if not _is_omnipbr(desc) or not _param(desc, "enable_opacity", False) or float(_param(desc, "opacity_threshold", 0.0)) > 0.0:
+        return e
+    t = _texture_id(desc, "opacity_texture", texture_ids) if _param(desc, "enable_opacity_texture", False) else 0
+    if t:
+        e["opacity_texture"], e["opacity_channel"] = t, 3 if int(_param(desc, "opacity_mode", 0)) == 0 else 0
+        e["opacity_scale"], e["active"] = np.float32(_param(desc, "opacity_scale", 1.0)), 1
+    else:
+        const = float(_param(desc, "opacity_constant", 1.0))
+        if const < 1.0:
+            e["opacity_scale"], e["opacity_bias"], e["active"] = 0.0, np.float32(const), 1
+    return e
+
+
+def material_blends_from_descriptions(descs, texture_ids=None):
+    """S.MATERIAL_BLEND array for skh_set_material_blend, or None when no description is blended"""
+    out = np.zeros(max(1, len(descs)), S.MATERIAL_BLEND)
+    out["opacity_channel"], out["opacity_scale"] = 3, 1.0
+    for k, d in enumerate(descs):
+        out[k] = material_blend_from_description(d, texture_ids)
+    return out if out["active"].any() else None
+
+
+def materials_from_descriptions(descs, alpha_blend=False):
     out = np.zeros(max(1, len(descs)), S.MATERIAL)
     if not descs:
         out[0]["base_color"] = 0.8  # material 0 = default.mdl::default_material
     for k, d in enumerate(descs):
-        out[k] = material_from_description(d)
+        out[k] = material_from_description(d, alpha_blend)
     return out

@@ -1,13 +1,17 @@
-"""Renders one of the stand-in scenes, or a glTF file, on the GPU and writes a tonemapped PNG (usage: render_png.py kitchen|cornell|hair|FILE.gltf|FILE.glb W H spp depth [exposure_scale] [out.png] [--env FILE.hdr [--env-rotate DEG]]:
+"""Renders one of the stand-in scenes, or a glTF file, on the GPU and writes a tonemapped PNG (usage: render_png.py kitchen|cornell|hair|FILE.gltf|FILE.glb W H spp depth [exposure_scale] [out.png] [--env FILE.hdr [--env-rotate DEG]] [--alpha-blend]:
 --env lights the scene with a lat-long Radiance map as its dome light, --env-rotate turns the dome about +Y).  A scene whose materials emit
 (Scene.addMaterial(emission=...), a glTF emissiveFactor) needs no flag: its arrays carry "emission" and Context.set_scene forwards it.  A glTF file is
-loaded with material_textures=True: its metallicRoughnessTexture and emissiveTexture are rendered (arrays()["material_textures"])."""
+loaded with material_textures=True: its metallicRoughnessTexture and emissiveTexture are rendered (arrays()["material_textures"]).
+--alpha-blend: a glTF file's alphaMode BLEND materials are rendered with fractional opacity (load_gltf(alpha_blend=True)) instead of as glass."""
 import sys, numpy as np
 sys.path.insert(0, ".")
 import math
 import torch
 from strelka_amd import capi, gltf, hdr, scene as S, scenes, png
 env_file = env_deg = None
+alpha_blend = "--alpha-blend" in sys.argv
+if alpha_blend:
+    sys.argv.remove("--alpha-blend")
 for flag in ("--env-rotate", "--env"):
     if flag in sys.argv:
         k = sys.argv.index(flag)
@@ -19,7 +23,7 @@ for flag in ("--env-rotate", "--env"):
             env_deg = float(val)
 name = sys.argv[1]; W, H, spp, depth = int(sys.argv[2]), int(sys.argv[3]), int(sys.argv[4]), int(sys.argv[5])
 if name.lower().endswith((".gltf", ".glb")):
-    sc, name = gltf.load_gltf(name, material_textures=True), name.replace("/", "_")
+    sc, name = gltf.load_gltf(name, material_textures=True, alpha_blend=alpha_blend), name.replace("/", "_")
 else:
     sc = {"kitchen": scenes.kitchen_standin, "cornell": scenes.cornell_box, "hair": scenes.hair_standin}[name]()
 if env_file:
