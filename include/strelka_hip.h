@@ -26,7 +26,7 @@
 extern "C" {
 #endif
 
-#define SKH_ABI_VERSION 5 /* 5 (round 6): + skh_refit_accel, skh_build_info.refit / ms_refit, then skh_update_accel (additive: refit = 2), then skh_set_environment / _transform / skh_get_environment_info + two unit probes (additive), then skh_set_emission / skh_get_emitter_info / skh_emitter_probe (additive), then skh_set_material_blend / skh_get_blend_info / skh_blend_probe (additive); options curve_merge, curve_segnode, curve_strand_major, split_pairs.  4 (round 5): + skh_get_build_info; options reinsert_rounds, reinsert_min_size; wide, tail_park, tail_lag removed.  3 (round 4): + skh_unit_probe, skh_copy_aov */
+#define SKH_ABI_VERSION 5 /* 5 (round 6): + skh_refit_accel, skh_build_info.refit / ms_refit, then skh_update_accel (additive: refit = 2), then skh_set_environment / _transform / skh_get_environment_info + two unit probes (additive), then skh_set_emission / skh_get_emitter_info / skh_emitter_probe (additive), then skh_set_material_blend / skh_get_blend_info / skh_blend_probe (additive), then skh_set_light_shapes / skh_get_light_shape_info / skh_light_shape_probe (additive); options curve_merge, curve_segnode, curve_strand_major, split_pairs.  4 (round 5): + skh_get_build_info; options reinsert_rounds, reinsert_min_size; wide, tail_park, tail_lag removed.  3 (round 4): + skh_unit_probe, skh_copy_aov */
 
 /* mirrors oka::Result (include/render/common.h:30-35) */
 typedef enum skh_status
@@ -446,6 +446,55 @@ typedef struct skh_blend_info
 skh_status skh_get_blend_info(skh_context* ctx, skh_blend_info* out);
 /* The draw, evaluated on the device by the function k_cutout calls: in = n x {px, py, pixel sample index, spp_total, depth, round}, xi = n floats in [0, 1). */
 skh_status skh_blend_probe(skh_context* ctx, uint32_t n, const uint32_t* in, float* xi);
+
+/* ---- Light shapes: sampled disk lights and UsdLux shaping cones (DESIGN.md section 2 "Light shapes") ----
+ * Two things the reference's analytic lights cannot do.  A disk light (type 1) has a proxy and neither a sampler nor a pdf (Lights.h): it shines only where a BSDF-sampled
+ * ray happens to hit its proxy, and wastes its share of the light pick.  And no light can be narrowed: UsdLux ShapingAPI (shaping:cone:angle, shaping:cone:softness,
+ * shaping:focus) is how every spot lamp is authored.  One entry per light, indexed as the light list is; 32 B.
+ *   SAMPLE_DISC   (type 1) the light takes part in next-event estimation.  The light is what rays can hit -- the 16-gon of the proxy, not the analytic disc: with
+ *                 O = points[1], X = points[2].xyz, Y = points[3].xyz the vertices v_k = O + cos(2 pi k / 16) X + sin(2 pi k / 16) Y, the area A = 8 sin(pi / 8) |X x Y|,
+ *                 the unit normal n = normalize(light.normal) (the reference stores it scaled by the radius; the flagged disk uses it normalised, in the sampler and at
+ *                 the hit).  A draw (ux, uy): sector k = min(int(16 ux), 15), u' = 16 ux - k (exact), a uniform point of the triangle (O, v_k, v_k+1) from (u', uy) by the
+ *                 emitter table's mapping.  Everything else is the rect light's protocol: pdf = dist^2 / (dot(-L, n) A), the two front-side tests,
+ *                 lrad = Li saturate(dot(N, L)), the pick's 1 / entries.  At a proxy hit the radiance term uses -dot(rayD, n) with the unit normal and the MIS weight
+ *                 the same pdf / entries of the pick.  A disk without the flag is what it was, bit for bit.
+ *   CONE          (types 0, 1, 2) emission scaled by s(c), c = dot(axis, w), w the unit direction from the light point to the shaded point (-L at a light sample,
+ *                 -rayD at a proxy hit -- at depth 0 and after a specular bounce too): s = 0 unless c > cos_outer; else t = min((c - cos_outer) / (cos_inner - cos_outer), 1)
+ *                 (1 for a hard edge), s = t^2 (3 - 2 t) * (focus > 0 ? pow(max(c, 0), focus) : 1).  Pdfs and the pick do not change: the estimator stays unbiased, a
+ *                 dark direction only wastes a pick (and queues no shadow ray).
+ * Not part of it: cylinder lights, IES profiles, focusTint, solid-angle sampling of sphere lights, cones on distant lights, the environment or emissive meshes. */
+#define SKH_LIGHT_SHAPE_SAMPLE_DISC 1u /* type 1 only: the light takes part in next-event estimation */
+#define SKH_LIGHT_SHAPE_CONE 2u /* types 0, 1, 2: emission scaled by s(c) */
+typedef struct skh_light_shape
+{
+    uint32_t flags;
+    float cos_outer;   /* cos(shaping:cone:angle) */
+    float cos_inner;   /* cos(angle * (1 - softness)) >= cos_outer; equal = hard edge */
+    float focus;       /* shaping:focus, >= 0; 0 = none */
+    float axis[3];     /* unit, world space: the direction the light shines along */
+    uint32_t reserved; /* must be 0 */
+} skh_light_shape;
+/* n_lights <= the light count; lights beyond n are plain.  NULL or 0 removes the table; a table in which no entry has a flag that applies to its light's type (SAMPLE_DISC:
+ * type 1; CONE: types 0, 1, 2; both ignored elsewhere) equals no table: the context launches the kernels and produces the bits of one that never had any.  Flags above 3,
+ * a cosine outside [-1, 1] or not finite, cos_inner < cos_outer, a focus that is negative or not finite, with CONE set an axis that is not finite or whose length is off 1
+ * by more than 1e-3, or a non-zero reserved word is refused with SKH_INVALID_ARGUMENT and leaves the previous table in place.  Discards sub-frames traced ahead; never
+ * touches the acceleration structures or the emitter table.  Which entries are in use is derived data, recomputed after skh_set_lights and skh_set_light_shapes. */
+skh_status skh_set_light_shapes(skh_context* ctx, const skh_light_shape* entries, uint32_t n_lights);
+typedef struct skh_light_shape_info
+{
+    uint32_t sampled_discs; /* entries in use inside the light list: SAMPLE_DISC on a type-1 light */
+    uint32_t cones; /* CONE on a light of type 0, 1 or 2; both 0: the kernels of a context without a table run */
+} skh_light_shape_info;
+skh_status skh_get_light_shape_info(skh_context* ctx, skh_light_shape_info* out);
+/* The device functions k_shade calls, on host arrays of packed 32-bit words (n records), against the context's light list and shape table:
+ *   SKH_LSHAPE_PROBE_SAMPLE  in  u32 light, f32 ux, uy, P[3] (the shaded point)
+ *                            out f32 point[3], normal[3], L[3], dist, pdf per solid angle (without the pick's factor), s, area
+ *   SKH_LSHAPE_PROBE_PDF     in  u32 light, f32 lightHitPoint[3], surfacePoint[3]      out f32 pdf, s
+ * Lights of types 0, 2 and 3 answer with the existing samplers' values (a rect light by the uniform method), s applied when a cone is set (else 1); a disk without
+ * SAMPLE_DISC with the zero sample it always was; a light index beyond the list with zeros. */
+#define SKH_LSHAPE_PROBE_SAMPLE 0u
+#define SKH_LSHAPE_PROBE_PDF 1u
+skh_status skh_light_shape_probe(skh_context* ctx, uint32_t kind, const void* in, uint32_t n, void* out);
 
 /* ---- createAccelerationStructure (OptixRender.cpp:388-496): per-mesh / per-curve BLAS + one TLAS ---- */
 skh_status skh_build_accel(skh_context* ctx, uint32_t flags);

@@ -179,6 +179,8 @@ void HipRender::uploadScene()
     check(skh_set_instances(mCtx, inst.data(), (uint32_t)inst.size()), "skh_set_instances");
     mSentInstances = inst;
     check(skh_set_lights(mCtx, reinterpret_cast<const skh_light*>(sc.getLights().data()), (uint32_t)sc.getLights().size()), "skh_set_lights");
+    mLightsUploaded = true;
+    applyLightShapes(); // (the table is indexed as the light list is: it follows every upload of the list)
     uploadMaterials();
     check(skh_build_accel(mCtx, SKH_BUILD_LBVH), "skh_build_accel");
 }
@@ -304,9 +306,29 @@ bool HipRender::setEnvironmentTransform(const float scale[3], const float* world
     return check(skh_set_environment_transform(mCtx, scale, m), "skh_set_environment_transform");
 }
 
+bool HipRender::applyLightShapes()
+{
+    return check(skh_set_light_shapes(mCtx, mLightShapes.empty() ? nullptr : mLightShapes.data(), (uint32_t)mLightShapes.size()), "skh_set_light_shapes");
+}
+
+bool HipRender::setLightShapes(const skh_light_shape* entries, uint32_t n)
+{
+    if (entries && n)
+        mLightShapes.assign(entries, entries + n);
+    else
+        mLightShapes.clear();
+    mLightShapesChanged = true;
+    return mLightsUploaded ? applyLightShapes() : true; // (before the first upload the library has no light list to hold the table against: uploadScene applies it)
+}
+
 void HipRender::render(Buffer* output)
 {
     SharedContext& sh = getSharedContext();
+    if (mLightShapesChanged)
+    {
+        sh.mSubframeIndex = 0; // other lights: the accumulated image is of the old ones
+        mLightShapesChanged = false;
+    }
     if (mEnvironmentChanged)
     {
         sh.mSubframeIndex = 0; // a new sky: the accumulated image is of the old one

@@ -83,6 +83,12 @@ public:
     bool setEnvironment(const float* rgb, uint32_t width, uint32_t height, const float scale[3], const float* worldToEnv = nullptr);
     // the same map under a new intensity x colour and rotation: no table rebuild (a viewer spinning its dome)
     bool setEnvironmentTransform(const float scale[3], const float* worldToEnv = nullptr);
+    // Light shapes (new: the reference's UniformLightDesc has no shaping fields, and its disk light is never sampled).  One skh_light_shape per light, indexed as
+    // Scene::getLights() is: SKH_LIGHT_SHAPE_SAMPLE_DISC lets a disk light take part in next-event estimation, SKH_LIGHT_SHAPE_CONE narrows a rect, disk or
+    // sphere light by a UsdLux ShapingAPI cone (include/strelka_hip.h has the definitions).  nullptr / 0 removes the table.  The table is kept: it is applied at
+    // once when the scene is uploaded already, and again after every upload of the light list.  Accumulation restarts at the next render().  With tile
+    // sharing every rank makes the same call.  INTEGRATION.md says what an HdStrelkaLight hands over.
+    bool setLightShapes(const skh_light_shape* entries, uint32_t n);
     // Fractional opacity (skh_set_material_blend), OFF by default: with it, a material description whose opacity has no threshold -- OmniPBR enable_opacity without
     // opacity_threshold, UsdPreviewSurface opacity < 1 without opacityThreshold -- is uploaded as a PBR material with a blend entry (skhmat::materialBlend), not as
     // glass or opaque.  Call before init() / before the materials are uploaded.
@@ -114,6 +120,9 @@ private:
     bool sendMovedInstances();
     std::vector<skh_instance> mSentInstances;
     bool mAlphaBlend = false;
+    std::vector<skh_light_shape> mLightShapes; // setLightShapes' table, re-applied after skh_set_lights
+    bool mLightsUploaded = false, mLightShapesChanged = false;
+    bool applyLightShapes();
     void uploadMaterials(); // MaterialDescription list -> skh_material blocks + textures (OptixRender.cpp:1270-1433)
 };
 

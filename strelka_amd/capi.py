@@ -30,7 +30,8 @@ SYMBOLS = ["skh_create", "skh_destroy", "skh_last_error", "skh_abi_version", "sk
            "skh_update_accel", "skh_set_environment", "skh_set_environment_transform", "skh_get_environment_info",
            "skh_set_emission", "skh_get_emitter_info", "skh_emitter_probe",
            "skh_set_material_textures", "skh_material_probe", "skh_set_material_cutouts", "skh_get_cutout_info",
-           "skh_set_material_blend", "skh_get_blend_info", "skh_blend_probe"]
+           "skh_set_material_blend", "skh_get_blend_info", "skh_blend_probe",
+           "skh_set_light_shapes", "skh_get_light_shape_info", "skh_light_shape_probe"]
 
 BUILD_INFO = np.dtype([("triangles", np.uint32), ("nodes", np.uint32), ("reinsert_rounds", np.uint32), ("reinsert_moves", np.uint32),
                        ("reinsert_min_size", np.uint32), ("refit", np.uint32), ("cost_before", np.float64), ("cost_after", np.float64),
@@ -44,6 +45,9 @@ CUTOUT_INFO = np.dtype([("active_materials", np.uint32), ("instances", np.uint32
 BLEND_INFO = np.dtype([("active_materials", np.uint32), ("instances", np.uint32), ("passed_radiance", np.uint64), ("crossed_shadow", np.uint64),
                        ("accepted_by_cap", np.uint64), ("bytes", np.uint64)])
 EMITTER_INFO = np.dtype([("triangles", np.uint32), ("instances", np.uint32), ("sum_w", np.float64), ("ms_build", np.float64), ("bytes", np.uint64)])
+LIGHT_SHAPE_INFO = np.dtype([("sampled_discs", np.uint32), ("cones", np.uint32)])
+# skh_light_shape_probe: kind -> (number, words in, words out) per record
+LSHAPE_PROBES = {"sample": (0, 6, 13), "pdf": (1, 7, 2)}
 # skh_emitter_probe: kind -> (number, words in, words out) per record
 EMIT_PROBES = {"sample": (0, 6, 13), "pdf": (1, 8, 4)}
 
@@ -105,6 +109,9 @@ def load():
     lib.skh_set_material_blend.argtypes = [vp, vp, u32]
     lib.skh_get_blend_info.argtypes = [vp, vp]
     lib.skh_blend_probe.argtypes = [vp, u32, vp, vp]
+    lib.skh_set_light_shapes.argtypes = [vp, vp, u32]
+    lib.skh_get_light_shape_info.argtypes = [vp, vp]
+    lib.skh_light_shape_probe.argtypes = [vp, u32, vp, u32, vp]
     lib.skh_resize.argtypes = [vp, u32, u32]
     lib.skh_set_tiles.argtypes = [vp, u32, vp, u32]
     lib.skh_render_subframe.argtypes = [vp, vp, vp]
@@ -204,6 +211,7 @@ class Context:
         self.set_material_textures(arr.get("material_textures"))  # (likewise)
         self.set_material_cutouts(arr.get("material_cutouts"))  # (likewise)
         self.set_material_blend(arr.get("material_blend"))  # (likewise)
+        self.set_light_shapes(arr.get("light_shapes"))  # (likewise)
         if build:
             self.build_accel(flags)
 
@@ -323,6 +331,31 @@ class Context:
         self._ck(self.lib.skh_blend_probe(self.h, len(t), _p(t), _p(out)), "skh_blend_probe")
         return out
 
+    def set_light_shapes(self, table):
+        """skh_set_light_shapes: `table` an S.LIGHT_SHAPE array, one entry per light (None or empty removes the table)"""
+        if table is None or len(table) == 0:
+            self._ck(self.lib.skh_set_light_shapes(self.h, None, 0), "skh_set_light_shapes")
+            return
+        t = np.ascontiguousarray(table, S.LIGHT_SHAPE).reshape(-1)
+        self._ck(self.lib.skh_set_light_shapes(self.h, _p(t), len(t)), "skh_set_light_shapes")
+
+    def light_shape_info(self):
+        """skh_get_light_shape_info: entries in use inside the light list -- sampled disks, cones"""
+        d = np.zeros((), LIGHT_SHAPE_INFO)
+        self._ck(self.lib.skh_get_light_shape_info(self.h, _p(d)), "skh_get_light_shape_info")
+        return {k: int(d[k]) for k in LIGHT_SHAPE_INFO.names}
+
+    def light_shape_probe(self, kind, records):
+        """skh_light_shape_probe: `kind` "sample" ({light, ux, uy, P[3]} -> point[3], normal[3], L[3], dist, pdf, s, area) or "pdf"
+        ({light, lightHitPoint[3], surfacePoint[3]} -> pdf, s); `records` an (n, words in) array of 32-bit words; returns (n, words out) float32."""
+        num, win, wout = LSHAPE_PROBES[kind]
+        rec = np.ascontiguousarray(records)
+        if rec.dtype.itemsize != 4 or rec.ndim != 2 or rec.shape[1] != win:
+            raise ValueError(f"{kind}: records must be (n, {win}) 32-bit words")
+        out = np.zeros((rec.shape[0], wout), np.float32)
+        self._ck(self.lib.skh_light_shape_probe(self.h, num, _p(rec), rec.shape[0], _p(out)), "skh_light_shape_probe")
+        return out
+
     def material_probe(self, material, uv):
         """skh_material_probe: the device function k_shade calls for a triangle hit of material[i] at uv[i] -> (n, 8) float32:
         base_color[3], roughness, metallic, Le[3]"""
@@ -405,6 +438,11 @@ class Context:
 
     def trace_device(self, d_rays, n, mode, d_hits, repeat=1):
         self._ck(self.lib.skh_trace_device(self.h, d_rays, n, mode, d_hits, repeat), "skh_trace_device")
+
+    def set_lights(self, lights):
+        """skh_set_lights alone: `lights` an S.LIGHT array (which light-shape entries are in use is derived again from it)"""
+        l = np.ascontiguousarray(lights, S.LIGHT).reshape(-1)
+        self._ck(self.lib.skh_set_lights(self.h, _p(l), len(l)), "skh_set_lights")
 
     def set_materials(self, materials):
         m = np.ascontiguousarray(materials, S.MATERIAL).reshape(-1)

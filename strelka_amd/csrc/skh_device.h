@@ -9,6 +9,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include "skh_libm.h"
+#include "skh_lshape.h"
 
 namespace skh
 {
@@ -569,6 +570,66 @@ SKH_DI LightSample sample_sphere_light(const Light& l, float ux, float uy, const
     d.pdf = 1.0f / (4.0f * SKH_PI);
     d.pointOnLight = lightPoint;
     return d;
+}
+
+// =================================================================================================
+// Light shapes -- not in the reference; DESIGN.md section 2 "Light shapes" is the definition, skh_lshape.h the arithmetic (a host program compiles it too).
+// One 32-byte entry per light, indexed as the light list is: a disk light that takes part in next-event estimation (the reference has no sampler and no
+// pdf for type 1) and the UsdLux shaping cone on rect, disk and sphere lights.
+// =================================================================================================
+struct LshapeP // by-value kernel argument; table == nullptr: no shape in use
+{
+    const float4* table; // 2 per light: {flags, cos_outer, cos_inner, focus} {axis, 0}; the flags already masked to those that apply to the light's type
+};
+struct Lshape
+{
+    uint32_t flags;
+    float cosOuter, cosInner, focus;
+    v3 axis;
+};
+SKH_DI Lshape lshape_fetch(const LshapeP& p, uint32_t light)
+{
+    const float4 a = p.table[2 * (size_t)light], b = p.table[2 * (size_t)light + 1];
+    Lshape e;
+    e.flags = __float_as_uint(a.x), e.cosOuter = a.y, e.cosInner = a.z, e.focus = a.w;
+    e.axis = mk3(b.x, b.y, b.z);
+    return e;
+}
+// s(c) for w, the unit direction from the light point to the shaded point; 1 for a light without a cone
+SKH_DI float lshape_cone(const Lshape& e, const v3& w)
+{
+    return (e.flags & SKH_LSHAPE_CONE) ? lshape_s(dot(e.axis, w), e.cosOuter, e.cosInner, e.focus) : 1.0f;
+}
+SKH_DI float disc_light_area(const Light& l)
+{
+    const float X[3] = { l.points[2].x, l.points[2].y, l.points[2].z }, Y[3] = { l.points[3].x, l.points[3].y, l.points[3].z };
+    return lshape_disc_area(X, Y);
+}
+// the sampled disk: the rect light's protocol (sample_rect_light_uniform) over the 16-gon of the proxy, the normal normalised
+SKH_DI LightSample sample_disc_light(const Light& l, float ux, float uy, const v3& hitPoint)
+{
+    const float O[3] = { l.points[1].x, l.points[1].y, l.points[1].z }, X[3] = { l.points[2].x, l.points[2].y, l.points[2].z },
+                Y[3] = { l.points[3].x, l.points[3].y, l.points[3].z };
+    float p[3];
+    (void)lshape_disc_point(O, X, Y, ux, uy, p);
+    LightSample d;
+    d.pointOnLight = mk3(p[0], p[1], p[2]);
+    d.area = lshape_disc_area(X, Y);
+    d.normal = normalize(mk3(l.normal));
+    const v3 toLight = d.pointOnLight - hitPoint;
+    d.distToLight = length(toLight);
+    d.L = toLight / d.distToLight;
+    d.pdf = lshape_area_pdf(d.distToLight, -dot(d.L, d.normal), d.area);
+    return d;
+}
+// get_light_pdf of the sampled disk: the sampler's own pdf for the point it would have drawn (the same operations on the same values: the same bits)
+SKH_DI float disc_light_pdf(const Light& l, const v3& lightHitPoint, const v3& surfaceHitPoint)
+{
+    const v3 n = normalize(mk3(l.normal));
+    const v3 toLight = lightHitPoint - surfaceHitPoint;
+    const float dist = length(toLight);
+    const v3 L = toLight / dist;
+    return lshape_area_pdf(dist, -dot(L, n), disc_light_area(l));
 }
 
 // =================================================================================================

@@ -137,6 +137,14 @@ struct skh_context
     std::vector<skh_material_blend> blends;
     DevBuf dBlend;
     uint32_t blendActiveMaterials = 0, blendInstances = 0; // blendInstances != 0: blending is in use
+    // light shapes (skh_set_light_shapes): the table as the caller gave it.  Which entries are IN USE -- a flag that applies to its light's type, inside the light
+    // list -- is derived (lshape_ensure, when lshapeStale): the device table holds one entry per light with the flags masked to those, and exists only when one is
+    // in use; only then do the k_shade builds with LSHAPE in them run
+    std::vector<skh_light_shape> lshapes;
+    std::vector<int32_t> lightTypes; // of the light list, kept for the derivation
+    DevBuf dLshape;
+    bool lshapeStale = false;
+    uint32_t lshapeDiscs = 0, lshapeCones = 0;
     // Speculative sub-frame batching for the reference's call pattern (one render() per sub-frame, RenderPass.cpp:441-447): once two
     // consecutive calls continue the same frame (same parameters, subframe_index + 1), the next call traces several sub-frames
     // ahead in ONE wavefront pass and the calls after it only apply their accumulation step to the radiances already in the path

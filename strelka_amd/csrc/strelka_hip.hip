@@ -308,6 +308,10 @@ skh_status skh_set_lights(skh_context* c, const skh_light* lights, uint32_t n)
     spec_drop(c);
     (void)hipSetDevice(c->device);
     c->nLights = n;
+    c->lightTypes.resize(n);
+    for (uint32_t k = 0; k < n; ++k)
+        c->lightTypes[k] = lights[k].type;
+    c->lshapeStale = true; // (which shape entries are in use depends on the lights' types and count)
     return dev_upload(c, c->dLights, lights, sizeof(skh_light) * (size_t)n);
 }
 
@@ -1125,6 +1129,135 @@ skh_status skh_blend_probe(skh_context* c, uint32_t n, const uint32_t* in, float
 
 static skh_status ensure_ready(skh_context* c);
 
+// ---- light shapes: skh_set_light_shapes, the LSHAPE builds of k_shade (skh_lshape.h, skh_device.h) ----
+static_assert(sizeof(skh_light_shape) == 32, "skh_light_shape");
+static_assert(SKH_LIGHT_SHAPE_SAMPLE_DISC == SKH_LSHAPE_SAMPLE_DISC && SKH_LIGHT_SHAPE_CONE == SKH_LSHAPE_CONE, "the flags of the ABI are the device's");
+
+// the flags of an entry that apply to a light of this type
+static uint32_t lshape_flags_for(uint32_t flags, int32_t type)
+{
+    return flags & ((type == 1 ? SKH_LIGHT_SHAPE_SAMPLE_DISC : 0u) | ((type == 0 || type == 1 || type == 2) ? SKH_LIGHT_SHAPE_CONE : 0u));
+}
+
+// Which entries are in use (derived: after skh_set_lights and skh_set_light_shapes)?  The device table -- one entry per light, flags masked to those in use, zeros
+// for lights beyond the caller's table -- exists only when one is.
+static skh_status lshape_ensure(skh_context* c)
+{
+    if (!c->lshapeStale)
+        return SKH_OK;
+    const uint32_t n = (uint32_t)std::min<size_t>(c->lshapes.size(), c->nLights);
+    uint32_t discs = 0, cones = 0;
+    std::vector<float> table(8 * (size_t)c->nLights, 0.0f);
+    for (uint32_t k = 0; k < n; ++k)
+    {
+        const skh_light_shape& e = c->lshapes[k];
+        const uint32_t f = lshape_flags_for(e.flags, c->lightTypes[k]);
+        discs += (f & SKH_LIGHT_SHAPE_SAMPLE_DISC) ? 1u : 0u, cones += (f & SKH_LIGHT_SHAPE_CONE) ? 1u : 0u;
+        float* o = &table[8 * (size_t)k];
+        memcpy(o, &f, 4);
+        o[1] = e.cos_outer, o[2] = e.cos_inner, o[3] = e.focus, o[4] = e.axis[0], o[5] = e.axis[1], o[6] = e.axis[2];
+    }
+    if (c->dLshape.p || discs || cones)
+        SKH_TRY(c, hipStreamSynchronize(c->stream)); // (the table is about to be replaced or freed)
+    if (discs || cones)
+    {
+        DevBuf d;
+        SKH_CHECK(dev_upload(c, d, table.data(), table.size() * sizeof(float)));
+        c->dLshape = std::move(d);
+    }
+    else
+        dev_free(c->dLshape);
+    c->lshapeDiscs = discs, c->lshapeCones = cones;
+    c->lshapeStale = false;
+    return SKH_OK;
+}
+
+static LshapeP make_lshape(const skh_context* c)
+{
+    LshapeP p;
+    p.table = (c->lshapeDiscs || c->lshapeCones) ? c->dLshape.as<float4>() : nullptr;
+    return p;
+}
+
+skh_status skh_set_light_shapes(skh_context* c, const skh_light_shape* entries, uint32_t n)
+{
+    if (!c)
+        return SKH_INVALID_ARGUMENT;
+    (void)hipSetDevice(c->device);
+    if (!entries || n == 0)
+    {
+        // remove: a no-op on a context that has none (nothing traced ahead is thrown away for it)
+        if (c->lshapes.empty())
+            return SKH_OK;
+        spec_drop(c);
+        c->lshapes.clear();
+        c->lshapeStale = true;
+        return SKH_OK;
+    }
+    if (n > c->nLights)
+    {
+        c->err = "skh_set_light_shapes: " + std::to_string(n) + " entries for " + std::to_string(c->nLights) + " lights (call skh_set_lights first)";
+        return SKH_INVALID_ARGUMENT;
+    }
+    for (uint32_t k = 0; k < n; ++k)
+    {
+        const skh_light_shape& e = entries[k];
+        bool ok = e.flags <= 3u && e.reserved == 0u && std::isfinite(e.cos_outer) && std::isfinite(e.cos_inner) && e.cos_outer >= -1.0f && e.cos_outer <= 1.0f &&
+                  e.cos_inner >= -1.0f && e.cos_inner <= 1.0f && e.cos_inner >= e.cos_outer && std::isfinite(e.focus) && e.focus >= 0.0f;
+        if (ok && (e.flags & SKH_LIGHT_SHAPE_CONE))
+        {
+            const double len = std::sqrt((double)e.axis[0] * e.axis[0] + (double)e.axis[1] * e.axis[1] + (double)e.axis[2] * e.axis[2]);
+            ok = std::isfinite(e.axis[0]) && std::isfinite(e.axis[1]) && std::isfinite(e.axis[2]) && std::fabs(len - 1.0) <= 1e-3;
+        }
+        if (!ok)
+        {
+            c->err = "skh_set_light_shapes: light " + std::to_string(k) +
+                     ": flags above 3, a cosine outside [-1, 1] or not finite, cos_inner < cos_outer, a focus that is negative or not finite, a cone axis that is not "
+                     "finite or not of unit length, or a non-zero reserved word";
+            return SKH_INVALID_ARGUMENT;
+        }
+    }
+    spec_drop(c);
+    c->lshapes.assign(entries, entries + n);
+    c->lshapeStale = true;
+    return SKH_OK;
+}
+
+skh_status skh_get_light_shape_info(skh_context* c, skh_light_shape_info* out)
+{
+    if (!c || !out)
+        return SKH_INVALID_ARGUMENT;
+    memset(out, 0, sizeof(*out));
+    (void)hipSetDevice(c->device);
+    SKH_CHECK(lshape_ensure(c));
+    out->sampled_discs = c->lshapeDiscs, out->cones = c->lshapeCones;
+    return SKH_OK;
+}
+
+skh_status skh_light_shape_probe(skh_context* c, uint32_t kind, const void* in, uint32_t n, void* out)
+{
+    if (!c)
+        return SKH_INVALID_ARGUMENT;
+    if (kind > SKH_LSHAPE_PROBE_PDF || (n && (!in || !out)))
+    {
+        c->err = "skh_light_shape_probe: unknown kind, or a missing input / output pointer";
+        return SKH_INVALID_ARGUMENT;
+    }
+    (void)hipSetDevice(c->device);
+    SKH_CHECK(lshape_ensure(c));
+    if (n == 0)
+        return SKH_OK;
+    const size_t inBytes = (kind == SKH_LSHAPE_PROBE_SAMPLE ? 6u : 7u) * sizeof(uint32_t), outBytes = (kind == SKH_LSHAPE_PROBE_SAMPLE ? 13u : 2u) * sizeof(float);
+    DevBuf di, dout;
+    SKH_CHECK(dev_upload(c, di, in, inBytes * n));
+    SKH_CHECK(dev_alloc(c, dout, outBytes * n));
+    k_lshape_probe<<<(n + 255) / 256, 256, 0, c->stream>>>(c->dLights.as<Light>(), c->nLights, make_lshape(c), 0u, kind, di.as<uint32_t>(), n, dout.as<float>());
+    SKH_TRY(c, hipGetLastError());
+    SKH_TRY(c, hipStreamSynchronize(c->stream));
+    SKH_TRY(c, hipMemcpy(out, dout.p, outBytes * n, hipMemcpyDeviceToHost));
+    return SKH_OK;
+}
+
 // ---- emissive meshes: skh_set_emission, the emitter table (skh_emit.h) ----
 static void emit_clear(skh_context* c)
 {
@@ -1358,6 +1491,7 @@ static skh_status ensure_ready(skh_context* c)
             return s;
     }
     SKH_CHECK(emit_ensure(c));
+    SKH_CHECK(lshape_ensure(c));
     SKH_CHECK(cut_ensure(c));
     return cut_alloc_frame(c);
 }
@@ -1498,6 +1632,7 @@ static skh_status render_one(skh_context* c, const skh_frame_params* p, uint32_t
     const EnvP envp = make_env(c);
     const EmitP emitp = make_emit(c);
     const MtexP mtexp = make_mtex(c);
+    const LshapeP lshp = make_lshape(c);
     const uint32_t N = c->numSlots * c->batchCapacity; // plane stride of the path-state buffer
     const uint32_t NQ = SKH_SHARDS * c->queueRegion; // plane stride of every queue (rays, hits, shadow contributions)
     const uint32_t NP = c->numSlots * batch; // paths in this pass
@@ -1614,14 +1749,24 @@ static skh_status render_one(skh_context* c, const skh_frame_params* p, uint32_t
                 // workgroup b on shard b & 7; those past the end of their shard leave at once
                 const uint32_t perShard = (((NP + SKH_SHARDS - 1u) / SKH_SHARDS) + 63u) & ~63u;
                 const dim3 sg(SKH_SHARDS * ((perShard + SKH_SHADE_BLOCK - 1) / SKH_SHADE_BLOCK));
-#define SKH_SHADE_LAUNCH_MTEX(HAIRB, ENVB, EMITB, MTEXB)                                                                                                                  \
-    k_shade<HAIRB, ENVB, EMITB, MTEXB><<<sg, SKH_SHADE_BLOCK, 0, st>>>(sc, fp, s, b, tiles, rq[b & 1], counts + 2 * b * QW, hq, ps, rq[(b + 1) & 1], counts + 2 * (b + 1) * QW, \
-                                                                       shq, c->dContrib.as<float4>(), counts + (2 * b + 1) * QW, envp, emitp, mtexp)
-#define SKH_SHADE_LAUNCH(HAIRB, ENVB, EMITB)             \
-    if (mtexp.count)                                     \
-        SKH_SHADE_LAUNCH_MTEX(HAIRB, ENVB, EMITB, true); \
-    else                                                 \
-        SKH_SHADE_LAUNCH_MTEX(HAIRB, ENVB, EMITB, false)
+                // (every HAIR x ENV x EMIT x MTEX build has a twin with light shapes in it, launched only when a shape is in use)
+#define SKH_SHADE_LAUNCH_MTEX(HAIRB, ENVB, EMITB, MTEXB)                                                                                                                             \
+    if (lshp.table)                                                                                                                                                                  \
+        k_shade_lshape<HAIRB, ENVB, EMITB, MTEXB><<<sg, SKH_SHADE_BLOCK, 0, st>>>(sc, fp, s, b, tiles, rq[b & 1], counts + 2 * b * QW, hq, ps, rq[(b + 1) & 1],                       \
+                                                                                  counts + 2 * (b + 1) * QW, shq, c->dContrib.as<float4>(), counts + (2 * b + 1) * QW, envp, emitp,  \
+                                                                                  mtexp, lshp);                                                                                      \
+    else                                                                                                                                                                             \
+        k_shade<HAIRB, ENVB, EMITB, MTEXB><<<sg, SKH_SHADE_BLOCK, 0, st>>>(sc, fp, s, b, tiles, rq[b & 1], counts + 2 * b * QW, hq, ps, rq[(b + 1) & 1], counts + 2 * (b + 1) * QW, \
+                                                                           shq, c->dContrib.as<float4>(), counts + (2 * b + 1) * QW, envp, emitp, mtexp)
+#define SKH_SHADE_LAUNCH(HAIRB, ENVB, EMITB)              \
+    if (mtexp.count)                                      \
+    {                                                     \
+        SKH_SHADE_LAUNCH_MTEX(HAIRB, ENVB, EMITB, true);  \
+    }                                                     \
+    else                                                  \
+    {                                                     \
+        SKH_SHADE_LAUNCH_MTEX(HAIRB, ENVB, EMITB, false); \
+    }
 #define SKH_SHADE_LAUNCH_EMIT(HAIRB, ENVB)     \
     if (emitp.count)                           \
     {                                          \

@@ -45,6 +45,10 @@ assert MATERIAL_TEXTURES.itemsize == 48 and MATERIAL_CUTOUT.itemsize == 32
 MATERIAL_BLEND = np.dtype([("opacity_texture", np.uint32), ("opacity_channel", np.uint32), ("opacity_scale", np.float32), ("opacity_bias", np.float32),
                            ("active", np.uint32), ("reserved", np.uint32, 3)])  # skh_material_blend, 32 B
 assert MATERIAL_BLEND.itemsize == 32
+LIGHT_SHAPE = np.dtype([("flags", np.uint32), ("cos_outer", np.float32), ("cos_inner", np.float32), ("focus", np.float32), ("axis", np.float32, 3),
+                        ("reserved", np.uint32)])  # skh_light_shape, 32 B
+assert LIGHT_SHAPE.itemsize == 32
+LIGHT_SHAPE_SAMPLE_DISC, LIGHT_SHAPE_CONE = 1, 2
 assert MATERIAL.itemsize == 64 and FRAME_PARAMS.itemsize == 176 and RAY.itemsize == 32 and HIT.itemsize == 20
 
 INSTANCE_MESH, INSTANCE_LIGHT, INSTANCE_CURVE = 0, 1, 2  # oka::Instance::Type
@@ -390,9 +394,49 @@ class Scene:
         L["color"] = np.append(col, np.float32(1.0)) * np.float32(desc.get("intensity", 1.0))
         self.mLights.append(L)
         self.mLightDesc.append(dict(desc))
+        shape = self._light_shape(desc, typ, L, lt)
+        if shape is not None:
+            if not hasattr(self, "mLightShapes"):
+                self.mLightShapes = {}
+            self.mLightShapes[light_id] = shape
         transform = (xform @ sm_inst) if use_xform else self._light_transform(desc)
         self.createInstance(INSTANCE_LIGHT, mesh, NO_ID, transform, light_id)
         return light_id
+
+    # -- light shapes: not in the reference's UniformLightDesc; what an HdStrelkaLight with a UsdLux ShapingAPI would hand over
+    @staticmethod
+    def _light_shape(desc, typ, L, lt):
+        """the skh_light_shape of a light description, None without one.  Keys: "sample": True (disks: the light takes part in next-event estimation);
+        "coneAngle" (radians, shaping:cone:angle), "coneSoftness" (0..1), "focus" (>= 0); "axis" (world space; default: the light's own emission normal for
+        rect and disk lights, xform * (0, 0, -1) for a sphere light)."""
+        sample, cone = bool(desc.get("sample", False)), "coneAngle" in desc
+        if sample and typ != 1:
+            raise ValueError('"sample" is for disk lights (type 1): the other types are sampled already')
+        if cone and typ not in (0, 1, 2):
+            raise ValueError("a shaping cone needs a rect, disk or sphere light")
+        if not sample and not cone:
+            return None
+        e = np.zeros((), LIGHT_SHAPE)
+        e["cos_outer"] = e["cos_inner"] = -1.0
+        e["flags"] = (LIGHT_SHAPE_SAMPLE_DISC if sample else 0) | (LIGHT_SHAPE_CONE if cone else 0)
+        if cone:
+            angle, soft = float(desc["coneAngle"]), float(desc.get("coneSoftness", 0.0))
+            if not (0.0 <= angle <= math.pi) or not (0.0 <= soft <= 1.0):
+                raise ValueError("coneAngle must lie in [0, pi] and coneSoftness in [0, 1]")
+            co, ci = np.float32(math.cos(angle)), np.float32(math.cos(angle * (1.0 - soft)))
+            e["cos_outer"], e["cos_inner"] = co, max(co, ci)
+            e["focus"] = float(desc.get("focus", 0.0))
+            if "axis" in desc:
+                a = np.asarray(desc["axis"], np.float64)
+            elif typ == 0:  # calc_light_normal: -normalize(cross(p1 - p0, p3 - p0))
+                p = L["points"].astype(np.float64)
+                a = -np.cross(p[1, :3] - p[0, :3], p[3, :3] - p[0, :3])
+            elif typ == 1:
+                a = L["normal"][:3].astype(np.float64)
+            else:
+                a = (lt @ np.array([0, 0, -1.0, 0]))[:3]
+            e["axis"] = (a / np.linalg.norm(a)).astype(np.float32) + np.float32(0.0)  # (+ 0: no negative zeros)
+        return e
 
     # -- environment (dome) light: not in the reference's Scene; what an HdStrelkaLight of type domeLight would hand over (INTEGRATION.md)
     def setEnvironment(self, rgb, scale=(1.0, 1.0, 1.0), world_to_env=None):
@@ -472,6 +516,12 @@ class Scene:
             for i, e in self.mMaterialBlend.items():
                 bt[i] = e
             out["material_blend"] = bt
+        if getattr(self, "mLightShapes", None):  # (likewise only when some light has a shape)
+            ls = np.zeros(len(lights), LIGHT_SHAPE)
+            ls["cos_outer"] = ls["cos_inner"] = -1.0
+            for i, e in self.mLightShapes.items():
+                ls[i] = e
+            out["light_shapes"] = ls
         return out
 
 

@@ -81,6 +81,10 @@ def save_scene(path, arrays, camera=None, material_descriptions=None):
         # fractional opacity (skh_set_material_blend): a section of its own -- a reader that does not know the tag skips it, a file without it has no blend
         bt = np.ascontiguousarray(arrays["material_blend"], S.MATERIAL_BLEND).reshape(-1)
         sections.append((b"MBLD", S.MATERIAL_BLEND.itemsize, len(bt), bt.tobytes()))
+    if arrays.get("light_shapes") is not None and len(arrays["light_shapes"]):
+        # light shapes (skh_set_light_shapes): likewise a section of its own, written only when present
+        ls = np.ascontiguousarray(arrays["light_shapes"], S.LIGHT_SHAPE).reshape(-1)
+        sections.append((b"LSHP", S.LIGHT_SHAPE.itemsize, len(ls), ls.tobytes()))
     if material_descriptions is not None:
         text = json.dumps(material_descriptions).encode()
         sections.append((b"MDSC", 1, len(text), text))
@@ -133,7 +137,7 @@ def load_scene(path, alpha_blend=False):
     arrays = {key: np.zeros((0,) + dt.shape, dt.base if dt.shape else dt) for _, key, dt in _SECTIONS}
     cameras, descs = [], None
     tex_desc, texels = np.zeros(0, S.TEXTURE_DESC), np.zeros(0, np.uint32)
-    blend = None
+    blend = shapes = None
     off = 16
     for _ in range(nsec):
         if off + 16 > len(blob):
@@ -161,6 +165,8 @@ def load_scene(path, alpha_blend=False):
             tex_desc = np.frombuffer(data, dtype=S.TEXTURE_DESC).copy()
         elif tag == b"MBLD" and esz == S.MATERIAL_BLEND.itemsize:
             blend = np.frombuffer(data, dtype=S.MATERIAL_BLEND).copy()
+        elif tag == b"LSHP" and esz == S.LIGHT_SHAPE.itemsize:
+            shapes = np.frombuffer(data, dtype=S.LIGHT_SHAPE).copy()
         elif tag == b"TXEL" and esz == 4:
             texels = np.frombuffer(data, dtype=np.uint32).copy()
         # unknown tags: skipped
@@ -185,6 +191,8 @@ def load_scene(path, alpha_blend=False):
         blend = material_blends_from_descriptions(descs or [])
     if blend is not None and len(blend) <= len(arrays["materials"]):
         arrays["material_blend"] = blend
+    if shapes is not None and len(shapes) <= len(arrays["lights"]):
+        arrays["light_shapes"] = shapes
     if not cameras:
         cameras.append(S.Camera())
     validate(arrays)

@@ -541,6 +541,24 @@ def light_zoo(seed=11, with_rect=True):
     return sc
 
 
+def spot_room(seed=11):
+    """light_zoo's room lit by shaped lights alone (skh_set_light_shapes): a SAMPLED DISK in the ceiling -- the disk of light_zoo, now part of next-event
+    estimation --, a SPHERE light with a soft 35 degree cone that points down and forward (a spot lamp as Blender and Omniverse export it) and a RECT light with
+    a 40 degree cone, softness 0.5 and focus 2 (a downlight).  Same room, objects, materials and camera as light_zoo(with_rect=False)."""
+    sc = light_zoo(seed, with_rect=False)
+    # (light_zoo's own two lights stay what they are in that scene; here they get their shapes: the lists are rebuilt through createLight)
+    sc.mLights, sc.mLightDesc = [], []
+    sc.mInstances = [i for i in sc.mInstances if i[1] != S.INSTANCE_LIGHT]
+    sc.createLight({"type": 2, "xform": S.translate((-0.9, 2.2, 0.2)), "useXform": True, "radius": 0.25, "color": (1.0, 0.85, 0.7), "intensity": 40.0,
+                    "coneAngle": math.radians(35.0), "coneSoftness": 0.3, "axis": (0.35, -0.9, -0.25)})
+    xf = S.translate((1.0, 2.97, -0.3)) @ S.rotate((1, 0, 0), math.radians(90))
+    sc.createLight({"type": 1, "xform": xf, "useXform": True, "radius": 0.45, "color": (0.8, 0.9, 1.0), "intensity": 30.0, "sample": True})
+    xf = S.translate((0.0, 2.98, 1.2)) @ S.rotate((1, 0, 0), math.radians(-90))
+    sc.createLight({"type": 0, "xform": xf, "useXform": True, "width": 0.8, "height": 0.5, "color": (1, 1, 1), "intensity": 12.0,
+                    "coneAngle": math.radians(40.0), "coneSoftness": 0.5, "focus": 2.0})
+    return sc
+
+
 def material_probe(kind, seed=5):
     """One material everywhere (floor, walls, three objects): a wrong branch of ONE BSDF cannot hide behind the others.
     kind: "diffuse" | "glossy" | "metal" | "glass" | "frosted" (OmniGlass with frosting_roughness, gltfloader.cpp:354-406)."""
