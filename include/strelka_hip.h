@@ -561,6 +561,41 @@ skh_status skh_render_subframe(skh_context* ctx, const skh_frame_params* params,
 skh_status skh_render_subframes(skh_context* ctx, const skh_frame_params* params, uint32_t n_subframes,
                                 void* d_image);
 
+/* ---- Adaptive sampling (new; the reference's only stopping rule is spp_total.  DESIGN.md section 2, "Adaptive sampling").
+ *      Opt-in.  Every pixel keeps a Welford state {n, mean, M2} of the LDR luminance y = 0.2126 r + 0.7152 g + 0.0722 b of
+ *      tonemap(observation, exposure), one observation per launch (the value the launch hands to the accumulator).  When the number of
+ *      observations n since sub-frame 0 reaches min_samples, and every `interval` after that, each tile is checked:
+ *      q = (M2 / n / n) / max(mean, dark_level)^2 per pixel, Q = the tile's largest q; the tile FREEZES iff Q <= threshold^2 (a NaN never
+ *      freezes).  A frozen tile is not traced again in this frame and holds, bit for bit, the accumulator of the non-adaptive frame after as
+ *      many launches.  The frame starts again -- all tiles active, statistics cleared -- at a call with subframe_index == 0 and after every
+ *      scene setter, skh_resize and skh_set_tiles.  Acts only on calls with enable_accumulation != 0 and debug == 0.
+ *      A context with adaptive sampling on renders one pass per skh_render_subframe call (nothing is traced ahead). ---- */
+typedef struct skh_adaptive
+{
+    float threshold;      /* relative standard error at which a tile stops; finite, >= 0 */
+    float dark_level;     /* LDR luminance below which the error is taken relative to this; finite, > 0 */
+    uint32_t min_samples; /* >= 2 */
+    uint32_t interval;    /* >= 1 */
+    uint32_t reserved[4]; /* 0 */
+} skh_adaptive;
+/* SKH_OK when *a is a setting skh_set_adaptive accepts (needs no context and no GPU) */
+skh_status skh_adaptive_check(const skh_adaptive* a);
+/* NULL = off (the context then launches the kernels it launched before and frees the feature's buffers).  A setting that fails
+ * skh_adaptive_check is refused with SKH_INVALID_ARGUMENT and the previous one stays. */
+skh_status skh_set_adaptive(skh_context* ctx, const skh_adaptive* a);
+typedef struct skh_adaptive_info
+{
+    uint32_t enabled;
+    uint32_t tiles, active_tiles;
+    uint32_t checks;                   /* done in this frame */
+    uint32_t min_observations, max_observations; /* over the tiles: a frozen tile's count at its freeze, an active tile's count so far */
+    uint64_t pixel_observations;       /* traced in this frame: valid pixels of active tiles, summed over the launches */
+    uint64_t pixel_observations_saved; /* ... and those the frozen tiles did not trace, against the non-adaptive frame so far */
+} skh_adaptive_info;
+skh_status skh_get_adaptive_info(skh_context* ctx, skh_adaptive_info* out);
+/* per pixel {n, mean, M2, q at the last check of its tile}; W*H float4, row-major; pixels of tiles this context does not own read as 0 */
+skh_status skh_read_adaptive(skh_context* ctx, float* host_rgba);
+
 /* ---- the tonemap() + gammaCorrection post pass (postprocessing/Tonemappers.cu:111-135), in place on a
  *      device float4 image.  type: 0 none, 1 Reinhard, 2 ACES fitted, 3 ACES film; gamma <= 0 = off ---- */
 skh_status skh_tonemap(skh_context* ctx, void* d_image, uint32_t width, uint32_t height, uint32_t type,

@@ -17,6 +17,7 @@
 
 #include <algorithm>
 #include <cassert>
+#include <cmath>
 #include <cstdlib>
 #include <cstring>
 #include <iostream>
@@ -321,6 +322,39 @@ bool HipRender::setLightShapes(const skh_light_shape* entries, uint32_t n)
     return mLightsUploaded ? applyLightShapes() : true; // (before the first upload the library has no light list to hold the table against: uploadScene applies it)
 }
 
+// the LDR luminance the accumulator's tonemap gives a grey pixel of radiance `radiance` under `exposure`
+static float adaptiveDarkLevel(float radiance, const float exposure[3])
+{
+    float t[3];
+    for (int i = 0; i < 3; ++i)
+    {
+        const float c = radiance * exposure[i];
+        t[i] = c / (c + 1.0f);
+    }
+    return 0.2126f * t[0] + 0.7152f * t[1] + 0.0722f * t[2];
+}
+
+bool HipRender::setAdaptiveSampling(float threshold, float darkRadiance, uint32_t minSamples, uint32_t interval)
+{
+    mConverged = false;
+    if (threshold < 0.0f)
+    {
+        mAdaptive = false;
+        return check(skh_set_adaptive(mCtx, nullptr), "skh_set_adaptive");
+    }
+    skh_adaptive a;
+    memset(&a, 0, sizeof(a));
+    a.threshold = threshold, a.min_samples = minSamples, a.interval = interval;
+    a.dark_level = 1.0f; // (checked here with a level that passes; the real one depends on the exposure: render())
+    if (!(darkRadiance > 0.0f) || !std::isfinite(darkRadiance) || skh_adaptive_check(&a) != SKH_OK)
+        return false; // (refused; the previous setting stays)
+    mAdaptive = true;
+    mAdaptiveSetting = a;
+    mAdaptiveDarkRadiance = darkRadiance;
+    memset(&mAdaptiveApplied, 0, sizeof(mAdaptiveApplied)); // (applied at the next render())
+    return true;
+}
+
 void HipRender::render(Buffer* output)
 {
     SharedContext& sh = getSharedContext();
@@ -415,13 +449,27 @@ void HipRender::render(Buffer* output)
     p.spp_total = totalSpp;
 
     void* dImage = static_cast<HipBuffer*>(output)->getNativePtr();
-    if (samplesThisLaunch != 0)
+    const bool adaptiveFrame = mAdaptive && enableAccumulation && p.debug == 0;
+    if (mAdaptive)
+    {
+        // the setting under this frame's exposure; a changed one restarts the library's adaptive frame (all tiles active)
+        skh_adaptive a = mAdaptiveSetting;
+        a.dark_level = adaptiveDarkLevel(mAdaptiveDarkRadiance, p.exposure);
+        if (memcmp(&a, &mAdaptiveApplied, sizeof(a)) != 0 && check(skh_set_adaptive(mCtx, &a), "skh_set_adaptive"))
+            mAdaptiveApplied = a;
+    }
+    if (sh.mSubframeIndex == 0 || !adaptiveFrame)
+        mConverged = false;
+    if (samplesThisLaunch != 0 && !mConverged)
     {
         check(skh_render_subframe(mCtx, &p, dImage), "skh_render_subframe");
         if (enableAccumulation)
             sh.mSubframeIndex += samplesThisLaunch;
         else
             sh.mSubframeIndex = 0;
+        skh_adaptive_info info;
+        if (adaptiveFrame && check(skh_get_adaptive_info(mCtx, &info), "skh_get_adaptive_info"))
+            mConverged = info.enabled != 0u && info.checks != 0u && info.active_tiles == 0u; // no active tile left: as sppTotal reached, from the next render() on
     }
     else
     {

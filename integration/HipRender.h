@@ -96,6 +96,18 @@ public:
     {
         mAlphaBlend = on;
     }
+    // Adaptive sampling (skh_set_adaptive; new: the reference's only stopping rule is sppTotal), OFF by default: what Hydra's convergedVariance and
+    // convergedSamplesPerPixel render settings and HdRenderPass::IsConverged ask of a delegate.  A tile stops once the relative standard error of every pixel's
+    // tonemapped luminance is at most `threshold`; darkRadiance is the scene radiance below which the error is taken relative to that level (turned into the
+    // LDR level under the frame's exposure at every render()); checks after minSamples launches and every `interval` after.  threshold < 0 turns it off.
+    // false: a parameter was refused (the previous setting stays).  Call after init().  With tile sharing every rank makes the same call.
+    bool setAdaptiveSampling(float threshold, float darkRadiance, uint32_t minSamples, uint32_t interval);
+    // true once no tile of this frame is active any more: render() then hands back the accumulated image as it does when sppTotal is reached, until something
+    // restarts the accumulation
+    bool isConverged() const
+    {
+        return mConverged;
+    }
 
 private:
     skh_context* mCtx = nullptr;
@@ -120,6 +132,9 @@ private:
     bool sendMovedInstances();
     std::vector<skh_instance> mSentInstances;
     bool mAlphaBlend = false;
+    bool mAdaptive = false, mConverged = false;
+    skh_adaptive mAdaptiveSetting = {}, mAdaptiveApplied = {}; // (dark_level of the setting: the RADIANCE; of the applied one: the LDR level)
+    float mAdaptiveDarkRadiance = 0.0f;
     std::vector<skh_light_shape> mLightShapes; // setLightShapes' table, re-applied after skh_set_lights
     bool mLightsUploaded = false, mLightShapesChanged = false;
     bool applyLightShapes();

@@ -31,7 +31,8 @@ SYMBOLS = ["skh_create", "skh_destroy", "skh_last_error", "skh_abi_version", "sk
            "skh_set_emission", "skh_get_emitter_info", "skh_emitter_probe",
            "skh_set_material_textures", "skh_material_probe", "skh_set_material_cutouts", "skh_get_cutout_info",
            "skh_set_material_blend", "skh_get_blend_info", "skh_blend_probe",
-           "skh_set_light_shapes", "skh_get_light_shape_info", "skh_light_shape_probe"]
+           "skh_set_light_shapes", "skh_get_light_shape_info", "skh_light_shape_probe",
+           "skh_adaptive_check", "skh_set_adaptive", "skh_get_adaptive_info", "skh_read_adaptive"]
 
 BUILD_INFO = np.dtype([("triangles", np.uint32), ("nodes", np.uint32), ("reinsert_rounds", np.uint32), ("reinsert_moves", np.uint32),
                        ("reinsert_min_size", np.uint32), ("refit", np.uint32), ("cost_before", np.float64), ("cost_after", np.float64),
@@ -46,6 +47,10 @@ BLEND_INFO = np.dtype([("active_materials", np.uint32), ("instances", np.uint32)
                        ("accepted_by_cap", np.uint64), ("bytes", np.uint64)])
 EMITTER_INFO = np.dtype([("triangles", np.uint32), ("instances", np.uint32), ("sum_w", np.float64), ("ms_build", np.float64), ("bytes", np.uint64)])
 LIGHT_SHAPE_INFO = np.dtype([("sampled_discs", np.uint32), ("cones", np.uint32)])
+ADAPTIVE = np.dtype([("threshold", np.float32), ("dark_level", np.float32), ("min_samples", np.uint32), ("interval", np.uint32), ("reserved", np.uint32, 4)])
+ADAPTIVE_INFO = np.dtype([("enabled", np.uint32), ("tiles", np.uint32), ("active_tiles", np.uint32), ("checks", np.uint32), ("min_observations", np.uint32),
+                          ("max_observations", np.uint32), ("pixel_observations", np.uint64), ("pixel_observations_saved", np.uint64)])
+assert ADAPTIVE.itemsize == 32 and ADAPTIVE_INFO.itemsize == 40
 # skh_light_shape_probe: kind -> (number, words in, words out) per record
 LSHAPE_PROBES = {"sample": (0, 6, 13), "pdf": (1, 7, 2)}
 # skh_emitter_probe: kind -> (number, words in, words out) per record
@@ -112,6 +117,10 @@ def load():
     lib.skh_set_light_shapes.argtypes = [vp, vp, u32]
     lib.skh_get_light_shape_info.argtypes = [vp, vp]
     lib.skh_light_shape_probe.argtypes = [vp, u32, vp, u32, vp]
+    lib.skh_adaptive_check.argtypes = [vp]
+    lib.skh_set_adaptive.argtypes = [vp, vp]
+    lib.skh_get_adaptive_info.argtypes = [vp, vp]
+    lib.skh_read_adaptive.argtypes = [vp, vp]
     lib.skh_resize.argtypes = [vp, u32, u32]
     lib.skh_set_tiles.argtypes = [vp, u32, vp, u32]
     lib.skh_render_subframe.argtypes = [vp, vp, vp]
@@ -156,6 +165,22 @@ def load():
 
 def _p(a):
     return a.ctypes.data_as(C.c_void_p) if a is not None else None
+
+
+def adaptive_record(threshold, dark_level, min_samples, interval):
+    """an skh_adaptive record (one ADAPTIVE element)"""
+    a = np.zeros((), ADAPTIVE)
+    a["threshold"], a["dark_level"], a["min_samples"], a["interval"] = threshold, dark_level, min_samples, interval
+    return a
+
+
+def adaptive_dark_level(radiance, exposure):
+    """skh_adaptive.dark_level for a scene radiance level: the LDR luminance the accumulator's tonemap gives a grey pixel of that radiance under the
+    frame's exposure (frame_params' `exposure`, three factors) -- below it, a pixel's error is taken relative to this level instead of its own mean."""
+    e = np.asarray(exposure, np.float32).reshape(3)
+    c = np.float32(radiance) * e
+    t = c / (c + np.float32(1.0))
+    return float(np.float32(0.2126) * t[0] + np.float32(0.7152) * t[1] + np.float32(0.0722) * t[2])
 
 
 class Context:
@@ -381,6 +406,26 @@ class Context:
         self.tile_xy = tile_xy
         self._ck(self.lib.skh_set_tiles(self.h, tile_size, _p(tile_xy), 0 if tile_xy is None else len(tile_xy)),
                  "skh_set_tiles")
+
+    def set_adaptive(self, threshold=None, dark_level=0.01, min_samples=16, interval=8):
+        """skh_set_adaptive: a tile stops once the relative standard error of every pixel's LDR luminance is at most `threshold` (checked at `min_samples`
+        observations and every `interval` after); None turns the feature off.  adaptive_dark_level() gives `dark_level` from a radiance."""
+        if threshold is None:
+            self._ck(self.lib.skh_set_adaptive(self.h, None), "skh_set_adaptive")
+            return
+        a = adaptive_record(threshold, dark_level, min_samples, interval)
+        self._ck(self.lib.skh_set_adaptive(self.h, _p(a)), "skh_set_adaptive")
+
+    def adaptive_info(self):
+        d = np.zeros((), ADAPTIVE_INFO)
+        self._ck(self.lib.skh_get_adaptive_info(self.h, _p(d)), "skh_get_adaptive_info")
+        return {k: int(d[k]) for k in ADAPTIVE_INFO.names}
+
+    def read_adaptive(self):
+        """skh_read_adaptive: (H, W, 4) float32 {n, mean, M2, q at the tile's last check}; 0 where this context owns no tile"""
+        out = np.zeros((self.height, self.width, 4), np.float32)
+        self._ck(self.lib.skh_read_adaptive(self.h, _p(out)), "skh_read_adaptive")
+        return out
 
     def render_subframe(self, params, d_image=None):
         p = np.ascontiguousarray(params, dtype=S.FRAME_PARAMS)

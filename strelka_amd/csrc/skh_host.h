@@ -212,6 +212,22 @@ struct skh_context
     bool customTiles = false;
     DevBuf dTileXY, dAccum, dDiffuse, dSpecular, dDiffCnt, dSpecCnt, dSums, dPath, dRayQ[2], dHits, dShadowQ, dContrib, dCounts,
         dOvf, dOvf2, dStats, dScratchImage;
+    // adaptive sampling (skh_set_adaptive; skh_adapt.h).  Nothing below exists in a context that never turned it on.  A pass of an adaptive call takes the
+    // RENDER tile list -- the context's list with the frozen tiles' origins moved off the image -- and the ray-generation tables computed for it, where it
+    // otherwise takes dTileXY / dRaygenBase / raygenValidPerSub; read-back, tile copies and the gather keep the home list.
+    struct Adaptive
+    {
+        bool on = false;
+        skh_adaptive cfg = {};
+        bool ready = false;      // buffers allocated for this frame geometry and the frame's state initialised (cleared by every reset)
+        bool now = false;        // set by the render entry points around render_one: this pass is an adaptive one
+        uint32_t delivered = 0;  // observations since the frame began
+        uint32_t checks = 0, activeTiles = 0, raygenValid = 0;
+        uint64_t pixelObs = 0, pixelObsSaved = 0;
+        std::vector<uint32_t> frozenAt; // per tile: 0 = active, else its observation count when it froze
+    } adapt;
+    std::vector<uint32_t> chunkValid; // valid pixels per 64-slot chunk (an 8 x 8 pixel block) of the home list: what the ray-generation tables are summed from
+    DevBuf dTileXYRender, dRaygenBaseRender, dAdaptState, dAdaptTileQ, dAdaptFrozenAt;
     uint32_t traceBlocks = 0;
     uint32_t curveSplitBuilt = 1;
     uint32_t numWorldCurves = 0; // curve instances under identity transforms that the world-only kernel walks itself (skh_build_accel)

@@ -1819,3 +1819,5 @@ __global__ void __launch_bounds__(256) k_instance_tight_boxes(const HostInstance
 }
 
 } // namespace skh
+
+#include "skh_adapt.h" // (adaptive sampling: its three kernels read what the accumulation kernels above read)

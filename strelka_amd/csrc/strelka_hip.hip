@@ -68,9 +68,13 @@ static void init_sobol_table(uint32_t tab[5][32])
 
 // Ends the speculation.  Whatever was traced ahead and not yet delivered is dropped: its share of the pass's rays (sub-frames of a
 // pass trace the same pixels with different samples: equal shares to a fraction of a per cent) leaves the ray counts.
-static void spec_drop(skh_context* c, bool keepLast = false)
+// A drop that forgets the previous call as well (keepLast = false) is what every scene setter, skh_resize and skh_set_tiles do first: there the adaptive frame
+// starts again too (all tiles active, statistics cleared: adapt_prepare at the next adaptive call) -- unless the caller is a render entry point (keepAdaptive).
+static void spec_drop(skh_context* c, bool keepLast = false, bool keepAdaptive = false)
 {
     skh_context::Speculation& sp = c->spec;
+    if (!keepLast && !keepAdaptive)
+        c->adapt.ready = false;
     if (sp.nextInFlight)
     {
         // a whole pass traced ahead that nobody will collect: wait for it (its buffers are about to be reused), take its rays out again
@@ -553,6 +557,22 @@ static skh_status build_shading_tables(skh_context* c)
 
 static size_t frame_count_words(const skh_context* c);
 
+// k_raygen's tables for the context's tile list with the tiles of `frozenAt` (per tile, != 0: frozen; NULL: none) left out: valid slots per 512-slot block as an
+// exclusive prefix sum, and their total
+static void raygen_tables(const skh_context* c, const uint32_t* frozenAt, std::vector<uint32_t>& base, uint32_t& total)
+{
+    const uint32_t blocks = (c->numSlots + 511u) / 512u, chunks = (uint32_t)c->chunkValid.size(), shift2 = 2 * c->tileShift;
+    base.assign(std::max(1u, blocks), 0u);
+    total = 0;
+    for (uint32_t b = 0; b < blocks; ++b)
+    {
+        base[b] = total;
+        for (uint32_t j = b * 8u; j < std::min(chunks, (b + 1) * 8u); ++j)
+            if (!frozenAt || frozenAt[(j * 64u) >> shift2] == 0u)
+                total += c->chunkValid[j];
+    }
+}
+
 static skh_status alloc_frame(skh_context* c)
 {
     const uint32_t T = c->tileSize;
@@ -581,7 +601,7 @@ static skh_status alloc_frame(skh_context* c)
     const size_t NQ = (size_t)SKH_SHARDS * c->queueRegion;
     SKH_CHECK(dev_upload(c, c->dTileXY, c->tileXY.data(), sizeof(uint32_t) * c->tileXY.size()));
     {
-        // k_raygen's tables: valid (inside the image) slots per 512-slot block, as an exclusive prefix sum
+        // valid (inside the image) slots per 64-slot chunk -- the 8 x 8 pixel block at the chunk's first pixel
         auto compact = [](uint32_t x) {
             x &= 0x55555555u;
             x = (x ^ (x >> 1)) & 0x33333333u;
@@ -590,25 +610,23 @@ static skh_status alloc_frame(skh_context* c)
             x = (x ^ (x >> 8)) & 0x0000ffffu;
             return x;
         };
-        const uint32_t blocks = (c->numSlots + 511u) / 512u;
-        std::vector<uint32_t> base(std::max(1u, blocks), 0u);
         const uint32_t shift2 = 2 * c->tileShift, mask = (1u << shift2) - 1u;
-        uint32_t total = 0;
-        for (uint32_t b = 0; b < blocks; ++b)
+        c->chunkValid.assign(c->numSlots / 64u, 0u);
+        for (uint32_t j = 0; j < c->numSlots / 64u; ++j)
         {
-            base[b] = total;
-            const uint32_t end = std::min(c->numSlots, (b + 1) * 512u);
-            for (uint32_t slot = b * 512u; slot < end; ++slot)
-            {
-                const uint32_t tile = slot >> shift2, m = slot & mask;
-                const uint32_t px = c->tileXY[2 * tile] + compact(m), py = c->tileXY[2 * tile + 1] + compact(m >> 1);
-                total += (px < c->width && py < c->height) ? 1u : 0u;
-            }
+            const uint32_t tile = (j * 64u) >> shift2, m = (j * 64u) & mask;
+            const uint32_t x0 = c->tileXY[2 * tile] + compact(m), y0 = c->tileXY[2 * tile + 1] + compact(m >> 1);
+            uint32_t n = 0;
+            for (uint32_t k = 0; k < 64u; ++k)
+                n += (x0 + compact(k) < c->width && y0 + compact(k >> 1) < c->height) ? 1u : 0u;
+            c->chunkValid[j] = n;
         }
-        c->raygenBlocksPerSub = blocks;
-        c->raygenValidPerSub = total;
+        std::vector<uint32_t> base;
+        raygen_tables(c, nullptr, base, c->raygenValidPerSub);
+        c->raygenBlocksPerSub = (uint32_t)((c->numSlots + 511u) / 512u);
         SKH_CHECK(dev_upload(c, c->dRaygenBase, base.data(), sizeof(uint32_t) * base.size()));
     }
+    c->adapt.ready = false; // (the feature's buffers follow the frame's: adapt_prepare)
     SKH_CHECK(dev_alloc(c, c->dAccum, sizeof(float4) * N1));
     SKH_CHECK(dev_alloc(c, c->dDiffuse, sizeof(float4) * N1));
     SKH_CHECK(dev_alloc(c, c->dSpecular, sizeof(float4) * N1));
@@ -1594,6 +1612,160 @@ static skh_status check_stack_overflow(skh_context* c, const char* where)
     return SKH_FAIL;
 }
 
+// ---- adaptive sampling (skh_adapt.h) ----
+static_assert(sizeof(skh_adaptive) == 32 && sizeof(skh_adaptive_info) == 40, "ABI layout");
+
+skh_status skh_adaptive_check(const skh_adaptive* a)
+{
+    if (!a || !std::isfinite(a->threshold) || a->threshold < 0.0f || !std::isfinite(a->dark_level) || !(a->dark_level > 0.0f) || a->min_samples < 2u ||
+        a->interval < 1u || a->reserved[0] || a->reserved[1] || a->reserved[2] || a->reserved[3])
+        return SKH_INVALID_ARGUMENT;
+    return SKH_OK;
+}
+
+skh_status skh_set_adaptive(skh_context* c, const skh_adaptive* a)
+{
+    if (!c || (a && skh_adaptive_check(a) != SKH_OK))
+    {
+        if (c)
+            c->err = "skh_set_adaptive: threshold finite and >= 0, dark_level finite and > 0, min_samples >= 2, interval >= 1, reserved words 0";
+        return SKH_INVALID_ARGUMENT;
+    }
+    (void)hipSetDevice(c->device);
+    spec_drop(c); // (also: the adaptive frame starts again)
+    c->adapt.on = a != nullptr;
+    if (a)
+        c->adapt.cfg = *a;
+    else
+    {
+        SKH_TRY(c, hipStreamSynchronize(c->stream));
+        dev_free(c->dTileXYRender), dev_free(c->dRaygenBaseRender), dev_free(c->dAdaptState), dev_free(c->dAdaptTileQ), dev_free(c->dAdaptFrozenAt);
+        c->adapt = skh_context::Adaptive();
+    }
+    return SKH_OK;
+}
+
+// whether this call is an adaptive one
+static inline bool adapt_applies(const skh_context* c, const skh_frame_params& p)
+{
+    return c->adapt.on && p.enable_accumulation != 0 && p.debug == 0;
+}
+
+// Before the first pass of an adaptive call: where the frame starts (sub-frame 0, or a reset since the last call) every tile becomes active and the statistics are
+// cleared -- the render list and its tables are the home list's again.  The accumulators need nothing: sub-frame 0 overwrites them.
+static skh_status adapt_prepare(skh_context* c, const skh_frame_params& p)
+{
+    skh_context::Adaptive& ad = c->adapt;
+    if (ad.ready && p.subframe_index != 0)
+        return SKH_OK;
+    const size_t N1 = std::max(1u, c->numSlots), nt = std::max(1u, c->numTiles);
+    const size_t baseBytes = sizeof(uint32_t) * std::max(1u, c->raygenBlocksPerSub);
+    SKH_CHECK(dev_alloc(c, c->dTileXYRender, sizeof(uint32_t) * 2 * nt));
+    SKH_CHECK(dev_alloc(c, c->dRaygenBaseRender, baseBytes));
+    SKH_CHECK(dev_alloc(c, c->dAdaptState, sizeof(float4) * N1));
+    SKH_CHECK(dev_alloc(c, c->dAdaptTileQ, sizeof(float) * nt));
+    SKH_CHECK(dev_alloc(c, c->dAdaptFrozenAt, sizeof(uint32_t) * nt));
+    SKH_TRY(c, hipMemcpyAsync(c->dTileXYRender.p, c->dTileXY.p, sizeof(uint32_t) * 2 * c->numTiles, hipMemcpyDeviceToDevice, c->stream));
+    SKH_TRY(c, hipMemcpyAsync(c->dRaygenBaseRender.p, c->dRaygenBase.p, baseBytes, hipMemcpyDeviceToDevice, c->stream));
+    SKH_TRY(c, hipMemsetAsync(c->dAdaptState.p, 0, sizeof(float4) * N1, c->stream));
+    SKH_TRY(c, hipMemsetAsync(c->dAdaptTileQ.p, 0, sizeof(float) * nt, c->stream));
+    SKH_TRY(c, hipMemsetAsync(c->dAdaptFrozenAt.p, 0, sizeof(uint32_t) * nt, c->stream));
+    ad.frozenAt.assign(c->numTiles, 0u);
+    ad.delivered = ad.checks = 0;
+    ad.activeTiles = c->numTiles;
+    ad.raygenValid = c->raygenValidPerSub;
+    ad.pixelObs = ad.pixelObsSaved = 0;
+    ad.ready = true;
+    return SKH_OK;
+}
+
+// launches until the next check, with `delivered` observations made (>= 1)
+static inline uint32_t adapt_to_next_check(const skh_context* c)
+{
+    const skh_context::Adaptive& ad = c->adapt;
+    if (ad.delivered < ad.cfg.min_samples)
+        return ad.cfg.min_samples - ad.delivered;
+    return ad.cfg.interval - (ad.delivered - ad.cfg.min_samples) % ad.cfg.interval;
+}
+
+static FrameP adapt_frame(const skh_context* c, const skh_frame_params& p)
+{
+    FrameP fp;
+    memset(&fp, 0, sizeof(fp));
+    memcpy(fp.exposure, p.exposure, sizeof(fp.exposure));
+    fp.width = c->width, fp.height = c->height, fp.tileSize = c->tileSize, fp.tileShift = c->tileShift, fp.numTiles = c->numTiles, fp.numSlots = c->numSlots;
+    return fp;
+}
+
+// After a pass of `launches` observations: count them, and where their number is one at which a check happens, run it: the decision kernel, the flags back (one word
+// per tile), and -- when a tile froze -- the ray-generation tables of the new render list up (the kernel has moved the origins in the device's list itself).
+static skh_status adapt_after_pass(skh_context* c, const skh_frame_params& p, uint32_t launches)
+{
+    skh_context::Adaptive& ad = c->adapt;
+    ad.delivered += launches;
+    ad.pixelObs += (uint64_t)ad.raygenValid * launches;
+    ad.pixelObsSaved += (uint64_t)(c->raygenValidPerSub - ad.raygenValid) * launches;
+    if (ad.delivered < ad.cfg.min_samples || (ad.delivered - ad.cfg.min_samples) % ad.cfg.interval != 0u || c->numTiles == 0u)
+        return SKH_OK;
+    const float thr2 = ad.cfg.threshold * ad.cfg.threshold;
+    {
+        SpanGuard g(c, KC_ACCUM);
+        k_adapt_tiles<<<c->numTiles, 256, 0, c->stream>>>(adapt_frame(c, p), c->dTileXYRender.as<uint32_t>(), c->dAdaptState.as<float4>(), ad.delivered, thr2,
+                                                          ad.cfg.dark_level, c->dAdaptTileQ.as<float>(), c->dAdaptFrozenAt.as<uint32_t>());
+    }
+    ad.checks++;
+    SKH_TRY(c, hipMemcpyAsync(ad.frozenAt.data(), c->dAdaptFrozenAt.p, sizeof(uint32_t) * c->numTiles, hipMemcpyDeviceToHost, c->stream));
+    SKH_TRY(c, hipStreamSynchronize(c->stream));
+    uint32_t active = 0;
+    for (uint32_t t = 0; t < c->numTiles; ++t)
+        active += ad.frozenAt[t] == 0u ? 1u : 0u;
+    if (active != ad.activeTiles)
+    {
+        std::vector<uint32_t> base;
+        raygen_tables(c, ad.frozenAt.data(), base, ad.raygenValid);
+        SKH_TRY(c, hipMemcpyAsync(c->dRaygenBaseRender.p, base.data(), sizeof(uint32_t) * base.size(), hipMemcpyHostToDevice, c->stream));
+        SKH_TRY(c, hipStreamSynchronize(c->stream)); // (`base` goes out of scope)
+        ad.activeTiles = active;
+    }
+    return SKH_OK;
+}
+
+// the frozen tiles' pixels of a call's d_image
+static void adapt_fill(skh_context* c, const skh_frame_params& p, void* d_image)
+{
+    if (!d_image || c->adapt.activeTiles == c->numTiles || c->numSlots == 0u)
+        return;
+    SpanGuard g(c, KC_ACCUM);
+    k_adapt_fill<<<(c->numSlots + 255) / 256, 256, 0, c->stream>>>(adapt_frame(c, p), c->dTileXY.as<uint32_t>(), c->dAdaptFrozenAt.as<uint32_t>(),
+                                                                 c->dAccum.as<float4>(), reinterpret_cast<float4*>(d_image));
+}
+
+skh_status skh_get_adaptive_info(skh_context* c, skh_adaptive_info* out)
+{
+    if (!c || !out)
+        return SKH_INVALID_ARGUMENT;
+    const skh_context::Adaptive& ad = c->adapt;
+    memset(out, 0, sizeof(*out));
+    out->enabled = ad.on ? 1u : 0u;
+    out->tiles = c->numTiles;
+    out->active_tiles = c->numTiles;
+    if (!ad.on || !ad.ready)
+        return SKH_OK; // (the frame has not begun: every tile active, nothing observed)
+    out->active_tiles = ad.activeTiles;
+    out->checks = ad.checks;
+    uint32_t lo = 0xffffffffu, hi = 0;
+    for (uint32_t t = 0; t < c->numTiles; ++t)
+    {
+        const uint32_t n = ad.frozenAt[t] ? ad.frozenAt[t] : ad.delivered;
+        lo = std::min(lo, n), hi = std::max(hi, n);
+    }
+    out->min_observations = c->numTiles ? lo : 0u;
+    out->max_observations = hi;
+    out->pixel_observations = ad.pixelObs;
+    out->pixel_observations_saved = ad.pixelObsSaved;
+    return SKH_OK;
+}
+
 // One wavefront pass: either one launch of p->samples_this_launch samples (batch = 1), or `batch` consecutive sub-frames
 // of one sample each traced together (more rays per launch; results identical, see k_finalize_batch).
 static skh_status render_one(skh_context* c, const skh_frame_params* p, uint32_t batch, void* d_image, bool trace = true, uint32_t finalFirst = 0,
@@ -1639,7 +1811,11 @@ static skh_status render_one(skh_context* c, const skh_frame_params* p, uint32_t
     if (NP == 0)
         return SKH_OK;
     const uint32_t gridSlots = (c->numSlots + 255) / 256;
-    const uint32_t* tiles = c->dTileXY.as<uint32_t>();
+    // (an adaptive pass: the render list and its tables -- frozen tiles are slots outside the image to every kernel below)
+    const bool adaptive = c->adapt.now;
+    const uint32_t* tiles = adaptive ? c->dTileXYRender.as<uint32_t>() : c->dTileXY.as<uint32_t>();
+    const uint32_t* raygenBase = adaptive ? c->dRaygenBaseRender.as<uint32_t>() : c->dRaygenBase.as<uint32_t>();
+    const uint32_t raygenValid = adaptive ? c->adapt.raygenValid : c->raygenValidPerSub;
     PathS ps{ pathSel ? c->dPathB.as<float>() : c->dPath.as<float>(), pathSel ? c->pathBStride : N };
     RayQ rq[2] = { RayQ{ c->dRayQ[0].as<float>(), NQ, c->queueRegion }, RayQ{ c->dRayQ[1].as<float>(), NQ, c->queueRegion } };
     RayQ shq{ c->dShadowQ.as<float>(), NQ, c->queueRegion };
@@ -1720,8 +1896,7 @@ static skh_status render_one(skh_context* c, const skh_frame_params* p, uint32_t
         blp.sampleBase = fp.subframeIndex + s;
         {
             SpanGuard g(c, KC_RAYGEN);
-            k_raygen<<<c->raygenBlocksPerSub * fp.batch, 512, 0, st>>>(fp, tiles, s, rq[0], counts, ps, c->dRaygenBase.as<uint32_t>(),
-                                                                       c->raygenBlocksPerSub, c->raygenValidPerSub);
+            k_raygen<<<c->raygenBlocksPerSub * fp.batch, 512, 0, st>>>(fp, tiles, s, rq[0], counts, ps, raygenBase, c->raygenBlocksPerSub, raygenValid);
         }
         for (uint32_t b = 0; b < rounds; ++b)
         {
@@ -1858,6 +2033,11 @@ static skh_status render_one(skh_context* c, const skh_frame_params* p, uint32_t
                                               c->dSpecular.as<float4>(), c->dDiffCnt.as<uint16_t>(), c->dSpecCnt.as<uint16_t>(),
                                               reinterpret_cast<float4*>(d_image));
     }
+    if (finalize && adaptive)
+    {
+        SpanGuard g(c, KC_ACCUM, fs);
+        k_adapt_moments<<<gridSlots, 256, 0, fs>>>(fp, tiles, ps, c->dSums.as<float>(), (batch > 1 || oneSampleDirect) ? 0u : 1u, c->dAdaptState.as<float4>());
+    }
     hipError_t e = hipGetLastError();
     if (e != hipSuccess)
     {
@@ -1881,20 +2061,36 @@ skh_status skh_render_subframes(skh_context* c, const skh_frame_params* params, 
     if (s != SKH_OK)
         return s;
     if (n_subframes != 1)
-        spec_drop(c); // (the path state is about to be reused)
+        spec_drop(c, false, true); // (the path state is about to be reused)
     else
         spec_drop(c, true);
     skh_frame_params p = *params;
     // single-sample sub-frames are traced `batchCapacity` at a time when that gives the GPU more rays per launch
     const uint32_t cap = (p.samples_this_launch == 1 && p.debug != 1) ? c->batchCapacity : 1u;
+    const bool adaptive = adapt_applies(c, p) && n_subframes != 0u;
+    if (adaptive && (s = adapt_prepare(c, p)) != SKH_OK)
+        return s;
     for (uint32_t k = 0; k < n_subframes;)
     {
-        const uint32_t b = std::min(cap, n_subframes - k);
-        if ((s = render_one(c, &p, b, d_image)) != SKH_OK)
+        if (adaptive && c->adapt.activeTiles == 0u)
+        {
+            // every tile is frozen: the rest of the call traces nothing
+            c->adapt.pixelObsSaved += (uint64_t)c->raygenValidPerSub * (n_subframes - k);
+            break;
+        }
+        uint32_t b = std::min(cap, n_subframes - k);
+        if (adaptive)
+            b = std::min(b, adapt_to_next_check(c)); // (a batch never straddles a check)
+        c->adapt.now = adaptive;
+        s = render_one(c, &p, b, d_image);
+        c->adapt.now = false;
+        if (s != SKH_OK || (adaptive && (s = adapt_after_pass(c, p, b)) != SKH_OK))
             return s;
         p.subframe_index += p.samples_this_launch * b;
         k += b;
     }
+    if (adaptive)
+        adapt_fill(c, p, d_image);
     SKH_TRY(c, hipStreamSynchronize(c->stream)); // the reference's render() is synchronous (OptixRender.cpp:1012)
     if (c->timing)
         harvest_spans(c);
@@ -1947,10 +2143,11 @@ skh_status skh_render_subframe(skh_context* c, const skh_frame_params* params, v
     if (!c || !params)
         return SKH_INVALID_ARGUMENT;
     skh_context::Speculation& sp = c->spec;
-    const bool eligible = c->speculateMax > 1 && params->samples_this_launch == 1 && params->debug == 0 && c->width != 0 && c->batchCapacity > 1;
+    const bool eligible = c->speculateMax > 1 && params->samples_this_launch == 1 && params->debug == 0 && c->width != 0 && c->batchCapacity > 1 &&
+                          !c->adapt.on; // (an adaptive context traces nothing ahead: a pass that begins at a check cannot start before the check has run)
     if (!eligible)
     {
-        spec_drop(c);
+        spec_drop(c, false, true);
         return skh_render_subframes(c, params, 1, d_image);
     }
     (void)hipSetDevice(c->device);
@@ -2122,6 +2319,17 @@ static skh_status read_slots(skh_context* c, const DevBuf& src, float* host)
 skh_status skh_read_accum(skh_context* c, float* host_rgba)
 {
     return read_slots(c, c->dAccum, host_rgba);
+}
+skh_status skh_read_adaptive(skh_context* c, float* host_rgba)
+{
+    if (!c || !host_rgba || !c->width)
+        return SKH_INVALID_ARGUMENT;
+    if (!c->adapt.on || !c->adapt.ready)
+    {
+        memset(host_rgba, 0, sizeof(float) * 4 * (size_t)c->width * c->height); // (no frame has begun: nothing observed)
+        return SKH_OK;
+    }
+    return read_slots(c, c->dAdaptState, host_rgba);
 }
 skh_status skh_read_aov(skh_context* c, uint32_t which, float* host_rgba)
 {

@@ -208,11 +208,44 @@ int main(int argc, char** argv)
             return 9;
         }
     }
+    if (mode == "gpu-adaptive")
+    {
+        // adaptive sampling with a threshold every tile meets at the first check (2 launches): render() then treats the frame as it treats sppTotal reached
+        if (hr->setAdaptiveSampling(0.05f, 0.0f, 16, 8) || hr->setAdaptiveSampling(0.05f, 0.01f, 1, 8) || hr->isConverged())
+            return 10; // (bad parameters are refused)
+        if (!hr->setAdaptiveSampling(1e3f, 0.01f, 2, 1))
+            return 10;
+    }
     Buffer* out = render->createBuffer(BufferDesc{ W, H, BufferFormat::FLOAT4 });
     for (int f = 0; f < frames; ++f)
     {
         render->render(out);
         out->map();
+    }
+    if (mode == "gpu-adaptive")
+    {
+        // converged after the second launch; every further render() hands back the same picture and traces nothing
+        skh_adaptive_info info;
+        if (!hr->isConverged() || ctx.mSubframeIndex != 2 || skh_get_adaptive_info(hr->context(), &info) != SKH_OK || info.active_tiles != 0 || info.max_observations != 2)
+            return 11;
+        std::vector<char> first((const char*)out->getHostPointer(), (const char*)out->getHostPointer() + out->getHostDataSize());
+        skh_stats before, after;
+        skh_get_stats(hr->context(), &before);
+        render->render(out);
+        out->map();
+        skh_get_stats(hr->context(), &after);
+        if (memcmp(first.data(), out->getHostPointer(), first.size()) != 0 || after.rays_radiance != before.rays_radiance || !hr->isConverged())
+            return 12;
+        // turned off, the frame runs on to sppTotal
+        if (!hr->setAdaptiveSampling(-1.0f, 0.01f, 2, 1))
+            return 13;
+        for (int f = 0; f < frames; ++f)
+        {
+            render->render(out);
+            out->map();
+        }
+        printf("host_test gpu-adaptive ok: subframeIndex %zu\n", ctx.mSubframeIndex);
+        frames = (int)ctx.mFrameNumber;
     }
     if (debugView)
     {

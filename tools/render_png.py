@@ -1,8 +1,11 @@
-"""Renders one of the stand-in scenes, or a glTF file, on the GPU and writes a tonemapped PNG (usage: render_png.py kitchen|cornell|hair|FILE.gltf|FILE.glb W H spp depth [exposure_scale] [out.png] [--env FILE.hdr [--env-rotate DEG]] [--alpha-blend]:
+"""Renders one of the stand-in scenes, or a glTF file, on the GPU and writes a tonemapped PNG (usage: render_png.py kitchen|cornell|hair|FILE.gltf|FILE.glb W H spp depth [exposure_scale] [out.png] [--env FILE.hdr [--env-rotate DEG]] [--alpha-blend] [--adaptive THR [--adaptive-min N --adaptive-interval K]] [--sample-map FILE.png]:
 --env lights the scene with a lat-long Radiance map as its dome light, --env-rotate turns the dome about +Y).  A scene whose materials emit
 (Scene.addMaterial(emission=...), a glTF emissiveFactor) needs no flag: its arrays carry "emission" and Context.set_scene forwards it.  A glTF file is
 loaded with material_textures=True: its metallicRoughnessTexture and emissiveTexture are rendered (arrays()["material_textures"]).
---alpha-blend: a glTF file's alphaMode BLEND materials are rendered with fractional opacity (load_gltf(alpha_blend=True)) instead of as glass."""
+--alpha-blend: a glTF file's alphaMode BLEND materials are rendered with fractional opacity (load_gltf(alpha_blend=True)) instead of as glass.
+--adaptive THR: adaptive sampling -- a tile stops at relative standard error THR of its pixels' tonemapped luminance (checked after --adaptive-min launches,
+default 16, and every --adaptive-interval after, default 8; dark level: radiance 0.05 under the frame's exposure); --sample-map FILE.png writes the per-pixel
+observation count as a grey image (white = spp)."""
 import sys, numpy as np
 sys.path.insert(0, ".")
 import math
@@ -12,15 +15,18 @@ env_file = env_deg = None
 alpha_blend = "--alpha-blend" in sys.argv
 if alpha_blend:
     sys.argv.remove("--alpha-blend")
-for flag in ("--env-rotate", "--env"):
+opts = {}
+for flag in ("--env-rotate", "--env", "--adaptive-min", "--adaptive-interval", "--adaptive", "--sample-map"):
     if flag in sys.argv:
         k = sys.argv.index(flag)
         val = sys.argv[k + 1]
         del sys.argv[k:k + 2]
         if flag == "--env":
             env_file = val
-        else:
+        elif flag == "--env-rotate":
             env_deg = float(val)
+        else:
+            opts[flag] = val
 name = sys.argv[1]; W, H, spp, depth = int(sys.argv[2]), int(sys.argv[3]), int(sys.argv[4]), int(sys.argv[5])
 if name.lower().endswith((".gltf", ".glb")):
     sc, name = gltf.load_gltf(name, material_textures=True, alpha_blend=alpha_blend), name.replace("/", "_")
@@ -31,7 +37,14 @@ if env_file:
     sc.setEnvironment(hdr.load_hdr(env_file), world_to_env=[[math.cos(a), 0, math.sin(a)], [0, 1, 0], [-math.sin(a), 0, math.cos(a)]])
 ctx = capi.Context(0); ctx.set_scene(sc.arrays()); ctx.resize(W, H)
 p = S.frame_params(sc.getCamera(), W, H, subframe_index=0, spp_total=spp, max_depth=depth)
+if "--adaptive" in opts:
+    ctx.set_adaptive(float(opts["--adaptive"]), capi.adaptive_dark_level(0.05, p["exposure"]), int(opts.get("--adaptive-min", 16)), int(opts.get("--adaptive-interval", 8)))
 ctx.render_subframes(p, spp, None)
+if "--adaptive" in opts:
+    print("adaptive:", ctx.adaptive_info(), "rays", ctx.stats()["rays_radiance"] + ctx.stats()["rays_shadow"])
+if "--sample-map" in opts:
+    n = ctx.read_adaptive()[..., 0] if "--adaptive" in opts else np.full((H, W), spp, np.float32)
+    png.save_png(opts["--sample-map"], np.repeat((n / np.float32(spp))[..., None], 3, -1), flipped=True)
 img = torch.from_numpy(ctx.read_accum()).cuda()
 e = S.default_exposure() * np.float32(float(sys.argv[6]) if len(sys.argv) > 6 else 1.0)
 ctx.tonemap(img.data_ptr(), W, H, 1, e, 2.2)   # Reinhard + gamma, as the reference's post chain
