@@ -26,7 +26,7 @@
 extern "C" {
 #endif
 
-#define SKH_ABI_VERSION 5 /* 5 (round 6): + skh_refit_accel, skh_build_info.refit / ms_refit, then skh_update_accel (additive: refit = 2), then skh_set_environment / _transform / skh_get_environment_info + two unit probes (additive), then skh_set_emission / skh_get_emitter_info / skh_emitter_probe (additive), then skh_set_material_blend / skh_get_blend_info / skh_blend_probe (additive), then skh_set_light_shapes / skh_get_light_shape_info / skh_light_shape_probe (additive); options curve_merge, curve_segnode, curve_strand_major, split_pairs.  4 (round 5): + skh_get_build_info; options reinsert_rounds, reinsert_min_size; wide, tail_park, tail_lag removed.  3 (round 4): + skh_unit_probe, skh_copy_aov */
+#define SKH_ABI_VERSION 5 /* 5 (round 6): + skh_refit_accel, skh_build_info.refit / ms_refit, then skh_update_accel (additive: refit = 2), then skh_set_environment / _transform / skh_get_environment_info + two unit probes (additive), then skh_set_emission / skh_get_emitter_info / skh_emitter_probe (additive), then skh_set_material_blend / skh_get_blend_info / skh_blend_probe (additive), then skh_set_light_shapes / skh_get_light_shape_info / skh_light_shape_probe (additive), then skh_adaptive_check / skh_set_adaptive / skh_get_adaptive_info / skh_read_adaptive (additive), then skh_aov_check / skh_render_aovs / skh_get_aov_info (additive; option aov_band); options curve_merge, curve_segnode, curve_strand_major, split_pairs.  4 (round 5): + skh_get_build_info; options reinsert_rounds, reinsert_min_size; wide, tail_park, tail_lag removed.  3 (round 4): + skh_unit_probe, skh_copy_aov */
 
 /* mirrors oka::Result (include/render/common.h:30-35) */
 typedef enum skh_status
@@ -596,6 +596,74 @@ skh_status skh_get_adaptive_info(skh_context* ctx, skh_adaptive_info* out);
 /* per pixel {n, mean, M2, q at the last check of its tile}; W*H float4, row-major; pixels of tiles this context does not own read as 0 */
 skh_status skh_read_adaptive(skh_context* ctx, float* host_rgba);
 
+/* ---- First-hit AOVs: what is under a pixel, and what the surface there looks like before lighting (new; DESIGN.md section 2, "First-hit AOVs").
+ *      Hydra's primId / instanceId / elementId / depth AOVs, picking, and the normal / position / albedo buffers a denoiser or a sampling metric reads.
+ *      A pass of its own, one ray per pixel of a region of the context's image, no accumulation, no anti-aliasing: a raw query, as skh_trace_device is.
+ *   ray      pixel (px, py): generate_camera_ray(px, py, W, H, clip_to_view, view_to_world, jx, jy), W, H from skh_resize.  sample_index ==
+ *            SKH_AOV_PIXEL_CENTRE: jx = jy = 0.5f.  Otherwise jx, jy = sampler_random(init_sampler(px, py, sample_index, spp_total, 52), DIM_PIXEL_X / DIM_PIXEL_Y):
+ *            the camera ray skh_render_subframe traces for that sample, bit for bit -- the planes then describe the first hit of that sample's path.
+ *            tmin from the parameters, tmax = 1e16f, closest hit.
+ *   hit      what skh_trace_device(..., SKH_TRACE_CLOSEST) returns for that ray: cutouts honoured, blend hits under the raw-query rule (a > 0), cutout_rounds applies;
+ *            independent of the builder and of every scheduling option; bake_world is part of its definition, as for every hit record.
+ *   layout   plane k is a caller-owned device buffer of 16 * width * height bytes, pixel (x, y) at (y - y0) * width + (x - x0), row 0 = launch y 0 as for
+ *            skh_read_accum.  A plane whose bit is clear is not touched and its pointer may be NULL.
+ *   words    no fma: every product and sum is rounded, as everywhere in the library.
+ *            kind         0 miss, 1 triangle of a mesh instance, 2 curve segment, 3 light proxy
+ *            instance_id, prim_id   skh_hit's; 0xffffffff at a miss
+ *            material     the index k_shade resolves (0xffffffff -> 0, beyond the list -> 0); 0xffffffff for kinds 0 and 3
+ *            t, u, v      skh_hit's; at a miss t = -1, u = v = 0
+ *            depth        clip = mul44(world_to_clip, (P, 1)) with P the POSITION plane's value, depth = clip.z / clip.w; 1 at a miss
+ *            kind 1       P, N, Ng = fill_triangle(instance, w2o, record, u, v, inside = false): the reference's fillTriangleGeomData; N then replaced by the
+ *                         normal-mapped normal exactly as k_shade does when the material's normal_texture is valid (the vector the debug = 1 view shows);
+ *                         TEXCOORD = the interpolated text_coords[0]; ALBEDO = the material's base_color after resolve_material: what skh_material_probe answers
+ *                         in out[0..2] for (material, u, v), for every material type
+ *            kind 2       P, N = fill_curve(...): the reference's fillCurveGeomData, P being o + t * d moved into the curve's cross-section at the hit's u and onto the
+ *                         radius there (what its normal function does to the point); Ng = N; TEXCOORD 0; ALBEDO = the material's base_color
+ *            kinds 1, 2   facing = dot(Ng, -d) >= 0 ? 1 : -1, d the ray's direction
+ *            kind 3       P = o + t * d (one product, one sum); N = Ng = 0, facing = 0; ALBEDO = (1, 1, 1, 1)
+ *            kind 0       every float plane 0 (POSITION.w too), except the HIT plane's words above
+ *   effects  none on the frame: the accumulator, the AOV accumulators and the adaptive statistics are not touched, tile ownership (skh_set_tiles) is ignored -- every
+ *            context answers for the whole image --, rays_radiance / rays_shadow do not move (the rays are counted in skh_aov_info.rays).  Like skh_trace it waits for
+ *            and drops sub-frames traced ahead: speculation is exact, so images do not change; the drop is counted in skh_stats.speculated_discarded.
+ *   refused  with SKH_INVALID_ARGUMENT, nothing written, the previous state kept: a region that leaves the image or has exactly one zero side; planes == 0 or bits at
+ *            or above SKH_AOV_COUNT; a set bit with a NULL pointer; a matrix entry that is not finite; tmin negative or not finite; with sample_index naming a
+ *            sample, spp_total == 0 or sample_index >= spp_total (an index outside the sequence); a non-zero reserved word; no skh_resize yet.  Without an
+ *            acceleration structure the call builds one, as skh_trace does.
+ *   cost     the region is processed in bands of at most option aov_band rays (2^22; 64 ... 2^26): a 32-byte ray and a 20-byte hit record per ray of a band,
+ *            freed before the call returns.  With option timing its spans are a class of their own: ms_trace_closest does not move.
+ * Not part of it: accumulated or anti-aliased planes, motion vectors, authored face ids (prim_id is the triangle), the eye-space normal, multi-rank gathering. */
+#define SKH_AOV_IDS         0u /* uint32 x 4: instance_id, prim_id, material, kind */
+#define SKH_AOV_HIT         1u /* float  x 4: t, u, v (skh_hit's), depth */
+#define SKH_AOV_NORMAL      2u /* float  x 4: N.xyz, facing */
+#define SKH_AOV_POSITION    3u /* float  x 4: P.xyz, 1 */
+#define SKH_AOV_GEOM_NORMAL 4u /* float  x 4: Ng.xyz, 0 */
+#define SKH_AOV_ALBEDO      5u /* float  x 4: rgb, 1 */
+#define SKH_AOV_TEXCOORD    6u /* float  x 4: text_coords[0].u, .v, 0, 0 */
+#define SKH_AOV_COUNT       7u
+#define SKH_AOV_PIXEL_CENTRE 0xffffffffu
+
+typedef struct skh_aov_params
+{
+    float view_to_world[16], clip_to_view[16]; /* as skh_frame_params: row-major */
+    float world_to_clip[16];                   /* row-major; used by the depth word only */
+    uint32_t x0, y0, width, height;            /* region of the context's image; width = height = 0: the whole image */
+    uint32_t sample_index;                     /* SKH_AOV_PIXEL_CENTRE, or the sample whose camera ray is traced */
+    uint32_t spp_total;                        /* the sampler's, when sample_index names a sample; else ignored */
+    float tmin;                                /* finite, >= 0 */
+    uint32_t reserved[5];                      /* 0 */
+} skh_aov_params;
+
+/* SKH_OK when *p is a setting skh_render_aovs accepts for an image of image_w x image_h pixels (needs no context and no GPU, as skh_adaptive_check) */
+skh_status skh_aov_check(const skh_aov_params* p, uint32_t image_w, uint32_t image_h);
+skh_status skh_render_aovs(skh_context* ctx, const skh_aov_params* p, uint32_t planes /* bit k = plane k */, void* const d_planes[SKH_AOV_COUNT]);
+typedef struct skh_aov_info
+{
+    uint64_t calls, rays; /* since the last skh_reset_stats */
+    double ms_last;       /* wall time of the last call, its synchronisation included */
+    uint64_t bytes_last;  /* plane bytes the last call wrote */
+} skh_aov_info;
+skh_status skh_get_aov_info(skh_context* ctx, skh_aov_info* out);
+
 /* ---- the tonemap() + gammaCorrection post pass (postprocessing/Tonemappers.cu:111-135), in place on a
  *      device float4 image.  type: 0 none, 1 Reinhard, 2 ACES fitted, 3 ACES film; gamma <= 0 = off ---- */
 skh_status skh_tonemap(skh_context* ctx, void* d_image, uint32_t width, uint32_t height, uint32_t type,
@@ -734,7 +802,7 @@ skh_status skh_unit_probe(skh_context* ctx, uint32_t unit, uint32_t param, const
  *                 fetch_chunk (-1 = auto: 128 when the triangle + curve trees hold <= 16384 nodes, else 0; queue positions a trace wave reserves per atomic on its shard's cursor),
  *                 node_break_closest / node_break_shadow (32 / 28, curves 20 / 20 until one is set explicitly: leave the node loop below x/64 descending rays),
  *                 leaf_min (16: lanes for the minority kind of leaf work), curve_min (48: lanes parked in front of the
- *                 curve intersector before it runs), subframe_batch (0 = auto: ~64 M paths per pass),
+ *                 curve intersector before it runs), subframe_batch (0 = auto: ~64 M paths per pass), aov_band (2^22; 64 ... 2^26: rays per band of skh_render_aovs),
  *                 speculate (8: sub-frames traced ahead when skh_render_subframe is called once per sub-frame; 0 = off),
  *                 speculate_async 1|0 (the pass after the one being collected is traced meanwhile, on the render stream, into a second
  *                 path-state buffer; accumulation steps and skh_buffer_download run beside it on their own stream: the caller's map()

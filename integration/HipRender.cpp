@@ -355,6 +355,147 @@ bool HipRender::setAdaptiveSampling(float threshold, float darkRadiance, uint32_
     return true;
 }
 
+// ---- first-hit AOVs: skh_render_aovs ----
+// inverse of a row-major 4 x 4 in double: Gauss-Jordan with partial pivoting; false: singular
+static bool invert4(const double* m, double* out)
+{
+    double a[4][8];
+    for (int r = 0; r < 4; ++r)
+        for (int c = 0; c < 8; ++c)
+            a[r][c] = c < 4 ? m[4 * r + c] : (c - 4 == r ? 1.0 : 0.0);
+    for (int col = 0; col < 4; ++col)
+    {
+        int piv = col;
+        for (int r = col + 1; r < 4; ++r)
+            if (std::fabs(a[r][col]) > std::fabs(a[piv][col]))
+                piv = r;
+        if (a[piv][col] == 0.0)
+            return false;
+        for (int c = 0; c < 8; ++c)
+            std::swap(a[col][c], a[piv][c]);
+        const double inv = 1.0 / a[col][col];
+        for (int c = 0; c < 8; ++c)
+            a[col][c] *= inv;
+        for (int r = 0; r < 4; ++r)
+        {
+            if (r == col)
+                continue;
+            const double f = a[r][col];
+            for (int c = 0; c < 8; ++c)
+                a[r][c] -= f * a[col][c];
+        }
+    }
+    for (int r = 0; r < 4; ++r)
+        for (int c = 0; c < 4; ++c)
+            out[4 * r + c] = a[r][c + 4];
+    return true;
+}
+
+bool HipRender::aovParams(skh_aov_params& p, const uint32_t* region, bool sampleZero)
+{
+    if (!mCtx || !mScene || mWidth == 0 || mHeight == 0)
+    {
+        mError = "renderAovs: call render() first (the scene and the image size are its)";
+        return false;
+    }
+    memset(&p, 0, sizeof(p));
+    Camera& camera = mScene->getCamera(0);
+    camera.updateAspectRatio(mWidth / (float)mHeight);
+    camera.updateViewMatrix();
+    const Mat4 v2w = inverse(camera.matrices.view); // (as render())
+    double dv[16], dc[16], iv[16], ic[16];
+    for (int r = 0; r < 4; ++r)
+        for (int c = 0; c < 4; ++c)
+        {
+            p.view_to_world[4 * r + c] = v2w[c][r];
+            p.clip_to_view[4 * r + c] = camera.matrices.invPerspective[c][r];
+            dv[4 * r + c] = p.view_to_world[4 * r + c], dc[4 * r + c] = p.clip_to_view[4 * r + c];
+        }
+    if (!invert4(dv, iv) || !invert4(dc, ic))
+    {
+        mError = "renderAovs: the camera's matrices are singular";
+        return false;
+    }
+    // world_to_clip = inverse(clip_to_view) . inverse(view_to_world), in double, rounded once
+    for (int r = 0; r < 4; ++r)
+        for (int c = 0; c < 4; ++c)
+        {
+            double s = 0.0;
+            for (int k = 0; k < 4; ++k)
+                s += ic[4 * r + k] * iv[4 * k + c];
+            p.world_to_clip[4 * r + c] = (float)s;
+        }
+    if (region)
+        p.x0 = region[0], p.y0 = region[1], p.width = region[2], p.height = region[3];
+    p.sample_index = sampleZero ? 0u : SKH_AOV_PIXEL_CENTRE;
+    p.spp_total = getSharedContext().mSettingsManager->getAs<uint32_t>("render/pt/sppTotal");
+    p.tmin = getSharedContext().mSettingsManager->getAs<float>("render/pt/dev/materialRayTmin");
+    return true;
+}
+
+bool HipRender::renderAovs(uint32_t planes, Buffer* const* out, const uint32_t* region, bool sampleZero)
+{
+    skh_aov_params p;
+    if (!aovParams(p, region, sampleZero))
+        return false;
+    const uint64_t pixels = region ? (uint64_t)region[2] * region[3] : (uint64_t)mWidth * mHeight;
+    void* d[SKH_AOV_COUNT] = {};
+    for (uint32_t k = 0; k < SKH_AOV_COUNT; ++k)
+    {
+        if (!((planes >> k) & 1u))
+            continue;
+        if (!out || !out[k] || out[k]->getFormat() != BufferFormat::FLOAT4 || (uint64_t)out[k]->width() * out[k]->height() < pixels)
+        {
+            mError = "renderAovs: plane " + std::to_string(k) + " needs a FLOAT4 buffer of the region's size";
+            return false;
+        }
+        d[k] = static_cast<HipBuffer*>(out[k])->getNativePtr();
+    }
+    // (a refusal is the caller's arguments, not a broken renderer: reported, not asserted)
+    if (skh_render_aovs(mCtx, &p, planes, d) != SKH_OK)
+    {
+        mError = std::string("skh_render_aovs: ") + skh_last_error(mCtx);
+        return false;
+    }
+    return true;
+}
+
+bool HipRender::pick(uint32_t x, uint32_t y, HipPick& out)
+{
+    const uint32_t region[4] = { x, y, 1u, 1u };
+    skh_aov_params p;
+    if (!aovParams(p, region, false))
+        return false;
+    void* d = nullptr; // the seven planes of one pixel, back to back
+    if (skh_buffer_alloc(mCtx, 16 * SKH_AOV_COUNT, &d) != SKH_OK)
+    {
+        mError = std::string("skh_buffer_alloc: ") + skh_last_error(mCtx);
+        return false;
+    }
+    void* planes[SKH_AOV_COUNT];
+    for (uint32_t k = 0; k < SKH_AOV_COUNT; ++k)
+        planes[k] = static_cast<char*>(d) + 16 * k;
+    uint32_t w[4 * SKH_AOV_COUNT];
+    const bool ok = skh_render_aovs(mCtx, &p, (1u << SKH_AOV_COUNT) - 1u, planes) == SKH_OK && skh_buffer_download(mCtx, d, w, sizeof(w)) == SKH_OK;
+    if (!ok)
+        mError = std::string("pick: ") + skh_last_error(mCtx);
+    skh_buffer_free(mCtx, d);
+    if (!ok)
+        return false;
+    float f[4 * SKH_AOV_COUNT];
+    memcpy(f, w, sizeof(f));
+    out.instanceId = w[0], out.primId = w[1], out.material = w[2], out.kind = w[3];
+    out.t = f[4 * SKH_AOV_HIT], out.u = f[4 * SKH_AOV_HIT + 1], out.v = f[4 * SKH_AOV_HIT + 2], out.depth = f[4 * SKH_AOV_HIT + 3];
+    for (int k = 0; k < 3; ++k)
+    {
+        out.normal[k] = f[4 * SKH_AOV_NORMAL + k], out.position[k] = f[4 * SKH_AOV_POSITION + k];
+        out.geomNormal[k] = f[4 * SKH_AOV_GEOM_NORMAL + k], out.albedo[k] = f[4 * SKH_AOV_ALBEDO + k];
+    }
+    out.facing = f[4 * SKH_AOV_NORMAL + 3];
+    out.texcoord[0] = f[4 * SKH_AOV_TEXCOORD], out.texcoord[1] = f[4 * SKH_AOV_TEXCOORD + 1];
+    return true;
+}
+
 void HipRender::render(Buffer* output)
 {
     SharedContext& sh = getSharedContext();

@@ -47,6 +47,17 @@ private:
     void* mRegistered = nullptr; // mHostData's storage while it is page-locked (skh_host_register)
 };
 
+struct HipPick // HipRender::pick: the words of skh_render_aovs' seven planes at one pixel
+{
+    uint32_t instanceId, primId, material, kind; // kind: 0 miss, 1 triangle, 2 curve segment, 3 light proxy; the ids are 0xffffffff at a miss
+    float t, u, v, depth;
+    float normal[3], facing;
+    float position[3];
+    float geomNormal[3];
+    float albedo[3];
+    float texcoord[2];
+};
+
 class HipRender : public Render
 {
 public:
@@ -108,6 +119,16 @@ public:
     {
         return mConverged;
     }
+    // First-hit AOVs (skh_render_aovs; new: the reference renders one image and nothing tells a host what is under a pixel).  planes: bit k = plane SKH_AOV_k;
+    // out[k]: a FLOAT4 buffer from createBuffer of at least the region's size for every set bit (the ids plane holds four uint32 per pixel in it), else ignored;
+    // region: {x0, y0, width, height} of the last render()'s image, nullptr = all of it; sampleZero: the camera ray of sample 0 of sppTotal (the first hit of the
+    // first path render() traces per pixel) instead of the ray through the pixel centre.  The camera is the one render() reads; call after the first render().
+    // The frame being accumulated is not disturbed.  false: refused or failed (lastError()).  INTEGRATION.md maps the planes to Hydra's AOVs.
+    bool renderAovs(uint32_t planes, Buffer* const* out, const uint32_t* region = nullptr, bool sampleZero = false);
+    // what is under pixel (x, y): a 1 x 1 region of every plane, through the pixel centre
+    bool pick(uint32_t x, uint32_t y, HipPick& out);
+    // the parameters renderAovs hands to skh_render_aovs for the current camera (world_to_clip: the two inverses in double, rounded once)
+    bool aovParams(skh_aov_params& p, const uint32_t* region, bool sampleZero);
 
 private:
     skh_context* mCtx = nullptr;

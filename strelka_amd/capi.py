@@ -32,7 +32,8 @@ SYMBOLS = ["skh_create", "skh_destroy", "skh_last_error", "skh_abi_version", "sk
            "skh_set_material_textures", "skh_material_probe", "skh_set_material_cutouts", "skh_get_cutout_info",
            "skh_set_material_blend", "skh_get_blend_info", "skh_blend_probe",
            "skh_set_light_shapes", "skh_get_light_shape_info", "skh_light_shape_probe",
-           "skh_adaptive_check", "skh_set_adaptive", "skh_get_adaptive_info", "skh_read_adaptive"]
+           "skh_adaptive_check", "skh_set_adaptive", "skh_get_adaptive_info", "skh_read_adaptive",
+           "skh_aov_check", "skh_render_aovs", "skh_get_aov_info"]
 
 BUILD_INFO = np.dtype([("triangles", np.uint32), ("nodes", np.uint32), ("reinsert_rounds", np.uint32), ("reinsert_moves", np.uint32),
                        ("reinsert_min_size", np.uint32), ("refit", np.uint32), ("cost_before", np.float64), ("cost_after", np.float64),
@@ -51,6 +52,8 @@ ADAPTIVE = np.dtype([("threshold", np.float32), ("dark_level", np.float32), ("mi
 ADAPTIVE_INFO = np.dtype([("enabled", np.uint32), ("tiles", np.uint32), ("active_tiles", np.uint32), ("checks", np.uint32), ("min_observations", np.uint32),
                           ("max_observations", np.uint32), ("pixel_observations", np.uint64), ("pixel_observations_saved", np.uint64)])
 assert ADAPTIVE.itemsize == 32 and ADAPTIVE_INFO.itemsize == 40
+AOV_INFO = np.dtype([("calls", np.uint64), ("rays", np.uint64), ("ms_last", np.float64), ("bytes_last", np.uint64)])
+assert AOV_INFO.itemsize == 32
 # skh_light_shape_probe: kind -> (number, words in, words out) per record
 LSHAPE_PROBES = {"sample": (0, 6, 13), "pdf": (1, 7, 2)}
 # skh_emitter_probe: kind -> (number, words in, words out) per record
@@ -121,6 +124,9 @@ def load():
     lib.skh_set_adaptive.argtypes = [vp, vp]
     lib.skh_get_adaptive_info.argtypes = [vp, vp]
     lib.skh_read_adaptive.argtypes = [vp, vp]
+    lib.skh_aov_check.argtypes = [vp, u32, u32]
+    lib.skh_render_aovs.argtypes = [vp, vp, u32, vp]
+    lib.skh_get_aov_info.argtypes = [vp, vp]
     lib.skh_resize.argtypes = [vp, u32, u32]
     lib.skh_set_tiles.argtypes = [vp, u32, vp, u32]
     lib.skh_render_subframe.argtypes = [vp, vp, vp]
@@ -172,6 +178,12 @@ def adaptive_record(threshold, dark_level, min_samples, interval):
     a = np.zeros((), ADAPTIVE)
     a["threshold"], a["dark_level"], a["min_samples"], a["interval"] = threshold, dark_level, min_samples, interval
     return a
+
+
+def aov_check(params, image_w, image_h):
+    """skh_aov_check: would skh_render_aovs accept these S.AOV_PARAMS for an image of image_w x image_h?  (needs no context and no GPU)"""
+    p = np.ascontiguousarray(params, dtype=S.AOV_PARAMS)
+    return load().skh_aov_check(_p(p), int(image_w), int(image_h)) == 0
 
 
 def adaptive_dark_level(radiance, exposure):
@@ -426,6 +438,59 @@ class Context:
         out = np.zeros((self.height, self.width, 4), np.float32)
         self._ck(self.lib.skh_read_adaptive(self.h, _p(out)), "skh_read_adaptive")
         return out
+
+    def buffer_alloc(self, nbytes):
+        """skh_buffer_alloc: a caller-owned device buffer (free it with buffer_free)"""
+        d = C.c_void_p()
+        self._ck(self.lib.skh_buffer_alloc(self.h, int(nbytes), C.byref(d)), "skh_buffer_alloc")
+        return d
+
+    def buffer_free(self, d_ptr):
+        self._ck(self.lib.skh_buffer_free(self.h, d_ptr), "skh_buffer_free")
+
+    def render_aovs_device(self, params, planes_mask, d_planes):
+        """skh_render_aovs on caller-owned device buffers: `d_planes` a sequence of len(S.AOV_PLANES) device pointers (None where the bit is clear)"""
+        p = np.ascontiguousarray(params, dtype=S.AOV_PARAMS)
+        ptrs = (C.c_void_p * len(S.AOV_PLANES))(*[getattr(d, "value", d) for d in d_planes])
+        self._ck(self.lib.skh_render_aovs(self.h, _p(p), int(planes_mask), C.cast(ptrs, C.c_void_p)), "skh_render_aovs")
+
+    def render_aovs(self, params, planes=S.AOV_PLANES, region=None, sample_index=None, spp_total=64):
+        """skh_render_aovs: the first-hit planes named in `planes` (S.AOV_PLANES) of `region` (x0, y0, width, height; None = the region of `params`, which
+        S.aov_params leaves at the whole image) -> {name: (h, w, 4) array}, `ids` uint32, the rest float32.  `sample_index` None = the ray of `params`
+        (S.aov_params: the pixel centre), else the camera ray of that sample of `spp_total`.  Device buffers come from skh_buffer_alloc and are freed here."""
+        p = np.array(params, dtype=S.AOV_PARAMS)
+        if region is not None:
+            p["x0"], p["y0"], p["width"], p["height"] = region
+        if sample_index is not None:
+            p["sample_index"], p["spp_total"] = sample_index, spp_total
+        w, h = (int(p["width"]), int(p["height"])) if int(p["width"]) or int(p["height"]) else (self.width, self.height)
+        names = [n for n in S.AOV_PLANES if n in planes]
+        if len(names) != len(set(planes)):
+            raise ValueError(f"planes must be among {S.AOV_PLANES}")
+        mask = sum(1 << S.AOV_PLANES.index(n) for n in names)
+        bufs = {}
+        try:
+            for n in names:
+                bufs[n] = self.buffer_alloc(16 * max(1, w * h))
+            self.render_aovs_device(p, mask, [bufs.get(n) for n in S.AOV_PLANES])
+            out = {}
+            for n in names:
+                out[n] = np.zeros((h, w, 4), np.uint32 if n == "ids" else np.float32)
+                self.buffer_download(bufs[n], out[n])
+            return out
+        finally:
+            for d in bufs.values():
+                self.buffer_free(d)
+
+    def pick(self, params, x, y):
+        """what is under pixel (x, y): a 1 x 1 region call of render_aovs with every plane -> {plane name: its four words}"""
+        return {n: a[0, 0] for n, a in self.render_aovs(params, region=(x, y, 1, 1)).items()}
+
+    def aov_info(self):
+        """skh_get_aov_info: calls and rays since the last reset_stats, the last call's wall time and plane bytes"""
+        d = np.zeros((), AOV_INFO)
+        self._ck(self.lib.skh_get_aov_info(self.h, _p(d)), "skh_get_aov_info")
+        return {k: (float(d[k]) if d[k].dtype.kind == "f" else int(d[k])) for k in AOV_INFO.names}
 
     def render_subframe(self, params, d_image=None):
         p = np.ascontiguousarray(params, dtype=S.FRAME_PARAMS)

@@ -62,6 +62,7 @@ enum KernelClass
     KC_RAYGEN,
     KC_ACCUM,
     KC_SORT,
+    KC_AOV, // skh_render_aovs: its ray generation, trace launches and resolve (in no field of skh_stats)
     KC_COUNT
 };
 
@@ -319,9 +320,12 @@ struct skh_context
     std::vector<TimedSpan> spans;
     std::vector<hipEvent_t> eventPool;
     size_t eventsUsed = 0;
-    double msClass[KC_COUNT] = { 0, 0, 0, 0, 0, 0 };
-    uint32_t launches[KC_COUNT] = { 0, 0, 0, 0, 0, 0 };
+    double msClass[KC_COUNT] = { 0, 0, 0, 0, 0, 0, 0 };
+    uint32_t launches[KC_COUNT] = { 0, 0, 0, 0, 0, 0, 0 };
     double msBuild = 0.0;
+    // first-hit AOVs (skh_render_aovs): nothing but these words lives between two calls
+    uint32_t aovBand = 1u << 22; // option aov_band: rays per band
+    skh_aov_info aovInfo = {};
 };
 
 // a failing HIP call ends the function: its message names the function, the call and the HIP error

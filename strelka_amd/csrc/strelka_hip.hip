@@ -36,6 +36,7 @@ static_assert(sizeof(skh_material) == 64 && sizeof(skh_frame_params) == 176 && s
 static_assert(sizeof(skh_hit) == 20 && sizeof(Light) == 112 && sizeof(Material) == 64 && sizeof(HostInstance) == 64, "layout");
 
 #include "skh_host.h"
+#include "skh_aov.h"
 
 // Sobol generator matrices for the 5 dimensions the reference tabulates (RandomSampler.h:139-164), produced from the
 // Joe-Kuo recurrences (d=2: s=1 a=0 m={1}; d=3: s=2 a=1 m={1,3}; d=4: s=3 a=1 m={1,3,1}; d=5: s=3 a=2 m={1,1,1}).
@@ -2791,7 +2792,8 @@ skh_status skh_probe_memory(skh_context* c, uint32_t kind, uint64_t bytes, uint3
     return SKH_OK;
 }
 
-skh_status skh_trace_device(skh_context* c, const void* d_rays, uint32_t n_rays, uint32_t mode, void* d_hits, uint32_t repeat)
+// skh_trace_device's path: `cls` is the kernel class its spans are counted under (skh_render_aovs traces through here under a class of its own)
+static skh_status trace_device_as(skh_context* c, const void* d_rays, uint32_t n_rays, uint32_t mode, void* d_hits, uint32_t repeat, KernelClass cls)
 {
     if (!c || (n_rays && (!d_rays || !d_hits)) || mode > 1)
         return SKH_INVALID_ARGUMENT;
@@ -2838,7 +2840,7 @@ skh_status skh_trace_device(skh_context* c, const void* d_rays, uint32_t n_rays,
     for (uint32_t r = 0; r < std::max(1u, repeat); ++r)
     {
         (void)hipMemsetAsync(dfetch, 0, sizeof(uint32_t) * (8 * SKH_FETCH_STRIDE + cutWordCount), c->stream);
-        SpanGuard g(c, mode == SKH_TRACE_SHADOW ? KC_TRACE_SHADOW : KC_TRACE_CLOSEST);
+        SpanGuard g(c, cls);
         if (cutOn)
         {
             const RayQ q0{ cq0.as<float>(), (uint32_t)NQ, per }, q1{ cq1.as<float>(), (uint32_t)NQ, per };
@@ -2897,6 +2899,11 @@ skh_status skh_trace_device(skh_context* c, const void* d_rays, uint32_t n_rays,
     return check_stack_overflow(c, "skh_trace");
 }
 
+skh_status skh_trace_device(skh_context* c, const void* d_rays, uint32_t n_rays, uint32_t mode, void* d_hits, uint32_t repeat)
+{
+    return trace_device_as(c, d_rays, n_rays, mode, d_hits, repeat, mode == SKH_TRACE_SHADOW ? KC_TRACE_SHADOW : KC_TRACE_CLOSEST);
+}
+
 skh_status skh_trace(skh_context* c, const skh_ray* rays, uint32_t n_rays, uint32_t mode, skh_hit* hits)
 {
     if (!c || (n_rays && (!rays || !hits)))
@@ -2918,6 +2925,107 @@ skh_status skh_trace(skh_context* c, const skh_ray* rays, uint32_t n_rays, uint3
         }
     }
     return s;
+}
+
+// ---- first-hit AOVs (skh_aov.h): skh_aov_check, skh_render_aovs, skh_get_aov_info ----
+static_assert(sizeof(skh_aov_params) == 240 && sizeof(skh_aov_info) == 32, "ABI layout");
+
+// why *p is refused for an image_w x image_h image, or nullptr
+static const char* aov_refusal(const skh_aov_params* p, uint32_t image_w, uint32_t image_h)
+{
+    if (!p)
+        return "no parameters";
+    if (image_w == 0u || image_h == 0u)
+        return "the image is empty (call skh_resize first)";
+    const bool whole = p->width == 0u && p->height == 0u;
+    if (whole ? (p->x0 != 0u || p->y0 != 0u) : (p->width == 0u || p->height == 0u || p->x0 >= image_w || p->y0 >= image_h || p->width > image_w - p->x0 || p->height > image_h - p->y0))
+        return "the region leaves the image or has one zero side";
+    for (int k = 0; k < 16; ++k)
+        if (!std::isfinite(p->view_to_world[k]) || !std::isfinite(p->clip_to_view[k]) || !std::isfinite(p->world_to_clip[k]))
+            return "a matrix entry that is not finite";
+    if (!std::isfinite(p->tmin) || p->tmin < 0.0f)
+        return "tmin negative or not finite";
+    if (p->sample_index != SKH_AOV_PIXEL_CENTRE && (p->spp_total == 0u || p->sample_index >= p->spp_total))
+        return "sample_index outside the sequence of spp_total samples";
+    for (uint32_t r : p->reserved)
+        if (r != 0u)
+            return "a non-zero reserved word";
+    return nullptr;
+}
+
+skh_status skh_aov_check(const skh_aov_params* p, uint32_t image_w, uint32_t image_h)
+{
+    return aov_refusal(p, image_w, image_h) ? SKH_INVALID_ARGUMENT : SKH_OK;
+}
+
+skh_status skh_render_aovs(skh_context* c, const skh_aov_params* p, uint32_t planes, void* const d_planes[SKH_AOV_COUNT])
+{
+    if (!c)
+        return SKH_INVALID_ARGUMENT;
+    const char* why = aov_refusal(p, c->width, c->height);
+    if (!why && (planes == 0u || (planes >> SKH_AOV_COUNT) != 0u))
+        why = "no plane asked for, or a bit at or above SKH_AOV_COUNT";
+    if (!why && !d_planes)
+        why = "no plane pointers";
+    for (uint32_t k = 0; !why && k < SKH_AOV_COUNT; ++k)
+        if (((planes >> k) & 1u) && !d_planes[k])
+            why = "a plane asked for without a buffer";
+    if (why)
+    {
+        c->err = std::string("skh_render_aovs: ") + why;
+        return SKH_INVALID_ARGUMENT;
+    }
+    (void)hipSetDevice(c->device);
+    const auto t0 = std::chrono::steady_clock::now();
+    SKH_CHECK(ensure_ready(c)); // (the scene record below is the built one's)
+    AovP ap;
+    memcpy(ap.viewToWorld, p->view_to_world, sizeof(ap.viewToWorld));
+    memcpy(ap.clipToView, p->clip_to_view, sizeof(ap.clipToView));
+    memcpy(ap.worldToClip, p->world_to_clip, sizeof(ap.worldToClip));
+    const bool whole = p->width == 0u && p->height == 0u;
+    ap.imageW = c->width, ap.imageH = c->height;
+    ap.x0 = p->x0, ap.y0 = p->y0, ap.width = whole ? c->width : p->width;
+    const uint32_t regionH = whole ? c->height : p->height;
+    ap.sampleIndex = p->sample_index, ap.sppTotal = p->spp_total, ap.tmin = p->tmin;
+    const uint64_t total = (uint64_t)ap.width * regionH;
+    const uint32_t band = (uint32_t)std::min<uint64_t>(total, c->aovBand);
+    DevBuf rays, hits; // (of one band; gone when the call returns)
+    SKH_CHECK(dev_alloc(c, rays, sizeof(skh_ray) * (size_t)band));
+    SKH_CHECK(dev_alloc(c, hits, sizeof(skh_hit) * (size_t)band));
+    const MtexP mtexp = make_mtex(c);
+    for (uint64_t first = 0; first < total; first += band)
+    {
+        ap.first = (uint32_t)first, ap.count = (uint32_t)std::min<uint64_t>(band, total - first);
+        {
+            SpanGuard g(c, KC_AOV);
+            k_aov_raygen<<<(ap.count + 255) / 256, 256, 0, c->stream>>>(ap, rays.as<float4>());
+        }
+        SKH_CHECK(trace_device_as(c, rays.p, ap.count, SKH_TRACE_CLOSEST, hits.p, 1, KC_AOV));
+        AovPlanes out;
+        for (uint32_t k = 0; k < SKH_AOV_COUNT; ++k)
+            out.p[k] = ((planes >> k) & 1u) ? reinterpret_cast<uint4*>(d_planes[k]) + first : nullptr;
+        {
+            SpanGuard g(c, KC_AOV);
+            k_aov_resolve<<<(ap.count + 255) / 256, 256, 0, c->stream>>>(make_dev_scene(c), mtexp, ap, planes, rays.as<float4>(), hits.as<skh_hit>(), out);
+        }
+        SKH_TRY(c, hipGetLastError());
+        SKH_TRY(c, hipStreamSynchronize(c->stream)); // (the band's buffers are reused)
+    }
+    if (c->timing)
+        harvest_spans(c);
+    c->aovInfo.calls++;
+    c->aovInfo.rays += total;
+    c->aovInfo.ms_last = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    c->aovInfo.bytes_last = 16ull * total * (uint64_t)__builtin_popcount(planes);
+    return SKH_OK;
+}
+
+skh_status skh_get_aov_info(skh_context* c, skh_aov_info* out)
+{
+    if (!c || !out)
+        return SKH_INVALID_ARGUMENT;
+    *out = c->aovInfo;
+    return SKH_OK;
 }
 
 // ---- BSDF probes (tests) ----
@@ -3158,6 +3266,7 @@ static const OptRow kOptions[] = {
     { "env_nee", 0, 1, OPT_NONE, OPT_U32(envNee) },
     { "emit_nee", 0, 1, OPT_NONE, OPT_U32(emitNee) },
     { "cutout_rounds", 1, 32, OPT_NONE, OPT_U32(cutoutRounds) }, // (the frame's counter words are sized by it: cut_alloc_frame before the next render)
+    { "aov_band", 64, 1 << 26, OPT_NONE, OPT_U32(aovBand) },
     { "speculate", 0, 64, OPT_NONE, OPT_U32(speculateMax) },
     { "speculate_grow", 2, 64, OPT_NONE, OPT_U32(speculateGrow) },
     { "speculate_async", 0, 1, OPT_NONE, [](skh_context* c, int64_t v) { spec_drop(c), c->speculateAsync = (uint32_t)v; } },
@@ -3372,6 +3481,7 @@ skh_status skh_reset_stats(skh_context* c)
     c->stackOverflows = 0;
     c->discardedRadiance = c->discardedShadow = 0;
     c->discardedSubframes = 0;
+    c->aovInfo.calls = c->aovInfo.rays = 0;
     for (int k = 0; k < KC_COUNT; ++k)
     {
         c->msClass[k] = 0.0;

@@ -50,6 +50,12 @@ LIGHT_SHAPE = np.dtype([("flags", np.uint32), ("cos_outer", np.float32), ("cos_i
 assert LIGHT_SHAPE.itemsize == 32
 LIGHT_SHAPE_SAMPLE_DISC, LIGHT_SHAPE_CONE = 1, 2
 assert MATERIAL.itemsize == 64 and FRAME_PARAMS.itemsize == 176 and RAY.itemsize == 32 and HIT.itemsize == 20
+AOV_PARAMS = np.dtype([("view_to_world", np.float32, 16), ("clip_to_view", np.float32, 16), ("world_to_clip", np.float32, 16),
+                       ("x0", np.uint32), ("y0", np.uint32), ("width", np.uint32), ("height", np.uint32), ("sample_index", np.uint32),
+                       ("spp_total", np.uint32), ("tmin", np.float32), ("reserved", np.uint32, 5)])  # skh_aov_params, 240 B
+assert AOV_PARAMS.itemsize == 240
+AOV_PLANES = ("ids", "hit", "normal", "position", "geom_normal", "albedo", "texcoord")  # SKH_AOV_*: plane k's name
+AOV_PIXEL_CENTRE = 0xFFFFFFFF
 
 INSTANCE_MESH, INSTANCE_LIGHT, INSTANCE_CURVE = 0, 1, 2  # oka::Instance::Type
 MAT_DIFFUSE, MAT_PBR, MAT_GLASS, MAT_HAIR = 0, 1, 2, 3
@@ -595,6 +601,21 @@ def frame_params(camera, width, height, subframe_index=0, samples_this_launch=1,
     p["exposure"] = default_exposure() if exposure is None else exposure
     p["enable_accumulation"], p["debug"] = enable_accumulation, debug
     p["shadow_ray_tmin"], p["material_ray_tmin"] = shadow_ray_tmin, material_ray_tmin
+    return p
+
+
+def aov_params(camera, width, height, region=None, sample_index=None, spp_total=64, tmin=0.0):
+    """skh_aov_params for skh_render_aovs: the two matrices as frame_params fills them; world_to_clip = inverse(clip_to_view) . inverse(view_to_world) of
+    those float32 matrices, in float64, rounded once.  `region` (x0, y0, width, height) or None = the whole image; `sample_index` None = the pixel centre."""
+    f = frame_params(camera, width, height)
+    p = np.zeros((), AOV_PARAMS)
+    p["view_to_world"], p["clip_to_view"] = f["view_to_world"], f["clip_to_view"]
+    v2w, c2v = (np.asarray(f[k], np.float64).reshape(4, 4) for k in ("view_to_world", "clip_to_view"))
+    p["world_to_clip"] = (np.linalg.inv(c2v) @ np.linalg.inv(v2w)).astype(np.float32).reshape(16)
+    if region is not None:
+        p["x0"], p["y0"], p["width"], p["height"] = region
+    p["sample_index"] = AOV_PIXEL_CENTRE if sample_index is None else sample_index
+    p["spp_total"], p["tmin"] = spp_total, tmin
     return p
 
 

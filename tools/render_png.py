@@ -5,7 +5,10 @@ loaded with material_textures=True: its metallicRoughnessTexture and emissiveTex
 --alpha-blend: a glTF file's alphaMode BLEND materials are rendered with fractional opacity (load_gltf(alpha_blend=True)) instead of as glass.
 --adaptive THR: adaptive sampling -- a tile stops at relative standard error THR of its pixels' tonemapped luminance (checked after --adaptive-min launches,
 default 16, and every --adaptive-interval after, default 8; dark level: radiance 0.05 under the frame's exposure); --sample-map FILE.png writes the per-pixel
-observation count as a grey image (white = spp)."""
+observation count as a grey image (white = spp).
+--aov NAME=FILE.png (repeatable): a first-hit plane of the same camera through the pixel centres (skh_render_aovs), NAME one of ids, depth, normal, geom_normal,
+position, albedo, uv: normals as (N + 1) / 2 (black where nothing is hit), depth normalised over the hits (near white, far black), ids as hashed colours of
+(instance, primitive), albedo, position and uv written straight (clipped to 0 ... 1 by the PNG)."""
 import sys, numpy as np
 sys.path.insert(0, ".")
 import math
@@ -15,6 +18,11 @@ env_file = env_deg = None
 alpha_blend = "--alpha-blend" in sys.argv
 if alpha_blend:
     sys.argv.remove("--alpha-blend")
+aov_out = []
+while "--aov" in sys.argv:
+    k = sys.argv.index("--aov")
+    aov_out.append(tuple(sys.argv[k + 1].split("=", 1)))
+    del sys.argv[k:k + 2]
 opts = {}
 for flag in ("--env-rotate", "--env", "--adaptive-min", "--adaptive-interval", "--adaptive", "--sample-map"):
     if flag in sys.argv:
@@ -45,6 +53,26 @@ if "--adaptive" in opts:
 if "--sample-map" in opts:
     n = ctx.read_adaptive()[..., 0] if "--adaptive" in opts else np.full((H, W), spp, np.float32)
     png.save_png(opts["--sample-map"], np.repeat((n / np.float32(spp))[..., None], 3, -1), flipped=True)
+if aov_out:
+    plane_of = {"ids": "ids", "depth": "hit", "normal": "normal", "geom_normal": "geom_normal", "position": "position", "albedo": "albedo", "uv": "texcoord"}
+    a = ctx.render_aovs(S.aov_params(sc.getCamera(), W, H), tuple({"ids"} | {plane_of[n] for n, _ in aov_out}))
+    hit = a["ids"][..., 3] != 0
+    surface = ((a["ids"][..., 3] == 1) | (a["ids"][..., 3] == 2))[..., None]
+    for n, path in aov_out:
+        if n == "ids":
+            h = (a["ids"][..., 0] * np.uint32(0x9E3779B1)) ^ (a["ids"][..., 1] * np.uint32(0x85EBCA6B))
+            h ^= h >> np.uint32(15)
+            rgb = np.stack([(h >> np.uint32(s)) & np.uint32(255) for s in (0, 8, 16)], -1).astype(np.float32) / 255.0 * hit[..., None]
+        elif n == "depth":
+            d = a["hit"][..., 3]
+            lo, hi = (float(d[hit].min()), float(d[hit].max())) if hit.any() else (0.0, 1.0)
+            rgb = np.repeat(np.where(hit, 1.0 - (d - lo) / max(hi - lo, 1e-30), 0.0)[..., None], 3, -1).astype(np.float32)
+        elif n in ("normal", "geom_normal"):
+            rgb = np.where(surface, (a[n][..., :3] + np.float32(1.0)) * np.float32(0.5), np.float32(0.0))
+        else:
+            rgb = a[plane_of[n]][..., :3]
+        png.save_png(path, np.ascontiguousarray(rgb, np.float32), flipped=True)
+        print("wrote", n, path)
 img = torch.from_numpy(ctx.read_accum()).cuda()
 e = S.default_exposure() * np.float32(float(sys.argv[6]) if len(sys.argv) > 6 else 1.0)
 ctx.tonemap(img.data_ptr(), W, H, 1, e, 2.2)   # Reinhard + gamma, as the reference's post chain
