@@ -664,6 +664,64 @@ typedef struct skh_aov_info
 } skh_aov_info;
 skh_status skh_get_aov_info(skh_context* ctx, skh_aov_info* out);
 
+/* ---- Denoiser: an edge-avoiding a-trous filter guided by the first-hit planes (new; DESIGN.md section 2, "Denoiser").  Dammertz et al., HPG 2010, with the
+ *      position term taken as the tap's distance from the centre's tangent plane and the colour filtered after division by the first-hit albedo.
+ *      The float32 planes below are the definition; what the kernels pack them into is a copy of their words.
+ *   inputs   caller-owned device images of width x height records of 16 bytes, row-major, in the layout of skh_render_aovs: the colour C (float rgba), and the planes
+ *            IDS (its `kind` word is used), NORMAL (xyz), POSITION (xyz), ALBEDO (rgb).
+ *   surface  a SURFACE pixel has kind 1 or 2 and a colour whose r, g, b are finite.  Every other pixel (a miss, a light proxy, a non-finite colour) is copied to the
+ *            output bit for bit and is never a tap of anybody else.  The alpha word of every pixel passes through bit for bit.
+ *   level l  step s = 1 << l; for a surface pixel p, from the level's input c (the first level's: C, or C demodulated; then the previous level's output):
+ *              taps   q = p + s (dx, dy), dy = -2 .. 2 outer, dx = -2 .. 2 inner; a tap outside the image or on a pixel that is no surface pixel is skipped
+ *              e = c(q) - c(p), n = N(q) - N(p), g = P(q) - P(p), each per component
+ *              a = (((e.x e.x + e.y e.y) + e.z e.z) kc + ((n.x n.x + n.y n.y) + n.z n.z) kn) + (d d) kp,   d = (N(p).x g.x + N(p).y g.y) + N(p).z g.z
+ *                  kc = 1 / (sc sc), sc = sigma_color 2^-l;  kn = 1 / (sigma_normal sigma_normal);  kp = 1 / (sigma_plane sigma_plane)   (float32; +inf gives 0)
+ *              an a that is not <= 64 counts as 64 (a NaN too)
+ *              w = (h[dx] h[dy]) exp(-a), h = {1/16, 1/4, 3/8, 1/4, 1/16}, exp = skh_libm.h's
+ *              sw += w, sc += w c(q) per channel, in tap order;  out(p) = sc / sw per channel
+ *            Every product, sum and quotient is a rounded float32 operation: no fma.  A skipped tap is selected out, never multiplied by zero (0 * NaN would
+ *            poison the sum).  The order is fixed, so the bits are a function of the inputs alone.
+ *   flags    SKH_DENOISE_DEMODULATE: the first level's input is C.rgb / m per channel on surface pixels, m = albedo > albedo_floor ? albedo : albedo_floor
+ *            SKH_DENOISE_REMODULATE: the last level's output is multiplied by the same m.  Two flags, so that calls can be chained: levels first_level ..
+ *            first_level + levels - 1 in one call give the bits of that many one-level calls, the first with DEMODULATE and the last with REMODULATE.
+ *   call     synchronous, as skh_render_aovs.  d_out == d_color is allowed and gives the bits of the out-of-place call.  d_albedo may be NULL when neither flag
+ *            is set.  params == NULL frees the scratch the context holds (the other arguments are ignored).
+ *   effects  none on the frame: the accumulator, the AOV accumulators, the adaptive statistics and the ray counts are not read or written; tile ownership plays no
+ *            part; sub-frames traced ahead are NOT dropped (the call reads nothing of the frame) -- it runs beside them, as skh_tonemap does.
+ *   refused  with SKH_INVALID_ARGUMENT, nothing written, the previous state kept: what skh_denoise_check refuses -- width or height 0 or width * height > 2^26;
+ *            levels 0 or first_level + levels > 8; a sigma that is <= 0 or NaN (+inf is legal and turns its term off); an albedo_floor that is <= 0 or not
+ *            finite; a flag bit other than the two; a non-zero reserved word -- and a NULL image that the call needs.
+ *   cost     scratch owned by the context, 56 bytes per pixel (two colour images, one guide record), grown when a larger image comes, freed by skh_destroy and
+ *            by skh_denoise(ctx, NULL, ...).  A context that never calls it allocates and launches nothing for it.
+ * Not part of it: variance guidance (SVGF), temporal accumulation or reprojection, separate diffuse / specular filtering, firefly clamping, a denoised accumulator. */
+#define SKH_DENOISE_DEMODULATE 1u
+#define SKH_DENOISE_REMODULATE 2u
+#define SKH_DENOISE_MAX_LEVEL  8u /* first_level + levels <= 8: steps up to 128 */
+
+typedef struct skh_denoise_params
+{
+    uint32_t width, height;      /* >= 1, width * height <= 2^26 */
+    uint32_t first_level, levels; /* levels >= 1, first_level + levels <= SKH_DENOISE_MAX_LEVEL */
+    float sigma_color;           /* > 0 (+inf: off); of the first level's input, halved per level */
+    float sigma_normal;          /* > 0 (+inf: off) */
+    float sigma_plane;           /* > 0 (+inf: off); scene units */
+    float albedo_floor;          /* finite, > 0 */
+    uint32_t flags;              /* SKH_DENOISE_* */
+    uint32_t reserved[7];        /* 0 */
+} skh_denoise_params;
+
+/* SKH_OK when *p is a setting skh_denoise accepts (needs no context and no GPU, as skh_aov_check) */
+skh_status skh_denoise_check(const skh_denoise_params* p);
+skh_status skh_denoise(skh_context* ctx, const skh_denoise_params* p, const void* d_color, const void* d_ids, const void* d_normal, const void* d_position,
+                       const void* d_albedo, void* d_out);
+typedef struct skh_denoise_info
+{
+    uint64_t calls, pixels;  /* since the last skh_reset_stats */
+    double ms_last;          /* wall time of the last call, its synchronisation included */
+    uint64_t scratch_bytes;  /* device bytes the context holds for the filter now */
+} skh_denoise_info;
+skh_status skh_get_denoise_info(skh_context* ctx, skh_denoise_info* out);
+
 /* ---- the tonemap() + gammaCorrection post pass (postprocessing/Tonemappers.cu:111-135), in place on a
  *      device float4 image.  type: 0 none, 1 Reinhard, 2 ACES fitted, 3 ACES film; gamma <= 0 = off ---- */
 skh_status skh_tonemap(skh_context* ctx, void* d_image, uint32_t width, uint32_t height, uint32_t type,
@@ -673,6 +731,8 @@ skh_status skh_tonemap(skh_context* ctx, void* d_image, uint32_t width, uint32_t
 skh_status skh_buffer_alloc(skh_context* ctx, size_t bytes, void** out_device_ptr);
 skh_status skh_buffer_free(skh_context* ctx, void* device_ptr);
 skh_status skh_buffer_download(skh_context* ctx, const void* device_ptr, void* host, size_t bytes);
+/* host -> device, the mirror of skh_buffer_download: how a caller hands planes of its own (skh_denoise's inputs, say) to the device.  Synchronous. */
+skh_status skh_buffer_upload(skh_context* ctx, void* device_ptr, const void* host, size_t bytes);
 /* Page-locks / releases a caller-owned host range so that skh_buffer_download into it runs at PCIe rate (the host mirror of
  * Buffer::map, OptixBuffer.cpp:37-43, is a pageable std::vector in the reference; the caller maps after EVERY sub-frame). */
 skh_status skh_host_register(skh_context* ctx, void* host, size_t bytes);

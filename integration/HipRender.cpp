@@ -86,6 +86,7 @@ void* HipBuffer::map()
 
 HipRender::~HipRender()
 {
+    freeGuides();
     if (mCtx && mGatherBuf)
         skh_buffer_free(mCtx, mGatherBuf);
     if (mCtx)
@@ -179,6 +180,7 @@ void HipRender::uploadScene()
     std::vector<skh_instance> inst = instanceTable(sc);
     check(skh_set_instances(mCtx, inst.data(), (uint32_t)inst.size()), "skh_set_instances");
     mSentInstances = inst;
+    measureScene(inst);
     check(skh_set_lights(mCtx, reinterpret_cast<const skh_light*>(sc.getLights().data()), (uint32_t)sc.getLights().size()), "skh_set_lights");
     mLightsUploaded = true;
     applyLightShapes(); // (the table is indexed as the light list is: it follows every upload of the list)
@@ -199,7 +201,110 @@ bool HipRender::sendMovedInstances()
     // (the caller's dirty set is left alone: it belongs to the scene's frame protocol, beginFrame / endFrame)
     check(skh_update_accel(mCtx, inst.data(), (uint32_t)inst.size()), "skh_update_accel");
     mSentInstances = inst;
+    measureScene(inst);
     return true;
+}
+
+// the diagonal of the world-space box around the mesh instances (each mesh's own box under its instance's transform): the denoiser's default sigmaPlane is a
+// fraction of it
+void HipRender::measureScene(const std::vector<skh_instance>& inst)
+{
+    Scene& sc = *mScene;
+    const auto& verts = sc.getVertices();
+    const auto& meshes = sc.getMeshes();
+    std::vector<double> box(6 * meshes.size());
+    std::vector<char> have(meshes.size(), 0);
+    double lo[3] = { INFINITY, INFINITY, INFINITY }, hi[3] = { -INFINITY, -INFINITY, -INFINITY };
+    for (const skh_instance& in : inst)
+    {
+        if (in.type != SKH_INSTANCE_MESH || in.geom_id >= meshes.size())
+            continue;
+        const skh_mesh& m = reinterpret_cast<const skh_mesh&>(meshes[in.geom_id]);
+        if (m.vertex_count == 0u || (size_t)m.vertex_offset + m.vertex_count > verts.size())
+            continue;
+        double* b = &box[6 * (size_t)in.geom_id];
+        if (!have[in.geom_id])
+        {
+            have[in.geom_id] = 1;
+            for (int k = 0; k < 3; ++k)
+                b[k] = INFINITY, b[3 + k] = -INFINITY;
+            for (uint32_t v = 0; v < m.vertex_count; ++v)
+            {
+                const float* pos = reinterpret_cast<const skh_vertex&>(verts[m.vertex_offset + v]).pos;
+                for (int k = 0; k < 3; ++k)
+                    b[k] = std::min(b[k], (double)pos[k]), b[3 + k] = std::max(b[3 + k], (double)pos[k]);
+            }
+        }
+        for (int corner = 0; corner < 8; ++corner)
+        {
+            const double p[3] = { b[(corner & 1) ? 3 : 0], b[(corner & 2) ? 4 : 1], b[(corner & 4) ? 5 : 2] };
+            for (int r = 0; r < 3; ++r)
+            {
+                const double w = in.transform[4 * r] * p[0] + in.transform[4 * r + 1] * p[1] + in.transform[4 * r + 2] * p[2] + in.transform[4 * r + 3];
+                lo[r] = std::min(lo[r], w), hi[r] = std::max(hi[r], w);
+            }
+        }
+    }
+    double d2 = 0.0;
+    for (int k = 0; k < 3; ++k)
+        d2 += hi[k] >= lo[k] ? (hi[k] - lo[k]) * (hi[k] - lo[k]) : 0.0;
+    mSceneDiagonal = (float)std::sqrt(d2);
+}
+
+void HipRender::freeGuides()
+{
+    for (void*& g : mGuide)
+    {
+        if (mCtx && g)
+            skh_buffer_free(mCtx, g);
+        g = nullptr;
+    }
+    mGuideWidth = mGuideHeight = 0;
+    mGuidesValid = false;
+}
+
+bool HipRender::setDenoiser(bool on, const HipDenoise* params)
+{
+    if (!on)
+    {
+        mDenoise = false;
+        freeGuides();
+        memset(&mDenoiseApplied, 0, sizeof(mDenoiseApplied));
+        return !mCtx || check(skh_denoise(mCtx, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr), "skh_denoise"); // (the library's scratch goes too)
+    }
+    const HipDenoise d = params ? *params : HipDenoise();
+    // (checked here with an image, an exposure and a scene that pass: the real ones are render()'s)
+    const float one[3] = { 1.0f, 1.0f, 1.0f };
+    const skh_denoise_params probe = hipDenoiseParams(d, 1u, 1u, one, 1.0f);
+    if (skh_denoise_check(&probe) != SKH_OK)
+    {
+        mError = "setDenoiser: the setting was refused (levels 1 .. 8, finite positive sigmas and floor)";
+        return false;
+    }
+    mDenoise = true;
+    mDenoiseSetting = d;
+    return true;
+}
+
+// the four guide planes of the whole image through the pixel centres, into buffers of this object
+bool HipRender::renderGuides()
+{
+    if (mGuideWidth != mWidth || mGuideHeight != mHeight)
+    {
+        freeGuides();
+        for (void*& g : mGuide)
+            if (!check(skh_buffer_alloc(mCtx, (size_t)16 * mWidth * mHeight, &g), "skh_buffer_alloc"))
+                return false;
+        mGuideWidth = mWidth, mGuideHeight = mHeight;
+    }
+    skh_aov_params ap;
+    if (!aovParams(ap, nullptr, false))
+        return false;
+    void* d[SKH_AOV_COUNT] = {};
+    d[SKH_AOV_IDS] = mGuide[0], d[SKH_AOV_NORMAL] = mGuide[1], d[SKH_AOV_POSITION] = mGuide[2], d[SKH_AOV_ALBEDO] = mGuide[3];
+    const uint32_t planes = (1u << SKH_AOV_IDS) | (1u << SKH_AOV_NORMAL) | (1u << SKH_AOV_POSITION) | (1u << SKH_AOV_ALBEDO);
+    mGuidesValid = check(skh_render_aovs(mCtx, &ap, planes, d), "skh_render_aovs");
+    return mGuidesValid;
 }
 
 void HipRender::uploadMaterials()
@@ -601,6 +706,10 @@ void HipRender::render(Buffer* output)
     }
     if (sh.mSubframeIndex == 0 || !adaptiveFrame)
         mConverged = false;
+    // the denoiser's guide planes belong to the accumulation: rendered when it (re)starts or the image size changed, before the frame's own work
+    const bool denoiseFrame = mDenoise && p.debug == 0 && (!mSharing || mRank == 0);
+    if (denoiseFrame && (sh.mSubframeIndex == 0 || !mGuidesValid || mGuideWidth != width || mGuideHeight != height))
+        renderGuides();
     if (samplesThisLaunch != 0 && !mConverged)
     {
         check(skh_render_subframe(mCtx, &p, dImage), "skh_render_subframe");
@@ -629,6 +738,13 @@ void HipRender::render(Buffer* output)
         if (mRank == 0)
             check(skh_scatter_tiles(mCtx, mGatherBuf, mAllTileXY.data(), (uint32_t)(mAllTileXY.size() / 2), mTileSize, dImage, width, height),
                   "skh_scatter_tiles");
+    }
+    if (denoiseFrame && mGuidesValid)
+    {
+        // the output image -- linear here --, in place; the accumulator is not touched
+        const skh_denoise_params dn = hipDenoiseParams(mDenoiseSetting, width, height, p.exposure, mSceneDiagonal);
+        if (check(skh_denoise(mCtx, &dn, dImage, mGuide[0], mGuide[1], mGuide[2], mGuide[3], dImage), "skh_denoise"))
+            mDenoiseApplied = dn;
     }
     if (p.debug != 1)
         check(skh_tonemap(mCtx, dImage, width, height, tonemapperType, p.exposure, gamma), "skh_tonemap");

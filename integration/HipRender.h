@@ -20,6 +20,7 @@
 #    include "../strelka_amd/host/oka_mirror.h"
 #endif
 
+#include <cmath>
 #include <string>
 #include <vector>
 
@@ -57,6 +58,33 @@ struct HipPick // HipRender::pick: the words of skh_render_aovs' seven planes at
     float albedo[3];
     float texcoord[2];
 };
+
+struct HipDenoise // HipRender::setDenoiser: a field that is 0 (or negative) takes its default
+{
+    uint32_t levels = 0;        // 5
+    float sigmaColor = 0.0f;    // radiance; default: 1 / the mean of the frame's three exposure factors -- what a Reinhard tonemap under that exposure shows as mid-grey
+    float sigmaNormal = 0.0f;   // 0.3
+    float sigmaPlane = 0.0f;    // scene units; default: planeFraction x the diagonal of the scene's bounding box
+    float planeFraction = 0.0f; // 0.005
+    float albedoFloor = 0.0f;   // 0.05
+};
+
+// the skh_denoise_params render() hands to skh_denoise for a HipDenoise setting: levels 0 .. levels - 1, both flags (the image is demodulated before the first
+// level and remodulated after the last)
+inline skh_denoise_params hipDenoiseParams(const HipDenoise& d, uint32_t width, uint32_t height, const float exposure[3], float sceneDiagonal)
+{
+    skh_denoise_params p = {};
+    p.width = width, p.height = height;
+    p.first_level = 0u, p.levels = d.levels ? d.levels : 5u;
+    const float meanExposure = (exposure[0] + exposure[1] + exposure[2]) / 3.0f;
+    p.sigma_color = d.sigmaColor > 0.0f ? d.sigmaColor : 1.0f / meanExposure;
+    p.sigma_normal = d.sigmaNormal > 0.0f ? d.sigmaNormal : 0.3f;
+    const float plane = d.sigmaPlane > 0.0f ? d.sigmaPlane : (d.planeFraction > 0.0f ? d.planeFraction : 0.005f) * sceneDiagonal;
+    p.sigma_plane = plane > 0.0f ? plane : HUGE_VALF; // (no mesh instance to measure: the term is off)
+    p.albedo_floor = d.albedoFloor > 0.0f ? d.albedoFloor : 0.05f;
+    p.flags = SKH_DENOISE_DEMODULATE | SKH_DENOISE_REMODULATE;
+    return p;
+}
 
 class HipRender : public Render
 {
@@ -129,6 +157,19 @@ public:
     bool pick(uint32_t x, uint32_t y, HipPick& out);
     // the parameters renderAovs hands to skh_render_aovs for the current camera (world_to_clip: the two inverses in double, rounded once)
     bool aovParams(skh_aov_params& p, const uint32_t* region, bool sampleZero);
+    // Denoiser (skh_denoise; new: the reference hands back raw samples), OFF by default.  With it on, render() with debug == 0 filters the OUTPUT image -- linear at
+    // that point -- between skh_render_subframe and skh_tonemap.  The accumulator is never filtered: the frame converges to what it converged to before.  The guide
+    // planes (ids, normal, position, albedo through the pixel centres: renderAovs' parameters) live in buffers this object owns and are rendered again only when
+    // the accumulation restarts -- a camera change, a scene change, a settings change -- or the image size changes.  With tile sharing rank 0 filters the gathered
+    // image.  params == nullptr: every default.  false: the setting was refused (skh_denoise_check; the previous one stays).  With it off, render() makes the calls
+    // it made before.  INTEGRATION.md has the defaults' reasons.
+    bool setDenoiser(bool on, const HipDenoise* params = nullptr);
+    // what the last filtered render() handed to skh_denoise (false: none yet)
+    bool denoiseParams(skh_denoise_params& p) const
+    {
+        p = mDenoiseApplied;
+        return mDenoiseApplied.width != 0u;
+    }
 
 private:
     skh_context* mCtx = nullptr;
@@ -159,6 +200,16 @@ private:
     std::vector<skh_light_shape> mLightShapes; // setLightShapes' table, re-applied after skh_set_lights
     bool mLightsUploaded = false, mLightShapesChanged = false;
     bool applyLightShapes();
+    bool mDenoise = false;
+    HipDenoise mDenoiseSetting;
+    skh_denoise_params mDenoiseApplied = {};
+    void* mGuide[4] = {}; // ids | normal | position | albedo of the whole image, through the pixel centres
+    uint32_t mGuideWidth = 0, mGuideHeight = 0;
+    bool mGuidesValid = false;
+    float mSceneDiagonal = 0.0f; // of the mesh instances' bounding box (uploadScene, sendMovedInstances)
+    void measureScene(const std::vector<skh_instance>& inst);
+    bool renderGuides();
+    void freeGuides();
     void uploadMaterials(); // MaterialDescription list -> skh_material blocks + textures (OptixRender.cpp:1270-1433)
 };
 

@@ -33,7 +33,8 @@ SYMBOLS = ["skh_create", "skh_destroy", "skh_last_error", "skh_abi_version", "sk
            "skh_set_material_blend", "skh_get_blend_info", "skh_blend_probe",
            "skh_set_light_shapes", "skh_get_light_shape_info", "skh_light_shape_probe",
            "skh_adaptive_check", "skh_set_adaptive", "skh_get_adaptive_info", "skh_read_adaptive",
-           "skh_aov_check", "skh_render_aovs", "skh_get_aov_info"]
+           "skh_aov_check", "skh_render_aovs", "skh_get_aov_info",
+           "skh_denoise_check", "skh_denoise", "skh_get_denoise_info", "skh_buffer_upload"]
 
 BUILD_INFO = np.dtype([("triangles", np.uint32), ("nodes", np.uint32), ("reinsert_rounds", np.uint32), ("reinsert_moves", np.uint32),
                        ("reinsert_min_size", np.uint32), ("refit", np.uint32), ("cost_before", np.float64), ("cost_after", np.float64),
@@ -54,6 +55,9 @@ ADAPTIVE_INFO = np.dtype([("enabled", np.uint32), ("tiles", np.uint32), ("active
 assert ADAPTIVE.itemsize == 32 and ADAPTIVE_INFO.itemsize == 40
 AOV_INFO = np.dtype([("calls", np.uint64), ("rays", np.uint64), ("ms_last", np.float64), ("bytes_last", np.uint64)])
 assert AOV_INFO.itemsize == 32
+DENOISE_INFO = np.dtype([("calls", np.uint64), ("pixels", np.uint64), ("ms_last", np.float64), ("scratch_bytes", np.uint64)])
+assert DENOISE_INFO.itemsize == 32
+DENOISE_GUIDES = ("ids", "normal", "position", "albedo")  # the planes skh_denoise reads, in its argument order
 # skh_light_shape_probe: kind -> (number, words in, words out) per record
 LSHAPE_PROBES = {"sample": (0, 6, 13), "pdf": (1, 7, 2)}
 # skh_emitter_probe: kind -> (number, words in, words out) per record
@@ -127,6 +131,10 @@ def load():
     lib.skh_aov_check.argtypes = [vp, u32, u32]
     lib.skh_render_aovs.argtypes = [vp, vp, u32, vp]
     lib.skh_get_aov_info.argtypes = [vp, vp]
+    lib.skh_denoise_check.argtypes = [vp]
+    lib.skh_denoise.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp]
+    lib.skh_get_denoise_info.argtypes = [vp, vp]
+    lib.skh_buffer_upload.argtypes = [vp, vp, vp, C.c_size_t]
     lib.skh_resize.argtypes = [vp, u32, u32]
     lib.skh_set_tiles.argtypes = [vp, u32, vp, u32]
     lib.skh_render_subframe.argtypes = [vp, vp, vp]
@@ -184,6 +192,12 @@ def aov_check(params, image_w, image_h):
     """skh_aov_check: would skh_render_aovs accept these S.AOV_PARAMS for an image of image_w x image_h?  (needs no context and no GPU)"""
     p = np.ascontiguousarray(params, dtype=S.AOV_PARAMS)
     return load().skh_aov_check(_p(p), int(image_w), int(image_h)) == 0
+
+
+def denoise_check(params):
+    """skh_denoise_check: would skh_denoise accept these S.DENOISE_PARAMS?  (needs no context and no GPU)"""
+    p = np.ascontiguousarray(params, dtype=S.DENOISE_PARAMS)
+    return load().skh_denoise_check(_p(p)) == 0
 
 
 def adaptive_dark_level(radiance, exposure):
@@ -491,6 +505,59 @@ class Context:
         d = np.zeros((), AOV_INFO)
         self._ck(self.lib.skh_get_aov_info(self.h, _p(d)), "skh_get_aov_info")
         return {k: (float(d[k]) if d[k].dtype.kind == "f" else int(d[k])) for k in AOV_INFO.names}
+
+    def buffer_upload(self, d_dst, host):
+        """skh_buffer_upload: host -> device copy of the numpy array `host` into a caller-owned device buffer"""
+        h = np.ascontiguousarray(host)
+        self._ck(self.lib.skh_buffer_upload(self.h, d_dst, _p(h), h.nbytes), "skh_buffer_upload")
+
+    def denoise_device(self, params, d_color, d_ids, d_normal, d_position, d_albedo, d_out):
+        """skh_denoise on caller-owned device images (d_out may be d_color; d_albedo may be None when neither flag is set); params None frees the scratch"""
+        p = None if params is None else np.ascontiguousarray(params, dtype=S.DENOISE_PARAMS)
+        self._ck(self.lib.skh_denoise(self.h, _p(p), d_color, d_ids, d_normal, d_position, d_albedo, d_out), "skh_denoise")
+
+    def denoise(self, image, guides, params):
+        """skh_denoise, numpy in and numpy out: `image` an (h, w, 4) float32 colour image, `guides` {"ids", "normal", "position", "albedo"} -> (h, w, 4) arrays as
+        render_aovs / render_guides return them ("albedo" may be missing when `params` sets neither flag), `params` S.denoise_params -> the filtered (h, w, 4) image.
+        Device buffers come from skh_buffer_alloc and are freed here."""
+        img = np.ascontiguousarray(image, np.float32)
+        p = np.array(params, dtype=S.DENOISE_PARAMS)
+        h, w = int(p["height"]), int(p["width"])
+        if img.shape != (h, w, 4):
+            raise ValueError(f"the image must be ({h}, {w}, 4)")
+        bufs = {}
+        try:
+            bufs["color"] = self.buffer_alloc(img.nbytes)
+            self.buffer_upload(bufs["color"], img)
+            for n in DENOISE_GUIDES:
+                if guides.get(n) is None:
+                    continue
+                g = np.ascontiguousarray(guides[n], np.uint32 if n == "ids" else np.float32)
+                if g.shape != (h, w, 4):
+                    raise ValueError(f"guide {n} must be ({h}, {w}, 4)")
+                bufs[n] = self.buffer_alloc(g.nbytes)
+                self.buffer_upload(bufs[n], g)
+            self.denoise_device(p, bufs["color"], bufs.get("ids"), bufs.get("normal"), bufs.get("position"), bufs.get("albedo"), bufs["color"])
+            out = np.zeros_like(img)
+            self.buffer_download(bufs["color"], out)
+            return out
+        finally:
+            for d in bufs.values():
+                self.buffer_free(d)
+
+    def render_guides(self, aov_params):
+        """the four planes skh_denoise reads -- ids, normal, position, albedo -- through the pixel centres of the whole image: render_aovs with the region
+        and the sample of `aov_params` set to that"""
+        p = np.array(aov_params, dtype=S.AOV_PARAMS)
+        p["x0"] = p["y0"] = p["width"] = p["height"] = 0
+        p["sample_index"] = S.AOV_PIXEL_CENTRE
+        return self.render_aovs(p, planes=DENOISE_GUIDES)
+
+    def denoise_info(self):
+        """skh_get_denoise_info: calls and pixels since the last reset_stats, the last call's wall time, the scratch bytes the context holds"""
+        d = np.zeros((), DENOISE_INFO)
+        self._ck(self.lib.skh_get_denoise_info(self.h, _p(d)), "skh_get_denoise_info")
+        return {k: (float(d[k]) if d[k].dtype.kind == "f" else int(d[k])) for k in DENOISE_INFO.names}
 
     def render_subframe(self, params, d_image=None):
         p = np.ascontiguousarray(params, dtype=S.FRAME_PARAMS)

@@ -326,6 +326,10 @@ struct skh_context
     // first-hit AOVs (skh_render_aovs): nothing but these words lives between two calls
     uint32_t aovBand = 1u << 22; // option aov_band: rays per band
     skh_aov_info aovInfo = {};
+    // the denoiser (skh_denoise; skh_denoise.h): its scratch -- two colour images and the packed guide record -- exists from the first call until
+    // skh_denoise(ctx, NULL, ...) or skh_destroy
+    DevBuf dDnColor[2], dDnG0, dDnG1;
+    skh_denoise_info dnInfo = {};
 };
 
 // a failing HIP call ends the function: its message names the function, the call and the HIP error

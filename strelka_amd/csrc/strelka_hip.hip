@@ -37,6 +37,7 @@ static_assert(sizeof(skh_hit) == 20 && sizeof(Light) == 112 && sizeof(Material) 
 
 #include "skh_host.h"
 #include "skh_aov.h"
+#include "skh_denoise.h"
 
 // Sobol generator matrices for the 5 dimensions the reference tabulates (RandomSampler.h:139-164), produced from the
 // Joe-Kuo recurrences (d=2: s=1 a=0 m={1}; d=3: s=2 a=1 m={1,3}; d=4: s=3 a=1 m={1,3,1}; d=5: s=3 a=2 m={1,1,1}).
@@ -2277,6 +2278,17 @@ skh_status skh_buffer_download(skh_context* c, const void* d, void* host, size_t
     SKH_TRY(c, hipMemcpy(host, d, bytes, hipMemcpyDeviceToHost));
     return SKH_OK;
 }
+// (the same choice of stream: beside a pass traced ahead, else behind whatever c->stream still does with the buffer)
+skh_status skh_buffer_upload(skh_context* c, void* d, const void* host, size_t bytes)
+{
+    if (!c || !d || !host)
+        return SKH_INVALID_ARGUMENT;
+    (void)hipSetDevice(c->device);
+    hipStream_t st = c->spec.nextInFlight ? c->stream3 : c->stream;
+    SKH_TRY(c, hipMemcpyAsync(d, host, bytes, hipMemcpyHostToDevice, st));
+    SKH_TRY(c, hipStreamSynchronize(st));
+    return SKH_OK;
+}
 
 skh_status skh_host_register(skh_context* c, void* host, size_t bytes)
 {
@@ -3028,6 +3040,108 @@ skh_status skh_get_aov_info(skh_context* c, skh_aov_info* out)
     return SKH_OK;
 }
 
+// ---- the denoiser (skh_denoise.h): skh_denoise_check, skh_denoise, skh_get_denoise_info ----
+static_assert(sizeof(skh_denoise_params) == 64 && sizeof(skh_denoise_info) == 32, "ABI layout");
+
+// why *p is refused, or nullptr
+static const char* denoise_refusal(const skh_denoise_params* p)
+{
+    if (!p)
+        return "no parameters";
+    if (p->width == 0u || p->height == 0u || (uint64_t)p->width * p->height > (1ull << 26))
+        return "an empty image, or one of more than 2^26 pixels";
+    if (p->levels == 0u || p->first_level > SKH_DENOISE_MAX_LEVEL || p->levels > SKH_DENOISE_MAX_LEVEL || p->first_level + p->levels > SKH_DENOISE_MAX_LEVEL)
+        return "no level, or a level beyond first_level + levels <= 8";
+    for (float s : { p->sigma_color, p->sigma_normal, p->sigma_plane })
+        if (!(s > 0.0f)) // (a NaN too)
+            return "a sigma that is <= 0 or NaN";
+    if (!std::isfinite(p->albedo_floor) || !(p->albedo_floor > 0.0f))
+        return "an albedo_floor that is <= 0 or not finite";
+    if (p->flags & ~(SKH_DENOISE_DEMODULATE | SKH_DENOISE_REMODULATE))
+        return "an unknown flag bit";
+    for (uint32_t r : p->reserved)
+        if (r != 0u)
+            return "a non-zero reserved word";
+    return nullptr;
+}
+
+skh_status skh_denoise_check(const skh_denoise_params* p)
+{
+    return denoise_refusal(p) ? SKH_INVALID_ARGUMENT : SKH_OK;
+}
+
+static uint64_t denoise_scratch_bytes(const skh_context* c)
+{
+    return (uint64_t)c->dDnColor[0].bytes + c->dDnColor[1].bytes + c->dDnG0.bytes + c->dDnG1.bytes;
+}
+
+skh_status skh_denoise(skh_context* c, const skh_denoise_params* p, const void* d_color, const void* d_ids, const void* d_normal, const void* d_position,
+                       const void* d_albedo, void* d_out)
+{
+    if (!c)
+        return SKH_INVALID_ARGUMENT;
+    (void)hipSetDevice(c->device);
+    if (!p) // free the scratch
+    {
+        dev_free(c->dDnColor[0]), dev_free(c->dDnColor[1]), dev_free(c->dDnG0), dev_free(c->dDnG1);
+        return SKH_OK;
+    }
+    const char* why = denoise_refusal(p);
+    if (!why && (!d_color || !d_ids || !d_normal || !d_position || !d_out))
+        why = "a NULL image";
+    if (!why && p->flags != 0u && !d_albedo)
+        why = "a flag that needs the albedo plane, and no albedo plane";
+    if (why)
+    {
+        c->err = std::string("skh_denoise: ") + why;
+        return SKH_INVALID_ARGUMENT;
+    }
+    const auto t0 = std::chrono::steady_clock::now();
+    const size_t n = (size_t)p->width * p->height;
+    SKH_CHECK(dev_alloc(c, c->dDnColor[0], 16 * n));
+    if (p->levels > 1u)
+        SKH_CHECK(dev_alloc(c, c->dDnColor[1], 16 * n));
+    SKH_CHECK(dev_alloc(c, c->dDnG0, 16 * n));
+    SKH_CHECK(dev_alloc(c, c->dDnG1, 8 * n));
+    hipStream_t st = c->spec.nextInFlight ? c->stream3 : c->stream; // (beside a pass traced ahead, not behind it: skh_tonemap's choice)
+    DnP dp;
+    dp.width = p->width, dp.height = p->height, dp.step = 1u, dp.kc = 0.0f;
+    dp.kn = 1.0f / (p->sigma_normal * p->sigma_normal), dp.kp = 1.0f / (p->sigma_plane * p->sigma_plane);
+    dp.albedoFloor = p->albedo_floor, dp.flags = p->flags;
+    k_dn_pack<<<(uint32_t)((n + 255) / 256), 256, 0, st>>>(dp, reinterpret_cast<const float4*>(d_color), reinterpret_cast<const uint4*>(d_ids),
+                                                          reinterpret_cast<const float4*>(d_normal), reinterpret_cast<const float4*>(d_position),
+                                                          reinterpret_cast<const float4*>(d_albedo), c->dDnColor[0].as<float4>(), c->dDnG0.as<float4>(),
+                                                          c->dDnG1.as<float2>());
+    const dim3 grid(((p->width + 63u) / 64u) * ((p->height + 3u) / 4u)), block(64, 4); // (<= 2^24 + 2^20 tiles of 64 x 4 pixels, row-major)
+    for (uint32_t k = 0; k < p->levels; ++k)
+    {
+        const uint32_t level = p->first_level + k;
+        const float sc = p->sigma_color * (1.0f / (float)(1u << level)); // (exact: a power of two)
+        dp.step = 1u << level, dp.kc = 1.0f / (sc * sc);
+        const float4* cin = c->dDnColor[k & 1u].as<float4>();
+        if (k + 1u < p->levels)
+            k_dn_level<false><<<grid, block, 0, st>>>(dp, cin, c->dDnG0.as<float4>(), c->dDnG1.as<float2>(), c->dDnColor[(k + 1u) & 1u].as<float4>(), nullptr, nullptr, nullptr);
+        else
+            k_dn_level<true><<<grid, block, 0, st>>>(dp, cin, c->dDnG0.as<float4>(), c->dDnG1.as<float2>(), nullptr, reinterpret_cast<const uint4*>(d_color),
+                                                    reinterpret_cast<const float4*>(d_albedo), reinterpret_cast<uint4*>(d_out));
+    }
+    SKH_TRY(c, hipGetLastError());
+    SKH_TRY(c, hipStreamSynchronize(st));
+    c->dnInfo.calls++;
+    c->dnInfo.pixels += n;
+    c->dnInfo.ms_last = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    return SKH_OK;
+}
+
+skh_status skh_get_denoise_info(skh_context* c, skh_denoise_info* out)
+{
+    if (!c || !out)
+        return SKH_INVALID_ARGUMENT;
+    *out = c->dnInfo;
+    out->scratch_bytes = denoise_scratch_bytes(c);
+    return SKH_OK;
+}
+
 // ---- BSDF probes (tests) ----
 static_assert(sizeof(skh_bsdf_query) == 84 && sizeof(skh_bsdf_result) == 64, "ABI layout");
 __global__ void k_bsdf_probe(const skh_bsdf_query* __restrict__ q, uint32_t n, const Material* __restrict__ mats, uint32_t numMaterials,
@@ -3482,6 +3596,7 @@ skh_status skh_reset_stats(skh_context* c)
     c->discardedRadiance = c->discardedShadow = 0;
     c->discardedSubframes = 0;
     c->aovInfo.calls = c->aovInfo.rays = 0;
+    c->dnInfo.calls = c->dnInfo.pixels = 0;
     for (int k = 0; k < KC_COUNT; ++k)
     {
         c->msClass[k] = 0.0;

@@ -619,6 +619,85 @@ def aov_params(camera, width, height, region=None, sample_index=None, spp_total=
     return p
 
 
+DENOISE_PARAMS = np.dtype([("width", np.uint32), ("height", np.uint32), ("first_level", np.uint32), ("levels", np.uint32), ("sigma_color", np.float32),
+                           ("sigma_normal", np.float32), ("sigma_plane", np.float32), ("albedo_floor", np.float32), ("flags", np.uint32),
+                           ("reserved", np.uint32, 7)])  # skh_denoise_params, 64 B
+assert DENOISE_PARAMS.itemsize == 64
+DENOISE_DEMODULATE, DENOISE_REMODULATE = 1, 2
+DENOISE_MAX_LEVEL = 8
+# the defaults of denoise_params (DESIGN.md section 2 "Denoiser" gives the reasons)
+DENOISE_SIGMA_NORMAL = 0.3       # |N(q) - N(p)| at which the normal term is 1: 17 degrees between unit normals
+DENOISE_PLANE_FRACTION = 0.005   # sigma_plane as a fraction of the scene's bounding-box diagonal
+DENOISE_ALBEDO_FLOOR = 0.05
+
+
+def scene_diagonal(arr):
+    """length of the diagonal of the world-space bounding box of a scene's mesh instances (`arr`: Scene.arrays()); the box of each mesh's own box under its
+    instance's transform, which contains the instance"""
+    pos, boxes = arr["vertices"]["pos"], {}
+    lo, hi = np.full(3, np.inf), np.full(3, -np.inf)
+    for inst in arr["instances"]:
+        if int(inst["type"]) != INSTANCE_MESH:
+            continue
+        g = int(inst["geom_id"])
+        if g not in boxes:
+            m = arr["meshes"][g]
+            v = pos[int(m["vertex_offset"]):int(m["vertex_offset"]) + int(m["vertex_count"])].astype(np.float64)
+            boxes[g] = None if len(v) == 0 else np.array([[x, y, z] for x in (v[:, 0].min(), v[:, 0].max()) for y in (v[:, 1].min(), v[:, 1].max())
+                                                          for z in (v[:, 2].min(), v[:, 2].max())])
+        if boxes[g] is None:
+            continue
+        t = np.asarray(inst["transform"], np.float64).reshape(3, 4)
+        w = boxes[g] @ t[:, :3].T + t[:, 3]
+        lo, hi = np.minimum(lo, w.min(axis=0)), np.maximum(hi, w.max(axis=0))
+    if not np.isfinite(lo).all():
+        raise ValueError("the scene has no mesh instance to take a bounding box from")
+    return float(np.linalg.norm(hi - lo))
+
+
+def denoise_sigma_color(image, guides=None, albedo_floor=DENOISE_ALBEDO_FLOOR, demodulate=True):
+    """the default sigma_color for an (h, w, 4) image: DENOISE_COLOR_FACTOR x the mean, over the pixels the filter works on, of the mean channel of its first level's
+    input -- with `guides` ({"ids", "albedo"}: render_guides') the surface pixels and the demodulated colour, without them every finite pixel of the image as it is"""
+    c = np.asarray(image, np.float64)[..., :3]
+    ok = np.isfinite(c).all(axis=-1)
+    if guides is not None and guides.get("ids") is not None:
+        kind = np.asarray(guides["ids"])[..., 3]
+        ok &= (kind == 1) | (kind == 2)
+    if demodulate and guides is not None and guides.get("albedo") is not None:
+        a = np.asarray(guides["albedo"], np.float64)[..., :3]
+        with np.errstate(all="ignore"):
+            c = c / np.where(a > albedo_floor, a, albedo_floor)
+    if not ok.any():
+        return 1.0
+    level = float(np.abs(c[ok]).mean())
+    return DENOISE_COLOR_FACTOR * level if level > 0.0 and np.isfinite(level) else 1.0
+
+
+DENOISE_COLOR_FACTOR = 2.0
+
+
+def denoise_params(width, height, levels=5, sigma_color=None, sigma_normal=DENOISE_SIGMA_NORMAL, sigma_plane=None, first_level=0, albedo_floor=DENOISE_ALBEDO_FLOOR,
+                   demodulate=True, remodulate=True, image=None, guides=None, exposure=None, scene=None):
+    """skh_denoise_params.  sigma_color applies to the first level's input (the demodulated colour when `demodulate`) and the filter halves it per level; None:
+    denoise_sigma_color(`image`, `guides`) when the image to be filtered is given, else 1 / the mean exposure factor (`exposure`: frame_params'; None =
+    default_exposure()) -- the radiance a Reinhard tonemap under that exposure shows as mid-grey, which is what a host that never sees the image can know of it.
+    sigma_plane is in scene units; None: DENOISE_PLANE_FRACTION of scene_diagonal(`scene`) (`scene`: Scene.arrays())."""
+    p = np.zeros((), DENOISE_PARAMS)
+    p["width"], p["height"], p["first_level"], p["levels"] = width, height, first_level, levels
+    if sigma_color is None and image is not None:
+        sigma_color = denoise_sigma_color(image, guides, albedo_floor, demodulate)
+    if sigma_color is None:
+        e = np.asarray(default_exposure() if exposure is None else exposure, np.float64).reshape(-1)
+        sigma_color = 1.0 / float(e.mean())
+    if sigma_plane is None:
+        if scene is None:
+            raise ValueError("sigma_plane is in scene units: give it, or give `scene` to take it as a fraction of the bounding-box diagonal")
+        sigma_plane = DENOISE_PLANE_FRACTION * scene_diagonal(scene)
+    p["sigma_color"], p["sigma_normal"], p["sigma_plane"], p["albedo_floor"] = sigma_color, sigma_normal, sigma_plane, albedo_floor
+    p["flags"] = (DENOISE_DEMODULATE if demodulate else 0) | (DENOISE_REMODULATE if remodulate else 0)
+    return p
+
+
 def default_exposure(filmIso=100.0, cm2_factor=1.0, fStop=4.0, shutterSpeed=100.0):
     """exposureValue of OptiXRender::render (OptixRender.cpp:961-987), fp32 arithmetic."""
     f = np.float32

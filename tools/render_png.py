@@ -8,7 +8,9 @@ default 16, and every --adaptive-interval after, default 8; dark level: radiance
 observation count as a grey image (white = spp).
 --aov NAME=FILE.png (repeatable): a first-hit plane of the same camera through the pixel centres (skh_render_aovs), NAME one of ids, depth, normal, geom_normal,
 position, albedo, uv: normals as (N + 1) / 2 (black where nothing is hit), depth normalised over the hits (near white, far black), ids as hashed colours of
-(instance, primitive), albedo, position and uv written straight (clipped to 0 ... 1 by the PNG)."""
+(instance, primitive), albedo, position and uv written straight (clipped to 0 ... 1 by the PNG).
+--denoise [LEVELS] (after the positional arguments, out.png among them): the picture once more through skh_denoise -- LEVELS levels, default 5, scene.denoise_params' defaults for this
+image and scene --, written next to the raw one as <out>_denoised.png."""
 import sys, numpy as np
 sys.path.insert(0, ".")
 import math
@@ -23,6 +25,12 @@ while "--aov" in sys.argv:
     k = sys.argv.index("--aov")
     aov_out.append(tuple(sys.argv[k + 1].split("=", 1)))
     del sys.argv[k:k + 2]
+denoise_levels = None
+if "--denoise" in sys.argv:
+    k = sys.argv.index("--denoise")
+    has_value = k + 1 < len(sys.argv) and sys.argv[k + 1].isdigit() and k >= 6  # (after the five positional arguments: a number there is LEVELS)
+    denoise_levels = int(sys.argv[k + 1]) if has_value else 5
+    del sys.argv[k:k + (2 if has_value else 1)]
 opts = {}
 for flag in ("--env-rotate", "--env", "--adaptive-min", "--adaptive-interval", "--adaptive", "--sample-map"):
     if flag in sys.argv:
@@ -35,6 +43,8 @@ for flag in ("--env-rotate", "--env", "--adaptive-min", "--adaptive-interval", "
             env_deg = float(val)
         else:
             opts[flag] = val
+if denoise_levels is not None and len(sys.argv) <= 7:
+    sys.exit("--denoise writes next to the raw picture: give exposure_scale and out.png")
 name = sys.argv[1]; W, H, spp, depth = int(sys.argv[2]), int(sys.argv[3]), int(sys.argv[4]), int(sys.argv[5])
 if name.lower().endswith((".gltf", ".glb")):
     sc, name = gltf.load_gltf(name, material_textures=True, alpha_blend=alpha_blend), name.replace("/", "_")
@@ -78,3 +88,14 @@ e = S.default_exposure() * np.float32(float(sys.argv[6]) if len(sys.argv) > 6 el
 ctx.tonemap(img.data_ptr(), W, H, 1, e, 2.2)   # Reinhard + gamma, as the reference's post chain
 png.save_png((sys.argv[7] if len(sys.argv) > 7 else f"gpurun_out/{name}.png"), img.cpu().numpy()[..., :3], flipped=True)
 print("wrote", name, float(img.mean()))
+if denoise_levels is not None:
+    # the same linear image through skh_denoise (guides through the pixel centres, default parameters), then the same post chain, next to the raw picture
+    raw, arr = ctx.read_accum(), sc.arrays()
+    guides = ctx.render_guides(S.aov_params(sc.getCamera(), W, H))
+    dp = S.denoise_params(W, H, levels=denoise_levels, scene=arr, image=raw, guides=guides)
+    den = torch.from_numpy(ctx.denoise(raw, guides, dp)).cuda()
+    ctx.tonemap(den.data_ptr(), W, H, 1, e, 2.2)
+    out_path = sys.argv[7]
+    den_path = out_path[:-4] + "_denoised.png" if out_path.lower().endswith(".png") else out_path + "_denoised.png"
+    png.save_png(den_path, den.cpu().numpy()[..., :3], flipped=True)
+    print("wrote", den_path, {k: float(dp[k]) for k in ("sigma_color", "sigma_normal", "sigma_plane")}, "ms", ctx.denoise_info()["ms_last"])
