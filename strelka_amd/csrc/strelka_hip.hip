@@ -779,6 +779,28 @@ static DevScene make_dev_scene(const skh_context* c)
     return sc;
 }
 
+// What the probes (tests' doors to single device functions) share: the inputs up (an input without bytes is left out), the output allocated, `launch(dIn, dOut)`
+// on c->stream, the launch checked, the stream waited for, the output back.
+struct ProbeIn
+{
+    const void* src;
+    size_t bytes;
+};
+template <size_t N, typename Launch>
+static skh_status probe_roundtrip(skh_context* c, const ProbeIn (&in)[N], void* out, size_t outBytes, Launch&& launch)
+{
+    DevBuf dIn[N], dOut;
+    for (size_t k = 0; k < N; ++k)
+        if (in[k].bytes)
+            SKH_CHECK(dev_upload(c, dIn[k], in[k].src, in[k].bytes));
+    SKH_CHECK(dev_alloc(c, dOut, outBytes));
+    launch(dIn, dOut);
+    SKH_TRY(c, hipGetLastError());
+    SKH_TRY(c, hipStreamSynchronize(c->stream));
+    SKH_TRY(c, hipMemcpy(out, dOut.p, outBytes, hipMemcpyDeviceToHost));
+    return SKH_OK;
+}
+
 // ---- material textures: skh_set_material_textures ----
 // an entry binds a texture that exists: the k_shade builds with MTEX in them run (anything else -- no table, all ids 0 or beyond the list -- runs the others)
 static bool mtex_active(const skh_context* c)
@@ -799,45 +821,60 @@ static MtexP make_mtex(const skh_context* c)
     return m;
 }
 
-skh_status skh_set_material_textures(skh_context* c, const skh_material_textures* entries, uint32_t n)
+// What the per-material table setters share.  Removal (no entries) is a no-op on a context that has none: nothing traced ahead is thrown away for it.  `check` validates
+// the entries, leaves the message of a refusal, and may point `src` / `bytes` at a packed form of the table; `stale`: the derived state to mark, if any.
+template <typename T, typename Check>
+static skh_status set_material_table(skh_context* c, const char* fn, const T* entries, uint32_t n, std::vector<T>& kept, DevBuf& dev, bool* stale, Check&& check)
 {
-    if (!c)
-        return SKH_INVALID_ARGUMENT;
     (void)hipSetDevice(c->device);
+    const void* src = entries;
+    size_t bytes = sizeof(T) * (size_t)n;
+    if (entries && n > c->nMaterials)
+    {
+        c->err = std::string(fn) + ": " + std::to_string(n) + " entries for " + std::to_string(c->nMaterials) + " materials (call skh_set_materials first)";
+        return SKH_INVALID_ARGUMENT;
+    }
     if (!entries || n == 0)
     {
-        // remove: a no-op on a context that has none (nothing traced ahead is thrown away for it)
-        if (c->mtex.empty())
+        if (kept.empty())
             return SKH_OK;
-        spec_drop(c);
-        SKH_TRY(c, hipStreamSynchronize(c->stream));
-        c->mtex.clear();
-        dev_free(c->dMtex);
-        return SKH_OK;
     }
-    if (n > c->nMaterials)
-    {
-        c->err = "skh_set_material_textures: " + std::to_string(n) + " entries for " + std::to_string(c->nMaterials) + " materials (call skh_set_materials first)";
-        return SKH_INVALID_ARGUMENT;
-    }
-    for (uint32_t k = 0; k < n; ++k)
-    {
-        const skh_material_textures& e = entries[k];
-        if (e.roughness_channel > 3u || e.metallic_channel > 3u || e.emission_channel > 4u || !std::isfinite(e.roughness_scale) || !std::isfinite(e.roughness_bias) ||
-            !std::isfinite(e.metallic_scale) || !std::isfinite(e.metallic_bias) || e.reserved[0] != 0u || e.reserved[1] != 0u)
-        {
-            c->err = "skh_set_material_textures: entry " + std::to_string(k) + ": a channel out of range (0..3, emission 0..4), a scale or bias that is not finite, or a non-zero reserved word";
-            return SKH_INVALID_ARGUMENT;
-        }
-    }
+    else
+        SKH_CHECK(check(src, bytes));
     spec_drop(c);
-    static_assert(sizeof(skh_material_textures) == 48 && sizeof(skh_material_textures) == sizeof(MtexEntry), "skh_material_textures");
     SKH_TRY(c, hipStreamSynchronize(c->stream)); // (the table is about to be replaced)
     DevBuf d;
-    SKH_CHECK(dev_upload(c, d, entries, sizeof(skh_material_textures) * (size_t)n));
-    c->dMtex = std::move(d);
-    c->mtex.assign(entries, entries + n);
+    if (entries && n)
+    {
+        SKH_CHECK(dev_upload(c, d, src, bytes));
+        kept.assign(entries, entries + n);
+    }
+    else
+        kept.clear();
+    dev = std::move(d);
+    if (stale)
+        *stale = true;
     return SKH_OK;
+}
+
+skh_status skh_set_material_textures(skh_context* c, const skh_material_textures* entries, uint32_t n)
+{
+    static_assert(sizeof(skh_material_textures) == 48 && sizeof(skh_material_textures) == sizeof(MtexEntry), "skh_material_textures");
+    if (!c)
+        return SKH_INVALID_ARGUMENT;
+    return set_material_table(c, "skh_set_material_textures", entries, n, c->mtex, c->dMtex, nullptr, [&](const void*&, size_t&) {
+        for (uint32_t k = 0; k < n; ++k)
+        {
+            const skh_material_textures& e = entries[k];
+            if (e.roughness_channel > 3u || e.metallic_channel > 3u || e.emission_channel > 4u || !std::isfinite(e.roughness_scale) || !std::isfinite(e.roughness_bias) ||
+                !std::isfinite(e.metallic_scale) || !std::isfinite(e.metallic_bias) || e.reserved[0] != 0u || e.reserved[1] != 0u)
+            {
+                c->err = "skh_set_material_textures: entry " + std::to_string(k) + ": a channel out of range (0..3, emission 0..4), a scale or bias that is not finite, or a non-zero reserved word";
+                return SKH_INVALID_ARGUMENT;
+            }
+        }
+        return SKH_OK;
+    });
 }
 
 skh_status skh_material_probe(skh_context* c, uint32_t n, const uint32_t* material, const float* uv, float* out)
@@ -860,17 +897,11 @@ skh_status skh_material_probe(skh_context* c, uint32_t n, const uint32_t* materi
     std::vector<float> le(4 * (size_t)c->nMaterials, 0.0f); // (materials beyond the emission list do not emit)
     for (uint32_t m = 0; m < c->nMaterials && 3 * (size_t)m + 2 < c->emission.size(); ++m)
         memcpy(&le[4 * (size_t)m], &c->emission[3 * (size_t)m], 3 * sizeof(float));
-    DevBuf dLe, dMat, dUv, dOut;
-    SKH_CHECK(dev_upload(c, dLe, le.data(), le.size() * sizeof(float)));
-    SKH_CHECK(dev_upload(c, dMat, material, sizeof(uint32_t) * (size_t)n));
-    SKH_CHECK(dev_upload(c, dUv, uv, 2 * sizeof(float) * (size_t)n));
-    SKH_CHECK(dev_alloc(c, dOut, 8 * sizeof(float) * (size_t)n));
-    k_material_probe<<<(n + 255) / 256, 256, 0, c->stream>>>(make_mtex(c), c->dMaterials.as<Material>(), c->nMaterials, dLe.as<float4>(), c->dTexels.as<uint32_t>(),
-                                                             c->dTexDesc.as<uint4>(), c->nTextures, dMat.as<uint32_t>(), dUv.as<float>(), n, dOut.as<float>());
-    SKH_TRY(c, hipGetLastError());
-    SKH_TRY(c, hipStreamSynchronize(c->stream));
-    SKH_TRY(c, hipMemcpy(out, dOut.p, 8 * sizeof(float) * (size_t)n, hipMemcpyDeviceToHost));
-    return SKH_OK;
+    const ProbeIn in[] = { { le.data(), le.size() * sizeof(float) }, { material, sizeof(uint32_t) * (size_t)n }, { uv, 2 * sizeof(float) * (size_t)n } };
+    return probe_roundtrip(c, in, out, 8 * sizeof(float) * (size_t)n, [&](const DevBuf* d, const DevBuf& dOut) {
+        k_material_probe<<<(n + 255) / 256, 256, 0, c->stream>>>(make_mtex(c), c->dMaterials.as<Material>(), c->nMaterials, d[0].as<float4>(), c->dTexels.as<uint32_t>(),
+                                                                 c->dTexDesc.as<uint4>(), c->nTextures, d[1].as<uint32_t>(), d[2].as<float>(), n, dOut.as<float>());
+    });
 }
 
 // ---- cutouts: skh_set_material_cutouts, the k_cutout stage between trace and shade (skh_kernels.h) ----
@@ -881,42 +912,19 @@ skh_status skh_set_material_cutouts(skh_context* c, const skh_material_cutout* e
 {
     if (!c)
         return SKH_INVALID_ARGUMENT;
-    (void)hipSetDevice(c->device);
-    if (!entries || n == 0)
-    {
-        // remove: a no-op on a context that has none (nothing traced ahead is thrown away for it)
-        if (c->cutouts.empty())
-            return SKH_OK;
-        spec_drop(c);
-        SKH_TRY(c, hipStreamSynchronize(c->stream));
-        c->cutouts.clear();
-        dev_free(c->dCutouts);
-        c->cutStale = true;
-        return SKH_OK;
-    }
-    if (n > c->nMaterials)
-    {
-        c->err = "skh_set_material_cutouts: " + std::to_string(n) + " entries for " + std::to_string(c->nMaterials) + " materials (call skh_set_materials first)";
-        return SKH_INVALID_ARGUMENT;
-    }
-    for (uint32_t k = 0; k < n; ++k)
-    {
-        const skh_material_cutout& e = entries[k];
-        if (e.opacity_channel > 3u || !std::isfinite(e.opacity_scale) || !std::isfinite(e.opacity_bias) || !(e.threshold >= 0.0f && e.threshold <= 1.0f) ||
-            e.reserved[0] != 0u || e.reserved[1] != 0u || e.reserved[2] != 0u)
+    return set_material_table(c, "skh_set_material_cutouts", entries, n, c->cutouts, c->dCutouts, &c->cutStale, [&](const void*&, size_t&) {
+        for (uint32_t k = 0; k < n; ++k)
         {
-            c->err = "skh_set_material_cutouts: entry " + std::to_string(k) + ": a channel above 3, a scale or bias that is not finite, a threshold outside [0, 1] or a non-zero reserved word";
-            return SKH_INVALID_ARGUMENT;
+            const skh_material_cutout& e = entries[k];
+            if (e.opacity_channel > 3u || !std::isfinite(e.opacity_scale) || !std::isfinite(e.opacity_bias) || !(e.threshold >= 0.0f && e.threshold <= 1.0f) ||
+                e.reserved[0] != 0u || e.reserved[1] != 0u || e.reserved[2] != 0u)
+            {
+                c->err = "skh_set_material_cutouts: entry " + std::to_string(k) + ": a channel above 3, a scale or bias that is not finite, a threshold outside [0, 1] or a non-zero reserved word";
+                return SKH_INVALID_ARGUMENT;
+            }
         }
-    }
-    spec_drop(c);
-    SKH_TRY(c, hipStreamSynchronize(c->stream)); // (the table is about to be replaced)
-    DevBuf d;
-    SKH_CHECK(dev_upload(c, d, entries, sizeof(skh_material_cutout) * (size_t)n));
-    c->dCutouts = std::move(d);
-    c->cutouts.assign(entries, entries + n);
-    c->cutStale = true;
-    return SKH_OK;
+        return SKH_OK;
+    });
 }
 
 // ---- fractional opacity: skh_set_material_blend, the BLEND build of k_cutout (skh_kernels.h) ----
@@ -926,47 +934,51 @@ skh_status skh_set_material_blend(skh_context* c, const skh_material_blend* entr
 {
     if (!c)
         return SKH_INVALID_ARGUMENT;
-    (void)hipSetDevice(c->device);
-    if (!entries || n == 0)
-    {
-        // remove: a no-op on a context that has none (nothing traced ahead is thrown away for it)
-        if (c->blends.empty())
-            return SKH_OK;
-        spec_drop(c);
-        SKH_TRY(c, hipStreamSynchronize(c->stream));
-        c->blends.clear();
-        dev_free(c->dBlend);
-        c->cutStale = true;
-        return SKH_OK;
-    }
-    if (n > c->nMaterials)
-    {
-        c->err = "skh_set_material_blend: " + std::to_string(n) + " entries for " + std::to_string(c->nMaterials) + " materials (call skh_set_materials first)";
-        return SKH_INVALID_ARGUMENT;
-    }
-    std::vector<uint4> packed(n);
-    for (uint32_t k = 0; k < n; ++k)
-    {
-        const skh_material_blend& e = entries[k];
-        if (e.opacity_channel > 3u || !std::isfinite(e.opacity_scale) || !std::isfinite(e.opacity_bias) || e.active > 1u || e.reserved[0] != 0u || e.reserved[1] != 0u ||
-            e.reserved[2] != 0u)
+    std::vector<uint4> packed; // what the device reads: one uint4 per material (BlendP)
+    return set_material_table(c, "skh_set_material_blend", entries, n, c->blends, c->dBlend, &c->cutStale, [&](const void*& src, size_t& bytes) {
+        packed.resize(n);
+        for (uint32_t k = 0; k < n; ++k)
         {
-            c->err = "skh_set_material_blend: material " + std::to_string(k) + ": a channel above 3, a scale or bias that is not finite, active above 1 or a non-zero reserved word";
-            return SKH_INVALID_ARGUMENT;
+            const skh_material_blend& e = entries[k];
+            if (e.opacity_channel > 3u || !std::isfinite(e.opacity_scale) || !std::isfinite(e.opacity_bias) || e.active > 1u || e.reserved[0] != 0u || e.reserved[1] != 0u ||
+                e.reserved[2] != 0u)
+            {
+                c->err = "skh_set_material_blend: material " + std::to_string(k) + ": a channel above 3, a scale or bias that is not finite, active above 1 or a non-zero reserved word";
+                return SKH_INVALID_ARGUMENT;
+            }
+            uint32_t sb, bb;
+            memcpy(&sb, &e.opacity_scale, 4);
+            memcpy(&bb, &e.opacity_bias, 4);
+            packed[k] = make_uint4(e.opacity_texture, e.opacity_channel | (e.active << 31), sb, bb);
         }
-        uint32_t sb, bb;
-        memcpy(&sb, &e.opacity_scale, 4);
-        memcpy(&bb, &e.opacity_bias, 4);
-        packed[k] = make_uint4(e.opacity_texture, e.opacity_channel | (e.active << 31), sb, bb);
-    }
-    spec_drop(c);
-    SKH_TRY(c, hipStreamSynchronize(c->stream)); // (the table is about to be replaced)
-    DevBuf d;
-    SKH_CHECK(dev_upload(c, d, packed.data(), sizeof(uint4) * (size_t)n));
-    c->dBlend = std::move(d);
-    c->blends.assign(entries, entries + n);
-    c->cutStale = true;
-    return SKH_OK;
+        src = packed.data(), bytes = sizeof(uint4) * (size_t)n;
+        return SKH_OK;
+    });
+}
+
+// the material an instance shades with, as k_shade reads it
+static inline uint32_t instance_material(const skh_context* c, const skh_instance& in)
+{
+    const uint32_t mid = in.material_id == 0xffffffffu ? 0u : in.material_id;
+    return mid < c->nMaterials ? mid : 0u;
+}
+
+// does material k emit (skh_set_emission)?
+static inline bool material_emits(const skh_context* c, size_t k)
+{
+    return 3 * k + 2 < c->emission.size() && (c->emission[3 * k] > 0.0f || c->emission[3 * k + 1] > 0.0f || c->emission[3 * k + 2] > 0.0f);
+}
+
+// the active entries among the first n of a per-material table, and the mesh instances that use one
+template <typename Active>
+static void count_in_use(const skh_context* c, uint32_t n, Active&& active, uint32_t& entries, uint32_t& users)
+{
+    entries = users = 0;
+    for (uint32_t k = 0; k < n; ++k)
+        entries += active(k) ? 1u : 0u;
+    if (entries)
+        for (const skh_instance& in : c->instances)
+            users += (in.type == SKH_INSTANCE_MESH && instance_material(c, in) < n && active(instance_material(c, in))) ? 1u : 0u;
 }
 
 // Is a cutout in use (derived: an active entry on a material that a mesh instance uses)?  And the one combination that is refused: a material that emits and is cut.
@@ -975,32 +987,10 @@ static skh_status cut_ensure(skh_context* c)
     if (c->cutStale)
     {
         const uint32_t nTab = (uint32_t)std::min<size_t>(c->cutouts.size(), c->nMaterials);
-        uint32_t active = 0, users = 0;
-        for (uint32_t k = 0; k < nTab; ++k)
-            active += c->cutouts[k].threshold > 0.0f ? 1u : 0u;
-        if (active)
-            for (const skh_instance& in : c->instances)
-            {
-                if (in.type != SKH_INSTANCE_MESH)
-                    continue;
-                const uint32_t mid0 = in.material_id == 0xffffffffu ? 0u : in.material_id, mid = mid0 < c->nMaterials ? mid0 : 0u; // (as k_shade reads it)
-                users += (mid < nTab && c->cutouts[mid].threshold > 0.0f) ? 1u : 0u;
-            }
-        c->cutActiveMaterials = active, c->cutInstances = users;
+        count_in_use(c, nTab, [&](uint32_t k) { return c->cutouts[k].threshold > 0.0f; }, c->cutActiveMaterials, c->cutInstances);
         // fractional opacity: the same derivation over the blend table
         const uint32_t nBl = (uint32_t)std::min<size_t>(c->blends.size(), c->nMaterials);
-        uint32_t bActive = 0, bUsers = 0;
-        for (uint32_t k = 0; k < nBl; ++k)
-            bActive += c->blends[k].active ? 1u : 0u;
-        if (bActive)
-            for (const skh_instance& in : c->instances)
-            {
-                if (in.type != SKH_INSTANCE_MESH)
-                    continue;
-                const uint32_t mid0 = in.material_id == 0xffffffffu ? 0u : in.material_id, mid = mid0 < c->nMaterials ? mid0 : 0u;
-                bUsers += (mid < nBl && c->blends[mid].active) ? 1u : 0u;
-            }
-        c->blendActiveMaterials = bActive, c->blendInstances = bUsers;
+        count_in_use(c, nBl, [&](uint32_t k) { return c->blends[k].active != 0u; }, c->blendActiveMaterials, c->blendInstances);
         c->cutStale = false;
     }
     if (c->blendActiveMaterials)
@@ -1013,15 +1003,15 @@ static skh_status cut_ensure(skh_context* c)
                 c->err = "material " + std::to_string(k) + " has both an active cutout (skh_set_material_cutouts) and an active blend entry (skh_set_material_blend): one opacity rule per material";
                 return SKH_INVALID_ARGUMENT;
             }
-            if (3 * (size_t)k + 2 < c->emission.size() && (c->emission[3 * (size_t)k] > 0.0f || c->emission[3 * (size_t)k + 1] > 0.0f || c->emission[3 * (size_t)k + 2] > 0.0f))
+            if (material_emits(c, k))
             {
                 c->err = "material " + std::to_string(k) + " both emits (skh_set_emission) and has an active blend entry (skh_set_material_blend): blended emitters are not supported";
                 return SKH_INVALID_ARGUMENT;
             }
         }
     if (c->cutActiveMaterials && !c->emission.empty())
-        for (uint32_t k = 0; k < c->cutouts.size() && k < c->nMaterials && 3 * (size_t)k + 2 < c->emission.size(); ++k)
-            if (c->cutouts[k].threshold > 0.0f && (c->emission[3 * (size_t)k] > 0.0f || c->emission[3 * (size_t)k + 1] > 0.0f || c->emission[3 * (size_t)k + 2] > 0.0f))
+        for (uint32_t k = 0; k < c->cutouts.size() && k < c->nMaterials; ++k)
+            if (c->cutouts[k].threshold > 0.0f && material_emits(c, k))
             {
                 c->err = "material " + std::to_string(k) + " both emits (skh_set_emission) and has an active cutout (skh_set_material_cutouts): cut-away emitters are not supported";
                 return SKH_INVALID_ARGUMENT;
@@ -1096,6 +1086,12 @@ static skh_status cut_alloc_frame(skh_context* c)
     return SKH_OK;
 }
 
+// bytes of the cutout stage's frame buffers
+static uint64_t cut_stage_bytes(const skh_context* c)
+{
+    return c->dCutQ[0].bytes + c->dCutQ[1].bytes + c->dCutHits.bytes + c->dCutShadowQ[0].bytes + c->dCutShadowQ[1].bytes + c->dCutShadowHits[0].bytes + c->dCutShadowHits[1].bytes;
+}
+
 skh_status skh_get_cutout_info(skh_context* c, skh_cutout_info* out)
 {
     if (!c || !out)
@@ -1109,7 +1105,7 @@ skh_status skh_get_cutout_info(skh_context* c, skh_cutout_info* out)
     out->active_materials = c->cutActiveMaterials, out->instances = c->cutInstances;
     out->continued_closest = sd.continued[0], out->continued_shadow = sd.continued[1];
     out->accepted_by_cap = sd.capped[0] + sd.capped[1];
-    out->bytes = c->dCutQ[0].bytes + c->dCutQ[1].bytes + c->dCutHits.bytes + c->dCutShadowQ[0].bytes + c->dCutShadowQ[1].bytes + c->dCutShadowHits[0].bytes + c->dCutShadowHits[1].bytes;
+    out->bytes = cut_stage_bytes(c);
     return SKH_OK;
 }
 
@@ -1125,8 +1121,7 @@ skh_status skh_get_blend_info(skh_context* c, skh_blend_info* out)
     SKH_TRY(c, hipMemcpy(&sd, c->dCutStats.p, sizeof(sd), hipMemcpyDeviceToHost));
     out->active_materials = c->blendActiveMaterials, out->instances = c->blendInstances;
     out->passed_radiance = sd.blendPassed, out->crossed_shadow = sd.blendCrossed, out->accepted_by_cap = sd.blendCapped;
-    out->bytes = c->dCutQ[0].bytes + c->dCutQ[1].bytes + c->dCutHits.bytes + c->dCutShadowQ[0].bytes + c->dCutShadowQ[1].bytes + c->dCutShadowHits[0].bytes +
-                 c->dCutShadowHits[1].bytes;
+    out->bytes = cut_stage_bytes(c);
     return SKH_OK;
 }
 
@@ -1137,14 +1132,9 @@ skh_status skh_blend_probe(skh_context* c, uint32_t n, const uint32_t* in, float
     if (!n)
         return SKH_OK;
     (void)hipSetDevice(c->device);
-    DevBuf dIn, dOut;
-    SKH_CHECK(dev_upload(c, dIn, in, sizeof(uint32_t) * 6 * (size_t)n));
-    SKH_CHECK(dev_alloc(c, dOut, sizeof(float) * (size_t)n));
-    k_blend_probe<<<(n + 255) / 256, 256, 0, c->stream>>>(n, dIn.as<uint32_t>(), dOut.as<float>());
-    SKH_TRY(c, hipGetLastError());
-    SKH_TRY(c, hipStreamSynchronize(c->stream));
-    SKH_TRY(c, hipMemcpy(xi, dOut.p, sizeof(float) * (size_t)n, hipMemcpyDeviceToHost));
-    return SKH_OK;
+    const ProbeIn pin[] = { { in, sizeof(uint32_t) * 6 * (size_t)n } };
+    return probe_roundtrip(c, pin, xi, sizeof(float) * (size_t)n,
+                           [&](const DevBuf* d, const DevBuf& dOut) { k_blend_probe<<<(n + 255) / 256, 256, 0, c->stream>>>(n, d[0].as<uint32_t>(), dOut.as<float>()); });
 }
 
 static skh_status ensure_ready(skh_context* c);
@@ -1268,14 +1258,10 @@ skh_status skh_light_shape_probe(skh_context* c, uint32_t kind, const void* in, 
     if (n == 0)
         return SKH_OK;
     const size_t inBytes = (kind == SKH_LSHAPE_PROBE_SAMPLE ? 6u : 7u) * sizeof(uint32_t), outBytes = (kind == SKH_LSHAPE_PROBE_SAMPLE ? 13u : 2u) * sizeof(float);
-    DevBuf di, dout;
-    SKH_CHECK(dev_upload(c, di, in, inBytes * n));
-    SKH_CHECK(dev_alloc(c, dout, outBytes * n));
-    k_lshape_probe<<<(n + 255) / 256, 256, 0, c->stream>>>(c->dLights.as<Light>(), c->nLights, make_lshape(c), 0u, kind, di.as<uint32_t>(), n, dout.as<float>());
-    SKH_TRY(c, hipGetLastError());
-    SKH_TRY(c, hipStreamSynchronize(c->stream));
-    SKH_TRY(c, hipMemcpy(out, dout.p, outBytes * n, hipMemcpyDeviceToHost));
-    return SKH_OK;
+    const ProbeIn pin[] = { { in, inBytes * n } };
+    return probe_roundtrip(c, pin, out, outBytes * n, [&](const DevBuf* d, const DevBuf& dOut) {
+        k_lshape_probe<<<(n + 255) / 256, 256, 0, c->stream>>>(c->dLights.as<Light>(), c->nLights, make_lshape(c), 0u, kind, d[0].as<uint32_t>(), n, dOut.as<float>());
+    });
 }
 
 // ---- emissive meshes: skh_set_emission, the emitter table (skh_emit.h) ----
@@ -1324,7 +1310,7 @@ static skh_status emit_ensure(skh_context* c)
         const skh_instance& in = c->instances[i];
         if (in.type != SKH_INSTANCE_MESH || in.geom_id >= nMeshes)
             continue;
-        const uint32_t mid0 = in.material_id == 0xffffffffu ? 0u : in.material_id, mid = mid0 < c->nMaterials ? mid0 : 0u; // (as k_shade reads it)
+        const uint32_t mid = instance_material(c, in);
         float w2o[12];
         const uint32_t tris = c->meshes[in.geom_id].index_count / 3u;
         if (!(le[4 * (size_t)mid + 3] > 0.0f) || tris == 0 || !invert_affine(in.transform, w2o)) // (a singular instance is disabled: no ray reaches it)
@@ -1474,21 +1460,17 @@ skh_status skh_emitter_probe(skh_context* c, uint32_t kind, const void* in, uint
     if (n == 0)
         return SKH_OK;
     const size_t inBytes = (kind == SKH_EMIT_PROBE_SAMPLE ? 6u : 8u) * sizeof(uint32_t), outBytes = (kind == SKH_EMIT_PROBE_SAMPLE ? 13u : 4u) * sizeof(uint32_t);
-    DevBuf di, dout;
-    SKH_CHECK(dev_upload(c, di, in, inBytes * n));
-    SKH_CHECK(dev_alloc(c, dout, outBytes * n));
-    if (kind == SKH_EMIT_PROBE_SAMPLE && mtex_active(c))
-    {
-        // (Le at the sampled point carries the emission map: the uv comes from the shading records, which the build makes)
+    // (Le at the sampled point carries the emission map: the uv comes from the shading records, which the build makes)
+    const bool withMaps = kind == SKH_EMIT_PROBE_SAMPLE && mtex_active(c);
+    if (withMaps)
         SKH_CHECK(ensure_ready(c));
-        k_emit_probe_mtex<<<(n + 255) / 256, 256, 0, c->stream>>>(make_emit(c), make_mtex(c), make_dev_scene(c), di.as<float>(), n, dout.as<uint32_t>());
-    }
-    else
-        k_emit_probe<<<(n + 255) / 256, 256, 0, c->stream>>>(make_emit(c), (uint32_t)c->instances.size(), kind, di.as<uint32_t>(), n, dout.as<uint32_t>());
-    SKH_TRY(c, hipGetLastError());
-    SKH_TRY(c, hipStreamSynchronize(c->stream));
-    SKH_TRY(c, hipMemcpy(out, dout.p, outBytes * n, hipMemcpyDeviceToHost));
-    return SKH_OK;
+    const ProbeIn pin[] = { { in, inBytes * n } };
+    return probe_roundtrip(c, pin, out, outBytes * n, [&](const DevBuf* d, const DevBuf& dOut) {
+        if (withMaps)
+            k_emit_probe_mtex<<<(n + 255) / 256, 256, 0, c->stream>>>(make_emit(c), make_mtex(c), make_dev_scene(c), d[0].as<float>(), n, dOut.as<uint32_t>());
+        else
+            k_emit_probe<<<(n + 255) / 256, 256, 0, c->stream>>>(make_emit(c), (uint32_t)c->instances.size(), kind, d[0].as<uint32_t>(), n, dOut.as<uint32_t>());
+    });
 }
 
 static skh_status ensure_ready(skh_context* c)
@@ -1516,90 +1498,155 @@ static skh_status ensure_ready(skh_context* c)
     return cut_alloc_frame(c);
 }
 
-// one launch of the persistent trace kernel over a sharded queue: picks the build (world-only / two-level / two-level + curves) and the grid
-template <bool ANY, bool COUNT>
-static void launch_trace(skh_context* c, const DevScene& sc, RayQ rq, const uint32_t* countPtr, uint32_t* fetch,
-                         HitQ hq, PathS ps, const float4* contrib, hipStream_t st = nullptr)
+// ---- the trace launch ----
+// The builds of k_trace a context can run; each exists for ANY x COUNT (no other combination of CURVES, WORLD and SPLIT is compiled).
+enum TraceBuild
 {
+    TB_GENERAL,        // two-level, without the curve intersector (fewer VGPRs)
+    TB_GENERAL_CURVES, // two-level with the curve intersector
+    TB_WORLD,          // every instance is baked: the world-only build of the kernel (no instance entry, no object-space copy of the ray)
+    TB_WORLD_SPLIT,    // ... whose tail phase hands stack entries to idle lanes (option tail_split)
+    TB_WORLD_CURVES,   // the world-only kernel with the curve block: curve instances under identity transforms
+    TB_COUNT
+};
+using TraceKernel = decltype(&k_trace<false, false, false>);
+static const TraceKernel kTraceKernels[TB_COUNT][2 /* ANY */][2 /* COUNT */] = {
+    { { k_trace<false, false, false>, k_trace<false, true, false> }, { k_trace<true, false, false>, k_trace<true, true, false> } },
+    { { k_trace<false, false, true>, k_trace<false, true, true> }, { k_trace<true, false, true>, k_trace<true, true, true> } },
+    { { k_trace<false, false, false, true>, k_trace<false, true, false, true> }, { k_trace<true, false, false, true>, k_trace<true, true, false, true> } },
+    { { k_trace<false, false, false, true, true>, k_trace<false, true, false, true, true> }, { k_trace<true, false, false, true, true>, k_trace<true, true, false, true, true> } },
+    { { k_trace<false, false, true, true>, k_trace<false, true, true, true> }, { k_trace<true, false, true, true>, k_trace<true, true, true, true> } },
+};
+
+// The build this context's launches run.  `split`: the pass asks for the SPLIT build (tail_split -1: render_one).
+static TraceBuild trace_build(const skh_context* c, bool split)
+{
+    const bool noTopLevel = c->tlasRoot == SKH_REF_INVALID && c->worldKernel;
+    if (!c->nSegs && noTopLevel && (c->worldRoot != SKH_REF_INVALID || c->lightRoot != SKH_REF_INVALID))
+        return (c->tailSplit == 2 || (c->tailSplit == 1 && c->hierNodes > 16384u) || split) ? TB_WORLD_SPLIT : TB_WORLD;
+    if (c->nSegs && noTopLevel && c->numWorldCurves > 0)
+        return TB_WORLD_CURVES;
     // scenes without curve instances run the build of the kernel that has no curve intersector in it (fewer VGPRs)
+    return c->nSegs ? TB_GENERAL_CURVES : TB_GENERAL;
+}
+
+// Everything one launch of the persistent trace kernel depends on beside the scene and the context's options.
+struct TraceLaunch
+{
+    RayQ rq;                // the queue,
+    const uint32_t* counts; // its length words
+    uint32_t* fetch;        // and its 8 fetch cursors, zeroed
+    HitQ hq;
+    PathS ps;
+    const float4* contrib; // any-hit launches of a render pass: the shadow rays' contributions
+    hipStream_t stream;
+    bool any;
+    uint32_t smallGrid; // an overlapped small pass: this launch's share of the machine, waves per (32-wave) CU x CUs; 0 = the build's full grid
+    bool split;         // the SPLIT build for this pass (trace_build)
+};
+
+// one launch of the persistent trace kernel over a sharded queue: picks the build and the grid
+static void launch_trace(skh_context* c, const DevScene& sc, const TraceLaunch& t)
+{
+    const bool any = t.any;
+    const TraceBuild build = trace_build(c, t.split);
     const bool curveBuild = c->nSegs != 0;
     // (small overlapped passes, triangle scenes: a closest-hit wave asks for rays when 48 instead of 32 of its lanes are idle -- 1-spp 1080p call 3.11 -> 3.01 ms; 40 / 56: 3.04 / 3.04; lower
     // thresholds lose: 24 / 16 / 8: 3.20 / 3.29 / 3.44; the any-hit threshold stays: 32 / 56 of 64: 3.16 / 3.12 against 3.11 at 48.  An explicit fetch_min_closest applies everywhere.)
-    const uint32_t fetchMinClosest = (c->gridOverride && !curveBuild && !c->fetchMinClosestSet) ? c->fetchMinClosestSmall : (curveBuild ? c->curveFetchMinClosest : c->fetchMinClosest);
-    const uint32_t fetchMin = ANY ? (curveBuild ? c->curveFetchMinShadow : c->fetchMinShadow) : fetchMinClosest;
-    const uint32_t nodeBreak = ANY ? (curveBuild ? c->curveNodeBreakShadow : c->nodeBreakShadow) : (curveBuild ? c->curveNodeBreakClosest : c->nodeBreakClosest);
+    const uint32_t fetchMinClosest = (t.smallGrid && !curveBuild && !c->fetchMinClosestSet) ? c->fetchMinClosestSmall : (curveBuild ? c->curveFetchMinClosest : c->fetchMinClosest);
+    const uint32_t fetchMin = any ? (curveBuild ? c->curveFetchMinShadow : c->fetchMinShadow) : fetchMinClosest;
+    const uint32_t nodeBreak = any ? (curveBuild ? c->curveNodeBreakShadow : c->nodeBreakShadow) : (curveBuild ? c->curveNodeBreakClosest : c->nodeBreakClosest);
     // (the world-only kernel with the curve block -- curve instances under identity transforms -- wants the triangle kernels' node-loop exits and
     // an earlier curve block: hair stand-in 1 862 -> 1 937 Mray/s with 32 / 28 / 32 against the two-level curve build's 20 / 20 / 48, gpurun_out/r5t)
-    const bool wcv = c->nSegs && c->tlasRoot == SKH_REF_INVALID && c->numWorldCurves > 0 && c->worldKernel;
-    const uint32_t nodeBreakW = wcv ? (ANY ? c->nodeBreakShadow : c->nodeBreakClosest) : nodeBreak;
-    const uint32_t fm = fetchMin | ((wcv ? c->worldCurveMin : c->curveMin) << 8) | (nodeBreakW << 16) | (c->leafMin << 24);
-    if (!st)
-        st = c->stream;
+    const bool worldCurves = build == TB_WORLD_CURVES;
+    const uint32_t nodeBreakW = worldCurves ? (any ? c->nodeBreakShadow : c->nodeBreakClosest) : nodeBreak;
+    const uint32_t fm = fetchMin | ((worldCurves ? c->worldCurveMin : c->curveMin) << 8) | (nodeBreakW << 16) | (c->leafMin << 24);
+    hipStream_t st = t.stream;
     int* ovf = st == c->stream ? c->dOvf.as<int>() : c->dOvf2.as<int>(); // (two trace kernels may be in flight)
     StatsDev* sd = c->dStats.as<StatsDev>();
-    const bool worldOnly = !c->nSegs && c->tlasRoot == SKH_REF_INVALID && (c->worldRoot != SKH_REF_INVALID || c->lightRoot != SKH_REF_INVALID) && c->worldKernel;
-    const bool worldCurves = c->nSegs && c->tlasRoot == SKH_REF_INVALID && c->numWorldCurves > 0 && c->worldKernel; // the world-only kernel with the curve block
+    const bool worldOnly = build == TB_WORLD || build == TB_WORLD_SPLIT;
     // (the world-only triangle builds run 8 waves per SIMD)
-    const uint32_t fullGrid = (ANY && !c->nSegs) ? (uint32_t)c->numCUs * (worldOnly ? c->wavesPerCUShadowWorld : c->wavesPerCUShadow)
+    const uint32_t fullGrid = (any && !c->nSegs) ? (uint32_t)c->numCUs * (worldOnly ? c->wavesPerCUShadowWorld : c->wavesPerCUShadow)
                                                  : (worldOnly ? (uint32_t)c->numCUs * c->wavesPerCUWorld : c->traceBlocks);
     // (overlapped small passes: small_waves_* are shares of a 32-wave CU; a build that fits fewer waves -- the curve builds: 24 -- takes the same share of what it fits,
     // so that the two concurrent launches still fit side by side: hair 1-spp calls 651 -> ~680 Mray/s against an unscaled 20 / 12)
-    const uint32_t scaledOverride = (uint32_t)((uint64_t)c->gridOverride * fullGrid / (32u * (uint32_t)c->numCUs));
-    const uint32_t blocks = c->gridOverride ? std::max((uint32_t)c->numCUs, std::min(scaledOverride, fullGrid)) : fullGrid;
+    const uint32_t scaledGrid = (uint32_t)((uint64_t)t.smallGrid * fullGrid / (32u * (uint32_t)c->numCUs));
+    const uint32_t blocks = t.smallGrid ? std::max((uint32_t)c->numCUs, std::min(scaledGrid, fullGrid)) : fullGrid;
     // A hierarchy that fits the L2 many times over (Cornell: 30 triangles) makes rays so cheap that the launch is bound by the eight queue cursors'
     // atomics (~88 M per second and address): such scenes reserve 128 positions per atomic (Cornell 13.5 -> 14.8 Gray/s).  Larger scenes lose by it
     // (neighbouring rays are then traced at different times by one wave instead of together by neighbouring waves: kitchen -1 %, hair -2 %;
     // docs/LOG.md, round 5); only the world-only triangle builds carry the code.
     const uint32_t chunk = c->fetchChunk >= 0 ? (uint32_t)c->fetchChunk : (c->hierNodes <= 16384u ? 128u : 0u);
 #ifdef SKH_TAIL_PROFILE
-    (void)hipMemsetAsync(&sd->launchT0[ANY ? 1 : 0], 0xff, sizeof(unsigned long long), st);
+    (void)hipMemsetAsync(&sd->launchT0[any ? 1 : 0], 0xff, sizeof(unsigned long long), st);
 #endif
-    if (worldOnly && (c->tailSplit == 2 || (c->tailSplit == 1 && c->hierNodes > 16384u) || c->splitNow))
-        k_trace<ANY, COUNT, false, true, true><<<blocks, SKH_TRACE_BLOCK, 0, st>>>(sc, rq, countPtr, fetch, fm, hq, ps, contrib, ovf, sd, c->lightBox, chunk);
-    else if (worldOnly)
-        // every instance is baked: the world-only build of the kernel (no instance entry, no object-space copy of the ray)
-        k_trace<ANY, COUNT, false, true><<<blocks, SKH_TRACE_BLOCK, 0, st>>>(sc, rq, countPtr, fetch, fm, hq, ps, contrib, ovf, sd, c->lightBox, chunk);
-    else if (worldCurves)
-        k_trace<ANY, COUNT, true, true><<<blocks, SKH_TRACE_BLOCK, 0, st>>>(sc, rq, countPtr, fetch, fm, hq, ps, contrib, ovf, sd, c->lightBox, chunk);
-    else if (c->nSegs)
-        k_trace<ANY, COUNT, true><<<blocks, SKH_TRACE_BLOCK, 0, st>>>(sc, rq, countPtr, fetch, fm, hq, ps, contrib, ovf, sd, c->lightBox, chunk);
-    else
-        k_trace<ANY, COUNT, false><<<blocks, SKH_TRACE_BLOCK, 0, st>>>(sc, rq, countPtr, fetch, fm, hq, ps, contrib, ovf, sd, c->lightBox, chunk);
+    kTraceKernels[build][any ? 1 : 0][c->countTraversal ? 1 : 0]<<<blocks, SKH_TRACE_BLOCK, 0, st>>>(sc, t.rq, t.counts, t.fetch, fm, t.hq, t.ps, t.contrib, ovf, sd, c->lightBox, chunk);
 }
 
-// The continuation rounds behind a trace launch whose hit records lie in h0 (rays: q0, lengths: count0): k_cutout on them, then cutout_rounds x {trace the continuation
-// queue into h2, k_cutout}.  `words`: cutout_rounds x SKH_CUT_WORDS zeroed words.  A round whose queue is empty costs two launches that return at once.
-template <bool SHADOW, bool COUNT>
-static void run_cutout_chain(skh_context* c, const DevScene& sc, const DevScene& scTrace, RayQ q0, const uint32_t* count0, HitQ h0, HitQ outH, float* rawOut, PathS ps,
-                             const float4* contrib, RayQ cq0, RayQ cq1, HitQ h2, uint32_t* words, uint32_t rays, hipStream_t st, BlendP bl)
+// what the closest-hit launches of SHADOW rays walk: not the baked light proxies' tree (shadow rays do not see lights)
+static DevScene shadow_scene(const skh_context* c, DevScene sc)
+{
+    if (c->worldRoot != SKH_REF_INVALID || c->tlasRoot != SKH_REF_INVALID)
+        sc.lightRoot = SKH_REF_INVALID;
+    return sc;
+}
+
+// what the cutout rounds behind a trace launch work in: two continuation queues, a second hit buffer, cutout_rounds x SKH_CUT_WORDS zeroed words
+struct CutRounds
+{
+    RayQ q[2];
+    HitQ h0, h2;   // h0: where a SHADOW step's first launch leaves its nearest hits (a closest step's lie where the caller wants them)
+    float* rawOut; // raw shadow queries: one float per ray
+    uint32_t* words;
+    uint32_t rays;
+    BlendP bl;
+};
+static const decltype(&k_cutout<false, false>) kCutoutKernels[2 /* SHADOW */][2 /* BLEND */] = { { k_cutout<false, false>, k_cutout<false, true> },
+                                                                                                  { k_cutout<true, false>, k_cutout<true, true> } };
+
+// The continuation rounds behind the trace launch `t`, whose hit records lie in t.hq: k_cutout on them, then cutout_rounds x {trace the continuation queue into h2,
+// k_cutout}; those launches take t's stream, grid share and split flag.  A round whose queue is empty costs two launches that return at once.
+static void run_cutout_chain(skh_context* c, const DevScene& sc, const DevScene& scTrace, const TraceLaunch& t, bool shadow, const float4* contrib, const CutRounds& cr)
 {
     const CutoutP cutp = make_cutout(c);
     // the BLEND build only where blending is in use (bl.count != 0: make_blend); round = hits the rays of a launch have already passed; the path ids lie in the first queue
-    const bool blend = bl.count != 0u;
-    bl.pathIds = reinterpret_cast<const uint32_t*>(q0.base + (size_t)8 * q0.stride);
+    BlendP bl = cr.bl;
+    const auto kernel = kCutoutKernels[shadow ? 1 : 0][bl.count != 0u ? 1 : 0];
+    bl.pathIds = reinterpret_cast<const uint32_t*>(t.rq.base + (size_t)8 * t.rq.stride);
     CutStatsDev* cst = c->dCutStats.as<CutStatsDev>();
-    const uint32_t perShard = (((rays + SKH_SHARDS - 1u) / SKH_SHARDS) + 63u) & ~63u;
-    const dim3 grid(SKH_SHARDS * ((std::min(perShard, q0.region) + SKH_CUTOUT_BLOCK - 1) / SKH_CUTOUT_BLOCK));
+    const uint32_t perShard = (((cr.rays + SKH_SHARDS - 1u) / SKH_SHARDS) + 63u) & ~63u;
+    const dim3 grid(SKH_SHARDS * ((std::min(perShard, t.rq.region) + SKH_CUTOUT_BLOCK - 1) / SKH_CUTOUT_BLOCK));
     const uint32_t R = c->cutoutRounds, QW = SKH_COUNT_STRIDE * SKH_SHARDS;
-    const RayQ cq[2] = { cq0, cq1 };
     bl.round = 0u;
-    if (blend)
-        k_cutout<SHADOW, true><<<grid, SKH_CUTOUT_BLOCK, 0, st>>>(sc, cutp, q0, count0, h0, 1u, 0u, outH, rawOut, ps, contrib, cq[0], words, cst, bl);
-    else
-        k_cutout<SHADOW, false><<<grid, SKH_CUTOUT_BLOCK, 0, st>>>(sc, cutp, q0, count0, h0, 1u, 0u, outH, rawOut, ps, contrib, cq[0], words, cst, bl);
+    kernel<<<grid, SKH_CUTOUT_BLOCK, 0, t.stream>>>(sc, cutp, t.rq, t.counts, t.hq, 1u, 0u, t.hq, cr.rawOut, t.ps, contrib, cr.q[0], cr.words, cst, bl);
+    TraceLaunch next = t; // (any = false, contrib = nullptr: trace_step)
+    next.hq = cr.h2;
     for (uint32_t r = 0; r < R; ++r)
     {
-        uint32_t* lens = words + (size_t)r * SKH_CUT_WORDS;
-        launch_trace<false, COUNT>(c, scTrace, cq[r & 1], lens, lens + QW, h2, ps, nullptr, st);
+        uint32_t* lens = cr.words + (size_t)r * SKH_CUT_WORDS;
+        next.rq = cr.q[r & 1], next.counts = lens, next.fetch = lens + QW;
+        launch_trace(c, scTrace, next);
         const bool last = r + 1 == R;
         bl.round = r + 1u;
-        if (blend)
-            k_cutout<SHADOW, true><<<grid, SKH_CUTOUT_BLOCK, 0, st>>>(sc, cutp, cq[r & 1], lens, h2, 0u, last ? 1u : 0u, outH, rawOut, ps, contrib, cq[(r + 1) & 1],
-                                                                      last ? lens : lens + SKH_CUT_WORDS, cst, bl);
-        else
-            k_cutout<SHADOW, false><<<grid, SKH_CUTOUT_BLOCK, 0, st>>>(sc, cutp, cq[r & 1], lens, h2, 0u, last ? 1u : 0u, outH, rawOut, ps, contrib, cq[(r + 1) & 1],
-                                                                       last ? lens : lens + SKH_CUT_WORDS, cst, bl);
+        kernel<<<grid, SKH_CUTOUT_BLOCK, 0, t.stream>>>(sc, cutp, next.rq, lens, cr.h2, 0u, last ? 1u : 0u, t.hq, cr.rawOut, t.ps, contrib, cr.q[(r + 1) & 1],
+                                                        last ? lens : lens + SKH_CUT_WORDS, cst, bl);
     }
+}
+
+// One trace step of a pass or of a raw query.  Without the cutout stage (cr == nullptr) it is the launch: any-hit for shadow rays.  With it, the nearest hits are
+// wanted: a closest-hit launch -- a shadow step's into cr->h0, past the light proxies -- and the rounds behind it, which add a shadow ray's contribution when it ends in a miss.
+static void trace_step(skh_context* c, const DevScene& sc, TraceLaunch t, bool shadow, const CutRounds* cr)
+{
+    t.any = shadow && !cr;
+    if (!cr)
+        return launch_trace(c, sc, t);
+    const float4* contrib = t.contrib;
+    t.contrib = nullptr;
+    if (shadow)
+        t.hq = cr->h0;
+    const DevScene scTrace = shadow ? shadow_scene(c, sc) : sc;
+    launch_trace(c, scTrace, t);
+    run_cutout_chain(c, sc, scTrace, t, shadow, contrib, *cr);
 }
 
 // After a synchronisation: did any traversal of the calls since the last check drop a stack entry (its result may miss hits)?
@@ -1690,12 +1737,18 @@ static inline uint32_t adapt_to_next_check(const skh_context* c)
     return ad.cfg.interval - (ad.delivered - ad.cfg.min_samples) % ad.cfg.interval;
 }
 
+// the fields of FrameP that describe the frame's geometry
+static void frame_geometry(const skh_context* c, FrameP& fp)
+{
+    fp.width = c->width, fp.height = c->height, fp.tileSize = c->tileSize, fp.tileShift = c->tileShift, fp.numTiles = c->numTiles, fp.numSlots = c->numSlots;
+}
+
 static FrameP adapt_frame(const skh_context* c, const skh_frame_params& p)
 {
     FrameP fp;
     memset(&fp, 0, sizeof(fp));
     memcpy(fp.exposure, p.exposure, sizeof(fp.exposure));
-    fp.width = c->width, fp.height = c->height, fp.tileSize = c->tileSize, fp.tileShift = c->tileShift, fp.numTiles = c->numTiles, fp.numSlots = c->numSlots;
+    frame_geometry(c, fp);
     return fp;
 }
 
@@ -1768,18 +1821,41 @@ skh_status skh_get_adaptive_info(skh_context* c, skh_adaptive_info* out)
     return SKH_OK;
 }
 
-// One wavefront pass: either one launch of p->samples_this_launch samples (batch = 1), or `batch` consecutive sub-frames
+// What one call of render_one does.  One wavefront pass: either one launch of p->samples_this_launch samples (batch = 1), or `batch` consecutive sub-frames
 // of one sample each traced together (more rays per launch; results identical, see k_finalize_batch).
-static skh_status render_one(skh_context* c, const skh_frame_params* p, uint32_t batch, void* d_image, bool trace = true, uint32_t finalFirst = 0,
-                             uint32_t finalCount = 0xffffffffu, uint32_t pathSel = 0 /* 1: the second path-state buffer */, bool finalize = true,
-                             hipStream_t finStream = nullptr /* where the accumulation step runs (default: the render stream) */)
+struct RenderPlan
 {
-    if (p->max_depth > 128 || p->samples_this_launch == 0)
-    {
-        c->err = "skh_render_subframe: max_depth must be <= 128 (MAX_BOUNCES, RandomSampler.h:35) and samples_this_launch >= 1";
-        return SKH_INVALID_ARGUMENT;
-    }
-    hipStream_t st = c->stream;
+    uint32_t batch = 1;
+    bool trace = true;                                 // false: the pass was traced ahead, only accumulation steps are left
+    uint32_t finalFirst = 0, finalCount = 0xffffffffu; // the sub-frames of the pass whose accumulation steps this call applies
+    uint32_t pathSel = 0;                              // 1: the second path-state buffer
+    bool finalize = true;
+    hipStream_t finStream = nullptr; // where the accumulation step runs (default: the render stream)
+    bool adaptive = false;           // an adaptive pass: the render list and its tables -- frozen tiles are slots outside the image to every kernel
+};
+
+// what the steps of a pass share
+struct RenderPass
+{
+    FrameP fp;
+    DevScene sc;
+    EnvP envp;
+    EmitP emitp;
+    MtexP mtexp;
+    LshapeP lshp;
+    hipStream_t st;
+    const uint32_t* tiles;
+    PathS ps;
+    RayQ rq[2], shq, cutQ[2], cutSQ[2];
+    HitQ hq, cutH, cutSH0, cutSH1;
+    uint32_t *counts, *fetch, *cutWords;
+    uint32_t QW, NP, rounds, cutBounceWords;
+    bool smallPass, useOverlap, split, cutOn;
+    BlendP blp;
+};
+
+static FrameP frame_params(const skh_context* c, const skh_frame_params* p, const RenderPlan& plan)
+{
     FrameP fp;
     memcpy(fp.viewToWorld, p->view_to_world, sizeof(fp.viewToWorld));
     memcpy(fp.clipToView, p->clip_to_view, sizeof(fp.clipToView));
@@ -1793,40 +1869,164 @@ static skh_status render_one(skh_context* c, const skh_frame_params* p, uint32_t
     fp.debug = p->debug;
     fp.shadowTmin = p->shadow_ray_tmin;
     fp.materialTmin = p->material_ray_tmin;
-    fp.width = c->width;
-    fp.height = c->height;
-    fp.tileSize = c->tileSize;
-    fp.tileShift = c->tileShift;
-    fp.numTiles = c->numTiles;
-    fp.numSlots = c->numSlots;
-    fp.batch = batch;
-    fp.finalFirst = std::min(finalFirst, batch);
-    fp.finalCount = std::min(finalCount, batch - fp.finalFirst);
-    const DevScene sc = make_dev_scene(c);
-    const EnvP envp = make_env(c);
-    const EmitP emitp = make_emit(c);
-    const MtexP mtexp = make_mtex(c);
-    const LshapeP lshp = make_lshape(c);
+    frame_geometry(c, fp);
+    fp.batch = plan.batch;
+    fp.finalFirst = std::min(plan.finalFirst, plan.batch);
+    fp.finalCount = std::min(plan.finalCount, plan.batch - fp.finalFirst);
+    return fp;
+}
+
+// tmin / tmax of every radiance ray and tmin of every shadow ray are constants of the frame parameters (OptixRender.cu:121-122, closest_hit.cu):
+// their queue planes are filled here, when the queues are new or a value has changed, and never written per ray (8 + 8 + 4 B per path and bounce)
+static void fill_queue_constants(skh_context* c, const RenderPass& rp)
+{
+    const uint32_t NQ = rp.shq.stride;
+    uint32_t bits[2];
+    memcpy(&bits[0], &rp.fp.materialTmin, 4);
+    memcpy(&bits[1], &rp.fp.shadowTmin, 4);
+    if (c->queueConstFilled && bits[0] == c->queueConstBits[0] && bits[1] == c->queueConstBits[1])
+        return;
+    const uint32_t fb = (uint32_t)c->numCUs * 8u;
+    for (int k = 0; k < 2; ++k)
+    {
+        k_fill_f32<<<fb, 256, 0, rp.st>>>(rp.rq[k].base + (size_t)6 * NQ, NQ, rp.fp.materialTmin);
+        k_fill_f32<<<fb, 256, 0, rp.st>>>(rp.rq[k].base + (size_t)7 * NQ, NQ, 1e16f);
+    }
+    k_fill_f32<<<fb, 256, 0, rp.st>>>(rp.shq.base + (size_t)6 * NQ, NQ, rp.fp.shadowTmin);
+    c->queueConstFilled = true;
+    c->queueConstBits[0] = bits[0];
+    c->queueConstBits[1] = bits[1];
+}
+
+// k_shade for bounce b of sample s: the build by HAIR x ENV x EMIT x MTEX (index 8 4 2 1); every one has a twin with light shapes in it, launched only when a shape
+// is in use (a context without an environment, without emitters and without material textures launches the builds it always launched)
+#define SKH_SHADE_BUILDS(K)                                                                                                                      \
+    {                                                                                                                                            \
+        K<false, false, false, false>, K<false, false, false, true>, K<false, false, true, false>, K<false, false, true, true>,                  \
+        K<false, true, false, false>, K<false, true, false, true>, K<false, true, true, false>, K<false, true, true, true>,                      \
+        K<true, false, false, false>, K<true, false, false, true>, K<true, false, true, false>, K<true, false, true, true>,                      \
+        K<true, true, false, false>, K<true, true, false, true>, K<true, true, true, false>, K<true, true, true, true>                           \
+    }
+static const decltype(&k_shade<false, false, false, false>) kShadeKernels[16] = SKH_SHADE_BUILDS(k_shade);
+static const decltype(&k_shade_lshape<false, false, false, false>) kShadeLshapeKernels[16] = SKH_SHADE_BUILDS(k_shade_lshape);
+#undef SKH_SHADE_BUILDS
+
+static void launch_shade(skh_context* c, const RenderPass& rp, uint32_t s, uint32_t b)
+{
+    // a shard holds at most an eighth of the pass's paths (rounded up to whole waves): SKH_SHARDS x that many workgroups,
+    // workgroup b on shard b & 7; those past the end of their shard leave at once
+    const uint32_t perShard = (((rp.NP + SKH_SHARDS - 1u) / SKH_SHARDS) + 63u) & ~63u;
+    const dim3 sg(SKH_SHARDS * ((perShard + SKH_SHADE_BLOCK - 1) / SKH_SHADE_BLOCK));
+    const uint32_t build = (c->hasHairMaterial ? 8u : 0u) | (c->envW ? 4u : 0u) | (rp.emitp.count ? 2u : 0u) | (rp.mtexp.count ? 1u : 0u), QW = rp.QW;
+    uint32_t* counts = rp.counts;
+    if (rp.lshp.table)
+        kShadeLshapeKernels[build]<<<sg, SKH_SHADE_BLOCK, 0, rp.st>>>(rp.sc, rp.fp, s, b, rp.tiles, rp.rq[b & 1], counts + 2 * b * QW, rp.hq, rp.ps, rp.rq[(b + 1) & 1],
+                                                                      counts + 2 * (b + 1) * QW, rp.shq, c->dContrib.as<float4>(), counts + (2 * b + 1) * QW, rp.envp,
+                                                                      rp.emitp, rp.mtexp, rp.lshp);
+    else
+        kShadeKernels[build]<<<sg, SKH_SHADE_BLOCK, 0, rp.st>>>(rp.sc, rp.fp, s, b, rp.tiles, rp.rq[b & 1], counts + 2 * b * QW, rp.hq, rp.ps, rp.rq[(b + 1) & 1],
+                                                                counts + 2 * (b + 1) * QW, rp.shq, c->dContrib.as<float4>(), counts + (2 * b + 1) * QW, rp.envp, rp.emitp,
+                                                                rp.mtexp);
+}
+
+// Bounce b of sample s: the closest-hit step, k_shade, the shadow step.  With `overlap`, shadow[b] runs on a second stream: it depends on shade[b] only, and so does
+// closest[b+1]; each fills the other's tail.
+static void render_bounce(skh_context* c, const RenderPass& rp, uint32_t s, uint32_t b)
+{
+    hipStream_t st = rp.st;
+    const bool smallGrids = rp.useOverlap && rp.smallPass;
+    BlendP blp = rp.blp;
+    blp.depth = b;
+    uint32_t* words = rp.cutOn ? rp.cutWords + (size_t)b * rp.cutBounceWords : nullptr; // this bounce's: the closest side's, then the shadow side's
+    TraceLaunch t;
+    t.ps = rp.ps, t.split = rp.split, t.any = false;
+    {
+        SpanGuard g(c, KC_TRACE_CLOSEST);
+        t.rq = rp.rq[b & 1], t.counts = rp.counts + 2 * b * rp.QW, t.fetch = rp.fetch + 16 * b * SKH_FETCH_STRIDE, t.hq = rp.hq, t.contrib = nullptr, t.stream = st;
+        t.smallGrid = smallGrids ? ((b == 0 && c->smallWavesFirst) ? c->smallWavesFirst : c->smallWavesClosest ? c->smallWavesClosest : (c->nSegs ? 16u : 20u)) * (uint32_t)c->numCUs : 0u;
+        const CutRounds cr{ { rp.cutQ[0], rp.cutQ[1] }, rp.hq, rp.cutH, nullptr, words, rp.NP, blp };
+        trace_step(c, rp.sc, t, false, rp.cutOn ? &cr : nullptr);
+    }
+    if (rp.useOverlap && b > 0)
+        (void)hipStreamWaitEvent(st, c->evShadow, 0); // shade[b] reads the radiance shadow[b-1] adds to and reuses its queue
+    {
+        SpanGuard g(c, KC_SHADE);
+        launch_shade(c, rp, s, b);
+    }
+    hipStream_t sst = rp.useOverlap ? c->stream2 : st;
+    if (rp.useOverlap)
+    {
+        (void)hipEventRecord(c->evShade, st);
+        (void)hipStreamWaitEvent(sst, c->evShade, 0);
+    }
+    {
+        SpanGuard g(c, KC_TRACE_SHADOW, sst);
+        t.rq = rp.shq, t.counts = rp.counts + (2 * b + 1) * rp.QW, t.fetch = rp.fetch + (16 * b + 8) * SKH_FETCH_STRIDE, t.hq = HitQ{ nullptr, 0 }, t.contrib = c->dContrib.as<float4>(), t.stream = sst;
+        t.smallGrid = smallGrids ? ((b + 1 == rp.rounds && (c->smallWavesLast || (!c->smallWavesShadow && !c->nSegs))) ? (c->smallWavesLast ? c->smallWavesLast : 20u) : c->smallWavesShadow ? c->smallWavesShadow : (c->nSegs ? 16u : 12u)) * (uint32_t)c->numCUs : 0u;
+        // (a cutout in use) the shadow rays' NEAREST hits, tested and continued like the radiance rays'; a ray that ends in a miss adds its contribution (k_cutout)
+        const CutRounds cr{ { rp.cutSQ[0], rp.cutSQ[1] }, rp.cutSH0, rp.cutSH1, nullptr, rp.cutOn ? words + c->cutoutRounds * SKH_CUT_WORDS : nullptr, rp.NP, blp };
+        trace_step(c, rp.sc, t, true, rp.cutOn ? &cr : nullptr);
+    }
+    if (rp.useOverlap)
+        (void)hipEventRecord(c->evShadow, sst);
+}
+
+// the accumulation steps of a pass into the frame's accumulators (and the call's d_image)
+static void render_accumulate(skh_context* c, const RenderPass& rp, const RenderPlan& plan, bool oneSampleDirect, void* d_image)
+{
+    if (!plan.finalize)
+        return;
+    const uint32_t gridSlots = (c->numSlots + 255) / 256;
+    const bool fromPaths = plan.batch > 1 || oneSampleDirect;
+    hipStream_t fs = plan.finStream ? plan.finStream : rp.st;
+    {
+        SpanGuard g(c, KC_ACCUM, fs);
+        if (fromPaths)
+            k_finalize_batch<<<gridSlots, 256, 0, fs>>>(rp.fp, rp.tiles, rp.ps, c->dAccum.as<float4>(), c->dDiffuse.as<float4>(), c->dSpecular.as<float4>(),
+                                                        c->dDiffCnt.as<uint16_t>(), c->dSpecCnt.as<uint16_t>(), reinterpret_cast<float4*>(d_image));
+        else
+            k_finalize<<<gridSlots, 256, 0, fs>>>(rp.fp, rp.tiles, c->dSums.as<float>(), c->dAccum.as<float4>(), c->dDiffuse.as<float4>(), c->dSpecular.as<float4>(),
+                                                  c->dDiffCnt.as<uint16_t>(), c->dSpecCnt.as<uint16_t>(), reinterpret_cast<float4*>(d_image));
+    }
+    if (plan.adaptive)
+    {
+        SpanGuard g(c, KC_ACCUM, fs);
+        k_adapt_moments<<<gridSlots, 256, 0, fs>>>(rp.fp, rp.tiles, rp.ps, c->dSums.as<float>(), fromPaths ? 0u : 1u, c->dAdaptState.as<float4>());
+    }
+}
+
+static skh_status render_one(skh_context* c, const skh_frame_params* p, const RenderPlan& plan, void* d_image)
+{
+    if (p->max_depth > 128 || p->samples_this_launch == 0)
+    {
+        c->err = "skh_render_subframe: max_depth must be <= 128 (MAX_BOUNCES, RandomSampler.h:35) and samples_this_launch >= 1";
+        return SKH_INVALID_ARGUMENT;
+    }
+    RenderPass rp;
+    hipStream_t st = rp.st = c->stream;
+    const FrameP& fp = rp.fp = frame_params(c, p, plan);
+    const uint32_t batch = plan.batch;
+    rp.sc = make_dev_scene(c);
+    rp.envp = make_env(c);
+    rp.emitp = make_emit(c);
+    rp.mtexp = make_mtex(c);
+    rp.lshp = make_lshape(c);
     const uint32_t N = c->numSlots * c->batchCapacity; // plane stride of the path-state buffer
     const uint32_t NQ = SKH_SHARDS * c->queueRegion; // plane stride of every queue (rays, hits, shadow contributions)
-    const uint32_t NP = c->numSlots * batch; // paths in this pass
+    const uint32_t NP = rp.NP = c->numSlots * batch; // paths in this pass
     if (NP == 0)
         return SKH_OK;
-    const uint32_t gridSlots = (c->numSlots + 255) / 256;
-    // (an adaptive pass: the render list and its tables -- frozen tiles are slots outside the image to every kernel below)
-    const bool adaptive = c->adapt.now;
-    const uint32_t* tiles = adaptive ? c->dTileXYRender.as<uint32_t>() : c->dTileXY.as<uint32_t>();
-    const uint32_t* raygenBase = adaptive ? c->dRaygenBaseRender.as<uint32_t>() : c->dRaygenBase.as<uint32_t>();
-    const uint32_t raygenValid = adaptive ? c->adapt.raygenValid : c->raygenValidPerSub;
-    PathS ps{ pathSel ? c->dPathB.as<float>() : c->dPath.as<float>(), pathSel ? c->pathBStride : N };
-    RayQ rq[2] = { RayQ{ c->dRayQ[0].as<float>(), NQ, c->queueRegion }, RayQ{ c->dRayQ[1].as<float>(), NQ, c->queueRegion } };
-    RayQ shq{ c->dShadowQ.as<float>(), NQ, c->queueRegion };
+    rp.tiles = plan.adaptive ? c->dTileXYRender.as<uint32_t>() : c->dTileXY.as<uint32_t>();
+    const uint32_t* raygenBase = plan.adaptive ? c->dRaygenBaseRender.as<uint32_t>() : c->dRaygenBase.as<uint32_t>();
+    const uint32_t raygenValid = plan.adaptive ? c->adapt.raygenValid : c->raygenValidPerSub;
+    rp.ps = PathS{ plan.pathSel ? c->dPathB.as<float>() : c->dPath.as<float>(), plan.pathSel ? c->pathBStride : N };
+    const auto queue = [&](const DevBuf& b) { return RayQ{ b.as<float>(), NQ, c->queueRegion }; };
+    rp.rq[0] = queue(c->dRayQ[0]), rp.rq[1] = queue(c->dRayQ[1]), rp.shq = queue(c->dShadowQ);
     HitQ hq{ c->dHits.as<float>(), NQ };
     {
         // 16-byte hit records where they are possible: the world-only triangle kernels (every mesh hit names its shading record) and an instance
         // count and a record count that share 32 bits with the all-ones word left for a miss
-        const bool worldKernels = c->tlasRoot == SKH_REF_INVALID && c->worldKernel &&
-                                  (c->nSegs ? c->numWorldCurves != 0u : (c->worldRoot != SKH_REF_INVALID || c->lightRoot != SKH_REF_INVALID));
+        const bool worldKernels = trace_build(c, false) >= TB_WORLD;
         const uint32_t range = std::max(1u, c->hitPrimRange); // shading records (or mesh-local indices), light proxies' triangles, curve segments: skh_build_accel
         uint32_t B = 1;
         while (B < 31u && (1u << B) < range)
@@ -1835,32 +2035,13 @@ static skh_status render_one(skh_context* c, const skh_frame_params* p, uint32_t
         hq.direct = c->directRecords;
         hq.recClamp = c->nShadeRecords ? c->nShadeRecords - 1u : 0u;
     }
-    HitQ nohq{ nullptr, 0 };
-    {
-        // tmin / tmax of every radiance ray and tmin of every shadow ray are constants of the frame parameters (OptixRender.cu:121-122, closest_hit.cu):
-        // their queue planes are filled here, when the queues are new or a value has changed, and never written per ray (8 + 8 + 4 B per path and bounce)
-        uint32_t bits[2];
-        memcpy(&bits[0], &fp.materialTmin, 4);
-        memcpy(&bits[1], &fp.shadowTmin, 4);
-        if (!c->queueConstFilled || bits[0] != c->queueConstBits[0] || bits[1] != c->queueConstBits[1])
-        {
-            const uint32_t fb = (uint32_t)c->numCUs * 8u;
-            for (int k = 0; k < 2; ++k)
-            {
-                k_fill_f32<<<fb, 256, 0, st>>>(rq[k].base + (size_t)6 * NQ, NQ, fp.materialTmin);
-                k_fill_f32<<<fb, 256, 0, st>>>(rq[k].base + (size_t)7 * NQ, NQ, 1e16f);
-            }
-            k_fill_f32<<<fb, 256, 0, st>>>(shq.base + (size_t)6 * NQ, NQ, fp.shadowTmin);
-            c->queueConstFilled = true;
-            c->queueConstBits[0] = bits[0];
-            c->queueConstBits[1] = bits[1];
-        }
-    }
+    rp.hq = hq;
+    fill_queue_constants(c, rp);
     // dCounts: 260 queues (2 per bounce) x SKH_SHARDS queue-length words, then the ray-fetch cursors (8 per trace launch); every word
     // that is the target of atomics has a 128-byte line of its own (returning atomics on one line serialise at ~88 per microsecond)
-    uint32_t* counts = c->dCounts.as<uint32_t>();
-    const uint32_t QW = SKH_COUNT_STRIDE * SKH_SHARDS; // words per queue's lengths
-    uint32_t* fetch = counts + QW * 2 * SKH_MAX_LAUNCH_ROUNDS;
+    uint32_t* counts = rp.counts = c->dCounts.as<uint32_t>();
+    const uint32_t QW = rp.QW = SKH_COUNT_STRIDE * SKH_SHARDS; // words per queue's lengths
+    rp.fetch = counts + QW * 2 * SKH_MAX_LAUNCH_ROUNDS;
     // shadow[b] on a second stream: it depends on shade[b] only, and so does closest[b+1]; each fills the other's tail.  Ray
     // sorting shares scratch buffers between the two and keeps everything on one stream.
     // overlap 1 (default): passes up to 32 M paths -- a rank's share of an N-GPU frame, the one-sub-frame-per-call pattern and its
@@ -1868,178 +2049,50 @@ static skh_status render_one(skh_context* c, const skh_frame_params* p, uint32_t
     // full grids, where the second kernel's blocks simply take the slots the first one's finishing waves leave (1/8 share of a 1080p
     // frame: 24.26 -> 23.87 ms, 93.3 -> 94.9 % of 1/8 of the full frame; 1/4: 97.0 -> 97.8 %).  The full single-GPU frame (64 M paths
     // per pass) gains 0.5 % and stays on one stream so that its per-kernel hipEvent spans do not overlap.  overlap 2: always, reduced grids.
-    const bool smallPass = NP <= (1u << 23) || c->overlap == 2;
-    const bool useOverlap = (c->overlap == 2 || (c->overlap == 1 && NP <= (1u << 25))) && fp.debug != 1;
-    const uint32_t rounds = fp.maxDepth;
+    rp.smallPass = NP <= (1u << 23) || c->overlap == 2;
+    rp.useOverlap = (c->overlap == 2 || (c->overlap == 1 && NP <= (1u << 25))) && fp.debug != 1;
+    const uint32_t rounds = rp.rounds = fp.maxDepth;
     // Cutouts (skh_set_material_cutouts), only in a context where one is in use: k_cutout and its continuation rounds between a bounce's closest-hit launch and k_shade, and
     // a closest-hit launch with the same rounds behind it in the any-hit launch's place.  Per bounce and side cutout_rounds x SKH_CUT_WORDS words, behind the fetch cursors.
-    const bool cutOn = cut_stage_on(c);
-    const uint32_t cutBounceWords = 2u * c->cutoutRounds * SKH_CUT_WORDS;
-    uint32_t* cutWords = fetch + 16 * SKH_FETCH_STRIDE * (rounds + 1);
-    const RayQ cutQ[2] = { RayQ{ c->dCutQ[0].as<float>(), NQ, c->queueRegion }, RayQ{ c->dCutQ[1].as<float>(), NQ, c->queueRegion } };
-    const RayQ cutSQ[2] = { RayQ{ c->dCutShadowQ[0].as<float>(), NQ, c->queueRegion }, RayQ{ c->dCutShadowQ[1].as<float>(), NQ, c->queueRegion } };
-    HitQ cutH = hq, cutSH0 = hq, cutSH1 = hq; // (records as the closest-hit launches of this pass write them)
-    cutH.base = c->dCutHits.as<float>(), cutSH0.base = c->dCutShadowHits[0].as<float>(), cutSH1.base = c->dCutShadowHits[1].as<float>();
-    DevScene scShadow = sc; // what the closest-hit launches of SHADOW rays walk: not the baked light proxies' tree (shadow rays do not see lights)
-    if (c->worldRoot != SKH_REF_INVALID || c->tlasRoot != SKH_REF_INVALID)
-        scShadow.lightRoot = SKH_REF_INVALID;
+    const bool cutOn = rp.cutOn = cut_stage_on(c);
+    rp.cutBounceWords = 2u * c->cutoutRounds * SKH_CUT_WORDS;
+    rp.cutWords = rp.fetch + 16 * SKH_FETCH_STRIDE * (rounds + 1);
+    rp.cutQ[0] = queue(c->dCutQ[0]), rp.cutQ[1] = queue(c->dCutQ[1]), rp.cutSQ[0] = queue(c->dCutShadowQ[0]), rp.cutSQ[1] = queue(c->dCutShadowQ[1]);
+    rp.cutH = rp.cutSH0 = rp.cutSH1 = hq; // (records as the closest-hit launches of this pass write them)
+    rp.cutH.base = c->dCutHits.as<float>(), rp.cutSH0.base = c->dCutShadowHits[0].as<float>(), rp.cutSH1.base = c->dCutShadowHits[1].as<float>();
     // fractional opacity (skh_set_material_blend), where it is in use: what the draw's path identity needs of the frame, and the contribution records, writable
-    BlendP blp = make_blend(c);
-    blp.tileXY = tiles, blp.sppTotal = fp.sppTotal, blp.numSlots = fp.numSlots, blp.tileShift = fp.tileShift;
-    blp.contrib = c->dContrib.as<float4>();
-    c->splitNow = c->tailSplit < 0 && smallPass && NP >= (1u << 17);
+    rp.blp = make_blend(c);
+    rp.blp.tileXY = rp.tiles, rp.blp.sppTotal = fp.sppTotal, rp.blp.numSlots = fp.numSlots, rp.blp.tileShift = fp.tileShift;
+    rp.blp.contrib = c->dContrib.as<float4>();
+    rp.split = c->tailSplit < 0 && rp.smallPass && NP >= (1u << 17);
     // One sub-frame of one sample, accumulated in this call (the reference caller's pattern): its sums ARE the path's radiance and event word -- the batch kernel reads
     // them where they lie (0.0f + radiance, / 1.0f: the same operations), and the k_collect launch and its 11 planes of sums are not needed.
-    const bool oneSampleDirect = batch == 1 && fp.samplesThisLaunch == 1 && finalize && fp.finalFirst == 0 && fp.finalCount == 1;
-    for (uint32_t s = 0; trace && s < fp.samplesThisLaunch; ++s)
+    const bool oneSampleDirect = batch == 1 && fp.samplesThisLaunch == 1 && plan.finalize && fp.finalFirst == 0 && fp.finalCount == 1;
+    for (uint32_t s = 0; plan.trace && s < fp.samplesThisLaunch; ++s)
     {
         // (a cutout in use: the words of its continuation rounds lie behind the fetch cursors this sample uses -- one memset for all of them)
-        SKH_TRY(c, hipMemsetAsync(counts, 0, sizeof(uint32_t) * (QW * 2 * SKH_MAX_LAUNCH_ROUNDS + 16 * SKH_FETCH_STRIDE * (rounds + 1) + (size_t)(cutOn ? rounds : 0u) * cutBounceWords), st));
-        blp.sampleBase = fp.subframeIndex + s;
+        SKH_TRY(c, hipMemsetAsync(counts, 0, sizeof(uint32_t) * (QW * 2 * SKH_MAX_LAUNCH_ROUNDS + 16 * SKH_FETCH_STRIDE * (rounds + 1) + (size_t)(cutOn ? rounds : 0u) * rp.cutBounceWords), st));
+        rp.blp.sampleBase = fp.subframeIndex + s;
         {
             SpanGuard g(c, KC_RAYGEN);
-            k_raygen<<<c->raygenBlocksPerSub * fp.batch, 512, 0, st>>>(fp, tiles, s, rq[0], counts, ps, raygenBase, c->raygenBlocksPerSub, raygenValid);
+            k_raygen<<<c->raygenBlocksPerSub * fp.batch, 512, 0, st>>>(fp, rp.tiles, s, rp.rq[0], counts, rp.ps, raygenBase, c->raygenBlocksPerSub, raygenValid);
         }
         for (uint32_t b = 0; b < rounds; ++b)
         {
-            {
-                SpanGuard g(c, KC_TRACE_CLOSEST);
-                c->gridOverride = (useOverlap && smallPass) ? ((b == 0 && c->smallWavesFirst) ? c->smallWavesFirst : c->smallWavesClosest ? c->smallWavesClosest : (c->nSegs ? 16u : 20u)) * (uint32_t)c->numCUs : 0u;
-                if (c->countTraversal)
-                    launch_trace<false, true>(c, sc, rq[b & 1], counts + 2 * b * QW, fetch + 16 * b * SKH_FETCH_STRIDE, hq, ps, nullptr);
-                else
-                    launch_trace<false, false>(c, sc, rq[b & 1], counts + 2 * b * QW, fetch + 16 * b * SKH_FETCH_STRIDE, hq, ps, nullptr);
-                if (cutOn)
-                {
-                    blp.depth = b;
-                    if (c->countTraversal)
-                        run_cutout_chain<false, true>(c, sc, sc, rq[b & 1], counts + 2 * b * QW, hq, hq, nullptr, ps, nullptr, cutQ[0], cutQ[1], cutH, cutWords + (size_t)b * cutBounceWords, NP, st, blp);
-                    else
-                        run_cutout_chain<false, false>(c, sc, sc, rq[b & 1], counts + 2 * b * QW, hq, hq, nullptr, ps, nullptr, cutQ[0], cutQ[1], cutH, cutWords + (size_t)b * cutBounceWords, NP, st, blp);
-                }
-            }
-            if (useOverlap && b > 0)
-                (void)hipStreamWaitEvent(st, c->evShadow, 0); // shade[b] reads the radiance shadow[b-1] adds to and reuses its queue
-            {
-                SpanGuard g(c, KC_SHADE);
-                // a shard holds at most an eighth of the pass's paths (rounded up to whole waves): SKH_SHARDS x that many workgroups,
-                // workgroup b on shard b & 7; those past the end of their shard leave at once
-                const uint32_t perShard = (((NP + SKH_SHARDS - 1u) / SKH_SHARDS) + 63u) & ~63u;
-                const dim3 sg(SKH_SHARDS * ((perShard + SKH_SHADE_BLOCK - 1) / SKH_SHADE_BLOCK));
-                // (every HAIR x ENV x EMIT x MTEX build has a twin with light shapes in it, launched only when a shape is in use)
-#define SKH_SHADE_LAUNCH_MTEX(HAIRB, ENVB, EMITB, MTEXB)                                                                                                                             \
-    if (lshp.table)                                                                                                                                                                  \
-        k_shade_lshape<HAIRB, ENVB, EMITB, MTEXB><<<sg, SKH_SHADE_BLOCK, 0, st>>>(sc, fp, s, b, tiles, rq[b & 1], counts + 2 * b * QW, hq, ps, rq[(b + 1) & 1],                       \
-                                                                                  counts + 2 * (b + 1) * QW, shq, c->dContrib.as<float4>(), counts + (2 * b + 1) * QW, envp, emitp,  \
-                                                                                  mtexp, lshp);                                                                                      \
-    else                                                                                                                                                                             \
-        k_shade<HAIRB, ENVB, EMITB, MTEXB><<<sg, SKH_SHADE_BLOCK, 0, st>>>(sc, fp, s, b, tiles, rq[b & 1], counts + 2 * b * QW, hq, ps, rq[(b + 1) & 1], counts + 2 * (b + 1) * QW, \
-                                                                           shq, c->dContrib.as<float4>(), counts + (2 * b + 1) * QW, envp, emitp, mtexp)
-#define SKH_SHADE_LAUNCH(HAIRB, ENVB, EMITB)              \
-    if (mtexp.count)                                      \
-    {                                                     \
-        SKH_SHADE_LAUNCH_MTEX(HAIRB, ENVB, EMITB, true);  \
-    }                                                     \
-    else                                                  \
-    {                                                     \
-        SKH_SHADE_LAUNCH_MTEX(HAIRB, ENVB, EMITB, false); \
-    }
-#define SKH_SHADE_LAUNCH_EMIT(HAIRB, ENVB)     \
-    if (emitp.count)                           \
-    {                                          \
-        SKH_SHADE_LAUNCH(HAIRB, ENVB, true);   \
-    }                                          \
-    else                                       \
-    {                                          \
-        SKH_SHADE_LAUNCH(HAIRB, ENVB, false);  \
-    }
-                // (a context without an environment, without emitters and without material textures launches the builds it always launched)
-                if (c->hasHairMaterial && c->envW)
-                {
-                    SKH_SHADE_LAUNCH_EMIT(true, true);
-                }
-                else if (c->hasHairMaterial)
-                {
-                    SKH_SHADE_LAUNCH_EMIT(true, false);
-                }
-                else if (c->envW)
-                {
-                    SKH_SHADE_LAUNCH_EMIT(false, true);
-                }
-                else
-                {
-                    SKH_SHADE_LAUNCH_EMIT(false, false);
-                }
-#undef SKH_SHADE_LAUNCH_EMIT
-#undef SKH_SHADE_LAUNCH
-#undef SKH_SHADE_LAUNCH_MTEX
-            }
-            {
-                hipStream_t sst = useOverlap ? c->stream2 : st;
-                if (useOverlap)
-                {
-                    (void)hipEventRecord(c->evShade, st);
-                    (void)hipStreamWaitEvent(sst, c->evShade, 0);
-                }
-                {
-                    SpanGuard g(c, KC_TRACE_SHADOW, sst);
-                    c->gridOverride = (useOverlap && smallPass) ? ((b + 1 == rounds && (c->smallWavesLast || (!c->smallWavesShadow && !c->nSegs))) ? (c->smallWavesLast ? c->smallWavesLast : 20u) : c->smallWavesShadow ? c->smallWavesShadow : (c->nSegs ? 16u : 12u)) * (uint32_t)c->numCUs : 0u;
-                    if (cutOn)
-                    {
-                        // the shadow rays' NEAREST hits, tested and continued like the radiance rays'; a ray that ends in a miss adds its contribution (k_cutout)
-                        uint32_t* w = cutWords + (size_t)b * cutBounceWords + c->cutoutRounds * SKH_CUT_WORDS;
-                        if (c->countTraversal)
-                        {
-                            launch_trace<false, true>(c, scShadow, shq, counts + (2 * b + 1) * QW, fetch + (16 * b + 8) * SKH_FETCH_STRIDE, cutSH0, ps, nullptr, sst);
-                            run_cutout_chain<true, true>(c, sc, scShadow, shq, counts + (2 * b + 1) * QW, cutSH0, cutSH0, nullptr, ps, c->dContrib.as<float4>(), cutSQ[0], cutSQ[1], cutSH1, w, NP, sst, blp);
-                        }
-                        else
-                        {
-                            launch_trace<false, false>(c, scShadow, shq, counts + (2 * b + 1) * QW, fetch + (16 * b + 8) * SKH_FETCH_STRIDE, cutSH0, ps, nullptr, sst);
-                            run_cutout_chain<true, false>(c, sc, scShadow, shq, counts + (2 * b + 1) * QW, cutSH0, cutSH0, nullptr, ps, c->dContrib.as<float4>(), cutSQ[0], cutSQ[1], cutSH1, w, NP, sst, blp);
-                        }
-                    }
-                    else if (c->countTraversal)
-                        launch_trace<true, true>(c, sc, shq, counts + (2 * b + 1) * QW, fetch + (16 * b + 8) * SKH_FETCH_STRIDE, nohq, ps, c->dContrib.as<float4>(), sst);
-                    else
-                        launch_trace<true, false>(c, sc, shq, counts + (2 * b + 1) * QW, fetch + (16 * b + 8) * SKH_FETCH_STRIDE, nohq, ps, c->dContrib.as<float4>(), sst);
-                }
-                c->gridOverride = 0;
-                if (useOverlap)
-                    (void)hipEventRecord(c->evShadow, sst);
-            }
+            render_bounce(c, rp, s, b);
             if (fp.debug == 1)
                 break;
         }
-        if (useOverlap)
+        if (rp.useOverlap)
             (void)hipStreamWaitEvent(st, c->evShadow, 0);
         {
             SpanGuard g(c, KC_ACCUM);
             k_add_stats<<<1, 64, 0, st>>>(counts, rounds, c->dStats.as<StatsDev>());
             if (batch == 1 && !oneSampleDirect)
-                k_collect<<<gridSlots, 256, 0, st>>>(fp, tiles, s, ps, c->dSums.as<float>());
+                k_collect<<<(c->numSlots + 255) / 256, 256, 0, st>>>(fp, rp.tiles, s, rp.ps, c->dSums.as<float>());
         }
     }
-    c->splitNow = false;
-    hipStream_t fs = finStream ? finStream : st;
-    if (finalize && (batch > 1 || oneSampleDirect))
-    {
-        SpanGuard g(c, KC_ACCUM, fs);
-        k_finalize_batch<<<gridSlots, 256, 0, fs>>>(fp, tiles, ps, c->dAccum.as<float4>(), c->dDiffuse.as<float4>(), c->dSpecular.as<float4>(),
-                                                    c->dDiffCnt.as<uint16_t>(), c->dSpecCnt.as<uint16_t>(), reinterpret_cast<float4*>(d_image));
-    }
-    else if (finalize)
-    {
-        SpanGuard g(c, KC_ACCUM, fs);
-        k_finalize<<<gridSlots, 256, 0, fs>>>(fp, tiles, c->dSums.as<float>(), c->dAccum.as<float4>(), c->dDiffuse.as<float4>(),
-                                              c->dSpecular.as<float4>(), c->dDiffCnt.as<uint16_t>(), c->dSpecCnt.as<uint16_t>(),
-                                              reinterpret_cast<float4*>(d_image));
-    }
-    if (finalize && adaptive)
-    {
-        SpanGuard g(c, KC_ACCUM, fs);
-        k_adapt_moments<<<gridSlots, 256, 0, fs>>>(fp, tiles, ps, c->dSums.as<float>(), (batch > 1 || oneSampleDirect) ? 0u : 1u, c->dAdaptState.as<float4>());
-    }
+    render_accumulate(c, rp, plan, oneSampleDirect, d_image);
     hipError_t e = hipGetLastError();
     if (e != hipSuccess)
     {
@@ -2083,9 +2136,9 @@ skh_status skh_render_subframes(skh_context* c, const skh_frame_params* params, 
         uint32_t b = std::min(cap, n_subframes - k);
         if (adaptive)
             b = std::min(b, adapt_to_next_check(c)); // (a batch never straddles a check)
-        c->adapt.now = adaptive;
-        s = render_one(c, &p, b, d_image);
-        c->adapt.now = false;
+        RenderPlan plan;
+        plan.batch = b, plan.adaptive = adaptive;
+        s = render_one(c, &p, plan, d_image);
         if (s != SKH_OK || (adaptive && (s = adapt_after_pass(c, p, b)) != SKH_OK))
             return s;
         p.subframe_index += p.samples_this_launch * b;
@@ -2133,7 +2186,9 @@ static skh_status spec_launch_next(skh_context* c)
     sp.nextParams = sp.params;
     sp.nextParams.subframe_index = nextStart;
     sp.nextCount = n;
-    skh_status s = render_one(c, &sp.nextParams, n, nullptr, true, 0, 0, other, false);
+    RenderPlan plan; // trace only, into the other path-state buffer
+    plan.batch = n, plan.finalCount = 0, plan.pathSel = other, plan.finalize = false;
+    skh_status s = render_one(c, &sp.nextParams, plan, nullptr);
     if (s != SKH_OK)
         return s;
     sp.nextInFlight = true;
@@ -2176,7 +2231,9 @@ skh_status skh_render_subframe(skh_context* c, const skh_frame_params* params, v
         // this sub-frame was traced ahead: its radiances wait in the path state, only its accumulation step is left (beside a pass in
         // flight it runs on its own stream)
         hipStream_t fin = sp.nextInFlight ? c->stream3 : c->stream;
-        if ((s = render_one(c, &sp.params, sp.count, d_image, false, sp.consumed, 1, sp.buf, true, fin)) != SKH_OK)
+        RenderPlan plan; // the accumulation step of sub-frame sp.consumed of the pass
+        plan.batch = sp.count, plan.trace = false, plan.finalFirst = sp.consumed, plan.finalCount = 1, plan.pathSel = sp.buf, plan.finStream = fin;
+        if ((s = render_one(c, &sp.params, plan, d_image)) != SKH_OK)
             return s;
         sp.consumed++;
         sp.last = *params;
@@ -2208,7 +2265,9 @@ skh_status skh_render_subframe(skh_context* c, const skh_frame_params* params, v
     }
     unsigned long long before[2] = { 0, 0 }, after[2] = { 0, 0 }; // (StatsDev starts with raysRadiance, raysShadow; the stream is idle here)
     SKH_TRY(c, hipMemcpy(before, c->dStats.p, sizeof(before), hipMemcpyDeviceToHost));
-    if ((s = render_one(c, params, ahead, d_image, true, 0, 1)) != SKH_OK)
+    RenderPlan plan; // `ahead` sub-frames traced, the first one delivered
+    plan.batch = ahead, plan.finalCount = 1;
+    if ((s = render_one(c, params, plan, d_image)) != SKH_OK)
         return s;
     SKH_TRY(c, hipStreamSynchronize(c->stream));
     SKH_TRY(c, hipMemcpy(after, c->dStats.p, sizeof(after), hipMemcpyDeviceToHost));
@@ -2656,153 +2715,7 @@ __global__ void k_hits_soa_to_aos(HitQ hq, uint32_t n, uint32_t per, uint32_t re
     hits[k] = h;
 }
 
-// ---- memory ceilings of this GPU, measured with the access shapes of the hot path (include/strelka_hip.h: skh_probe_memory) ----
-__global__ __launch_bounds__(256) void k_probe_fill(uint4* __restrict__ buf, size_t n)
-{
-    for (size_t i = blockIdx.x * (size_t)blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x)
-    {
-        const uint32_t h = hash_murmur((uint32_t)i * 0x9e3779b9u + (uint32_t)(i >> 32));
-        buf[i] = make_uint4(h, h * 0x85ebca6bu, h ^ 0xc2b2ae35u, h * 0x27d4eb2fu + 1u);
-    }
-}
-
-__global__ __launch_bounds__(256) void k_probe_copy(const uint4* __restrict__ src, uint4* __restrict__ dst, size_t n)
-{
-    for (size_t i = blockIdx.x * (size_t)blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x)
-        dst[i] = src[i];
-}
-
-// one-wave workgroups like k_trace; every lane fetches `perLane` records of R uint4 (R = 4: 64 bytes = one BVH node) at pseudo-random,
-// record-aligned places of the buffer.  DEPENDENT: the next place comes out of the record just loaded (a traversal step); otherwise
-// four fetches are in flight.
-template <bool DEPENDENT, int R>
-__global__ __launch_bounds__(SKH_TRACE_BLOCK) void k_probe_gather(const uint4* __restrict__ buf, uint32_t nRec, uint32_t perLane, uint32_t* __restrict__ sink)
-{
-    uint32_t s = hash_murmur(blockIdx.x * SKH_TRACE_BLOCK + threadIdx.x + 1u);
-    uint32_t acc = 0u;
-    if (DEPENDENT)
-    {
-        for (uint32_t i = 0; i < perLane; ++i)
-        {
-            const uint4* p = buf + R * (size_t)__umulhi(s, nRec);
-            uint32_t x = 0u;
-#pragma unroll
-            for (int j = 0; j < R; ++j)
-            {
-                const uint4 a = p[j];
-                x ^= a.x ^ a.y ^ a.z ^ a.w;
-            }
-            acc += x;
-            s = s * 1664525u + 1013904223u + x;
-        }
-    }
-    else
-    {
-        for (uint32_t i = 0; i < perLane; i += 4)
-        {
-            uint4 v[4][R];
-#pragma unroll
-            for (int k = 0; k < 4; ++k)
-            {
-                const uint4* p = buf + R * (size_t)__umulhi(s, nRec);
-                s = s * 1664525u + 1013904223u;
-#pragma unroll
-                for (int j = 0; j < R; ++j)
-                    v[k][j] = p[j];
-            }
-#pragma unroll
-            for (int k = 0; k < 4; ++k)
-#pragma unroll
-                for (int j = 0; j < R; ++j)
-                    acc += v[k][j].x ^ v[k][j].y ^ v[k][j].z ^ v[k][j].w;
-        }
-    }
-    if (acc == 0x12345u) // (keeps the loads alive; practically never true)
-        sink[0] = s;
-}
-
-skh_status skh_probe_memory(skh_context* c, uint32_t kind, uint64_t bytes, uint32_t record_bytes, uint32_t repeat, double* out_gbps, double* out_ms)
-{
-    if (!c || kind > SKH_PROBE_CHASE || bytes < (1u << 20) || !out_gbps ||
-        (kind != SKH_PROBE_COPY && record_bytes != 32 && record_bytes != 64 && record_bytes != 128))
-        return SKH_INVALID_ARGUMENT;
-    (void)hipSetDevice(c->device);
-    DevBuf a, b;
-    const size_t n16 = (size_t)(bytes / 64) * 4; // uint4 elements, whole 64-byte records
-    SKH_CHECK(dev_alloc(c, a, n16 * 16));
-    if (kind == SKH_PROBE_COPY)
-        SKH_CHECK(dev_alloc(c, b, n16 * 16));
-    struct Events // (destroyed on every exit)
-    {
-        hipEvent_t e0 = nullptr, e1 = nullptr;
-        ~Events()
-        {
-            if (e0)
-                (void)hipEventDestroy(e0);
-            if (e1)
-                (void)hipEventDestroy(e1);
-        }
-    } ev;
-    hipEvent_t &e0 = ev.e0, &e1 = ev.e1;
-    const uint32_t grid = (uint32_t)c->numCUs * c->wavesPerCU; // the trace kernels' grid
-    const uint32_t perLane = 256;
-    repeat = std::max(1u, repeat);
-    k_probe_fill<<<c->numCUs * 8, 256, 0, c->stream>>>(a.as<uint4>(), n16);
-    double moved = 0.0;
-    for (uint32_t r = 0; r <= repeat; ++r) // (pass 0 is the warm-up)
-    {
-        if (r == 1)
-        {
-            if (hipEventCreate(&e0) != hipSuccess || hipEventCreate(&e1) != hipSuccess || hipEventRecord(e0, c->stream) != hipSuccess)
-            {
-                c->err = "skh_probe_memory: hipEvent";
-                return SKH_FAIL;
-            }
-        }
-        if (kind == SKH_PROBE_COPY)
-        {
-            k_probe_copy<<<c->numCUs * 16, 256, 0, c->stream>>>(a.as<uint4>(), b.as<uint4>(), n16);
-            moved = 2.0 * 16.0 * (double)n16;
-        }
-        else
-        {
-            const uint32_t nRec = (uint32_t)(n16 * 16 / record_bytes);
-            uint32_t* sink = a.as<uint32_t>();
-#define SKH_PROBE_LAUNCH(DEP, R) k_probe_gather<DEP, R><<<grid, SKH_TRACE_BLOCK, 0, c->stream>>>(a.as<uint4>(), nRec, perLane, sink)
-            if (kind == SKH_PROBE_CHASE)
-            {
-                if (record_bytes == 32)
-                    SKH_PROBE_LAUNCH(true, 2);
-                else if (record_bytes == 64)
-                    SKH_PROBE_LAUNCH(true, 4);
-                else
-                    SKH_PROBE_LAUNCH(true, 8);
-            }
-            else
-            {
-                if (record_bytes == 32)
-                    SKH_PROBE_LAUNCH(false, 2);
-                else if (record_bytes == 64)
-                    SKH_PROBE_LAUNCH(false, 4);
-                else
-                    SKH_PROBE_LAUNCH(false, 8);
-            }
-#undef SKH_PROBE_LAUNCH
-            moved = (double)record_bytes * perLane * SKH_TRACE_BLOCK * (double)grid;
-        }
-    }
-    float ms = 0.0f;
-    if (hipEventRecord(e1, c->stream) != hipSuccess || hipEventSynchronize(e1) != hipSuccess || hipEventElapsedTime(&ms, e0, e1) != hipSuccess)
-    {
-        c->err = "skh_probe_memory: timing failed";
-        return SKH_FAIL;
-    }
-    ms /= (float)repeat;
-    *out_gbps = moved / (ms * 1e-3) / 1e9;
-    if (out_ms)
-        *out_ms = ms;
-    return SKH_OK;
-}
+#include "skh_probes.inc"
 
 // skh_trace_device's path: `cls` is the kernel class its spans are counted under (skh_render_aovs traces through here under a class of its own)
 static skh_status trace_device_as(skh_context* c, const void* d_rays, uint32_t n_rays, uint32_t mode, void* d_hits, uint32_t repeat, KernelClass cls)
@@ -2853,51 +2766,13 @@ static skh_status trace_device_as(skh_context* c, const void* d_rays, uint32_t n
     {
         (void)hipMemsetAsync(dfetch, 0, sizeof(uint32_t) * (8 * SKH_FETCH_STRIDE + cutWordCount), c->stream);
         SpanGuard g(c, cls);
-        if (cutOn)
-        {
-            const RayQ q0{ cq0.as<float>(), (uint32_t)NQ, per }, q1{ cq1.as<float>(), (uint32_t)NQ, per };
-            const HitQ hq2{ h2.as<float>(), (uint32_t)NQ }, hq0{ h0.as<float>(), (uint32_t)NQ };
-            uint32_t* words = dfetch + 8 * SKH_FETCH_STRIDE;
-            DevScene scShadow = sc; // (shadow rays do not see lights: their closest-hit launches leave the baked light proxies' tree out)
-            if (c->worldRoot != SKH_REF_INVALID || c->tlasRoot != SKH_REF_INVALID)
-                scShadow.lightRoot = SKH_REF_INVALID;
-            BlendP blp = make_blend(c);
-            blp.raw = 1u; // (no sample: a blend hit counts iff a > 0)
-            if (mode == SKH_TRACE_SHADOW && c->countTraversal)
-            {
-                launch_trace<false, true>(c, scShadow, rq, dcount, dfetch, hq0, ps, nullptr);
-                run_cutout_chain<true, true>(c, sc, scShadow, rq, dcount, hq0, hq0, hq.base, ps, nullptr, q0, q1, hq2, words, n_rays, c->stream, blp);
-            }
-            else if (mode == SKH_TRACE_SHADOW)
-            {
-                launch_trace<false, false>(c, scShadow, rq, dcount, dfetch, hq0, ps, nullptr);
-                run_cutout_chain<true, false>(c, sc, scShadow, rq, dcount, hq0, hq0, hq.base, ps, nullptr, q0, q1, hq2, words, n_rays, c->stream, blp);
-            }
-            else if (c->countTraversal)
-            {
-                launch_trace<false, true>(c, sc, rq, dcount, dfetch, hq, ps, nullptr);
-                run_cutout_chain<false, true>(c, sc, sc, rq, dcount, hq, hq, nullptr, ps, nullptr, q0, q1, hq2, words, n_rays, c->stream, blp);
-            }
-            else
-            {
-                launch_trace<false, false>(c, sc, rq, dcount, dfetch, hq, ps, nullptr);
-                run_cutout_chain<false, false>(c, sc, sc, rq, dcount, hq, hq, nullptr, ps, nullptr, q0, q1, hq2, words, n_rays, c->stream, blp);
-            }
-        }
-        else if (mode == SKH_TRACE_SHADOW)
-        {
-            if (c->countTraversal)
-                launch_trace<true, true>(c, sc, rq, dcount, dfetch, hq, ps, nullptr);
-            else
-                launch_trace<true, false>(c, sc, rq, dcount, dfetch, hq, ps, nullptr);
-        }
-        else
-        {
-            if (c->countTraversal)
-                launch_trace<false, true>(c, sc, rq, dcount, dfetch, hq, ps, nullptr);
-            else
-                launch_trace<false, false>(c, sc, rq, dcount, dfetch, hq, ps, nullptr);
-        }
+        const bool shadow = mode == SKH_TRACE_SHADOW;
+        const TraceLaunch t{ rq, dcount, dfetch, hq, ps, nullptr, c->stream, shadow, 0u, false };
+        // (a cutout in use) no sample: a blend hit counts iff a > 0; a shadow query's result is one float per ray
+        CutRounds cr{ { RayQ{ cq0.as<float>(), (uint32_t)NQ, per }, RayQ{ cq1.as<float>(), (uint32_t)NQ, per } }, HitQ{ h0.as<float>(), (uint32_t)NQ }, HitQ{ h2.as<float>(), (uint32_t)NQ },
+                      shadow ? hq.base : nullptr, dfetch + 8 * SKH_FETCH_STRIDE, n_rays, make_blend(c) };
+        cr.bl.raw = 1u;
+        trace_step(c, sc, t, shadow, cutOn ? &cr : nullptr);
     }
     k_hits_soa_to_aos<<<(n_rays + 255) / 256, 256, 0, c->stream>>>(hq, n_rays, per, per, mode, reinterpret_cast<skh_hit*>(d_hits), c->dShadeInst.as<skh_instance>());
     hipError_t e = hipStreamSynchronize(c->stream);
@@ -3139,199 +3014,6 @@ skh_status skh_get_denoise_info(skh_context* c, skh_denoise_info* out)
         return SKH_INVALID_ARGUMENT;
     *out = c->dnInfo;
     out->scratch_bytes = denoise_scratch_bytes(c);
-    return SKH_OK;
-}
-
-// ---- BSDF probes (tests) ----
-static_assert(sizeof(skh_bsdf_query) == 84 && sizeof(skh_bsdf_result) == 64, "ABI layout");
-__global__ void k_bsdf_probe(const skh_bsdf_query* __restrict__ q, uint32_t n, const Material* __restrict__ mats, uint32_t numMaterials,
-                             skh_bsdf_result* __restrict__ out)
-{
-    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= n)
-        return;
-    const skh_bsdf_query in = q[i];
-    const Material m = mats[in.material < numMaterials ? in.material : 0u];
-    const v3 N = mk3(in.normal[0], in.normal[1], in.normal[2]), Ng = mk3(in.geom_normal[0], in.geom_normal[1], in.geom_normal[2]);
-    const v3 T = mk3(in.tangent_u[0], in.tangent_u[1], in.tangent_u[2]);
-    const v3 k1 = mk3(in.k1[0], in.k1[1], in.k1[2]), k2 = mk3(in.k2[0], in.k2[1], in.k2[2]);
-    const HairConst hc = hair_const(m); // (what k_hair_consts tabulates per material for k_shade)
-    BsdfSample bs;
-    bsdf_sample<true>(m, N, Ng, T, k1, in.xi[0], in.xi[1], in.xi[2], in.xi[3], in.inside != 0u, bs, &hc);
-    BsdfEval ev;
-    bsdf_evaluate<true>(m, N, Ng, T, k1, k2, in.inside != 0u, ev, &hc);
-    skh_bsdf_result r;
-    r.k2[0] = bs.k2.x, r.k2[1] = bs.k2.y, r.k2[2] = bs.k2.z;
-    r.bsdf_over_pdf[0] = bs.bsdf_over_pdf.x, r.bsdf_over_pdf[1] = bs.bsdf_over_pdf.y, r.bsdf_over_pdf[2] = bs.bsdf_over_pdf.z;
-    r.pdf = bs.pdf;
-    r.event_type = bs.event_type;
-    r.bsdf_diffuse[0] = ev.bsdf_diffuse.x, r.bsdf_diffuse[1] = ev.bsdf_diffuse.y, r.bsdf_diffuse[2] = ev.bsdf_diffuse.z;
-    r.bsdf_glossy[0] = ev.bsdf_glossy.x, r.bsdf_glossy[1] = ev.bsdf_glossy.y, r.bsdf_glossy[2] = ev.bsdf_glossy.z;
-    r.eval_pdf = ev.pdf;
-    r.reserved0 = 0u;
-    out[i] = r;
-}
-
-skh_status skh_bsdf_probe(skh_context* c, const skh_bsdf_query* queries, uint32_t n, skh_bsdf_result* results)
-{
-    if (!c || (n && (!queries || !results)))
-        return SKH_INVALID_ARGUMENT;
-    (void)hipSetDevice(c->device);
-    if (n == 0)
-        return SKH_OK;
-    if (c->nMaterials == 0)
-    {
-        c->err = "skh_bsdf_probe: call skh_set_materials first";
-        return SKH_INVALID_ARGUMENT;
-    }
-    DevBuf dq, dr;
-    SKH_CHECK(dev_upload(c, dq, queries, sizeof(skh_bsdf_query) * (size_t)n));
-    SKH_CHECK(dev_alloc(c, dr, sizeof(skh_bsdf_result) * (size_t)n));
-    k_bsdf_probe<<<(n + 127) / 128, 128, 0, c->stream>>>(dq.as<skh_bsdf_query>(), n, c->dMaterials.as<Material>(), c->nMaterials, dr.as<skh_bsdf_result>());
-    hipError_t e = hipStreamSynchronize(c->stream);
-    if (e == hipSuccess)
-        e = hipMemcpy(results, dr.p, sizeof(skh_bsdf_result) * (size_t)n, hipMemcpyDeviceToHost);
-    if (e != hipSuccess)
-    {
-        c->err = std::string("skh_bsdf_probe: ") + hipGetErrorString(e);
-        return SKH_FAIL;
-    }
-    return SKH_OK;
-}
-
-// ---- unit probes (tests): the device functions of the sampler, the light samplers and the accumulator, one call per record, so that
-// GPU tests can hold the HIP code against the reference-generated fixtures of tests/golden/ directly ----
-static const uint32_t kUnitIn[SKH_UNIT_COUNT] = { 20, 8, 20, 24, 12, 8, 12, 12, 8, 8, 12 }, kUnitOut[SKH_UNIT_COUNT] = { 12, 4, 48, 4, 16, 4, 12, 24, 40, 36, 24 };
-static const uint32_t kUnitConst[SKH_UNIT_COUNT] = { 0, 0, 112, 112, 112, 0, 12, 12, 0, 0, 0 };
-__global__ void __launch_bounds__(256) k_unit_probe(uint32_t unit, uint32_t param, const float* __restrict__ consts, const uint32_t* __restrict__ in, uint32_t n,
-                                                    uint32_t* __restrict__ out)
-{
-    __shared__ uint32_t s_lut[SKH_SOBOL_LUT_WORDS]; // the byte-folded Sobol table as k_shade stages it
-    for (uint32_t k = threadIdx.x; k < SKH_SOBOL_LUT_WORDS; k += blockDim.x)
-        s_lut[k] = g_sobol_lut[k];
-    __syncthreads();
-    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= n)
-        return;
-    const float* fin = reinterpret_cast<const float*>(in);
-    float* fout = reinterpret_cast<float*>(out);
-    Light l;
-    if (unit == SKH_UNIT_LIGHT_SAMPLE || unit == SKH_UNIT_LIGHT_PDF || unit == SKH_UNIT_LIGHT_NORMAL)
-        l = *reinterpret_cast<const Light*>(consts);
-    switch (unit)
-    {
-    case SKH_UNIT_SAMPLER: {
-        const uint32_t* r = in + 5 * (size_t)i;
-        Sampler s = init_sampler(r[0], r[1], r[2], param, 52u); // seed 52: OptixRender.cu:101
-        s.depth = r[3];
-        out[3 * (size_t)i] = __float_as_uint(sampler_random(s, r[4]));
-        out[3 * (size_t)i + 1] = __float_as_uint(sampler_random_lut(s, r[4], s_lut));
-        out[3 * (size_t)i + 2] = s.sampleIdx;
-        break;
-    }
-    case SKH_UNIT_SOBOL:
-        out[i] = sobol_uint(in[2 * (size_t)i], in[2 * (size_t)i + 1]);
-        break;
-    case SKH_UNIT_LIGHT_SAMPLE: {
-        const float* r = fin + 5 * (size_t)i;
-        const v3 P = mk3(r[0], r[1], r[2]);
-        LightSample d;
-        if (param == 0)
-            d = sample_rect_light_uniform(l, r[3], r[4], P);
-        else if (param == 1)
-            d = sample_rect_light(l, r[3], r[4], P);
-        else if (param == 2)
-            d = sample_sphere_light(l, r[3], r[4], P);
-        else
-            d = sample_distant_light(l, r[3], r[4]);
-        float* o = fout + 12 * (size_t)i;
-        o[0] = d.pointOnLight.x, o[1] = d.pointOnLight.y, o[2] = d.pointOnLight.z, o[3] = d.pdf;
-        o[4] = d.normal.x, o[5] = d.normal.y, o[6] = d.normal.z, o[7] = d.area;
-        o[8] = d.L.x, o[9] = d.L.y, o[10] = d.L.z, o[11] = d.distToLight;
-        break;
-    }
-    case SKH_UNIT_LIGHT_PDF: {
-        const float* r = fin + 6 * (size_t)i;
-        fout[i] = get_light_pdf(l, mk3(r[0], r[1], r[2]), mk3(r[3], r[4], r[5]));
-        break;
-    }
-    case SKH_UNIT_LIGHT_NORMAL: {
-        const float* r = fin + 3 * (size_t)i;
-        const v3 nn = calc_light_normal(l, mk3(r[0], r[1], r[2]));
-        fout[4 * (size_t)i] = nn.x, fout[4 * (size_t)i + 1] = nn.y, fout[4 * (size_t)i + 2] = nn.z, fout[4 * (size_t)i + 3] = calc_light_area(l);
-        break;
-    }
-    case SKH_UNIT_MIS:
-        fout[i] = mis_weight_balance(fin[2 * (size_t)i], fin[2 * (size_t)i + 1]);
-        break;
-    case SKH_UNIT_ACCUMULATE: {
-        // a SEQUENCE: record k is folded into the running value of records 0..k-1 (sub-frame index param + k): one thread
-        if (i != 0)
-            return;
-        const v3 e = mk3(consts[0], consts[1], consts[2]);
-        v3 prev = mk3(0.0f);
-        for (uint32_t k = 0; k < n; ++k)
-        {
-            prev = accumulate(prev, mk3(fin[3 * (size_t)k], fin[3 * (size_t)k + 1], fin[3 * (size_t)k + 2]), e, param + k);
-            fout[3 * (size_t)k] = prev.x, fout[3 * (size_t)k + 1] = prev.y, fout[3 * (size_t)k + 2] = prev.z;
-        }
-        break;
-    }
-    case SKH_UNIT_TONEMAP: {
-        const v3 e = mk3(consts[0], consts[1], consts[2]);
-        const v3 c = mk3(fin[3 * (size_t)i], fin[3 * (size_t)i + 1], fin[3 * (size_t)i + 2]);
-        const v3 t = tonemap(c, e), iv = inverse_tonemap(c, e);
-        float* o = fout + 6 * (size_t)i;
-        o[0] = t.x, o[1] = t.y, o[2] = t.z, o[3] = iv.x, o[4] = iv.y, o[5] = iv.z;
-        break;
-    }
-    case SKH_UNIT_LIBM: {
-        // skh_libm.h on the device: the bits the CPU checker's copy of the same text must reproduce
-        const float x = fin[2 * (size_t)i], y = fin[2 * (size_t)i + 1];
-        float* o = fout + 10 * (size_t)i;
-        o[0] = skm::sinf_(x), o[1] = skm::cosf_(x), o[2] = skm::acosf_(x), o[3] = skm::asinf_(x), o[4] = skm::atan2f_(y, x);
-        o[5] = skm::expf_(x), o[6] = skm::logf_(x), o[7] = skm::sinhf_(x), o[8] = skm::powf_(x, y), o[9] = skm::atan2f_(x, y);
-        break;
-    }
-    default:
-        break;
-    }
-}
-
-skh_status skh_unit_probe(skh_context* c, uint32_t unit, uint32_t param, const void* consts, const void* in, uint32_t n, void* out)
-{
-    if (!c || unit >= SKH_UNIT_COUNT || (n && (!in || !out)) || (kUnitConst[unit] && !consts))
-    {
-        if (c)
-            c->err = "skh_unit_probe: unknown unit, or a missing input / output / constants pointer";
-        return SKH_INVALID_ARGUMENT;
-    }
-    const bool envUnit = unit == SKH_UNIT_ENV_SAMPLE || unit == SKH_UNIT_ENV_EVAL;
-    if (envUnit && c->envW == 0)
-    {
-        c->err = "skh_unit_probe: the context has no environment";
-        return SKH_INVALID_ARGUMENT;
-    }
-    (void)hipSetDevice(c->device);
-    if (n == 0)
-        return SKH_OK;
-    DevBuf di, dc, dout; // (the Sobol tables were uploaded by skh_create)
-    SKH_CHECK(dev_upload(c, di, in, (size_t)kUnitIn[unit] * n));
-    SKH_CHECK(dev_alloc(c, dout, (size_t)kUnitOut[unit] * n));
-    if (kUnitConst[unit])
-        SKH_CHECK(dev_upload(c, dc, consts, kUnitConst[unit]));
-    if (envUnit)
-        k_env_probe<<<(n + 255) / 256, 256, 0, c->stream>>>(make_env(c), unit == SKH_UNIT_ENV_SAMPLE ? 1u : 0u, di.as<float>(), n, dout.as<uint32_t>());
-    else
-        k_unit_probe<<<(n + 255) / 256, 256, 0, c->stream>>>(unit, param, dc.as<float>(), di.as<uint32_t>(), n, dout.as<uint32_t>());
-    hipError_t e = hipStreamSynchronize(c->stream);
-    if (e == hipSuccess)
-        e = hipMemcpy(out, dout.p, (size_t)kUnitOut[unit] * n, hipMemcpyDeviceToHost);
-    if (e != hipSuccess)
-    {
-        c->err = std::string("skh_unit_probe: ") + hipGetErrorString(e);
-        return SKH_FAIL;
-    }
     return SKH_OK;
 }
 
