@@ -73,7 +73,7 @@ struct LbvhWork // the collapse's queues and orders (freed before the build's la
 // group bounds, Morton keys, radix sort over the Morton bits + the group bits: out.sortedVals = primitives in key order
 static skh_status lbvh_sort(skh_context* c, const LbvhArgs& a, LbvhOut& out, LbvhSorted& so)
 {
-    hipStream_t st = c->stream;
+    hipStream_t st = c->dev.stream;
     const uint32_t n = a.n, nGroups = a.nGroups;
     SKH_CHECK(dev_alloc(c, so.gbU, sizeof(uint32_t) * 6 * (size_t)nGroups));
     SKH_CHECK(dev_alloc(c, so.keysA, sizeof(uint64_t) * (size_t)n));
@@ -94,7 +94,7 @@ static skh_status lbvh_sort(skh_context* c, const LbvhArgs& a, LbvhOut& out, Lbv
     uint32_t gbits = 0;
     while ((1ull << gbits) < (unsigned long long)nGroups)
         ++gbits;
-    const uint32_t mb = std::min<uint32_t>(c->mortonBits, (64u - gbits) / 3u);
+    const uint32_t mb = std::min<uint32_t>(c->opt.mortonBits, (64u - gbits) / 3u);
     so.keyShift = 3u * mb;
     k_morton<<<G1, B, 0, st>>>(a.boxLo, a.boxHi, a.grp, out.groupBounds.as<float>(), n, mb, so.keysA.as<uint64_t>(), valsA);
     uint64_t* kin = so.keysA.as<uint64_t>();
@@ -125,7 +125,7 @@ static skh_status lbvh_sort(skh_context* c, const LbvhArgs& a, LbvhOut& out, Lbv
 // agglomerative clustering over the Morton order; its own buffers die here.  Returns the node ids it handed out.
 static skh_status lbvh_ploc(skh_context* c, const LbvhArgs& a, const LbvhOut& out, const LbvhSorted& so, LbvhBinary& bt, LbvhWork& wk, uint32_t& nInternal)
 {
-    hipStream_t st = c->stream;
+    hipStream_t st = c->dev.stream;
     const uint32_t n = a.n, B = 256, G1 = (n + B - 1) / B;
     DevBuf cLo[2], cHi[2], nn, pflags, ppos, scanSums;
     for (int k = 0; k < 2; ++k)
@@ -158,7 +158,7 @@ static skh_status lbvh_ploc(skh_context* c, const LbvhArgs& a, const LbvhOut& ou
             k_ploc_nn<SKH_PLOC_RADIUS_TLAS><<<gm, SKH_PLOC_BLOCK, 0, st>>>(cLo[cur].as<float4>(), cHi[cur].as<float4>(), m, nn.as<uint32_t>());
         else if (a.search == 2)
             k_ploc_nn<SKH_PLOC_RADIUS_SEGS><<<gm, SKH_PLOC_BLOCK, 0, st>>>(cLo[cur].as<float4>(), cHi[cur].as<float4>(), m, nn.as<uint32_t>());
-        else if (m <= c->plocTop)
+        else if (m <= c->opt.plocTop)
             // the top of the tree -- the levels every ray walks -- clustered with the wide search of the TLAS builder (few clusters left: cheap)
             k_ploc_nn<SKH_PLOC_RADIUS_TLAS><<<gm, SKH_PLOC_BLOCK, 0, st>>>(cLo[cur].as<float4>(), cHi[cur].as<float4>(), m, nn.as<uint32_t>());
         else
@@ -192,7 +192,7 @@ static skh_status lbvh_ploc(skh_context* c, const LbvhArgs& a, const LbvhOut& ou
 static skh_status lbvh_reinsert_refit(skh_context* c, uint32_t n, uint32_t round, LbvhBinary& bt, LbvhWork& wk, DevBuf& stamp, DevBuf& rflags, DevBuf& refitList,
                                       DevBuf& refitCount)
 {
-    hipStream_t st = c->stream;
+    hipStream_t st = c->dev.stream;
     const uint32_t B = 256;
     uint32_t* lv = refitCount.as<uint32_t>();
     SKH_TRY(c, hipMemsetAsync(lv, 0, sizeof(uint32_t) * SKH_RI_MAX_LEVELS, st));
@@ -217,14 +217,14 @@ static skh_status lbvh_reinsert_refit(skh_context* c, uint32_t n, uint32_t round
                 return SKH_OK;
         }
     }
-    c->err = "lbvh_build: the reinsertion pass's refit did not finish within n levels (a cycle in the tree?)";
+    c->dev.err = "lbvh_build: the reinsertion pass's refit did not finish within n levels (a cycle in the tree?)";
     return SKH_FAIL;
 }
 
 // parallel reinsertion over the binary tree (skh_bvh.h): rounds of search / claim / own / check / apply / refit; its twelve buffers die here
 static skh_status lbvh_reinsert(skh_context* c, const LbvhArgs& a, uint32_t nInternal, LbvhBinary& bt, LbvhWork& wk, LbvhOut& out)
 {
-    hipStream_t st = c->stream;
+    hipStream_t st = c->dev.stream;
     const uint32_t n = a.n, B = 256;
     DevBuf moves, lock, moving, win, rflags, cost, cand, stamp, refitList, refitCount, activeA, activeB;
     const size_t N2 = 2 * (size_t)n;
@@ -293,7 +293,7 @@ static skh_status lbvh_reinsert(skh_context* c, const LbvhArgs& a, uint32_t nInt
 // Karras radix tree over the sorted keys
 static skh_status lbvh_karras(skh_context* c, const LbvhArgs& a, const LbvhOut& out, const LbvhSorted& so, LbvhBinary& bt, LbvhWork& wk)
 {
-    hipStream_t st = c->stream;
+    hipStream_t st = c->dev.stream;
     const uint32_t n = a.n, B = 256, G1 = (n + B - 1) / B;
     SKH_CHECK(dev_alloc(c, bt.parent, sizeof(int) * 2 * (size_t)n));
     SKH_CHECK(dev_alloc(c, bt.rangeF, sizeof(int) * (size_t)n));
@@ -314,7 +314,7 @@ static skh_status lbvh_karras(skh_context* c, const LbvhArgs& a, const LbvhOut& 
 static skh_status lbvh_collapse(skh_context* c, const LbvhArgs& a, const std::vector<int>& preset /* leaf refs of groups with <= leafMax primitives, INVALID otherwise */,
                                 LbvhBinary& bt, LbvhWork& wk, LbvhOut& out)
 {
-    hipStream_t st = c->stream;
+    hipStream_t st = c->dev.stream;
     const uint32_t n = a.n, nGroups = a.nGroups, B = 256, G1 = (n + B - 1) / B;
     uint32_t* valsA = out.sortedVals.as<uint32_t>();
     SKH_TRY(c, hipMemcpyAsync(out.hostGroupRoot.data(), out.groupRoot.p, sizeof(int) * nGroups, hipMemcpyDeviceToHost, st));
@@ -344,7 +344,7 @@ static skh_status lbvh_collapse(skh_context* c, const LbvhArgs& a, const std::ve
     {
         k_collapse<<<(cnt + B - 1) / B, B, 0, st>>>(wk.q[cur].as<CollapseItem>(), cnt, bt.childL.as<int>(), bt.childR.as<int>(), wk.nodeSize.as<int>(),
                                                        bt.nodeLo.as<float4>(), bt.nodeHi.as<float4>(), (int)n, a.leafMax, out.nodes.p, wk.ctr.as<uint32_t>(),
-                                                       wk.q[cur ^ 1].as<CollapseItem>(), wk.ctr.as<uint32_t>() + 1, wk.leafOrder.as<uint32_t>(), a.search == 0 ? c->splitPairs * 0.1f : 0.0f);
+                                                       wk.q[cur ^ 1].as<CollapseItem>(), wk.ctr.as<uint32_t>() + 1, wk.leafOrder.as<uint32_t>(), a.search == 0 ? c->opt.splitPairs * 0.1f : 0.0f);
         SKH_TRY(c, hipMemcpyAsync(hctr, wk.ctr.p, sizeof(hctr), hipMemcpyDeviceToHost, st));
         SKH_TRY(c, hipStreamSynchronize(st));
         cnt = hctr[1];
@@ -366,7 +366,7 @@ static skh_status lbvh_collapse(skh_context* c, const LbvhArgs& a, const std::ve
 // leaves by 128-byte line (skh_bvh.h: k_leaf_place): padding slots in front of the leaves that would straddle; its buffers (and the unpadded order) die here
 static skh_status lbvh_leaf_lines(skh_context* c, const LbvhArgs& a, uint32_t lineRecBytes, LbvhOut& out)
 {
-    hipStream_t st = c->stream;
+    hipStream_t st = c->dev.stream;
     const uint32_t n = a.n, nGroups = a.nGroups, B = 256, G1 = (n + B - 1) / B;
     DevBuf leafCnt, chunk, remap, sums, vals3;
     const uint32_t nCh = (n + SKH_LEAF_CHUNK - 1u) / SKH_LEAF_CHUNK;
@@ -392,7 +392,7 @@ static skh_status lbvh_leaf_lines(skh_context* c, const LbvhArgs& a, uint32_t li
     const uint64_t total = (uint64_t)lastBase + lastLen;
     if (total >= (1ull << 28))
     {
-        c->err = "lbvh_build: more than 2^28 leaf slots";
+        c->dev.err = "lbvh_build: more than 2^28 leaf slots";
         return SKH_INVALID_ARGUMENT;
     }
     SKH_CHECK(dev_alloc(c, vals3, sizeof(uint32_t) * (size_t)std::max<uint64_t>(1, total)));
@@ -412,7 +412,7 @@ static skh_status lbvh_leaf_lines(skh_context* c, const LbvhArgs& a, uint32_t li
 // the binary tree (PLOC + reinsertion, or Karras), its collapse and the leaf layout: everything a group of two or more primitives needs
 static skh_status lbvh_tree(skh_context* c, const LbvhArgs& a, bool ploc, uint32_t lineRecBytes, const LbvhSorted& so, LbvhBinary& bt, LbvhOut& out)
 {
-    hipStream_t st = c->stream;
+    hipStream_t st = c->dev.stream;
     const uint32_t n = a.n, nGroups = a.nGroups;
     LbvhWork wk;
     SKH_CHECK(dev_alloc(c, bt.childL, sizeof(int) * (size_t)n));
@@ -451,7 +451,7 @@ static skh_status lbvh_build(skh_context* c, uint32_t n, uint32_t nGroups, const
                              int search = 0 /* PLOC search radius: 0 triangles, 1 TLAS, 2 curve sub-segments */, uint32_t lineRecBytes = 0 /* > 0: leaf records of this size, laid out by 128-byte line */,
                              uint32_t riRounds = 0 /* reinsertion rounds after PLOC */, uint32_t riMinSize = 1)
 {
-    hipStream_t st = c->stream;
+    hipStream_t st = c->dev.stream;
     out.numSlots = n;
     SKH_CHECK(dev_alloc(c, out.groupBounds, sizeof(float) * 6 * (size_t)std::max(1u, nGroups)));
     SKH_CHECK(dev_alloc(c, out.groupRoot, sizeof(int) * (size_t)std::max(1u, nGroups)));
@@ -699,42 +699,42 @@ static void set_light_box(skh_context* c, bool any, const float* b6)
     {
         const float ext = (b6[3 + k] + mAll * 0x1p-20f) - (b6[k] - mAll * 0x1p-20f);
         const float m = any ? mAll * 0x1p-20f + 1e-30f + 2.0f * (2.0f * ext / 255.0f) : 0.0f;
-        c->lightBox.lo[k] = any ? b6[k] - m : -INFINITY;
-        c->lightBox.hi[k] = any ? b6[3 + k] + m : INFINITY;
+        c->accel.lightBox.lo[k] = any ? b6[k] - m : -INFINITY;
+        c->accel.lightBox.hi[k] = any ? b6[3 + k] + m : INFINITY;
     }
 }
 
 // ---------------------------------------------------------------------------------------------------------------
 // Launches the build and the in-place update share: both read the tables the last build published in the context.
 // ---------------------------------------------------------------------------------------------------------------
-// leaf records of the triangle tree, in leaf order (c->nTriSlots of them)
+// leaf records of the triangle tree, in leaf order (c->accel.nTriSlots of them)
 static void launch_gather_tris(skh_context* c)
 {
     const uint32_t B = 256;
-    k_gather_tris<<<(c->nTriSlots + B - 1) / B, B, 0, c->stream>>>(c->dVerts.as<uint8_t>(), c->dIndices.as<uint32_t>(), c->dMeshes.as<uint4>(), c->dTriMeshK.as<uint32_t>(),
-                                                                    c->dTriLocalK.as<uint32_t>(), c->dTriOrder.as<uint32_t>(), c->nTriSlots, c->nMeshTrisBuilt, c->dInstances.as<uint8_t>(),
-                                                                    c->dShadeInst.as<uint8_t>(), c->dWInstK.as<uint32_t>(), c->dWFirstK.as<uint32_t>(), c->nWInstBuilt, c->directRecords,
-                                                                    c->dTris.as<float4>());
+    k_gather_tris<<<(c->accel.nTriSlots + B - 1) / B, B, 0, c->dev.stream>>>(c->scene.dVerts.as<uint8_t>(), c->scene.dIndices.as<uint32_t>(), c->scene.dMeshes.as<uint4>(), c->accel.dTriMeshK.as<uint32_t>(),
+                                                                    c->accel.dTriLocalK.as<uint32_t>(), c->accel.dTriOrder.as<uint32_t>(), c->accel.nTriSlots, c->accel.nMeshTrisBuilt, c->scene.dInstances.as<uint8_t>(),
+                                                                    c->accel.dShadeInst.as<uint8_t>(), c->accel.dWInstK.as<uint32_t>(), c->accel.dWFirstK.as<uint32_t>(), c->accel.nWInstBuilt, c->accel.directRecords,
+                                                                    c->accel.dTris.as<float4>());
 }
-// leaf records of the curve tree (control points, bounding cylinders), in leaf order (c->nSubBuilt of them)
+// leaf records of the curve tree (control points, bounding cylinders), in leaf order (c->accel.nSubBuilt of them)
 static void launch_gather_segs(skh_context* c, uint32_t strandMajor)
 {
     const uint32_t B = 256;
-    k_gather_segs<<<(c->nSubBuilt + B - 1) / B, B, 0, c->stream>>>(c->dPoints.as<float>(), c->dRadii.as<float>(), c->dSegBuildStartK.as<uint32_t>(), c->dSegLocalK.as<uint32_t>(),
-                                                                   c->dSegInstOfK.as<uint32_t>(), c->dSegOrder.as<uint32_t>(), c->nSubBuilt, c->curveSplitBuilt, c->dSegs.as<float4>(), strandMajor);
+    k_gather_segs<<<(c->accel.nSubBuilt + B - 1) / B, B, 0, c->dev.stream>>>(c->scene.dPoints.as<float>(), c->scene.dRadii.as<float>(), c->accel.dSegBuildStartK.as<uint32_t>(), c->accel.dSegLocalK.as<uint32_t>(),
+                                                                   c->accel.dSegInstOfK.as<uint32_t>(), c->accel.dSegOrder.as<uint32_t>(), c->accel.nSubBuilt, c->accel.curveSplitBuilt, c->accel.dSegs.as<float4>(), strandMajor);
 }
-// instance records (c->dDevInst) and world boxes from the BLASes' group roots and bounds (curve set s = group SKH_WORLD_CURVES + s)
+// instance records (c->accel.dDevInst) and world boxes from the BLASes' group roots and bounds (curve set s = group SKH_WORLD_CURVES + s)
 static void launch_instance_boxes(skh_context* c, const DevBuf& w2o, const DevBuf& triBounds, const DevBuf& triRoot, const DevBuf& segBounds, const DevBuf& segRoot,
                                   DevBuf& lo, DevBuf& hi, DevBuf& grp)
 {
-    const uint32_t B = 256, nInst = c->nInstances, nMeshes = (uint32_t)c->meshes.size(), nCurves = (uint32_t)c->curves.size();
+    const uint32_t B = 256, nInst = c->scene.nInstances, nMeshes = (uint32_t)c->scene.meshes.size(), nCurves = (uint32_t)c->scene.curves.size();
     if (!nInst)
         return;
-    k_instance_boxes<<<(nInst + B - 1) / B, B, 0, c->stream>>>(c->dInstances.as<HostInstance>(), w2o.as<float>(), c->dBuiltValid.as<uint8_t>(), triBounds.as<float>(),
+    k_instance_boxes<<<(nInst + B - 1) / B, B, 0, c->dev.stream>>>(c->scene.dInstances.as<HostInstance>(), w2o.as<float>(), c->accel.dBuiltValid.as<uint8_t>(), triBounds.as<float>(),
                                                               triRoot.as<int>(), segBounds.as<float>() + 6 * SKH_WORLD_CURVES, segRoot.as<int>() + SKH_WORLD_CURVES,
-                                                              nMeshes, nCurves, nInst, c->dDevInst.as<DevInstance>(), lo.as<float4>(), hi.as<float4>(), grp.as<uint32_t>());
-    if (c->tightInstanceBoxes)
-        k_instance_tight_boxes<<<nInst, 256, 0, c->stream>>>(c->dInstances.as<HostInstance>(), c->dDevInst.as<DevInstance>(), c->dMeshes.as<uint4>(), c->dVerts.as<uint8_t>(), nMeshes,
+                                                              nMeshes, nCurves, nInst, c->accel.dDevInst.as<DevInstance>(), lo.as<float4>(), hi.as<float4>(), grp.as<uint32_t>());
+    if (c->opt.tightInstanceBoxes)
+        k_instance_tight_boxes<<<nInst, 256, 0, c->dev.stream>>>(c->scene.dInstances.as<HostInstance>(), c->accel.dDevInst.as<DevInstance>(), c->scene.dMeshes.as<uint4>(), c->scene.dVerts.as<uint8_t>(), nMeshes,
                                                              1u << 22, lo.as<float4>(), hi.as<float4>());
 }
 // boxes of a 4-wide tree level by level, deepest first (skh_bvh.h k_node4_refit_level: one launch per level, no atomics)
@@ -746,7 +746,7 @@ static void launch_refit_levels(skh_context* c, const std::vector<uint32_t>& lev
     {
         const uint32_t first = levelStart[L], count = levelStart[L + 1] - first;
         if (count)
-            k_node4_refit_level<<<(count + B - 1) / B, B, 0, c->stream>>>(nodes.as<Node4>(), nodeBox.as<float4>(), first, count, leaves);
+            k_node4_refit_level<<<(count + B - 1) / B, B, 0, c->dev.stream>>>(nodes.as<Node4>(), nodeBox.as<float4>(), first, count, leaves);
     }
 }
 
@@ -756,20 +756,20 @@ static void launch_refit_levels(skh_context* c, const std::vector<uint32_t>& lev
 // ---------------------------------------------------------------------------------------------------------------
 static skh_status check_instance_ids(skh_context* c)
 {
-    for (uint32_t i = 0; i < c->nInstances; ++i)
+    for (uint32_t i = 0; i < c->scene.nInstances; ++i)
     {
         // what the kernels index with an instance's ids: a mesh / curve set (traversal, shading) and, for light proxies, a light
-        const skh_instance& in = c->instances[i];
+        const skh_instance& in = c->scene.instances[i];
         const char* what = nullptr;
         if (in.type > SKH_INSTANCE_CURVE)
             what = "type";
-        else if (in.type == SKH_INSTANCE_CURVE ? in.geom_id >= c->curves.size() : in.geom_id >= c->meshes.size())
+        else if (in.type == SKH_INSTANCE_CURVE ? in.geom_id >= c->scene.curves.size() : in.geom_id >= c->scene.meshes.size())
             what = "geom_id";
-        else if (in.type == SKH_INSTANCE_LIGHT && in.light_id >= c->nLights)
+        else if (in.type == SKH_INSTANCE_LIGHT && in.light_id >= c->scene.nLights)
             what = "light_id";
         if (what)
         {
-            c->err = "skh_build_accel: instance " + std::to_string(i) + " has an out-of-range " + what;
+            c->dev.err = "skh_build_accel: instance " + std::to_string(i) + " has an out-of-range " + what;
             return SKH_INVALID_ARGUMENT;
         }
     }
@@ -795,7 +795,7 @@ struct BakePlan
 };
 static BakePlan plan_bake(const skh_context* c)
 {
-    const uint32_t nMeshes = (uint32_t)c->meshes.size(), nInst = c->nInstances;
+    const uint32_t nMeshes = (uint32_t)c->scene.meshes.size(), nInst = c->scene.nInstances;
     BakePlan p;
     std::vector<float>& w2o = p.w2o;
     std::vector<uint8_t>& valid = p.valid;
@@ -806,34 +806,34 @@ static BakePlan plan_bake(const skh_context* c)
     w2o.resize(12 * (size_t)std::max(1u, nInst));
     valid.resize(std::max(1u, nInst));
     for (uint32_t i = 0; i < nInst; ++i)
-        valid[i] = invert_affine(c->instances[i].transform, &w2o[12 * (size_t)i]) ? 1 : 0;
+        valid[i] = invert_affine(c->scene.instances[i].transform, &w2o[12 * (size_t)i]) ? 1 : 0;
     p.invOk = valid;
     meshUsers.assign(nMeshes, 0u), meshUsersLeft.assign(nMeshes, 0u);
     p.baked.assign(std::max(1u, nInst), 0);
     uint64_t uniqueTris = 0;
-    for (const skh_mesh& me : c->meshes)
+    for (const skh_mesh& me : c->scene.meshes)
         uniqueTris += me.index_count / 3;
     for (uint32_t i = 0; i < nInst; ++i)
-        if (c->instances[i].type != SKH_INSTANCE_CURVE && valid[i]) // (a singular instance is disabled: the reference's distant-light proxy is one, of mesh 0, scene.cpp:337-345)
-            meshUsers[c->instances[i].geom_id]++;
+        if (c->scene.instances[i].type != SKH_INSTANCE_CURVE && valid[i]) // (a singular instance is disabled: the reference's distant-light proxy is one, of mesh 0, scene.cpp:337-345)
+            meshUsers[c->scene.instances[i].geom_id]++;
     const uint64_t smallBudget = std::max<uint64_t>(uniqueTris, 1ull << 20);
     uint64_t total = 0;
     std::vector<uint8_t> pick(std::max(1u, nInst), 0);
-    auto trisOf = [&](uint32_t i) { return c->meshes[c->instances[i].geom_id].index_count / 3; };
-    auto eligible = [&](uint32_t i) { return c->bakeWorld >= 1 && c->instances[i].type != SKH_INSTANCE_CURVE && valid[i] && trisOf(i) > 0; };
+    auto trisOf = [&](uint32_t i) { return c->scene.meshes[c->scene.instances[i].geom_id].index_count / 3; };
+    auto eligible = [&](uint32_t i) { return c->opt.bakeWorld >= 1 && c->scene.instances[i].type != SKH_INSTANCE_CURVE && valid[i] && trisOf(i) > 0; };
     // mode 4 (default) = everything (3) while the instanced triangles stay within bake_budget_mtris million, else 2: a scene
     // whose instancing fits in memory many times over is fastest with no instancing at all (kitchen stand-in, 23 M instanced
     // triangles = 1.8 GB of leaf records + nodes of 288 GB: closest-hit 98.0 -> 91.0 ms), a forest of 10^9 instanced triangles is not
-    uint32_t mode = c->bakeWorld;
+    uint32_t mode = c->opt.bakeWorld;
     if (mode == 4)
     {
         uint64_t all = 0;
         for (uint32_t i = 0; i < nInst; ++i)
             all += eligible(i) ? trisOf(i) : 0u;
-        mode = all <= (uint64_t)c->bakeBudgetMTris * 1000000ull ? 3u : 2u;
+        mode = all <= (uint64_t)c->opt.bakeBudgetMTris * 1000000ull ? 3u : 2u;
     }
     for (uint32_t i = 0; i < nInst; ++i)
-        pick[i] = eligible(i) && (meshUsers[c->instances[i].geom_id] == 1 || mode >= 3) ? 1 : 0;
+        pick[i] = eligible(i) && (meshUsers[c->scene.instances[i].geom_id] == 1 || mode >= 3) ? 1 : 0;
     if (mode == 2)
     {
         // Small SHARED meshes (boards, quads) follow only when that leaves no mesh instance behind: beside a populated top level
@@ -841,14 +841,14 @@ static BakePlan plan_bake(const skh_context* c)
         bool all = true;
         uint64_t sum = 0;
         for (uint32_t i = 0; i < nInst; ++i)
-            if (c->instances[i].type == SKH_INSTANCE_MESH && eligible(i) && !pick[i])
+            if (c->scene.instances[i].type == SKH_INSTANCE_MESH && eligible(i) && !pick[i])
             {
-                all = all && trisOf(i) <= c->bakeSmallTris;
+                all = all && trisOf(i) <= c->opt.bakeSmallTris;
                 sum += trisOf(i);
             }
         all = all && sum <= smallBudget;
         for (uint32_t i = 0; i < nInst; ++i)
-            if (eligible(i) && !pick[i] && trisOf(i) <= c->bakeSmallTris && (all || c->instances[i].type == SKH_INSTANCE_LIGHT))
+            if (eligible(i) && !pick[i] && trisOf(i) <= c->opt.bakeSmallTris && (all || c->scene.instances[i].type == SKH_INSTANCE_LIGHT))
                 pick[i] = 1;
     }
     for (uint32_t i = 0; i < nInst; ++i)
@@ -870,22 +870,22 @@ static BakePlan plan_bake(const skh_context* c)
     std::vector<uint32_t> curveInst;
     for (uint32_t i = 0; i < nInst; ++i)
     {
-        const skh_instance& in = c->instances[i];
+        const skh_instance& in = c->scene.instances[i];
         if (in.type == SKH_INSTANCE_CURVE)
         {
             uint32_t segs = 0; // (a curve set without a segment has no BLAS and no leaf)
-            if (in.geom_id < c->curves.size())
-                for (uint32_t k = 0; k < c->curves[in.geom_id].vertex_counts_count; ++k)
-                    segs += std::max(3u, c->curveVertexCounts[c->curves[in.geom_id].vertex_counts_start + k]) - 3u;
+            if (in.geom_id < c->scene.curves.size())
+                for (uint32_t k = 0; k < c->scene.curves[in.geom_id].vertex_counts_count; ++k)
+                    segs += std::max(3u, c->scene.curveVertexCounts[c->scene.curves[in.geom_id].vertex_counts_start + k]) - 3u;
             if (valid[i] && segs > 0)
                 curveInst.push_back(i);
         }
         else if (in.type == SKH_INSTANCE_MESH)
-            meshStays = meshStays || (valid[i] && !pick[i] && c->meshes[in.geom_id].index_count >= 3);
+            meshStays = meshStays || (valid[i] && !pick[i] && c->scene.meshes[in.geom_id].index_count >= 3);
     }
     bool lightsAllPicked = true; // (a light proxy the bake mode leaves behind keeps the top level alive as well)
     for (uint32_t i = 0; i < nInst; ++i)
-        if (c->instances[i].type == SKH_INSTANCE_LIGHT && eligible(i) && !pick[i])
+        if (c->scene.instances[i].type == SKH_INSTANCE_LIGHT && eligible(i) && !pick[i])
             lightsAllPicked = false;
     // (round 6) Curve instances under the SAME transform, bit for bit -- a groom handed over as several HdBasisCurves rprims, under the identity or
     // under the one Xform the whole character sits under -- do not take a table entry each: the segments of such a group are MERGED into one
@@ -897,7 +897,7 @@ static BakePlan plan_bake(const skh_context* c)
     {
         size_t g = 0;
         for (; g < xformGroups.size(); ++g)
-            if (memcmp(c->instances[xformGroups[g][0]].transform, c->instances[i].transform, sizeof(float) * 12) == 0)
+            if (memcmp(c->scene.instances[xformGroups[g][0]].transform, c->scene.instances[i].transform, sizeof(float) * 12) == 0)
                 break;
         if (g == xformGroups.size())
             xformGroups.emplace_back();
@@ -907,7 +907,7 @@ static BakePlan plan_bake(const skh_context* c)
     if (worldCurves)
     {
         // option curve_merge = 0 (A/B, tests): every instance keeps a tree and a table entry of its own while the table can hold them all
-        const bool merge = c->curveMerge || curveInst.size() > SKH_WORLD_CURVES;
+        const bool merge = c->opt.curveMerge || curveInst.size() > SKH_WORLD_CURVES;
         if (merge)
             mergedGroups = xformGroups;
         else
@@ -916,7 +916,7 @@ static BakePlan plan_bake(const skh_context* c)
     const bool tlasStays = meshStays || (!curveInst.empty() && !worldCurves);
     for (uint32_t i = 0; i < nInst; ++i)
     {
-        const skh_instance& in = c->instances[i];
+        const skh_instance& in = c->scene.instances[i];
         if (in.type == SKH_INSTANCE_CURVE)
             continue;
         if (in.type == SKH_INSTANCE_LIGHT && tlasStays)
@@ -928,14 +928,14 @@ static BakePlan plan_bake(const skh_context* c)
     for (uint32_t g = 0; g < 2; ++g)
         for (uint32_t i = 0; i < nInst; ++i)
         {
-            const skh_instance& in = c->instances[i];
+            const skh_instance& in = c->scene.instances[i];
             if (!pick[i] || (in.type == SKH_INSTANCE_LIGHT ? 1u : 0u) != g)
                 continue;
             p.baked[i] = 1;
             valid[i] = 0; // no TLAS leaf
             wInst.push_back(i);
             wFirst.push_back((uint32_t)total);
-            const uint32_t nt = c->meshes[in.geom_id].index_count / 3;
+            const uint32_t nt = c->scene.meshes[in.geom_id].index_count / 3;
             total += nt;
             nBakedG[g] += nt;
         }
@@ -960,32 +960,32 @@ struct TriBuild
 // a closest-hit lane's second scattered store costs more than that step (kitchen closest-hit -4 %).
 static void choose_hit_word(skh_context* c)
 {
-    const uint32_t nMeshes = (uint32_t)c->meshes.size(), nInst = c->nInstances;
+    const uint32_t nMeshes = (uint32_t)c->scene.meshes.size(), nInst = c->scene.nInstances;
     uint32_t maxMeshTris = 1;
     for (uint32_t m = 0; m < nMeshes; ++m)
-        maxMeshTris = std::max(maxMeshTris, c->meshes[m].index_count / 3u);
+        maxMeshTris = std::max(maxMeshTris, c->scene.meshes[m].index_count / 3u);
     auto fits = [&](uint32_t range) {
         uint32_t B = 1;
         while (B < 31u && (1u << B) < range)
             ++B;
         return (1ull << B) >= range && (uint64_t)nInst <= (1ull << (32u - B)) - 1ull;
     };
-    const uint32_t nSegAll = (uint32_t)std::min<uint64_t>(0x7fffffffull, [&]() { uint64_t n = 0; for (const skh_curve& cu : c->curves) for (uint32_t k = 0; k < cu.vertex_counts_count; ++k) { const uint32_t ncp = c->curveVertexCounts[cu.vertex_counts_start + k]; n += ncp > 3u ? ncp - 3u : 0u; } return n; }());
-    const uint32_t rangeDirect = std::max(c->nShadeRecords, nSegAll), rangeLocal = std::max(maxMeshTris, nSegAll);
-    c->directRecords = c->directRecordsOpt >= 0 ? (uint32_t)c->directRecordsOpt : ((c->compactHits && !fits(rangeDirect) && fits(rangeLocal)) ? 0u : 1u);
-    c->hitPrimRange = c->directRecords ? rangeDirect : rangeLocal;
+    const uint32_t nSegAll = (uint32_t)std::min<uint64_t>(0x7fffffffull, [&]() { uint64_t n = 0; for (const skh_curve& cu : c->scene.curves) for (uint32_t k = 0; k < cu.vertex_counts_count; ++k) { const uint32_t ncp = c->scene.curveVertexCounts[cu.vertex_counts_start + k]; n += ncp > 3u ? ncp - 3u : 0u; } return n; }());
+    const uint32_t rangeDirect = std::max(c->accel.nShadeRecords, nSegAll), rangeLocal = std::max(maxMeshTris, nSegAll);
+    c->accel.directRecords = c->opt.directRecords >= 0 ? (uint32_t)c->opt.directRecords : ((c->opt.compactHits && !fits(rangeDirect) && fits(rangeLocal)) ? 0u : 1u);
+    c->accel.hitPrimRange = c->accel.directRecords ? rangeDirect : rangeLocal;
 }
 
 // triangles of all meshes (a mesh whose users were all baked needs no object-space tree) + the baked groups: boxes, tree, leaf records, roots, light box
 static skh_status build_tri_tree(skh_context* c, uint32_t flags, bool usePloc, const BakePlan& p, BuildScratch& sx, TriBuild& tri)
 {
-    hipStream_t st = c->stream;
-    const uint32_t B = 256, nMeshes = (uint32_t)c->meshes.size();
+    hipStream_t st = c->dev.stream;
+    const uint32_t B = 256, nMeshes = (uint32_t)c->scene.meshes.size();
     const uint32_t nBaked = p.nBakedG[0] + p.nBakedG[1], nW = (uint32_t)p.wInst.size();
     std::vector<uint32_t> triMesh, triLocal, meshTriCount(nMeshes + 2u);
     for (uint32_t m = 0; m < nMeshes; ++m)
     {
-        const uint32_t nt = (p.meshUsers[m] > 0 && p.meshUsersLeft[m] == 0) ? 0u : c->meshes[m].index_count / 3;
+        const uint32_t nt = (p.meshUsers[m] > 0 && p.meshUsersLeft[m] == 0) ? 0u : c->scene.meshes[m].index_count / 3;
         meshTriCount[m] = nt;
         for (uint32_t t = 0; t < nt; ++t)
         {
@@ -995,14 +995,14 @@ static skh_status build_tri_tree(skh_context* c, uint32_t flags, bool usePloc, c
     }
     // (merge_light_proxies: one world-space group for both kinds -- a light proxy is told from a mesh triangle by its primitive word, which
     // lacks SKH_PRIM_DIRECT (k_gather_tris); any-hit queries, which must not see lights (RAY_MASK_SHADOW, closest_hit.cu:191), skip those triangles)
-    const bool mergeLights = c->mergeLightProxies != 0u && p.nBakedG[0] != 0u && p.nBakedG[1] != 0u;
+    const bool mergeLights = c->opt.mergeLightProxies != 0u && p.nBakedG[0] != 0u && p.nBakedG[1] != 0u;
     const uint32_t nGroup0 = mergeLights ? p.nBakedG[0] + p.nBakedG[1] : p.nBakedG[0], nGroup1 = mergeLights ? 0u : p.nBakedG[1];
     meshTriCount[nMeshes] = nGroup0;
     meshTriCount[nMeshes + 1u] = nGroup1;
     const uint32_t nMeshTris = (uint32_t)triMesh.size();
     const uint32_t nTris = nMeshTris + nBaked;
     tri.nMeshTris = nMeshTris, tri.nGroup0 = nGroup0, tri.nGroup1 = nGroup1;
-    c->nTris = nTris;
+    c->accel.nTris = nTris;
     SKH_CHECK(dev_upload(c, tri.triMesh, triMesh.data(), sizeof(uint32_t) * (size_t)nMeshTris));
     SKH_CHECK(dev_upload(c, tri.triLocal, triLocal.data(), sizeof(uint32_t) * (size_t)nMeshTris));
     SKH_CHECK(dev_upload(c, tri.wInst, p.wInst.data(), sizeof(uint32_t) * p.wInst.size()));
@@ -1011,49 +1011,49 @@ static skh_status build_tri_tree(skh_context* c, uint32_t flags, bool usePloc, c
     SKH_CHECK(dev_alloc(c, sx.boxHi, sizeof(float4) * (size_t)std::max(1u, nTris)));
     SKH_CHECK(dev_alloc(c, sx.grp, sizeof(uint32_t) * (size_t)std::max(1u, nTris)));
     if (nMeshTris)
-        k_tri_boxes<<<(nMeshTris + B - 1) / B, B, 0, st>>>(c->dVerts.as<uint8_t>(), c->dIndices.as<uint32_t>(), c->dMeshes.as<uint4>(),
+        k_tri_boxes<<<(nMeshTris + B - 1) / B, B, 0, st>>>(c->scene.dVerts.as<uint8_t>(), c->scene.dIndices.as<uint32_t>(), c->scene.dMeshes.as<uint4>(),
                                                           tri.triMesh.as<uint32_t>(), tri.triLocal.as<uint32_t>(), nMeshTris, sx.boxLo.as<float4>(),
                                                           sx.boxHi.as<float4>(), sx.grp.as<uint32_t>());
     if (nBaked)
-        k_baked_tri_boxes<<<(nBaked + B - 1) / B, B, 0, st>>>(c->dInstances.as<uint8_t>(), tri.wInst.as<uint32_t>(), tri.wFirst.as<uint32_t>(),
-                                                             nW, c->dVerts.as<uint8_t>(), c->dIndices.as<uint32_t>(),
-                                                             c->dMeshes.as<uint4>(), nBaked, nMeshTris, nMeshes, nGroup0, sx.boxLo.as<float4>(),
+        k_baked_tri_boxes<<<(nBaked + B - 1) / B, B, 0, st>>>(c->scene.dInstances.as<uint8_t>(), tri.wInst.as<uint32_t>(), tri.wFirst.as<uint32_t>(),
+                                                             nW, c->scene.dVerts.as<uint8_t>(), c->scene.dIndices.as<uint32_t>(),
+                                                             c->scene.dMeshes.as<uint4>(), nBaked, nMeshTris, nMeshes, nGroup0, sx.boxLo.as<float4>(),
                                                              sx.boxHi.as<float4>(), sx.grp.as<uint32_t>());
-    const uint32_t riMin = c->reinsertMinSize ? c->reinsertMinSize : (nTris <= (4u << 20) ? 1u : 32u);
+    const uint32_t riMin = c->opt.reinsertMinSize ? c->opt.reinsertMinSize : (nTris <= (4u << 20) ? 1u : 32u);
     LbvhOut& triOut = tri.out;
-    SKH_CHECK(lbvh_build(c, nTris, nMeshes + 2u, meshTriCount, sx.boxLo.as<float4>(), sx.boxHi.as<float4>(), sx.grp.as<uint32_t>(), (int)c->leafMaxTris, usePloc, triOut,
-                         0, c->leafLines ? 48u : 0u, usePloc ? c->reinsertRounds : 0u, riMin));
-    memset(&c->buildInfo, 0, sizeof(c->buildInfo));
-    c->buildInfo.triangles = nTris;
-    c->buildInfo.nodes = triOut.numNodes;
-    c->hierNodes = triOut.numNodes;
-    c->buildInfo.reinsert_rounds = triOut.riRounds;
-    c->buildInfo.reinsert_moves = triOut.riMoves;
-    c->buildInfo.reinsert_min_size = triOut.riMinSize;
-    c->buildInfo.cost_before = triOut.riCostBefore;
-    c->buildInfo.cost_after = triOut.riRounds ? triOut.riCostAfter : triOut.riCostBefore;
-    c->buildInfo.ms_reinsert = triOut.riMs;
+    SKH_CHECK(lbvh_build(c, nTris, nMeshes + 2u, meshTriCount, sx.boxLo.as<float4>(), sx.boxHi.as<float4>(), sx.grp.as<uint32_t>(), (int)c->opt.leafMaxTris, usePloc, triOut,
+                         0, c->opt.leafLines ? 48u : 0u, usePloc ? c->opt.reinsertRounds : 0u, riMin));
+    memset(&c->accel.buildInfo, 0, sizeof(c->accel.buildInfo));
+    c->accel.buildInfo.triangles = nTris;
+    c->accel.buildInfo.nodes = triOut.numNodes;
+    c->accel.hierNodes = triOut.numNodes;
+    c->accel.buildInfo.reinsert_rounds = triOut.riRounds;
+    c->accel.buildInfo.reinsert_moves = triOut.riMoves;
+    c->accel.buildInfo.reinsert_min_size = triOut.riMinSize;
+    c->accel.buildInfo.cost_before = triOut.riCostBefore;
+    c->accel.buildInfo.cost_after = triOut.riRounds ? triOut.riCostAfter : triOut.riCostBefore;
+    c->accel.buildInfo.ms_reinsert = triOut.riMs;
     choose_hit_word(c);
-    c->nTriSlots = triOut.numSlots; // >= nTris: the line layout pads in front of leaves that would straddle a 128-byte line
-    SKH_CHECK(dev_alloc(c, c->dTris, sizeof(float4) * 3 * (size_t)std::max(1u, c->nTriSlots)));
+    c->accel.nTriSlots = triOut.numSlots; // >= nTris: the line layout pads in front of leaves that would straddle a 128-byte line
+    SKH_CHECK(dev_alloc(c, c->accel.dTris, sizeof(float4) * 3 * (size_t)std::max(1u, c->accel.nTriSlots)));
     // what skh_refit_accel needs of this build: k_gather_tris' tables and the tree's levels (the old ones go out with this call's temporaries)
-    std::swap(c->dTriOrder, triOut.sortedVals);
-    std::swap(c->dTriMeshK, tri.triMesh);
-    std::swap(c->dTriLocalK, tri.triLocal);
-    std::swap(c->dWInstK, tri.wInst);
-    std::swap(c->dWFirstK, tri.wFirst);
-    c->nMeshTrisBuilt = nMeshTris, c->nWInstBuilt = nW;
-    if (c->nTriSlots)
+    std::swap(c->accel.dTriOrder, triOut.sortedVals);
+    std::swap(c->accel.dTriMeshK, tri.triMesh);
+    std::swap(c->accel.dTriLocalK, tri.triLocal);
+    std::swap(c->accel.dWInstK, tri.wInst);
+    std::swap(c->accel.dWFirstK, tri.wFirst);
+    c->accel.nMeshTrisBuilt = nMeshTris, c->accel.nWInstBuilt = nW;
+    if (c->accel.nTriSlots)
         launch_gather_tris(c);
-    c->dTriNodes = std::move(triOut.nodes);
-    c->triLevelStart = triOut.levelStart;
-    c->triNumNodes = triOut.numNodes, c->lastBuildFlags = flags, c->nGroup1Built = nGroup1;
-    c->builtGeomSig = c->geomSig, c->builtNVerts = c->nVerts;
-    c->refitReady = true; // (either builder ends in the same collapse)
-    c->worldRoot = nGroup0 ? triOut.hostGroupRoot[nMeshes] : SKH_REF_INVALID;
-    c->lightRoot = nGroup1 ? triOut.hostGroupRoot[nMeshes + 1u] : SKH_REF_INVALID;
+    c->accel.dTriNodes = std::move(triOut.nodes);
+    c->accel.triLevelStart = triOut.levelStart;
+    c->accel.triNumNodes = triOut.numNodes, c->accel.lastBuildFlags = flags, c->accel.nGroup1Built = nGroup1;
+    c->accel.builtGeomSig = c->scene.geomSig, c->accel.builtNVerts = c->scene.nVerts;
+    c->accel.refitReady = true; // (either builder ends in the same collapse)
+    c->accel.worldRoot = nGroup0 ? triOut.hostGroupRoot[nMeshes] : SKH_REF_INVALID;
+    c->accel.lightRoot = nGroup1 ? triOut.hostGroupRoot[nMeshes + 1u] : SKH_REF_INVALID;
     for (int k = 0; k < 3; ++k)
-        c->lightBox.lo[k] = -INFINITY, c->lightBox.hi[k] = INFINITY;
+        c->accel.lightBox.lo[k] = -INFINITY, c->accel.lightBox.hi[k] = INFINITY;
     if (nBaked)
     {
         float gb[12];
@@ -1072,17 +1072,17 @@ struct CurveTables
 };
 static skh_status enumerate_curve_segments(skh_context* c, CurveTables& ct)
 {
-    const uint32_t nCurves = (uint32_t)c->curves.size();
+    const uint32_t nCurves = (uint32_t)c->scene.curves.size();
     std::vector<uint32_t>&setSegStart = ct.setSegStart, &curveSegCount = ct.curveSegCount, &curveSegBase = ct.curveSegBase;
     curveSegCount.resize(nCurves), curveSegBase.resize(nCurves);
     for (uint32_t ci = 0; ci < nCurves; ++ci)
     {
-        const skh_curve& cu = c->curves[ci];
+        const skh_curve& cu = c->scene.curves[ci];
         curveSegBase[ci] = (uint32_t)setSegStart.size();
         uint32_t off = 0, local = 0;
         for (uint32_t k = 0; k < cu.vertex_counts_count; ++k)
         {
-            const uint32_t ncp = c->curveVertexCounts[cu.vertex_counts_start + k];
+            const uint32_t ncp = c->scene.curveVertexCounts[cu.vertex_counts_start + k];
             for (int i = 0; i < (int)ncp - 3; ++i, ++local)
                 setSegStart.push_back(cu.points_start + off + (uint32_t)i);
             off += ncp;
@@ -1090,9 +1090,9 @@ static skh_status enumerate_curve_segments(skh_context* c, CurveTables& ct)
         curveSegCount[ci] = local;
     }
     for (uint32_t k = 0; k < (uint32_t)setSegStart.size(); ++k)
-        if ((uint64_t)setSegStart[k] + 4 > c->nPoints)
+        if ((uint64_t)setSegStart[k] + 4 > c->scene.nPoints)
         {
-            c->err = "skh_build_accel: curve segment reads past the control-point buffer";
+            c->dev.err = "skh_build_accel: curve segment reads past the control-point buffer";
             return SKH_INVALID_ARGUMENT;
         }
     return SKH_OK;
@@ -1101,7 +1101,7 @@ static skh_status enumerate_curve_segments(skh_context* c, CurveTables& ct)
 // group's transform; the record names the instance), group SKH_WORLD_CURVES + s = curve set s (skipped when every instance of the set was merged).
 static void group_curve_segments(const skh_context* c, const std::vector<std::vector<uint32_t>>& mergedGroups, CurveTables& ct)
 {
-    const uint32_t nCurves = (uint32_t)c->curves.size(), nInst = c->nInstances;
+    const uint32_t nCurves = (uint32_t)c->scene.curves.size(), nInst = c->scene.nInstances;
     const std::vector<uint32_t>&setSegStart = ct.setSegStart, &curveSegCount = ct.curveSegCount, &curveSegBase = ct.curveSegBase;
     std::vector<uint32_t>&segStart = ct.segStart, &segCurve = ct.segCurve, &segLocal = ct.segLocal, &segInstOf = ct.segInstOf, &curveGroupCount = ct.curveGroupCount;
     curveGroupCount.assign(nCurves + SKH_WORLD_CURVES, 0u);
@@ -1113,13 +1113,13 @@ static void group_curve_segments(const skh_context* c, const std::vector<std::ve
             for (uint32_t i : grp)
                 isMerged[i] = 1;
         for (uint32_t i = 0; i < nInst; ++i)
-            if (c->instances[i].type == SKH_INSTANCE_CURVE && !isMerged[i] && c->instances[i].geom_id < nCurves)
-                setNeeded[c->instances[i].geom_id] = 1;
+            if (c->scene.instances[i].type == SKH_INSTANCE_CURVE && !isMerged[i] && c->scene.instances[i].geom_id < nCurves)
+                setNeeded[c->scene.instances[i].geom_id] = 1;
     }
     for (size_t g = 0; g < mergedGroups.size(); ++g)
         for (uint32_t i : mergedGroups[g])
         {
-            const uint32_t ci = c->instances[i].geom_id;
+            const uint32_t ci = c->scene.instances[i].geom_id;
             for (uint32_t l = 0; l < curveSegCount[ci]; ++l)
             {
                 segStart.push_back(setSegStart[curveSegBase[ci] + l]);
@@ -1154,13 +1154,13 @@ struct CurveBuild
 // redirected to the segment node in front of the leaf
 static skh_status grow_segment_nodes(skh_context* c, uint32_t nSegs, uint32_t nCurveGroups, uint32_t strandMajor, const DevBuf& segBuildStart, LbvhOut& segOut)
 {
-    hipStream_t st = c->stream;
+    hipStream_t st = c->dev.stream;
     const uint32_t B = 256;
     DevBuf grown;
     SKH_CHECK(dev_alloc(c, grown, sizeof(Node4) * ((size_t)segOut.numNodes + nSegs + 1)));
     if (segOut.numNodes)
         SKH_TRY(c, hipMemcpyAsync(grown.p, segOut.nodes.p, sizeof(Node4) * (size_t)segOut.numNodes, hipMemcpyDeviceToDevice, st));
-    k_segnode_emit<<<(nSegs + B - 1) / B, B, 0, st>>>(c->dPoints.as<float>(), c->dRadii.as<float>(), segBuildStart.as<uint32_t>(), segOut.sortedVals.as<uint32_t>(), nSegs,
+    k_segnode_emit<<<(nSegs + B - 1) / B, B, 0, st>>>(c->scene.dPoints.as<float>(), c->scene.dRadii.as<float>(), segBuildStart.as<uint32_t>(), segOut.sortedVals.as<uint32_t>(), nSegs,
                                                      strandMajor, grown.as<Node4>() + segOut.numNodes);
     if (segOut.numNodes)
         k_segnode_patch<<<(segOut.numNodes * 4u + B - 1) / B, B, 0, st>>>(reinterpret_cast<int*>(grown.p) + 12, segOut.numNodes * 4u, 16u, 4u, segOut.sortedVals.as<uint32_t>(),
@@ -1175,21 +1175,21 @@ static skh_status grow_segment_nodes(skh_context* c, uint32_t nSegs, uint32_t nC
 
 static skh_status build_curve_tree(skh_context* c, bool usePloc, const CurveTables& ct, BuildScratch& sx, CurveBuild& cur)
 {
-    hipStream_t st = c->stream;
-    const uint32_t B = 256, nCurves = (uint32_t)c->curves.size();
+    hipStream_t st = c->dev.stream;
+    const uint32_t B = 256, nCurves = (uint32_t)c->scene.curves.size();
     const uint32_t nSegs = (uint32_t)ct.segStart.size();
-    c->nSegs = nSegs;
-    SKH_CHECK(dev_upload(c, c->dSegStartAll, ct.setSegStart.data(), sizeof(uint32_t) * ct.setSegStart.size()));
-    SKH_CHECK(dev_upload(c, c->dCurveSegBase, ct.curveSegBase.data(), sizeof(uint32_t) * (size_t)nCurves));
+    c->accel.nSegs = nSegs;
+    SKH_CHECK(dev_upload(c, c->accel.dSegStartAll, ct.setSegStart.data(), sizeof(uint32_t) * ct.setSegStart.size()));
+    SKH_CHECK(dev_upload(c, c->accel.dCurveSegBase, ct.curveSegBase.data(), sizeof(uint32_t) * (size_t)nCurves));
     SKH_CHECK(dev_upload(c, cur.segBuildStart, ct.segStart.data(), sizeof(uint32_t) * (size_t)nSegs));
     SKH_CHECK(dev_upload(c, cur.segInstOf, ct.segInstOf.data(), sizeof(uint32_t) * (size_t)nSegs));
     SKH_CHECK(dev_upload(c, cur.segCurve, ct.segCurve.data(), sizeof(uint32_t) * (size_t)nSegs));
     SKH_CHECK(dev_upload(c, cur.segLocal, ct.segLocal.data(), sizeof(uint32_t) * (size_t)nSegs));
-    const bool segNode = c->curveSegNode != 0 && nSegs > 0;
-    const uint32_t K = segNode ? 1u : std::max(1u, std::min(c->curveSplit, 8u)); // (segment nodes: the tree's primitives are whole segments)
+    const bool segNode = c->opt.curveSegNode != 0 && nSegs > 0;
+    const uint32_t K = segNode ? 1u : std::max(1u, std::min(c->opt.curveSplit, 8u)); // (segment nodes: the tree's primitives are whole segments)
     if ((uint64_t)nSegs * K >= (1ull << 28) || (segNode && (uint64_t)nSegs * 2 >= (1ull << 28)))
     {
-        c->err = "skh_build_accel: more than 2^28 curve sub-segments (lower the curve_split option)";
+        c->dev.err = "skh_build_accel: more than 2^28 curve sub-segments (lower the curve_split option)";
         return SKH_INVALID_ARGUMENT;
     }
     const uint32_t nSub = nSegs * K;
@@ -1197,37 +1197,37 @@ static skh_status build_curve_tree(skh_context* c, bool usePloc, const CurveTabl
     std::vector<uint32_t> curveSubCount(nCurveGroups);
     for (uint32_t g = 0; g < nCurveGroups; ++g)
         curveSubCount[g] = ct.curveGroupCount[g] * K;
-    SKH_CHECK(dev_alloc(c, sx.boxLo, sizeof(float4) * (size_t)std::max(nSub, std::max(1u, c->nInstances))));
-    SKH_CHECK(dev_alloc(c, sx.boxHi, sizeof(float4) * (size_t)std::max(nSub, std::max(1u, c->nInstances))));
-    SKH_CHECK(dev_alloc(c, sx.grp, sizeof(uint32_t) * (size_t)std::max(nSub, std::max(1u, c->nInstances))));
+    SKH_CHECK(dev_alloc(c, sx.boxLo, sizeof(float4) * (size_t)std::max(nSub, std::max(1u, c->scene.nInstances))));
+    SKH_CHECK(dev_alloc(c, sx.boxHi, sizeof(float4) * (size_t)std::max(nSub, std::max(1u, c->scene.nInstances))));
+    SKH_CHECK(dev_alloc(c, sx.grp, sizeof(uint32_t) * (size_t)std::max(nSub, std::max(1u, c->scene.nInstances))));
     if (nSub && segNode)
-        k_seg_union_boxes<<<(nSegs + B - 1) / B, B, 0, st>>>(c->dPoints.as<float>(), c->dRadii.as<float>(), cur.segBuildStart.as<uint32_t>(),
+        k_seg_union_boxes<<<(nSegs + B - 1) / B, B, 0, st>>>(c->scene.dPoints.as<float>(), c->scene.dRadii.as<float>(), cur.segBuildStart.as<uint32_t>(),
                                                             cur.segCurve.as<uint32_t>(), nSegs, sx.boxLo.as<float4>(), sx.boxHi.as<float4>(), sx.grp.as<uint32_t>());
     else if (nSub)
-        k_seg_boxes<<<(nSub + B - 1) / B, B, 0, st>>>(c->dPoints.as<float>(), c->dRadii.as<float>(), cur.segBuildStart.as<uint32_t>(),
+        k_seg_boxes<<<(nSub + B - 1) / B, B, 0, st>>>(c->scene.dPoints.as<float>(), c->scene.dRadii.as<float>(), cur.segBuildStart.as<uint32_t>(),
                                                       cur.segCurve.as<uint32_t>(), nSub, K, sx.boxLo.as<float4>(), sx.boxHi.as<float4>(),
                                                       sx.grp.as<uint32_t>());
     LbvhOut& segOut = cur.out;
-    SKH_CHECK(lbvh_build(c, nSub, nCurveGroups, curveSubCount, sx.boxLo.as<float4>(), sx.boxHi.as<float4>(), sx.grp.as<uint32_t>(), segNode ? 1 : (int)c->curveLeaf, usePloc, segOut, 2, 0u,
-                         usePloc ? c->reinsertCurveRounds : 0u, c->reinsertMinSize ? c->reinsertMinSize : (nSub <= (8u << 20) ? 1u : 32u)));
-    const uint32_t strandMajor = segNode && c->curveStrandMajor ? 1u : 0u;
+    SKH_CHECK(lbvh_build(c, nSub, nCurveGroups, curveSubCount, sx.boxLo.as<float4>(), sx.boxHi.as<float4>(), sx.grp.as<uint32_t>(), segNode ? 1 : (int)c->opt.curveLeaf, usePloc, segOut, 2, 0u,
+                         usePloc ? c->opt.reinsertCurveRounds : 0u, c->opt.reinsertMinSize ? c->opt.reinsertMinSize : (nSub <= (8u << 20) ? 1u : 32u)));
+    const uint32_t strandMajor = segNode && c->opt.curveStrandMajor ? 1u : 0u;
     if (segNode)
         SKH_CHECK(grow_segment_nodes(c, nSegs, nCurveGroups, strandMajor, cur.segBuildStart, segOut));
-    SKH_CHECK(dev_alloc(c, c->dSegs, sizeof(float4) * SKH_SEG_STRIDE * (size_t)std::max(1u, nSub)));
+    SKH_CHECK(dev_alloc(c, c->accel.dSegs, sizeof(float4) * SKH_SEG_STRIDE * (size_t)std::max(1u, nSub)));
     // what skh_refit_accel needs of the curve build (segment nodes carry boxes of their own kind: no refit for that experimental build)
-    std::swap(c->dSegOrder, segOut.sortedVals);
-    std::swap(c->dSegBuildStartK, cur.segBuildStart);
-    std::swap(c->dSegLocalK, cur.segLocal);
-    std::swap(c->dSegInstOfK, cur.segInstOf);
-    c->nSubBuilt = nSub, c->curveSplitBuilt = K;
+    std::swap(c->accel.dSegOrder, segOut.sortedVals);
+    std::swap(c->accel.dSegBuildStartK, cur.segBuildStart);
+    std::swap(c->accel.dSegLocalK, cur.segLocal);
+    std::swap(c->accel.dSegInstOfK, cur.segInstOf);
+    c->accel.nSubBuilt = nSub, c->accel.curveSplitBuilt = K;
     if (nSub)
         launch_gather_segs(c, strandMajor);
-    c->dSegNodes = std::move(segOut.nodes);
-    c->hierNodes += segOut.numNodes;
-    c->segLevelStart = segOut.levelStart;
-    c->segNumNodes = segOut.numNodes;
-    c->builtCurveSig = c->curveSig, c->curvePointsEdited = false;
-    c->curveRefitReady = !segNode;
+    c->accel.dSegNodes = std::move(segOut.nodes);
+    c->accel.hierNodes += segOut.numNodes;
+    c->accel.segLevelStart = segOut.levelStart;
+    c->accel.segNumNodes = segOut.numNodes;
+    c->accel.builtCurveSig = c->scene.curveSig, c->accel.curvePointsEdited = false;
+    c->accel.curveRefitReady = !segNode;
     cur.setRoot.assign(nCurves, SKH_REF_INVALID);
     for (uint32_t ci = 0; ci < nCurves; ++ci)
         cur.setRoot[ci] = segOut.hostGroupRoot[SKH_WORLD_CURVES + ci];
@@ -1238,41 +1238,41 @@ static skh_status build_curve_tree(skh_context* c, bool usePloc, const CurveTabl
 // validity flags go to the device: both TLAS builders then agree on which instances have a leaf (ADVICE r5).
 static void assign_world_curves(skh_context* c, bool worldCurveKernel, BakePlan& p, const CurveBuild& cur)
 {
-    const uint32_t nCurves = (uint32_t)c->curves.size();
+    const uint32_t nCurves = (uint32_t)c->scene.curves.size();
     const std::vector<int>&curveSetRoot = cur.setRoot, &mergedRoot = cur.out.hostGroupRoot;
     std::vector<uint32_t>& worldCurveInst = p.worldCurveInst;
     const std::vector<std::vector<uint32_t>>& mergedGroups = p.mergedGroups;
     std::vector<uint8_t>& valid = p.valid;
-    c->numWorldCurves = 0;
-    c->worldCurveIdentLast = 0;
-    c->worldCurveMerged = 0;
-    c->numMergedCurveInst = 0;
+    c->accel.numWorldCurves = 0;
+    c->accel.worldCurveIdentLast = 0;
+    c->accel.worldCurveMerged = 0;
+    c->accel.numMergedCurveInst = 0;
     if (worldCurveKernel)
     {
         // (an entry under a bit-exact identity transform goes LAST in the table = first off every ray's stack: the kernel skips its matrix fetch)
         static const float kIdentity[12] = { 1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0 };
         for (size_t k = 0; k + 1 < worldCurveInst.size(); ++k)
-            if (memcmp(c->instances[worldCurveInst[k]].transform, kIdentity, sizeof(kIdentity)) == 0)
+            if (memcmp(c->scene.instances[worldCurveInst[k]].transform, kIdentity, sizeof(kIdentity)) == 0)
             {
                 std::swap(worldCurveInst[k], worldCurveInst.back());
                 break;
             }
         for (uint32_t i : worldCurveInst)
         {
-            const int root = c->instances[i].geom_id < nCurves ? curveSetRoot[c->instances[i].geom_id] : SKH_REF_INVALID;
+            const int root = c->scene.instances[i].geom_id < nCurves ? curveSetRoot[c->scene.instances[i].geom_id] : SKH_REF_INVALID;
             if (root == SKH_REF_INVALID)
                 continue;
-            c->worldCurveRoot[c->numWorldCurves] = root;
-            c->worldCurveInst[c->numWorldCurves++] = i;
-            c->worldCurveIdentLast = memcmp(c->instances[i].transform, kIdentity, sizeof(kIdentity)) == 0 ? 1u : 0u; // (of the last one entered)
+            c->accel.worldCurveRoot[c->accel.numWorldCurves] = root;
+            c->accel.worldCurveInst[c->accel.numWorldCurves++] = i;
+            c->accel.worldCurveIdentLast = memcmp(c->scene.instances[i].transform, kIdentity, sizeof(kIdentity)) == 0 ? 1u : 0u; // (of the last one entered)
             valid[i] = 0; // no TLAS leaf
         }
         std::vector<size_t> order; // merged groups: the identity group last
         for (size_t g = 0; g < mergedGroups.size(); ++g)
-            if (memcmp(c->instances[mergedGroups[g][0]].transform, kIdentity, sizeof(kIdentity)) != 0)
+            if (memcmp(c->scene.instances[mergedGroups[g][0]].transform, kIdentity, sizeof(kIdentity)) != 0)
                 order.push_back(g);
         for (size_t g = 0; g < mergedGroups.size(); ++g)
-            if (memcmp(c->instances[mergedGroups[g][0]].transform, kIdentity, sizeof(kIdentity)) == 0)
+            if (memcmp(c->scene.instances[mergedGroups[g][0]].transform, kIdentity, sizeof(kIdentity)) == 0)
                 order.push_back(g);
         for (size_t g : order)
         {
@@ -1280,11 +1280,11 @@ static void assign_world_curves(skh_context* c, bool worldCurveKernel, BakePlan&
                 valid[i] = 0;
             if (mergedRoot[g] == SKH_REF_INVALID)
                 continue;
-            c->worldCurveMerged |= 1u << c->numWorldCurves; // = "the segment record names the instance" (DevScene::segInst); the entry's instance lends its transform
-            c->worldCurveRoot[c->numWorldCurves] = mergedRoot[g];
-            c->worldCurveInst[c->numWorldCurves++] = mergedGroups[g][0];
-            c->worldCurveIdentLast = memcmp(c->instances[mergedGroups[g][0]].transform, kIdentity, sizeof(kIdentity)) == 0 ? 1u : 0u;
-            c->numMergedCurveInst += (uint32_t)mergedGroups[g].size();
+            c->accel.worldCurveMerged |= 1u << c->accel.numWorldCurves; // = "the segment record names the instance" (DevScene::segInst); the entry's instance lends its transform
+            c->accel.worldCurveRoot[c->accel.numWorldCurves] = mergedRoot[g];
+            c->accel.worldCurveInst[c->accel.numWorldCurves++] = mergedGroups[g][0];
+            c->accel.worldCurveIdentLast = memcmp(c->scene.instances[mergedGroups[g][0]].transform, kIdentity, sizeof(kIdentity)) == 0 ? 1u : 0u;
+            c->accel.numMergedCurveInst += (uint32_t)mergedGroups[g].size();
         }
     }
 }
@@ -1293,8 +1293,8 @@ static void assign_world_curves(skh_context* c, bool worldCurveKernel, BakePlan&
 static skh_status build_instance_boxes(skh_context* c, const BakePlan& p, const TriBuild& tri, const CurveBuild& cur, BuildScratch& sx)
 {
     SKH_CHECK(dev_upload(c, sx.w2o, p.w2o.data(), sizeof(float) * p.w2o.size()));
-    SKH_CHECK(dev_upload(c, c->dBuiltValid, p.valid.data(), p.valid.size()));
-    SKH_CHECK(dev_alloc(c, c->dDevInst, sizeof(DevInstance) * (size_t)std::max(1u, c->nInstances)));
+    SKH_CHECK(dev_upload(c, c->accel.dBuiltValid, p.valid.data(), p.valid.size()));
+    SKH_CHECK(dev_alloc(c, c->accel.dDevInst, sizeof(DevInstance) * (size_t)std::max(1u, c->scene.nInstances)));
     launch_instance_boxes(c, sx.w2o, tri.out.groupBounds, tri.out.groupRoot, cur.out.groupBounds, cur.out.groupRoot, sx.boxLo, sx.boxHi, sx.grp);
     return SKH_OK;
 }
@@ -1303,25 +1303,25 @@ static skh_status build_instance_boxes(skh_context* c, const BakePlan& p, const 
 // take part is known on the host without reading anything back: a finite inverse and a non-empty BLAS.
 static skh_status build_tlas_gpu(skh_context* c, const BakePlan& p, const TriBuild& tri, const CurveBuild& cur, const BuildScratch& sx)
 {
-    hipStream_t st = c->stream;
-    const uint32_t B = 256, nInst = c->nInstances;
+    hipStream_t st = c->dev.stream;
+    const uint32_t B = 256, nInst = c->scene.nInstances;
     std::vector<uint32_t> leafInst;
     for (uint32_t i = 0; i < nInst; ++i)
     {
-        const skh_instance& in = c->instances[i];
+        const skh_instance& in = c->scene.instances[i];
         const std::vector<int>& roots = in.type == SKH_INSTANCE_CURVE ? cur.setRoot : tri.out.hostGroupRoot;
         if (p.valid[i] && in.geom_id < roots.size() && roots[in.geom_id] != SKH_REF_INVALID)
             leafInst.push_back(i);
     }
     const uint32_t nLeaves = (uint32_t)leafInst.size();
-    c->numTlasLeaves = nLeaves;
-    dev_free(c->dTlasNodes);
-    dev_free(c->dTlasInst);
-    c->tlasLevelStart.clear();
+    c->accel.numTlasLeaves = nLeaves;
+    dev_free(c->accel.dTlasNodes);
+    dev_free(c->accel.dTlasInst);
+    c->accel.tlasLevelStart.clear();
     if (nLeaves == 0)
     {
-        dev_free(c->dTravInst);
-        c->tlasRoot = SKH_REF_INVALID;
+        dev_free(c->accel.dTravInst);
+        c->accel.tlasRoot = SKH_REF_INVALID;
         return SKH_OK;
     }
     DevBuf dLeafInst, dLeafLo, dLeafHi, dLeafGrp, dTinstTmp;
@@ -1331,19 +1331,19 @@ static skh_status build_tlas_gpu(skh_context* c, const BakePlan& p, const TriBui
     SKH_CHECK(dev_alloc(c, dLeafHi, sizeof(float4) * (size_t)nLeaves));
     SKH_CHECK(dev_alloc(c, dLeafGrp, sizeof(uint32_t) * (size_t)nLeaves));
     SKH_CHECK(dev_alloc(c, dTinstTmp, sizeof(DevInstance) * (size_t)nLeaves));
-    SKH_CHECK(dev_alloc(c, c->dTravInst, sizeof(DevInstance) * (size_t)nLeaves));
-    k_tlas_leaves<<<(nLeaves + B - 1) / B, B, 0, st>>>(dLeafInst.as<uint32_t>(), nLeaves, c->dDevInst.as<DevInstance>(), sx.boxLo.as<float4>(),
+    SKH_CHECK(dev_alloc(c, c->accel.dTravInst, sizeof(DevInstance) * (size_t)nLeaves));
+    k_tlas_leaves<<<(nLeaves + B - 1) / B, B, 0, st>>>(dLeafInst.as<uint32_t>(), nLeaves, c->accel.dDevInst.as<DevInstance>(), sx.boxLo.as<float4>(),
                                                        sx.boxHi.as<float4>(), dLeafLo.as<float4>(), dLeafHi.as<float4>(), dLeafGrp.as<uint32_t>(),
                                                        dTinstTmp.as<DevInstance>());
     SKH_CHECK(lbvh_build(c, nLeaves, 1, std::vector<uint32_t>{ nLeaves }, dLeafLo.as<float4>(), dLeafHi.as<float4>(), dLeafGrp.as<uint32_t>(), 1, true, tlasOut, 1));
     // traversal records into leaf order (a TLAS leaf ref carries its position: sc.tinst + first)
     k_permute_instances<<<(nLeaves + B - 1) / B, B, 0, st>>>(dTinstTmp.as<DevInstance>(), tlasOut.sortedVals.as<uint32_t>(), nLeaves,
-                                                             c->dTravInst.as<DevInstance>());
-    c->tlasRoot = tlasOut.hostGroupRoot[0];
-    c->dTlasNodes = std::move(tlasOut.nodes);
-    c->tlasLevelStart = tlasOut.levelStart; // (skh_update_accel refits the TLAS level by level; its leaf order is the one dTravInst holds)
+                                                             c->accel.dTravInst.as<DevInstance>());
+    c->accel.tlasRoot = tlasOut.hostGroupRoot[0];
+    c->accel.dTlasNodes = std::move(tlasOut.nodes);
+    c->accel.tlasLevelStart = tlasOut.levelStart; // (skh_update_accel refits the TLAS level by level; its leaf order is the one dTravInst holds)
     if (getenv("SKH_DEBUG"))
-        fprintf(stderr, "[skh] TLAS (GPU PLOC): %u instances, %u leaves, %u nodes, root %d\n", nInst, nLeaves, tlasOut.numNodes, c->tlasRoot);
+        fprintf(stderr, "[skh] TLAS (GPU PLOC): %u instances, %u leaves, %u nodes, root %d\n", nInst, nLeaves, tlasOut.numNodes, c->accel.tlasRoot);
     return SKH_OK;
 }
 
@@ -1356,17 +1356,17 @@ static skh_status build_tlas_gpu(skh_context* c, const BakePlan& p, const TriBui
 static skh_status open_tlas_leaves(skh_context* c, const std::vector<DevInstance>& hinst, const std::vector<float4>& hlo, const std::vector<float4>& hhi,
                                    std::vector<HostBox>& hb, std::vector<uint32_t>& ids, std::vector<DevInstance>& tinst)
 {
-    const uint32_t nInst = c->nInstances;
+    const uint32_t nInst = c->scene.nInstances;
     std::vector<Node4> hTri, hSeg;
-    const bool open = c->tlasOpen > 1;
+    const bool open = c->opt.tlasOpen > 1;
     if (open)
     {
-        hTri.resize(c->triNumNodes);
-        hSeg.resize(c->segNumNodes);
+        hTri.resize(c->accel.triNumNodes);
+        hSeg.resize(c->accel.segNumNodes);
         if (!hTri.empty())
-            SKH_TRY(c, hipMemcpy(hTri.data(), c->dTriNodes.p, sizeof(Node4) * hTri.size(), hipMemcpyDeviceToHost));
+            SKH_TRY(c, hipMemcpy(hTri.data(), c->accel.dTriNodes.p, sizeof(Node4) * hTri.size(), hipMemcpyDeviceToHost));
         if (!hSeg.empty())
-            SKH_TRY(c, hipMemcpy(hSeg.data(), c->dSegNodes.p, sizeof(Node4) * hSeg.size(), hipMemcpyDeviceToHost));
+            SKH_TRY(c, hipMemcpy(hSeg.data(), c->accel.dSegNodes.p, sizeof(Node4) * hSeg.size(), hipMemcpyDeviceToHost));
     }
     struct Ref
     {
@@ -1388,7 +1388,7 @@ static skh_status open_tlas_leaves(skh_context* c, const std::vector<DevInstance
             ++nValid;
         }
     std::make_heap(heap.begin(), heap.end(), cmp);
-    const size_t budget = open ? (size_t)nValid * c->tlasOpen : (size_t)nValid;
+    const size_t budget = open ? (size_t)nValid * c->opt.tlasOpen : (size_t)nValid;
     while (!heap.empty())
     {
         std::pop_heap(heap.begin(), heap.end(), cmp);
@@ -1401,7 +1401,7 @@ static skh_status open_tlas_leaves(skh_context* c, const std::vector<DevInstance
             continue;
         }
         const Node4& nd = bn[(size_t)r.node];
-        const float* M = c->instances[r.inst].transform; // object -> world, 3x4 row-major
+        const float* M = c->scene.instances[r.inst].transform; // object -> world, 3x4 row-major
         for (int ch = 0; ch < 4; ++ch)
         {
             if (nd.child[ch] == SKH_REF_INVALID)
@@ -1454,38 +1454,38 @@ static skh_status open_tlas_leaves(skh_context* c, const std::vector<DevInstance
         tinst[r].rootRef = done[r].node;
         tinst[r].pad = done[r].inst;
     }
-    c->numTlasLeaves = (uint32_t)done.size();
+    c->accel.numTlasLeaves = (uint32_t)done.size();
     return SKH_OK;
 }
 
 // TLAS on the host: the instance boxes were produced on the device (k_instance_boxes); the sweep runs on the host
 static skh_status build_tlas_host(skh_context* c, const BuildScratch& sx)
 {
-    const uint32_t nInst = c->nInstances;
+    const uint32_t nInst = c->scene.nInstances;
     std::vector<float4> hlo(nInst), hhi(nInst);
     std::vector<DevInstance> hinst(nInst);
-    SKH_TRY(c, hipStreamSynchronize(c->stream));
+    SKH_TRY(c, hipStreamSynchronize(c->dev.stream));
     SKH_TRY(c, hipMemcpy(hlo.data(), sx.boxLo.p, sizeof(float4) * nInst, hipMemcpyDeviceToHost));
     SKH_TRY(c, hipMemcpy(hhi.data(), sx.boxHi.p, sizeof(float4) * nInst, hipMemcpyDeviceToHost));
-    SKH_TRY(c, hipMemcpy(hinst.data(), c->dDevInst.p, sizeof(DevInstance) * nInst, hipMemcpyDeviceToHost));
+    SKH_TRY(c, hipMemcpy(hinst.data(), c->accel.dDevInst.p, sizeof(DevInstance) * nInst, hipMemcpyDeviceToHost));
     std::vector<HostBox> hb;
     std::vector<uint32_t> ids;
     std::vector<DevInstance> tinst;
     SKH_CHECK(open_tlas_leaves(c, hinst, hlo, hhi, hb, ids, tinst));
-    SKH_CHECK(dev_upload(c, c->dTravInst, tinst.data(), sizeof(DevInstance) * tinst.size()));
+    SKH_CHECK(dev_upload(c, c->accel.dTravInst, tinst.data(), sizeof(DevInstance) * tinst.size()));
     std::vector<Node4> hnodes;
     std::vector<uint32_t> horder;
-    c->tlasRoot = tlas_sah_build(hb, ids, hnodes, horder, c->tlasLevelStart);
+    c->accel.tlasRoot = tlas_sah_build(hb, ids, hnodes, horder, c->accel.tlasLevelStart);
     if (getenv("SKH_DEBUG"))
     {
-        fprintf(stderr, "[skh] TLAS: %u instances, %zu leaves, %zu nodes, root %d\n", nInst, ids.size(), hnodes.size(), c->tlasRoot);
+        fprintf(stderr, "[skh] TLAS: %u instances, %zu leaves, %zu nodes, root %d\n", nInst, ids.size(), hnodes.size(), c->accel.tlasRoot);
         for (uint32_t i = 0; i < std::min((uint32_t)hb.size(), 8u); ++i)
             fprintf(stderr, "[skh]  leaf %u inst %u root %d box %g %g %g .. %g %g %g\n", i, tinst[i].pad, tinst[i].rootRef, hb[i].lo[0], hb[i].lo[1], hb[i].lo[2], hb[i].hi[0], hb[i].hi[1], hb[i].hi[2]);
     }
-    dev_free(c->dTlasNodes);
-    dev_free(c->dTlasInst);
-    SKH_CHECK(dev_upload(c, c->dTlasNodes, hnodes.data(), sizeof(Node4) * hnodes.size()));
-    SKH_CHECK(dev_upload(c, c->dTlasInst, horder.data(), sizeof(uint32_t) * horder.size()));
+    dev_free(c->accel.dTlasNodes);
+    dev_free(c->accel.dTlasInst);
+    SKH_CHECK(dev_upload(c, c->accel.dTlasNodes, hnodes.data(), sizeof(Node4) * hnodes.size()));
+    SKH_CHECK(dev_upload(c, c->accel.dTlasInst, horder.data(), sizeof(uint32_t) * horder.size()));
     return SKH_OK;
 }
 
@@ -1494,18 +1494,18 @@ skh_status skh_build_accel(skh_context* c, uint32_t flags)
     if (!c)
         return SKH_INVALID_ARGUMENT;
     spec_drop(c);
-    (void)hipSetDevice(c->device);
+    (void)hipSetDevice(c->dev.device);
     SKH_CHECK(build_shading_tables(c));
     SKH_CHECK(check_instance_ids(c));
-    c->updateReady = false;
-    const bool usePloc = (flags & SKH_BUILD_SAH) != 0 || c->buildQuality != 0;
+    c->accel.updateReady = false;
+    const bool usePloc = (flags & SKH_BUILD_SAH) != 0 || c->opt.buildQuality != 0;
     const auto t0 = std::chrono::steady_clock::now();
-    const uint32_t nInst = c->nInstances;
+    const uint32_t nInst = c->scene.nInstances;
     BakePlan plan = plan_bake(c);
-    c->builtInvOk = plan.invOk;
-    c->baked = plan.baked;
-    c->nBakedTris = plan.nBakedG[0] + plan.nBakedG[1];
-    c->nBakedInst = (uint32_t)plan.wInst.size();
+    c->accel.builtInvOk = plan.invOk;
+    c->accel.baked = plan.baked;
+    c->accel.nBakedTris = plan.nBakedG[0] + plan.nBakedG[1];
+    c->accel.nBakedInst = (uint32_t)plan.wInst.size();
     // (declared before the stages run: whatever a stage allocated is freed when this function returns, by any exit)
     BuildScratch sx;
     TriBuild tri;
@@ -1518,15 +1518,15 @@ skh_status skh_build_accel(skh_context* c, uint32_t flags)
     // (the host-sweep TLAS path picks its leaves by the device's flags: ADVICE r5).
     bool othersInTlas = false;
     for (uint32_t i = 0; i < nInst; ++i)
-        if (plan.valid[i] && c->instances[i].type != SKH_INSTANCE_CURVE)
+        if (plan.valid[i] && c->scene.instances[i].type != SKH_INSTANCE_CURVE)
         {
             const std::vector<int>& roots = tri.out.hostGroupRoot;
-            othersInTlas = othersInTlas || (c->instances[i].geom_id < roots.size() && roots[c->instances[i].geom_id] != SKH_REF_INVALID);
+            othersInTlas = othersInTlas || (c->scene.instances[i].geom_id < roots.size() && roots[c->scene.instances[i].geom_id] != SKH_REF_INVALID);
         }
-    const bool worldCurveKernel = plan.worldCurves && c->worldKernel && !othersInTlas;
+    const bool worldCurveKernel = plan.worldCurves && c->opt.worldKernel && !othersInTlas;
     if (!worldCurveKernel)
         plan.mergedGroups.clear(); // (every curve instance keeps its TLAS leaf and its set's own tree)
-    c->builtMergedGroups = plan.mergedGroups;
+    c->accel.builtMergedGroups = plan.mergedGroups;
     group_curve_segments(c, plan.mergedGroups, ct);
     SKH_CHECK(build_curve_tree(c, usePloc, ct, sx, cur));
     assign_world_curves(c, worldCurveKernel, plan, cur); // (plan.valid is final from here on)
@@ -1534,34 +1534,34 @@ skh_status skh_build_accel(skh_context* c, uint32_t flags)
     uint32_t nValidHost = 0;
     for (uint32_t i = 0; i < nInst; ++i)
         nValidHost += plan.valid[i] ? 1u : 0u;
-    const bool tlasOnGpu = c->tlasBuild == 1 || (c->tlasBuild == 2 && nValidHost > 8192u);
-    if (nInst > 0 && tlasOnGpu && c->tlasOpen <= 1)
+    const bool tlasOnGpu = c->opt.tlasBuild == 1 || (c->opt.tlasBuild == 2 && nValidHost > 8192u);
+    if (nInst > 0 && tlasOnGpu && c->opt.tlasOpen <= 1)
         SKH_CHECK(build_tlas_gpu(c, plan, tri, cur, sx));
     else if (nInst > 0)
         SKH_CHECK(build_tlas_host(c, sx));
     else
     {
-        dev_free(c->dTlasNodes);
-        dev_free(c->dTlasInst);
-        dev_free(c->dTravInst);
-        c->tlasRoot = SKH_REF_INVALID;
-        c->tlasLevelStart.clear();
+        dev_free(c->accel.dTlasNodes);
+        dev_free(c->accel.dTlasInst);
+        dev_free(c->accel.dTravInst);
+        c->accel.tlasRoot = SKH_REF_INVALID;
+        c->accel.tlasLevelStart.clear();
     }
     if (getenv("SKH_DEBUG"))
-        fprintf(stderr, "[skh] bake_world %u: %u of %u instances baked, %u + %u world-space triangles, roots %d %d; %u object-space triangles; TLAS root %d\n", c->bakeWorld,
-                c->nBakedInst, nInst, plan.nBakedG[0], plan.nBakedG[1], c->worldRoot, c->lightRoot, tri.nMeshTris, c->tlasRoot);
+        fprintf(stderr, "[skh] bake_world %u: %u of %u instances baked, %u + %u world-space triangles, roots %d %d; %u object-space triangles; TLAS root %d\n", c->opt.bakeWorld,
+                c->accel.nBakedInst, nInst, plan.nBakedG[0], plan.nBakedG[1], c->accel.worldRoot, c->accel.lightRoot, tri.nMeshTris, c->accel.tlasRoot);
     // k_instance_boxes' inputs for skh_update_accel (the previous build's are freed with this call's temporaries)
-    std::swap(c->dTriGroupRoot, tri.out.groupRoot);
-    std::swap(c->dTriGroupBounds, tri.out.groupBounds);
-    std::swap(c->dSegGroupRoot, cur.out.groupRoot);
-    std::swap(c->dSegGroupBounds, cur.out.groupBounds);
-    SKH_TRY(c, hipStreamSynchronize(c->stream));
+    std::swap(c->accel.dTriGroupRoot, tri.out.groupRoot);
+    std::swap(c->accel.dTriGroupBounds, tri.out.groupBounds);
+    std::swap(c->accel.dSegGroupRoot, cur.out.groupRoot);
+    std::swap(c->accel.dSegGroupBounds, cur.out.groupBounds);
+    SKH_TRY(c, hipStreamSynchronize(c->dev.stream));
     SKH_TRY(c, hipGetLastError());
-    c->accelBuilt = true;
-    c->builtInstances = c->instances;
-    c->vertsEdited = false;
-    c->updateReady = true;
-    c->msBuild = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    c->accel.built = true;
+    c->accel.builtInstances = c->scene.instances;
+    c->accel.vertsEdited = false;
+    c->accel.updateReady = true;
+    c->accel.msBuild = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
     return SKH_OK;
 }
 
@@ -1580,42 +1580,42 @@ skh_status skh_build_accel(skh_context* c, uint32_t flags)
 static skh_status update_stages(skh_context* c, bool verts, bool moved, const std::vector<float>& w2o, uint32_t kind)
 {
     const auto t0 = std::chrono::steady_clock::now();
-    hipStream_t st = c->stream;
+    hipStream_t st = c->dev.stream;
     const uint32_t B = 256;
-    const uint32_t nInst = c->nInstances, nMeshes = (uint32_t)c->meshes.size(), nCurves = (uint32_t)c->curves.size();
+    const uint32_t nInst = c->scene.nInstances, nMeshes = (uint32_t)c->scene.meshes.size(), nCurves = (uint32_t)c->scene.curves.size();
     DevBuf dRefs, dOut;
-    if (nInst != c->builtInstances.size() || c->instances.size() != nInst)
+    if (nInst != c->accel.builtInstances.size() || c->scene.instances.size() != nInst)
     {
         // (the records below -- dDevInst, the validity flags, the TLAS leaves -- are the build's, sized by its instance count; the callers admit nothing else)
-        c->err = std::string(kind == 1 ? "skh_refit_accel" : "skh_update_accel") + ": the instance table does not have the built count";
+        c->dev.err = std::string(kind == 1 ? "skh_refit_accel" : "skh_update_accel") + ": the instance table does not have the built count";
         return SKH_INVALID_ARGUMENT;
     }
     SKH_CHECK(build_shading_tables(c)); // (normals, tangents, uvs may have changed with the positions; the instance copy carries the transforms)
     // ---- bottom level: the triangle tree (baked world-space triangles move with their instances) and the curve tree ----
-    const bool tris = (verts || (moved && c->nBakedTris > 0)) && c->nTriSlots > 0;
+    const bool tris = (verts || (moved && c->accel.nBakedTris > 0)) && c->accel.nTriSlots > 0;
     if (tris)
     {
         launch_gather_tris(c);
-        SKH_CHECK(dev_alloc(c, c->dTriNodeBox, sizeof(float4) * 2 * (size_t)std::max(1u, c->triNumNodes)));
-        const TriLeaves leaves{ c->dTris.as<float4>() };
-        launch_refit_levels(c, c->triLevelStart, c->dTriNodes, c->dTriNodeBox, leaves);
+        SKH_CHECK(dev_alloc(c, c->accel.dTriNodeBox, sizeof(float4) * 2 * (size_t)std::max(1u, c->accel.triNumNodes)));
+        const TriLeaves leaves{ c->accel.dTris.as<float4>() };
+        launch_refit_levels(c, c->accel.triLevelStart, c->accel.dTriNodes, c->accel.dTriNodeBox, leaves);
         // the BLASes' root boxes: k_instance_boxes' input from now on
-        k_ref_boxes<<<(nMeshes + 2u + 63u) / 64u, 64, 0, st>>>(c->dTriGroupRoot.as<int>(), nMeshes + 2u, leaves, c->dTriNodeBox.as<float4>(), c->dTriGroupBounds.as<float>());
+        k_ref_boxes<<<(nMeshes + 2u + 63u) / 64u, 64, 0, st>>>(c->accel.dTriGroupRoot.as<int>(), nMeshes + 2u, leaves, c->accel.dTriNodeBox.as<float4>(), c->accel.dTriGroupBounds.as<float>());
     }
-    const bool segs = c->curvePointsEdited && c->nSubBuilt > 0;
+    const bool segs = c->accel.curvePointsEdited && c->accel.nSubBuilt > 0;
     if (segs)
     {
         // leaf records (control points, bounding cylinders) gathered again from the new points, boxes level by level
         launch_gather_segs(c, 0u);
-        SKH_CHECK(dev_alloc(c, c->dSegNodeBox, sizeof(float4) * 2 * (size_t)std::max(1u, c->segNumNodes)));
-        const CurveLeaves leaves{ c->dSegs.as<float4>(), c->curveSplitBuilt };
-        launch_refit_levels(c, c->segLevelStart, c->dSegNodes, c->dSegNodeBox, leaves);
-        k_ref_boxes<<<(nCurves + SKH_WORLD_CURVES + 63u) / 64u, 64, 0, st>>>(c->dSegGroupRoot.as<int>(), nCurves + SKH_WORLD_CURVES, leaves, c->dSegNodeBox.as<float4>(),
-                                                                             c->dSegGroupBounds.as<float>());
+        SKH_CHECK(dev_alloc(c, c->accel.dSegNodeBox, sizeof(float4) * 2 * (size_t)std::max(1u, c->accel.segNumNodes)));
+        const CurveLeaves leaves{ c->accel.dSegs.as<float4>(), c->accel.curveSplitBuilt };
+        launch_refit_levels(c, c->accel.segLevelStart, c->accel.dSegNodes, c->accel.dSegNodeBox, leaves);
+        k_ref_boxes<<<(nCurves + SKH_WORLD_CURVES + 63u) / 64u, 64, 0, st>>>(c->accel.dSegGroupRoot.as<int>(), nCurves + SKH_WORLD_CURVES, leaves, c->accel.dSegNodeBox.as<float4>(),
+                                                                             c->accel.dSegGroupBounds.as<float>());
     }
-    c->curvePointsEdited = false;
+    c->accel.curvePointsEdited = false;
     // ---- instance records and boxes, then the top level ----
-    const bool tlas = c->tlasRoot != SKH_REF_INVALID && nInst > 0 && (moved || tris || segs); // (the instance stage runs, and with it the TLAS refit)
+    const bool tlas = c->accel.tlasRoot != SKH_REF_INVALID && nInst > 0 && (moved || tris || segs); // (the instance stage runs, and with it the TLAS refit)
     if (nInst > 0 && (moved || tlas))
     {
         std::vector<float> w2oNow;
@@ -1624,44 +1624,44 @@ static skh_status update_stages(skh_context* c, bool verts, bool moved, const st
         {
             w2oNow.resize(12 * (size_t)nInst);
             for (uint32_t i = 0; i < nInst; ++i)
-                (void)invert_affine(c->instances[i].transform, &w2oNow[12 * (size_t)i]);
+                (void)invert_affine(c->scene.instances[i].transform, &w2oNow[12 * (size_t)i]);
             W = &w2oNow;
         }
-        SKH_CHECK(dev_upload(c, c->dW2o, W->data(), sizeof(float) * 12 * (size_t)nInst));
-        SKH_CHECK(dev_alloc(c, c->dInstLo, sizeof(float4) * (size_t)nInst));
-        SKH_CHECK(dev_alloc(c, c->dInstHi, sizeof(float4) * (size_t)nInst));
-        SKH_CHECK(dev_alloc(c, c->dInstGrp, sizeof(uint32_t) * (size_t)nInst));
-        launch_instance_boxes(c, c->dW2o, c->dTriGroupBounds, c->dTriGroupRoot, c->dSegGroupBounds, c->dSegGroupRoot, c->dInstLo, c->dInstHi, c->dInstGrp);
+        SKH_CHECK(dev_upload(c, c->accel.dW2o, W->data(), sizeof(float) * 12 * (size_t)nInst));
+        SKH_CHECK(dev_alloc(c, c->accel.dInstLo, sizeof(float4) * (size_t)nInst));
+        SKH_CHECK(dev_alloc(c, c->accel.dInstHi, sizeof(float4) * (size_t)nInst));
+        SKH_CHECK(dev_alloc(c, c->accel.dInstGrp, sizeof(uint32_t) * (size_t)nInst));
+        launch_instance_boxes(c, c->accel.dW2o, c->accel.dTriGroupBounds, c->accel.dTriGroupRoot, c->accel.dSegGroupBounds, c->accel.dSegGroupRoot, c->accel.dInstLo, c->accel.dInstHi, c->accel.dInstGrp);
         if (tlas)
         {
-            k_tlas_records<<<(c->numTlasLeaves + B - 1) / B, B, 0, st>>>(c->dTravInst.as<DevInstance>(), c->numTlasLeaves, c->dDevInst.as<DevInstance>());
-            const uint32_t nNodes = c->tlasLevelStart.empty() ? 0u : c->tlasLevelStart.back();
-            SKH_CHECK(dev_alloc(c, c->dTlasNodeBox, sizeof(float4) * 2 * (size_t)std::max(1u, nNodes)));
-            const TlasLeaves leaves{ c->dTravInst.as<DevInstance>(), c->dInstLo.as<float4>(), c->dInstHi.as<float4>() };
-            launch_refit_levels(c, c->tlasLevelStart, c->dTlasNodes, c->dTlasNodeBox, leaves);
+            k_tlas_records<<<(c->accel.numTlasLeaves + B - 1) / B, B, 0, st>>>(c->accel.dTravInst.as<DevInstance>(), c->accel.numTlasLeaves, c->accel.dDevInst.as<DevInstance>());
+            const uint32_t nNodes = c->accel.tlasLevelStart.empty() ? 0u : c->accel.tlasLevelStart.back();
+            SKH_CHECK(dev_alloc(c, c->accel.dTlasNodeBox, sizeof(float4) * 2 * (size_t)std::max(1u, nNodes)));
+            const TlasLeaves leaves{ c->accel.dTravInst.as<DevInstance>(), c->accel.dInstLo.as<float4>(), c->accel.dInstHi.as<float4>() };
+            launch_refit_levels(c, c->accel.tlasLevelStart, c->accel.dTlasNodes, c->accel.dTlasNodeBox, leaves);
         }
     }
     // ---- the box the host keeps: around the baked light proxies (radiance rays that miss it skip their tree) ----
     float gb[12];
     if (tris)
     {
-        const int refs[2] = { c->worldRoot, c->lightRoot };
+        const int refs[2] = { c->accel.worldRoot, c->accel.lightRoot };
         SKH_CHECK(dev_upload(c, dRefs, refs, sizeof(refs)));
         SKH_CHECK(dev_alloc(c, dOut, sizeof(gb)));
-        k_ref_boxes<<<1, 64, 0, st>>>(dRefs.as<int>(), 2u, TriLeaves{ c->dTris.as<float4>() }, c->dTriNodeBox.as<float4>(), dOut.as<float>()); // (INVALID roots give empty boxes)
+        k_ref_boxes<<<1, 64, 0, st>>>(dRefs.as<int>(), 2u, TriLeaves{ c->accel.dTris.as<float4>() }, c->accel.dTriNodeBox.as<float4>(), dOut.as<float>()); // (INVALID roots give empty boxes)
         SKH_TRY(c, hipMemcpyAsync(gb, dOut.p, sizeof(gb), hipMemcpyDeviceToHost, st));
     }
     SKH_TRY(c, hipStreamSynchronize(st));
     SKH_TRY(c, hipGetLastError());
     if (tris)
-        set_light_box(c, c->lightRoot != SKH_REF_INVALID && c->nGroup1Built != 0u, gb + 6);
-    c->builtInstances = c->instances;
-    c->vertsEdited = false;
-    c->accelBuilt = true;
-    c->buildInfo.refit = kind;
-    c->msRefit = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
-    c->buildInfo.ms_refit = c->msRefit;
-    c->refits++;
+        set_light_box(c, c->accel.lightRoot != SKH_REF_INVALID && c->accel.nGroup1Built != 0u, gb + 6);
+    c->accel.builtInstances = c->scene.instances;
+    c->accel.vertsEdited = false;
+    c->accel.built = true;
+    c->accel.buildInfo.refit = kind;
+    c->accel.msRefit = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    c->accel.buildInfo.ms_refit = c->accel.msRefit;
+    c->accel.refits++;
     return SKH_OK;
 }
 // (an update that fails leaves no hierarchy behind: the next call builds)
@@ -1670,7 +1670,7 @@ static skh_status update_in_place(skh_context* c, bool verts /* vertices may hav
 {
     const skh_status s = update_stages(c, verts, moved, w2o, kind);
     if (s != SKH_OK)
-        c->accelBuilt = false, c->refitReady = false, c->updateReady = false;
+        touched(c, skh_stale::IN_FAILED_UPDATE);
     return s;
 }
 
@@ -1681,16 +1681,16 @@ skh_status skh_refit_accel(skh_context* c)
     if (!c)
         return SKH_INVALID_ARGUMENT;
     spec_drop(c);
-    (void)hipSetDevice(c->device);
+    (void)hipSetDevice(c->dev.device);
     // (curves: control points and radii may have changed -- skh_set_curves with the built sets' table and vertex counts --; their tree is refitted the same way)
-    const bool curvesOk = c->curves.empty() ? c->nSubBuilt == 0 : (c->curveRefitReady && c->curveSig == c->builtCurveSig);
-    const bool sameInstances = c->instances.size() == c->builtInstances.size() &&
-                               (c->instances.empty() || memcmp(c->instances.data(), c->builtInstances.data(), sizeof(skh_instance) * c->instances.size()) == 0);
-    const bool can = c->refitReady && c->updateReady && c->geomSig == c->builtGeomSig && c->nVerts == c->builtNVerts && c->tlasRoot == SKH_REF_INVALID && curvesOk &&
-                     sameInstances && (c->triNumNodes > 0 || c->segNumNodes > 0);
-    c->buildInfo.refit = 0;
+    const bool curvesOk = c->scene.curves.empty() ? c->accel.nSubBuilt == 0 : (c->accel.curveRefitReady && c->scene.curveSig == c->accel.builtCurveSig);
+    const bool sameInstances = c->scene.instances.size() == c->accel.builtInstances.size() &&
+                               (c->scene.instances.empty() || memcmp(c->scene.instances.data(), c->accel.builtInstances.data(), sizeof(skh_instance) * c->scene.instances.size()) == 0);
+    const bool can = c->accel.refitReady && c->accel.updateReady && c->scene.geomSig == c->accel.builtGeomSig && c->scene.nVerts == c->accel.builtNVerts && c->accel.tlasRoot == SKH_REF_INVALID && curvesOk &&
+                     sameInstances && (c->accel.triNumNodes > 0 || c->accel.segNumNodes > 0);
+    c->accel.buildInfo.refit = 0;
     if (!can)
-        return skh_build_accel(c, c->lastBuildFlags);
+        return skh_build_accel(c, c->accel.lastBuildFlags);
     return update_in_place(c, true, false, std::vector<float>(), 1u);
 }
 
@@ -1699,34 +1699,34 @@ static const char* update_blocker(const skh_context* c, const skh_instance* in, 
 {
     static const float kIdentity[12] = { 1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0 };
     moved = false;
-    if (!c->refitReady || !c->updateReady)
+    if (!c->accel.refitReady || !c->accel.updateReady)
         return "no build since the context was created or an option changed";
-    if (c->geomSig != c->builtGeomSig || c->nVerts != c->builtNVerts)
+    if (c->scene.geomSig != c->accel.builtGeomSig || c->scene.nVerts != c->accel.builtNVerts)
         return "another mesh table or index buffer";
-    if (!(c->curves.empty() ? c->nSubBuilt == 0 : (c->curveRefitReady && c->curveSig == c->builtCurveSig)))
+    if (!(c->scene.curves.empty() ? c->accel.nSubBuilt == 0 : (c->accel.curveRefitReady && c->scene.curveSig == c->accel.builtCurveSig)))
         return "another curve-set table or vertex counts, or the segment-node curve build";
-    if (c->tlasOpen > 1)
+    if (c->opt.tlasOpen > 1)
         return "tlas_open > 1 (opened TLAS leaves are BLAS subtrees)";
-    if (n != c->builtInstances.size())
+    if (n != c->accel.builtInstances.size())
         return "another instance count";
     w2o.resize(12 * (size_t)std::max(1u, n));
     for (uint32_t i = 0; i < n; ++i)
     {
-        const skh_instance &a = in[i], &b = c->builtInstances[i];
+        const skh_instance &a = in[i], &b = c->accel.builtInstances[i];
         if (a.type != b.type || a.geom_id != b.geom_id || a.material_id != b.material_id || a.light_id != b.light_id)
             return "an instance's type, geom_id, material_id or light_id";
-        if (invert_affine(a.transform, &w2o[12 * (size_t)i]) != (c->builtInvOk[i] != 0))
+        if (invert_affine(a.transform, &w2o[12 * (size_t)i]) != (c->accel.builtInvOk[i] != 0))
             return "a transform that became singular, or stopped being singular";
         moved = moved || memcmp(a.transform, b.transform, sizeof(a.transform)) != 0;
     }
     // decisions the build took from the transforms: which world-curve entry sits under a bit-exact identity (SKH_REF_CURVEROOT_IDENT), which curve instances share one
-    for (uint32_t k = 0; k < c->numWorldCurves; ++k)
+    for (uint32_t k = 0; k < c->accel.numWorldCurves; ++k)
     {
-        const uint32_t i = c->worldCurveInst[k];
-        if ((memcmp(in[i].transform, kIdentity, sizeof(kIdentity)) == 0) != (memcmp(c->builtInstances[i].transform, kIdentity, sizeof(kIdentity)) == 0))
+        const uint32_t i = c->accel.worldCurveInst[k];
+        if ((memcmp(in[i].transform, kIdentity, sizeof(kIdentity)) == 0) != (memcmp(c->accel.builtInstances[i].transform, kIdentity, sizeof(kIdentity)) == 0))
             return "a world-curve entry that left or reached the identity transform";
     }
-    for (const std::vector<uint32_t>& grp : c->builtMergedGroups)
+    for (const std::vector<uint32_t>& grp : c->accel.builtMergedGroups)
         for (uint32_t i : grp)
             if (memcmp(in[i].transform, in[grp[0]].transform, sizeof(in[i].transform)) != 0)
                 return "a merged curve group whose members no longer share one transform";
@@ -1738,42 +1738,41 @@ skh_status skh_update_accel(skh_context* c, const skh_instance* instances, uint3
     if (!c || (n_instances && !instances))
         return SKH_INVALID_ARGUMENT;
     spec_drop(c);
-    (void)hipSetDevice(c->device);
-    const skh_instance* in = instances ? instances : c->instances.data();
-    const uint32_t n = instances ? n_instances : (uint32_t)c->instances.size();
+    (void)hipSetDevice(c->dev.device);
+    const skh_instance* in = instances ? instances : c->scene.instances.data();
+    const uint32_t n = instances ? n_instances : (uint32_t)c->scene.instances.size();
     std::vector<float> w2o;
     bool moved = false;
     const char* why = update_blocker(c, in, n, w2o, moved);
-    c->buildInfo.refit = 0;
+    c->accel.buildInfo.refit = 0;
     if (why)
     {
         if (getenv("SKH_DEBUG"))
             fprintf(stderr, "[skh] skh_update_accel: full build (%s)\n", why);
         skh_status s = instances ? skh_set_instances(c, instances, n_instances) : SKH_OK;
-        return s != SKH_OK ? s : skh_build_accel(c, c->lastBuildFlags);
+        return s != SKH_OK ? s : skh_build_accel(c, c->accel.lastBuildFlags);
     }
     if (instances)
     {
-        c->emitStale = true; // (the emitter table is in world space: it moves with the instances)
-        c->cutStale = true;
+        touched(c, skh_stale::IN_UPDATED_INSTANCES);
         // (the table replaces whatever skh_set_instances set since the build -- which may have had another count: n is the built count here)
-        c->instances.assign(instances, instances + n);
-        c->nInstances = n;
-        const skh_status s = dev_upload(c, c->dInstances, instances, sizeof(skh_instance) * (size_t)n);
+        c->scene.instances.assign(instances, instances + n);
+        c->scene.nInstances = n;
+        const skh_status s = dev_upload(c, c->scene.dInstances, instances, sizeof(skh_instance) * (size_t)n);
         if (s != SKH_OK)
         {
-            c->accelBuilt = false, c->refitReady = false, c->updateReady = false;
+            touched(c, skh_stale::IN_FAILED_UPDATE);
             return s;
         }
     }
-    return update_in_place(c, c->vertsEdited, moved, w2o, 2u);
+    return update_in_place(c, c->accel.vertsEdited, moved, w2o, 2u);
 }
 
 skh_status skh_get_baked(skh_context* c, uint8_t* flags, uint32_t n_instances, uint32_t* out_baked_instances, uint32_t* out_baked_triangles)
 {
     if (!c)
         return SKH_INVALID_ARGUMENT;
-    if (!c->accelBuilt)
+    if (!c->accel.built)
     {
         const skh_status s = skh_build_accel(c, SKH_BUILD_LBVH);
         if (s != SKH_OK)
@@ -1782,10 +1781,10 @@ skh_status skh_get_baked(skh_context* c, uint8_t* flags, uint32_t n_instances, u
     const bool on = true;
     if (flags)
         for (uint32_t i = 0; i < n_instances; ++i)
-            flags[i] = (on && i < c->nInstances && i < c->baked.size()) ? c->baked[i] : 0;
+            flags[i] = (on && i < c->scene.nInstances && i < c->accel.baked.size()) ? c->accel.baked[i] : 0;
     if (out_baked_instances)
-        *out_baked_instances = on ? c->nBakedInst : 0u;
+        *out_baked_instances = on ? c->accel.nBakedInst : 0u;
     if (out_baked_triangles)
-        *out_baked_triangles = on ? c->nBakedTris : 0u;
+        *out_baked_triangles = on ? c->accel.nBakedTris : 0u;
     return SKH_OK;
 }

@@ -71,7 +71,7 @@ skh_status skh_probe_memory(skh_context* c, uint32_t kind, uint64_t bytes, uint3
     if (!c || kind > SKH_PROBE_CHASE || bytes < (1u << 20) || !out_gbps ||
         (kind != SKH_PROBE_COPY && record_bytes != 32 && record_bytes != 64 && record_bytes != 128))
         return SKH_INVALID_ARGUMENT;
-    (void)hipSetDevice(c->device);
+    (void)hipSetDevice(c->dev.device);
     DevBuf a, b;
     const size_t n16 = (size_t)(bytes / 64) * 4; // uint4 elements, whole 64-byte records
     SKH_CHECK(dev_alloc(c, a, n16 * 16));
@@ -89,24 +89,24 @@ skh_status skh_probe_memory(skh_context* c, uint32_t kind, uint64_t bytes, uint3
         }
     } ev;
     hipEvent_t &e0 = ev.e0, &e1 = ev.e1;
-    const uint32_t grid = (uint32_t)c->numCUs * c->wavesPerCU; // the trace kernels' grid
+    const uint32_t grid = (uint32_t)c->dev.numCUs * c->opt.wavesPerCU; // the trace kernels' grid
     const uint32_t perLane = 256;
     repeat = std::max(1u, repeat);
-    k_probe_fill<<<c->numCUs * 8, 256, 0, c->stream>>>(a.as<uint4>(), n16);
+    k_probe_fill<<<c->dev.numCUs * 8, 256, 0, c->dev.stream>>>(a.as<uint4>(), n16);
     double moved = 0.0;
     for (uint32_t r = 0; r <= repeat; ++r) // (pass 0 is the warm-up)
     {
         if (r == 1)
         {
-            if (hipEventCreate(&e0) != hipSuccess || hipEventCreate(&e1) != hipSuccess || hipEventRecord(e0, c->stream) != hipSuccess)
+            if (hipEventCreate(&e0) != hipSuccess || hipEventCreate(&e1) != hipSuccess || hipEventRecord(e0, c->dev.stream) != hipSuccess)
             {
-                c->err = "skh_probe_memory: hipEvent";
+                c->dev.err = "skh_probe_memory: hipEvent";
                 return SKH_FAIL;
             }
         }
         if (kind == SKH_PROBE_COPY)
         {
-            k_probe_copy<<<c->numCUs * 16, 256, 0, c->stream>>>(a.as<uint4>(), b.as<uint4>(), n16);
+            k_probe_copy<<<c->dev.numCUs * 16, 256, 0, c->dev.stream>>>(a.as<uint4>(), b.as<uint4>(), n16);
             moved = 2.0 * 16.0 * (double)n16;
         }
         else
@@ -116,14 +116,14 @@ skh_status skh_probe_memory(skh_context* c, uint32_t kind, uint64_t bytes, uint3
             // (the build by dependence and uint4s per record)
             static const decltype(&k_probe_gather<false, 2>) kGather[2][3] = { { k_probe_gather<false, 2>, k_probe_gather<false, 4>, k_probe_gather<false, 8> },
                                                                                 { k_probe_gather<true, 2>, k_probe_gather<true, 4>, k_probe_gather<true, 8> } };
-            kGather[kind == SKH_PROBE_CHASE ? 1 : 0][record_bytes == 32 ? 0 : record_bytes == 64 ? 1 : 2]<<<grid, SKH_TRACE_BLOCK, 0, c->stream>>>(a.as<uint4>(), nRec, perLane, sink);
+            kGather[kind == SKH_PROBE_CHASE ? 1 : 0][record_bytes == 32 ? 0 : record_bytes == 64 ? 1 : 2]<<<grid, SKH_TRACE_BLOCK, 0, c->dev.stream>>>(a.as<uint4>(), nRec, perLane, sink);
             moved = (double)record_bytes * perLane * SKH_TRACE_BLOCK * (double)grid;
         }
     }
     float ms = 0.0f;
-    if (hipEventRecord(e1, c->stream) != hipSuccess || hipEventSynchronize(e1) != hipSuccess || hipEventElapsedTime(&ms, e0, e1) != hipSuccess)
+    if (hipEventRecord(e1, c->dev.stream) != hipSuccess || hipEventSynchronize(e1) != hipSuccess || hipEventElapsedTime(&ms, e0, e1) != hipSuccess)
     {
-        c->err = "skh_probe_memory: timing failed";
+        c->dev.err = "skh_probe_memory: timing failed";
         return SKH_FAIL;
     }
     ms /= (float)repeat;
@@ -167,17 +167,17 @@ skh_status skh_bsdf_probe(skh_context* c, const skh_bsdf_query* queries, uint32_
 {
     if (!c || (n && (!queries || !results)))
         return SKH_INVALID_ARGUMENT;
-    (void)hipSetDevice(c->device);
+    (void)hipSetDevice(c->dev.device);
     if (n == 0)
         return SKH_OK;
-    if (c->nMaterials == 0)
+    if (c->scene.nMaterials == 0)
     {
-        c->err = "skh_bsdf_probe: call skh_set_materials first";
+        c->dev.err = "skh_bsdf_probe: call skh_set_materials first";
         return SKH_INVALID_ARGUMENT;
     }
     const ProbeIn in[] = { { queries, sizeof(skh_bsdf_query) * (size_t)n } };
     return probe_roundtrip(c, in, results, sizeof(skh_bsdf_result) * (size_t)n, [&](const DevBuf* d, const DevBuf& dOut) {
-        k_bsdf_probe<<<(n + 127) / 128, 128, 0, c->stream>>>(d[0].as<skh_bsdf_query>(), n, c->dMaterials.as<Material>(), c->nMaterials, dOut.as<skh_bsdf_result>());
+        k_bsdf_probe<<<(n + 127) / 128, 128, 0, c->dev.stream>>>(d[0].as<skh_bsdf_query>(), n, c->scene.dMaterials.as<Material>(), c->scene.nMaterials, dOut.as<skh_bsdf_result>());
     });
 }
 
@@ -285,23 +285,23 @@ skh_status skh_unit_probe(skh_context* c, uint32_t unit, uint32_t param, const v
     if (!c || unit >= SKH_UNIT_COUNT || (n && (!in || !out)) || (kUnitConst[unit] && !consts))
     {
         if (c)
-            c->err = "skh_unit_probe: unknown unit, or a missing input / output / constants pointer";
+            c->dev.err = "skh_unit_probe: unknown unit, or a missing input / output / constants pointer";
         return SKH_INVALID_ARGUMENT;
     }
     const bool envUnit = unit == SKH_UNIT_ENV_SAMPLE || unit == SKH_UNIT_ENV_EVAL;
-    if (envUnit && c->envW == 0)
+    if (envUnit && c->env.w == 0)
     {
-        c->err = "skh_unit_probe: the context has no environment";
+        c->dev.err = "skh_unit_probe: the context has no environment";
         return SKH_INVALID_ARGUMENT;
     }
-    (void)hipSetDevice(c->device);
+    (void)hipSetDevice(c->dev.device);
     if (n == 0)
         return SKH_OK;
     const ProbeIn pin[] = { { in, (size_t)kUnitIn[unit] * n }, { consts, kUnitConst[unit] } }; // (the Sobol tables were uploaded by skh_create)
     return probe_roundtrip(c, pin, out, (size_t)kUnitOut[unit] * n, [&](const DevBuf* d, const DevBuf& dOut) {
         if (envUnit)
-            k_env_probe<<<(n + 255) / 256, 256, 0, c->stream>>>(make_env(c), unit == SKH_UNIT_ENV_SAMPLE ? 1u : 0u, d[0].as<float>(), n, dOut.as<uint32_t>());
+            k_env_probe<<<(n + 255) / 256, 256, 0, c->dev.stream>>>(make_env(c), unit == SKH_UNIT_ENV_SAMPLE ? 1u : 0u, d[0].as<float>(), n, dOut.as<uint32_t>());
         else
-            k_unit_probe<<<(n + 255) / 256, 256, 0, c->stream>>>(unit, param, d[1].as<float>(), d[0].as<uint32_t>(), n, dOut.as<uint32_t>());
+            k_unit_probe<<<(n + 255) / 256, 256, 0, c->dev.stream>>>(unit, param, d[1].as<float>(), d[0].as<uint32_t>(), n, dOut.as<uint32_t>());
     });
 }

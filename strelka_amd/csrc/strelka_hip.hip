@@ -81,26 +81,32 @@ static void spec_drop(skh_context* c, bool keepLast = false, bool keepAdaptive =
     {
         // a whole pass traced ahead that nobody will collect: wait for it (its buffers are about to be reused), take its rays out again
         unsigned long long after[2] = { 0, 0 };
-        (void)hipStreamSynchronize(c->stream);
-        if (hipMemcpy(after, c->dStats.p, sizeof(after), hipMemcpyDeviceToHost) == hipSuccess)
+        (void)hipStreamSynchronize(c->dev.stream);
+        if (hipMemcpy(after, c->timing.dStats.p, sizeof(after), hipMemcpyDeviceToHost) == hipSuccess)
         {
-            c->discardedRadiance += after[0] - sp.statsMark[0];
-            c->discardedShadow += after[1] - sp.statsMark[1];
+            c->spec.discardedRadiance += after[0] - sp.statsMark[0];
+            c->spec.discardedShadow += after[1] - sp.statsMark[1];
         }
-        c->discardedSubframes += sp.nextCount;
+        c->spec.discardedSubframes += sp.nextCount;
         sp.nextInFlight = false;
     }
     if (sp.valid && sp.consumed < sp.count && sp.count > 0)
     {
         const uint32_t left = sp.count - sp.consumed;
-        c->discardedRadiance += sp.passRadiance * left / sp.count;
-        c->discardedShadow += sp.passShadow * left / sp.count;
-        c->discardedSubframes += left;
+        c->spec.discardedRadiance += sp.passRadiance * left / sp.count;
+        c->spec.discardedShadow += sp.passShadow * left / sp.count;
+        c->spec.discardedSubframes += left;
     }
     sp.valid = false;
     sp.buf = 0;
     if (!keepLast)
         sp.haveLast = false;
+}
+
+// Where work on what an earlier pass delivered runs (accumulation steps, tone mapping, image copies): beside a pass traced ahead, not behind it.
+static inline hipStream_t side_stream(const skh_context* c)
+{
+    return c->spec.nextInFlight ? c->dev.stream3 : c->dev.stream;
 }
 
 uint32_t skh_abi_version(void)
@@ -117,16 +123,16 @@ skh_status skh_create(int device_ordinal, skh_context** out_ctx)
     if (hipGetDeviceCount(&count) != hipSuccess || count <= 0 || device_ordinal < 0 || device_ordinal >= count)
         return SKH_FAIL; // no GPU: the product path fails loudly, there is no CPU fallback
     skh_context* c = new skh_context();
-    c->device = device_ordinal;
-    if (hipSetDevice(device_ordinal) != hipSuccess || hipStreamCreate(&c->stream) != hipSuccess || hipStreamCreate(&c->stream2) != hipSuccess || hipStreamCreateWithFlags(&c->stream3, hipStreamNonBlocking) != hipSuccess ||
-        hipEventCreateWithFlags(&c->evShade, hipEventDisableTiming) != hipSuccess || hipEventCreateWithFlags(&c->evShadow, hipEventDisableTiming) != hipSuccess)
+    c->dev.device = device_ordinal;
+    if (hipSetDevice(device_ordinal) != hipSuccess || hipStreamCreate(&c->dev.stream) != hipSuccess || hipStreamCreate(&c->dev.stream2) != hipSuccess || hipStreamCreateWithFlags(&c->dev.stream3, hipStreamNonBlocking) != hipSuccess ||
+        hipEventCreateWithFlags(&c->dev.evShade, hipEventDisableTiming) != hipSuccess || hipEventCreateWithFlags(&c->dev.evShadow, hipEventDisableTiming) != hipSuccess)
     {
         delete c;
         return SKH_FAIL;
     }
     hipDeviceProp_t prop;
     if (hipGetDeviceProperties(&prop, device_ordinal) == hipSuccess)
-        c->numCUs = prop.multiProcessorCount;
+        c->dev.numCUs = prop.multiProcessorCount;
     uint32_t tab[5][32];
     init_sobol_table(tab);
     std::vector<uint32_t> lut(SKH_SOBOL_LUT_WORDS);
@@ -146,14 +152,14 @@ skh_status skh_create(int device_ordinal, skh_context** out_ctx)
         delete c;
         return SKH_FAIL;
     }
-    if (dev_alloc(c, c->dStats, sizeof(StatsDev)) != SKH_OK || hipMemset(c->dStats.p, 0, sizeof(StatsDev)) != hipSuccess ||
-        dev_alloc(c, c->dCutStats, sizeof(CutStatsDev)) != SKH_OK || hipMemset(c->dCutStats.p, 0, sizeof(CutStatsDev)) != hipSuccess ||
-        hipHostMalloc(reinterpret_cast<void**>(&c->hOverflow), 64, hipHostMallocMapped) != hipSuccess)
+    if (dev_alloc(c, c->timing.dStats, sizeof(StatsDev)) != SKH_OK || hipMemset(c->timing.dStats.p, 0, sizeof(StatsDev)) != hipSuccess ||
+        dev_alloc(c, c->cut.dStats, sizeof(CutStatsDev)) != SKH_OK || hipMemset(c->cut.dStats.p, 0, sizeof(CutStatsDev)) != hipSuccess ||
+        hipHostMalloc(reinterpret_cast<void**>(&c->dev.hOverflow), 64, hipHostMallocMapped) != hipSuccess)
     {
         delete c;
         return SKH_FAIL;
     }
-    *c->hOverflow = 0u;
+    *c->dev.hOverflow = 0u;
     *out_ctx = c;
     return SKH_OK;
 }
@@ -162,31 +168,41 @@ void skh_destroy(skh_context* c)
 {
     if (!c)
         return;
-    (void)hipSetDevice(c->device);
-    (void)hipStreamSynchronize(c->stream);
-    if (c->stream3)
-        (void)hipStreamSynchronize(c->stream3);
-    if (c->comm)
+    (void)hipSetDevice(c->dev.device);
+    (void)hipStreamSynchronize(c->dev.stream);
+    if (c->dev.stream3)
+        (void)hipStreamSynchronize(c->dev.stream3);
+    if (c->multi.comm)
         (void)skh_comm_destroy(c);
-    for (hipEvent_t e : c->eventPool)
+    for (hipEvent_t e : c->timing.eventPool)
         (void)hipEventDestroy(e);
-    (void)hipStreamDestroy(c->stream);
-    if (c->stream2)
-        (void)hipStreamDestroy(c->stream2);
-    if (c->stream3)
-        (void)hipStreamDestroy(c->stream3);
-    if (c->evShade)
-        (void)hipEventDestroy(c->evShade);
-    if (c->evShadow)
-        (void)hipEventDestroy(c->evShadow);
-    if (c->hOverflow)
-        (void)hipHostFree(c->hOverflow);
+    (void)hipStreamDestroy(c->dev.stream);
+    if (c->dev.stream2)
+        (void)hipStreamDestroy(c->dev.stream2);
+    if (c->dev.stream3)
+        (void)hipStreamDestroy(c->dev.stream3);
+    if (c->dev.evShade)
+        (void)hipEventDestroy(c->dev.evShade);
+    if (c->dev.evShadow)
+        (void)hipEventDestroy(c->dev.evShadow);
+    if (c->dev.hOverflow)
+        (void)hipHostFree(c->dev.hOverflow);
     delete c; // (frees every device buffer the context owns)
 }
 
 const char* skh_last_error(const skh_context* c)
 {
-    return c ? c->err.c_str() : "null context";
+    return c ? c->dev.err.c_str() : "null context";
+}
+
+// FNV-1a over 32-bit words, continued from h: the topology signatures of skh_set_geometry and skh_set_curves
+static const uint64_t kFnv1aSeed = 1469598103934665603ull;
+static uint64_t fnv1a_words(uint64_t h, const void* words, size_t n)
+{
+    const uint32_t* w = static_cast<const uint32_t*>(words);
+    for (size_t k = 0; k < n; ++k)
+        h = (h ^ w[k]) * 1099511628211ull;
+    return h;
 }
 
 skh_status skh_set_geometry(skh_context* c, const skh_vertex* verts, uint32_t n_verts, const uint32_t* indices, uint32_t n_indices,
@@ -195,14 +211,14 @@ skh_status skh_set_geometry(skh_context* c, const skh_vertex* verts, uint32_t n_
     if (!c || (n_verts && !verts) || (n_indices && !indices) || (n_meshes && !meshes))
         return SKH_INVALID_ARGUMENT;
     spec_drop(c);
-    (void)hipSetDevice(c->device);
+    (void)hipSetDevice(c->dev.device);
     for (uint32_t m = 0; m < n_meshes; ++m)
     {
         const skh_mesh& me = meshes[m];
         if ((uint64_t)me.index_offset + me.index_count > n_indices || (uint64_t)me.vertex_offset + me.vertex_count > n_verts ||
             me.index_count % 3 != 0)
         {
-            c->err = "skh_set_geometry: mesh " + std::to_string(m) + " is out of range";
+            c->dev.err = "skh_set_geometry: mesh " + std::to_string(m) + " is out of range";
             return SKH_INVALID_ARGUMENT;
         }
         // indices are mesh-local (closest_hit.cu:365-376 adds mVbOffset): every one must address a vertex of its own mesh
@@ -212,34 +228,23 @@ skh_status skh_set_geometry(skh_context* c, const skh_vertex* verts, uint32_t n_
             worst = std::max(worst, ib[k]);
         if (me.index_count && worst >= me.vertex_count)
         {
-            c->err = "skh_set_geometry: mesh " + std::to_string(m) + " has index " + std::to_string(worst) + " >= its vertex_count " +
+            c->dev.err = "skh_set_geometry: mesh " + std::to_string(m) + " has index " + std::to_string(worst) + " >= its vertex_count " +
                      std::to_string(me.vertex_count);
             return SKH_INVALID_ARGUMENT;
         }
     }
-    c->meshes.assign(meshes, meshes + n_meshes);
-    c->nVerts = n_verts;
-    c->nIndices = n_indices;
-    c->accelBuilt = false;
-    c->vertsEdited = true;
-    c->emitStale = true;
-    {
-        // signature of the TOPOLOGY (mesh table + index buffer, FNV-1a over their words): skh_refit_accel keeps the hierarchy only while it is the built one
-        uint64_t h = 1469598103934665603ull;
-        auto mix = [&](const uint32_t* w, size_t nw) {
-            for (size_t k = 0; k < nw; ++k)
-                h = (h ^ w[k]) * 1099511628211ull;
-        };
-        mix(reinterpret_cast<const uint32_t*>(meshes), sizeof(skh_mesh) / 4 * (size_t)n_meshes);
-        mix(indices, n_indices);
-        c->geomSig = h ^ ((uint64_t)n_verts << 32);
-    }
+    c->scene.meshes.assign(meshes, meshes + n_meshes);
+    c->scene.nVerts = n_verts;
+    c->scene.nIndices = n_indices;
+    touched(c, skh_stale::IN_GEOMETRY);
+    // signature of the TOPOLOGY (mesh table + index buffer): skh_refit_accel keeps the hierarchy only while it is the built one
+    c->scene.geomSig = fnv1a_words(fnv1a_words(kFnv1aSeed, meshes, sizeof(skh_mesh) / 4 * (size_t)n_meshes), indices, n_indices) ^ ((uint64_t)n_verts << 32);
     skh_status s;
-    if ((s = dev_upload(c, c->dVerts, verts, sizeof(skh_vertex) * (size_t)n_verts)) != SKH_OK)
+    if ((s = dev_upload(c, c->scene.dVerts, verts, sizeof(skh_vertex) * (size_t)n_verts)) != SKH_OK)
         return s;
-    if ((s = dev_upload(c, c->dIndices, indices, sizeof(uint32_t) * (size_t)n_indices)) != SKH_OK)
+    if ((s = dev_upload(c, c->scene.dIndices, indices, sizeof(uint32_t) * (size_t)n_indices)) != SKH_OK)
         return s;
-    return dev_upload(c, c->dMeshes, meshes, sizeof(skh_mesh) * (size_t)n_meshes);
+    return dev_upload(c, c->scene.dMeshes, meshes, sizeof(skh_mesh) * (size_t)n_meshes);
 }
 
 skh_status skh_set_curves(skh_context* c, const float* points_xyz, uint32_t n_points, const float* radii, uint32_t n_radii,
@@ -250,10 +255,10 @@ skh_status skh_set_curves(skh_context* c, const float* points_xyz, uint32_t n_po
     spec_drop(c);
     if (n_radii != n_points)
     {
-        c->err = "skh_set_curves: one radius per control point is required";
+        c->dev.err = "skh_set_curves: one radius per control point is required";
         return SKH_INVALID_ARGUMENT;
     }
-    (void)hipSetDevice(c->device);
+    (void)hipSetDevice(c->dev.device);
     for (uint32_t k = 0; k < n_curves; ++k)
     {
         // ranges of oka::Curve (scene.h:29-42) against the arrays they address; the strands of a set must fit its point range
@@ -265,30 +270,20 @@ skh_status skh_set_curves(skh_context* c, const float* points_xyz, uint32_t n_po
             used += vertex_counts[cu.vertex_counts_start + j];
         if (!ok || used > cu.points_count)
         {
-            c->err = "skh_set_curves: curve set " + std::to_string(k) + " addresses data outside the arrays passed in";
+            c->dev.err = "skh_set_curves: curve set " + std::to_string(k) + " addresses data outside the arrays passed in";
             return SKH_INVALID_ARGUMENT;
         }
     }
-    c->curves.assign(curves, curves + n_curves);
-    c->curveVertexCounts.assign(vertex_counts, vertex_counts + n_vertex_counts);
-    c->nPoints = n_points;
-    c->accelBuilt = false;
-    {
-        // signature of the curve sets' TOPOLOGY (set table + vertex counts + array sizes): control points and radii may change under skh_refit_accel
-        uint64_t h = 1469598103934665603ull;
-        auto mix = [&](const uint32_t* w, size_t nw) {
-            for (size_t k = 0; k < nw; ++k)
-                h = (h ^ w[k]) * 1099511628211ull;
-        };
-        mix(reinterpret_cast<const uint32_t*>(curves), sizeof(skh_curve) / 4 * (size_t)n_curves);
-        mix(vertex_counts, n_vertex_counts);
-        c->curveSig = h ^ ((uint64_t)n_points << 32);
-        c->curvePointsEdited = true;
-    }
+    c->scene.curves.assign(curves, curves + n_curves);
+    c->scene.curveVertexCounts.assign(vertex_counts, vertex_counts + n_vertex_counts);
+    c->scene.nPoints = n_points;
+    touched(c, skh_stale::IN_CURVES);
+    // signature of the curve sets' TOPOLOGY (set table + vertex counts + array sizes): control points and radii may change under skh_refit_accel
+    c->scene.curveSig = fnv1a_words(fnv1a_words(kFnv1aSeed, curves, sizeof(skh_curve) / 4 * (size_t)n_curves), vertex_counts, n_vertex_counts) ^ ((uint64_t)n_points << 32);
     skh_status s;
-    if ((s = dev_upload(c, c->dPoints, points_xyz, sizeof(float) * 3 * (size_t)n_points)) != SKH_OK)
+    if ((s = dev_upload(c, c->scene.dPoints, points_xyz, sizeof(float) * 3 * (size_t)n_points)) != SKH_OK)
         return s;
-    return dev_upload(c, c->dRadii, radii, sizeof(float) * (size_t)n_radii);
+    return dev_upload(c, c->scene.dRadii, radii, sizeof(float) * (size_t)n_radii);
 }
 
 skh_status skh_set_instances(skh_context* c, const skh_instance* instances, uint32_t n)
@@ -296,15 +291,13 @@ skh_status skh_set_instances(skh_context* c, const skh_instance* instances, uint
     if (!c || (n && !instances))
         return SKH_INVALID_ARGUMENT;
     spec_drop(c);
-    (void)hipSetDevice(c->device);
+    (void)hipSetDevice(c->dev.device);
     // (skh_refit_accel compares the table with the build's: the same table again -- a caller that re-sends the whole scene with edited vertices -- keeps a refit
     // possible; skh_update_accel takes edited transforms in place)
-    c->instances.assign(instances, instances + n);
-    c->nInstances = n;
-    c->accelBuilt = false;
-    c->emitStale = true;
-    c->cutStale = true;
-    return dev_upload(c, c->dInstances, instances, sizeof(skh_instance) * (size_t)n);
+    c->scene.instances.assign(instances, instances + n);
+    c->scene.nInstances = n;
+    touched(c, skh_stale::IN_INSTANCES);
+    return dev_upload(c, c->scene.dInstances, instances, sizeof(skh_instance) * (size_t)n);
 }
 
 skh_status skh_set_lights(skh_context* c, const skh_light* lights, uint32_t n)
@@ -312,13 +305,13 @@ skh_status skh_set_lights(skh_context* c, const skh_light* lights, uint32_t n)
     if (!c || (n && !lights))
         return SKH_INVALID_ARGUMENT;
     spec_drop(c);
-    (void)hipSetDevice(c->device);
-    c->nLights = n;
-    c->lightTypes.resize(n);
+    (void)hipSetDevice(c->dev.device);
+    c->scene.nLights = n;
+    c->scene.lightTypes.resize(n);
     for (uint32_t k = 0; k < n; ++k)
-        c->lightTypes[k] = lights[k].type;
-    c->lshapeStale = true; // (which shape entries are in use depends on the lights' types and count)
-    return dev_upload(c, c->dLights, lights, sizeof(skh_light) * (size_t)n);
+        c->scene.lightTypes[k] = lights[k].type;
+    touched(c, skh_stale::IN_LIGHTS);
+    return dev_upload(c, c->scene.dLights, lights, sizeof(skh_light) * (size_t)n);
 }
 
 static bool env_transform_ok(const float scale[3], const float w2e[9])
@@ -336,16 +329,16 @@ static EnvP make_env(const skh_context* c)
 {
     EnvP e;
     memset(&e, 0, sizeof(e));
-    if (c->envW == 0)
+    if (c->env.w == 0)
         return e;
-    e.texels = c->dEnvTexels.as<float4>();
-    e.rowCdf = c->dEnvRowCdf.as<float>();
-    e.colCdf = c->dEnvColCdf.as<float>();
-    e.width = c->envW, e.height = c->envH;
-    e.pdfScale = (float)((double)c->envW * (double)c->envH / (2.0 * 3.14159265358979323846 * 3.14159265358979323846));
-    e.nee = c->envNee;
-    memcpy(e.scale, c->envScale, sizeof(e.scale));
-    memcpy(e.w2e, c->envW2E, sizeof(e.w2e));
+    e.texels = c->env.dTexels.as<float4>();
+    e.rowCdf = c->env.dRowCdf.as<float>();
+    e.colCdf = c->env.dColCdf.as<float>();
+    e.width = c->env.w, e.height = c->env.h;
+    e.pdfScale = (float)((double)c->env.w * (double)c->env.h / (2.0 * 3.14159265358979323846 * 3.14159265358979323846));
+    e.nee = c->opt.envNee;
+    memcpy(e.scale, c->env.scale, sizeof(e.scale));
+    memcpy(e.w2e, c->env.w2e, sizeof(e.w2e));
     return e;
 }
 
@@ -355,30 +348,30 @@ skh_status skh_set_environment(skh_context* c, const skh_environment* env)
         return SKH_INVALID_ARGUMENT;
     if (!env)
     {
-        c->err = "skh_set_environment: null description (rgb = NULL inside it removes the environment)";
+        c->dev.err = "skh_set_environment: null description (rgb = NULL inside it removes the environment)";
         return SKH_INVALID_ARGUMENT;
     }
-    (void)hipSetDevice(c->device);
+    (void)hipSetDevice(c->dev.device);
     if (!env->rgb)
     {
         // remove: a no-op on a context that has none (nothing traced ahead is thrown away for it)
-        if (c->envW == 0)
+        if (c->env.w == 0)
             return SKH_OK;
         spec_drop(c);
-        SKH_TRY(c, hipStreamSynchronize(c->stream));
-        dev_free(c->dEnvTexels), dev_free(c->dEnvColCdf), dev_free(c->dEnvRowCdf);
-        c->envW = c->envH = 0;
-        c->envSumW = c->envMsBuild = 0.0;
+        SKH_TRY(c, hipStreamSynchronize(c->dev.stream));
+        dev_free(c->env.dTexels), dev_free(c->env.dColCdf), dev_free(c->env.dRowCdf);
+        c->env.w = c->env.h = 0;
+        c->env.sumW = c->env.msBuild = 0.0;
         return SKH_OK;
     }
     if (env->width < 2 || env->width > SKH_ENV_MAX_WIDTH || env->height < 2 || env->height > SKH_ENV_MAX_HEIGHT)
     {
-        c->err = "skh_set_environment: the map must be 2..8192 texels wide and 2..4096 high";
+        c->dev.err = "skh_set_environment: the map must be 2..8192 texels wide and 2..4096 high";
         return SKH_INVALID_ARGUMENT;
     }
     if (!env_transform_ok(env->scale, env->world_to_env))
     {
-        c->err = "skh_set_environment: scale must be finite and >= 0, world_to_env finite";
+        c->dev.err = "skh_set_environment: scale must be finite and >= 0, world_to_env finite";
         return SKH_INVALID_ARGUMENT;
     }
     spec_drop(c);
@@ -394,20 +387,20 @@ skh_status skh_set_environment(skh_context* c, const skh_environment* env)
     double* rowSum = dTmp.as<double>();
     double* sumW = rowSum + H;
     uint32_t* bad = reinterpret_cast<uint32_t*>(rowSum + H + 1);
-    hipError_t e = hipMemsetAsync(bad, 0, sizeof(double), c->stream);
+    hipError_t e = hipMemsetAsync(bad, 0, sizeof(double), c->dev.stream);
     if (e == hipSuccess)
-        e = hipStreamSynchronize(c->stream);
+        e = hipStreamSynchronize(c->dev.stream);
     const auto t0 = std::chrono::steady_clock::now();
     if (e == hipSuccess)
     {
-        k_env_rows<<<H, SKH_ENV_BLOCK, 0, c->stream>>>(dRgb.as<float>(), W, H, dTex.as<float4>(), dCol.as<float>(), rowSum, bad);
-        k_env_marginal<<<1, SKH_ENV_BLOCK, 0, c->stream>>>(rowSum, H, dRow.as<float>(), sumW);
-        const uint32_t blocks = (uint32_t)std::min<size_t>((n + SKH_ENV_BLOCK - 1) / SKH_ENV_BLOCK, (size_t)c->numCUs * 16u);
-        k_env_normalise<<<blocks, SKH_ENV_BLOCK, 0, c->stream>>>(dTex.as<float4>(), n, sumW);
+        k_env_rows<<<H, SKH_ENV_BLOCK, 0, c->dev.stream>>>(dRgb.as<float>(), W, H, dTex.as<float4>(), dCol.as<float>(), rowSum, bad);
+        k_env_marginal<<<1, SKH_ENV_BLOCK, 0, c->dev.stream>>>(rowSum, H, dRow.as<float>(), sumW);
+        const uint32_t blocks = (uint32_t)std::min<size_t>((n + SKH_ENV_BLOCK - 1) / SKH_ENV_BLOCK, (size_t)c->dev.numCUs * 16u);
+        k_env_normalise<<<blocks, SKH_ENV_BLOCK, 0, c->dev.stream>>>(dTex.as<float4>(), n, sumW);
         e = hipGetLastError();
     }
     if (e == hipSuccess)
-        e = hipStreamSynchronize(c->stream);
+        e = hipStreamSynchronize(c->dev.stream);
     const double ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
     double total = 0.0;
     uint32_t badHost = 0;
@@ -417,20 +410,20 @@ skh_status skh_set_environment(skh_context* c, const skh_environment* env)
         e = hipMemcpy(&badHost, bad, sizeof(uint32_t), hipMemcpyDeviceToHost);
     if (e != hipSuccess)
     {
-        c->err = std::string("skh_set_environment: ") + hipGetErrorString(e);
+        c->dev.err = std::string("skh_set_environment: ") + hipGetErrorString(e);
         return e == hipErrorOutOfMemory ? SKH_OUT_OF_MEMORY : SKH_FAIL;
     }
     if (badHost)
     {
-        c->err = "skh_set_environment: the map holds a negative or non-finite value";
+        c->dev.err = "skh_set_environment: the map holds a negative or non-finite value";
         return SKH_INVALID_ARGUMENT;
     }
-    c->dEnvTexels = std::move(dTex), c->dEnvColCdf = std::move(dCol), c->dEnvRowCdf = std::move(dRow); // (the previous tables are freed here)
-    c->envW = W, c->envH = H;
-    memcpy(c->envScale, env->scale, sizeof(c->envScale));
-    memcpy(c->envW2E, env->world_to_env, sizeof(c->envW2E));
-    c->envSumW = total;
-    c->envMsBuild = ms;
+    c->env.dTexels = std::move(dTex), c->env.dColCdf = std::move(dCol), c->env.dRowCdf = std::move(dRow); // (the previous tables are freed here)
+    c->env.w = W, c->env.h = H;
+    memcpy(c->env.scale, env->scale, sizeof(c->env.scale));
+    memcpy(c->env.w2e, env->world_to_env, sizeof(c->env.w2e));
+    c->env.sumW = total;
+    c->env.msBuild = ms;
     return SKH_OK;
 }
 
@@ -438,15 +431,15 @@ skh_status skh_set_environment_transform(skh_context* c, const float scale[3], c
 {
     if (!c)
         return SKH_INVALID_ARGUMENT;
-    if (!scale || !world_to_env || c->envW == 0 || !env_transform_ok(scale, world_to_env))
+    if (!scale || !world_to_env || c->env.w == 0 || !env_transform_ok(scale, world_to_env))
     {
-        c->err = c->envW == 0 ? "skh_set_environment_transform: the context has no environment" :
+        c->dev.err = c->env.w == 0 ? "skh_set_environment_transform: the context has no environment" :
                                 "skh_set_environment_transform: scale must be finite and >= 0, world_to_env finite";
         return SKH_INVALID_ARGUMENT;
     }
     spec_drop(c); // sub-frames traced ahead hold radiance of the old sky
-    memcpy(c->envScale, scale, sizeof(c->envScale));
-    memcpy(c->envW2E, world_to_env, sizeof(c->envW2E));
+    memcpy(c->env.scale, scale, sizeof(c->env.scale));
+    memcpy(c->env.w2e, world_to_env, sizeof(c->env.w2e));
     return SKH_OK;
 }
 
@@ -455,10 +448,10 @@ skh_status skh_get_environment_info(skh_context* c, skh_environment_info* out)
     if (!c || !out)
         return SKH_INVALID_ARGUMENT;
     memset(out, 0, sizeof(*out));
-    out->width = c->envW, out->height = c->envH;
-    out->sum_w = c->envSumW;
-    out->ms_build = c->envMsBuild;
-    out->bytes = c->envW ? (uint64_t)c->envW * c->envH * (sizeof(float4) + sizeof(float)) + (uint64_t)c->envH * sizeof(float) : 0u;
+    out->width = c->env.w, out->height = c->env.h;
+    out->sum_w = c->env.sumW;
+    out->ms_build = c->env.msBuild;
+    out->bytes = c->env.w ? (uint64_t)c->env.w * c->env.h * (sizeof(float4) + sizeof(float)) + (uint64_t)c->env.h * sizeof(float) : 0u;
     return SKH_OK;
 }
 
@@ -467,32 +460,32 @@ skh_status skh_set_textures(skh_context* c, const skh_texture* textures, uint32_
     if (!c || (n && !textures))
         return SKH_INVALID_ARGUMENT;
     spec_drop(c);
-    (void)hipSetDevice(c->device);
+    (void)hipSetDevice(c->dev.device);
     std::vector<uint4> desc(n);
     uint64_t total = 0;
     for (uint32_t k = 0; k < n; ++k)
     {
         if (!textures[k].rgba8 || textures[k].width == 0 || textures[k].height == 0)
         {
-            c->err = "skh_set_textures: texture " + std::to_string(k) + " is empty";
+            c->dev.err = "skh_set_textures: texture " + std::to_string(k) + " is empty";
             return SKH_INVALID_ARGUMENT;
         }
         desc[k] = make_uint4((uint32_t)total, textures[k].width, textures[k].height, 0u);
         total += (uint64_t)textures[k].width * textures[k].height;
         if (total >= (1ull << 32))
         {
-            c->err = "skh_set_textures: more than 2^32 texels";
+            c->dev.err = "skh_set_textures: more than 2^32 texels";
             return SKH_INVALID_ARGUMENT;
         }
     }
     std::vector<uint32_t> texels((size_t)total);
     for (uint32_t k = 0; k < n; ++k)
         memcpy(texels.data() + desc[k].x, textures[k].rgba8, (size_t)textures[k].width * textures[k].height * 4);
-    skh_status s = dev_upload(c, c->dTexels, texels.data(), sizeof(uint32_t) * texels.size());
+    skh_status s = dev_upload(c, c->scene.dTexels, texels.data(), sizeof(uint32_t) * texels.size());
     if (s == SKH_OK)
-        s = dev_upload(c, c->dTexDesc, desc.data(), sizeof(uint4) * desc.size());
-    c->nTextures = s == SKH_OK ? n : 0;
-    c->cutStale = true;
+        s = dev_upload(c, c->scene.dTexDesc, desc.data(), sizeof(uint4) * desc.size());
+    c->scene.nTextures = s == SKH_OK ? n : 0;
+    touched(c, skh_stale::IN_TEXTURES);
     return s;
 }
 skh_status skh_set_materials(skh_context* c, const skh_material* materials, uint32_t n)
@@ -500,58 +493,57 @@ skh_status skh_set_materials(skh_context* c, const skh_material* materials, uint
     if (!c || (n && !materials))
         return SKH_INVALID_ARGUMENT;
     spec_drop(c);
-    (void)hipSetDevice(c->device);
-    c->nMaterials = n;
-    c->emitStale = true;
-    c->cutStale = true;
-    c->hasHairMaterial = false;
+    (void)hipSetDevice(c->dev.device);
+    c->scene.nMaterials = n;
+    touched(c, skh_stale::IN_MATERIALS);
+    c->scene.hasHairMaterial = false;
     for (uint32_t k = 0; k < n; ++k)
-        c->hasHairMaterial = c->hasHairMaterial || materials[k].type == SKH_MAT_HAIR;
-    skh_status s = dev_upload(c, c->dMaterials, materials, sizeof(skh_material) * (size_t)n);
+        c->scene.hasHairMaterial = c->scene.hasHairMaterial || materials[k].type == SKH_MAT_HAIR;
+    skh_status s = dev_upload(c, c->scene.dMaterials, materials, sizeof(skh_material) * (size_t)n);
     if (s != SKH_OK)
         return s;
     // the material-only terms of the hair BSDF, computed once per material ON THE DEVICE by the code the per-call path ran (skh_device.h hair_const)
-    if ((s = dev_alloc(c, c->dHairConst, sizeof(HairConst) * (size_t)std::max(1u, n))) != SKH_OK)
+    if ((s = dev_alloc(c, c->scene.dHairConst, sizeof(HairConst) * (size_t)std::max(1u, n))) != SKH_OK)
         return s;
     if (n)
-        k_hair_consts<<<(n + 63) / 64, 64, 0, c->stream>>>(c->dMaterials.as<Material>(), n, c->dHairConst.as<HairConst>());
-    SKH_TRY(c, hipStreamSynchronize(c->stream));
+        k_hair_consts<<<(n + 63) / 64, 64, 0, c->dev.stream>>>(c->scene.dMaterials.as<Material>(), n, c->scene.dHairConst.as<HairConst>());
+    SKH_TRY(c, hipStreamSynchronize(c->dev.stream));
     return SKH_OK;
 }
 
 static skh_status build_shading_tables(skh_context* c)
 {
-    const uint32_t nMeshes = (uint32_t)c->meshes.size();
+    const uint32_t nMeshes = (uint32_t)c->scene.meshes.size();
     std::vector<uint32_t> base(nMeshes + 1u, 0u);
     uint64_t total = 0; // (summed wide and tested before narrowing: a 32-bit sum that wraps would pass the test below with aliased bases)
     for (uint32_t m = 0; m < nMeshes; ++m)
     {
-        total += c->meshes[m].index_count / 3u;
+        total += c->scene.meshes[m].index_count / 3u;
         base[m + 1] = (uint32_t)std::min<uint64_t>(total, 0xffffffffull);
     }
     const uint32_t nTris = base[nMeshes];
-    c->nShadeRecords = nTris;
+    c->accel.nShadeRecords = nTris;
     if (total >= SKH_PRIM_DIRECT)
     {
-        c->err = "skh_build_accel: more than 2^31 - 1 triangles (the primitive word of a hit keeps its top bit for SKH_PRIM_DIRECT)";
+        c->dev.err = "skh_build_accel: more than 2^31 - 1 triangles (the primitive word of a hit keeps its top bit for SKH_PRIM_DIRECT)";
         return SKH_INVALID_ARGUMENT;
     }
-    SKH_CHECK(dev_alloc(c, c->dShadeTris, std::max<size_t>(96, (size_t)nTris * 96)));
+    SKH_CHECK(dev_alloc(c, c->accel.dShadeTris, std::max<size_t>(96, (size_t)nTris * 96)));
     if (nTris)
     {
         DevBuf dBase;
         SKH_CHECK(dev_upload(c, dBase, base.data(), sizeof(uint32_t) * base.size()));
-        k_gather_shade_tris<<<(nTris + 255u) / 256u, 256, 0, c->stream>>>(c->dVerts.as<uint8_t>(), c->dIndices.as<uint32_t>(), c->dMeshes.as<uint4>(),
-                                                                         dBase.as<uint32_t>(), nMeshes, nTris, c->dShadeTris.as<float4>());
-        SKH_TRY(c, hipStreamSynchronize(c->stream));
+        k_gather_shade_tris<<<(nTris + 255u) / 256u, 256, 0, c->dev.stream>>>(c->scene.dVerts.as<uint8_t>(), c->scene.dIndices.as<uint32_t>(), c->scene.dMeshes.as<uint4>(),
+                                                                         dBase.as<uint32_t>(), nMeshes, nTris, c->accel.dShadeTris.as<float4>());
+        SKH_TRY(c, hipStreamSynchronize(c->dev.stream));
     }
-    std::vector<skh_instance> inst = c->instances;
+    std::vector<skh_instance> inst = c->scene.instances;
     for (skh_instance& i : inst)
         if (i.type == SKH_INSTANCE_MESH)
             i.light_id = i.geom_id < nMeshes ? base[i.geom_id] : 0u;
     if (inst.empty())
         inst.resize(1);
-    return dev_upload(c, c->dShadeInst, inst.data(), sizeof(skh_instance) * inst.size());
+    return dev_upload(c, c->accel.dShadeInst, inst.data(), sizeof(skh_instance) * inst.size());
 }
 
 #include "skh_accel.inc"
@@ -563,7 +555,7 @@ static size_t frame_count_words(const skh_context* c);
 // exclusive prefix sum, and their total
 static void raygen_tables(const skh_context* c, const uint32_t* frozenAt, std::vector<uint32_t>& base, uint32_t& total)
 {
-    const uint32_t blocks = (c->numSlots + 511u) / 512u, chunks = (uint32_t)c->chunkValid.size(), shift2 = 2 * c->tileShift;
+    const uint32_t blocks = (c->frame.numSlots + 511u) / 512u, chunks = (uint32_t)c->frame.chunkValid.size(), shift2 = 2 * c->frame.tileShift;
     base.assign(std::max(1u, blocks), 0u);
     total = 0;
     for (uint32_t b = 0; b < blocks; ++b)
@@ -571,37 +563,37 @@ static void raygen_tables(const skh_context* c, const uint32_t* frozenAt, std::v
         base[b] = total;
         for (uint32_t j = b * 8u; j < std::min(chunks, (b + 1) * 8u); ++j)
             if (!frozenAt || frozenAt[(j * 64u) >> shift2] == 0u)
-                total += c->chunkValid[j];
+                total += c->frame.chunkValid[j];
     }
 }
 
 static skh_status alloc_frame(skh_context* c)
 {
-    const uint32_t T = c->tileSize;
-    if (!c->customTiles)
+    const uint32_t T = c->frame.tileSize;
+    if (!c->frame.customTiles)
     {
-        c->tileXY.clear();
-        for (uint32_t y = 0; y < c->height; y += T)
-            for (uint32_t x = 0; x < c->width; x += T)
+        c->frame.tileXY.clear();
+        for (uint32_t y = 0; y < c->frame.height; y += T)
+            for (uint32_t x = 0; x < c->frame.width; x += T)
             {
-                c->tileXY.push_back(x);
-                c->tileXY.push_back(y);
+                c->frame.tileXY.push_back(x);
+                c->frame.tileXY.push_back(y);
             }
     }
-    c->numTiles = (uint32_t)(c->tileXY.size() / 2);
-    c->numSlots = c->numTiles * T * T;
+    c->frame.numTiles = (uint32_t)(c->frame.tileXY.size() / 2);
+    c->frame.numSlots = c->frame.numTiles * T * T;
     // sub-frame batching: aim at ~64 M paths per wavefront pass.  The persistent trace kernels have a long tail (a few
     // rays walk 10x the average number of nodes); at 2 M rays per launch the tail is half of the kernel time, at 64 M it
     // is amortised (measured at 1080p, Mray/s: 1 sub-frame per pass 1104, 16: 1942, 64: 2055 before the kernel work; with
     // the final kernels 8: 3455, 16: 3579, 32: 3678).  ~270 B per path: 18 GB of 288 GB at the default.
-    c->batchCapacity = c->subframeBatch ? c->subframeBatch : std::min(64u, std::max(1u, (1u << 27) / std::max(1u, c->numSlots)));
-    const size_t N1 = std::max(1u, c->numSlots);
-    const size_t N = N1 * c->batchCapacity;
+    c->frame.batchCapacity = c->opt.subframeBatch ? c->opt.subframeBatch : std::min(64u, std::max(1u, (1u << 27) / std::max(1u, c->frame.numSlots)));
+    const size_t N1 = std::max(1u, c->frame.numSlots);
+    const size_t N = N1 * c->frame.batchCapacity;
     // queues are sharded SKH_SHARDS ways: a shard's region holds an eighth of the paths (rounded up to whole waves); k_raygen deals the
     // first queue out in equal runs, and a k_shade workgroup emits into the shard it read from, so no shard outgrows its region
-    c->queueRegion = (uint32_t)((((N + SKH_SHARDS - 1) / SKH_SHARDS) + 63) & ~(size_t)63);
-    const size_t NQ = (size_t)SKH_SHARDS * c->queueRegion;
-    SKH_CHECK(dev_upload(c, c->dTileXY, c->tileXY.data(), sizeof(uint32_t) * c->tileXY.size()));
+    c->frame.queueRegion = (uint32_t)((((N + SKH_SHARDS - 1) / SKH_SHARDS) + 63) & ~(size_t)63);
+    const size_t NQ = (size_t)SKH_SHARDS * c->frame.queueRegion;
+    SKH_CHECK(dev_upload(c, c->frame.dTileXY, c->frame.tileXY.data(), sizeof(uint32_t) * c->frame.tileXY.size()));
     {
         // valid (inside the image) slots per 64-slot chunk -- the 8 x 8 pixel block at the chunk's first pixel
         auto compact = [](uint32_t x) {
@@ -612,46 +604,46 @@ static skh_status alloc_frame(skh_context* c)
             x = (x ^ (x >> 8)) & 0x0000ffffu;
             return x;
         };
-        const uint32_t shift2 = 2 * c->tileShift, mask = (1u << shift2) - 1u;
-        c->chunkValid.assign(c->numSlots / 64u, 0u);
-        for (uint32_t j = 0; j < c->numSlots / 64u; ++j)
+        const uint32_t shift2 = 2 * c->frame.tileShift, mask = (1u << shift2) - 1u;
+        c->frame.chunkValid.assign(c->frame.numSlots / 64u, 0u);
+        for (uint32_t j = 0; j < c->frame.numSlots / 64u; ++j)
         {
             const uint32_t tile = (j * 64u) >> shift2, m = (j * 64u) & mask;
-            const uint32_t x0 = c->tileXY[2 * tile] + compact(m), y0 = c->tileXY[2 * tile + 1] + compact(m >> 1);
+            const uint32_t x0 = c->frame.tileXY[2 * tile] + compact(m), y0 = c->frame.tileXY[2 * tile + 1] + compact(m >> 1);
             uint32_t n = 0;
             for (uint32_t k = 0; k < 64u; ++k)
-                n += (x0 + compact(k) < c->width && y0 + compact(k >> 1) < c->height) ? 1u : 0u;
-            c->chunkValid[j] = n;
+                n += (x0 + compact(k) < c->frame.width && y0 + compact(k >> 1) < c->frame.height) ? 1u : 0u;
+            c->frame.chunkValid[j] = n;
         }
         std::vector<uint32_t> base;
-        raygen_tables(c, nullptr, base, c->raygenValidPerSub);
-        c->raygenBlocksPerSub = (uint32_t)((c->numSlots + 511u) / 512u);
-        SKH_CHECK(dev_upload(c, c->dRaygenBase, base.data(), sizeof(uint32_t) * base.size()));
+        raygen_tables(c, nullptr, base, c->frame.raygenValidPerSub);
+        c->frame.raygenBlocksPerSub = (uint32_t)((c->frame.numSlots + 511u) / 512u);
+        SKH_CHECK(dev_upload(c, c->frame.dRaygenBase, base.data(), sizeof(uint32_t) * base.size()));
     }
     c->adapt.ready = false; // (the feature's buffers follow the frame's: adapt_prepare)
-    SKH_CHECK(dev_alloc(c, c->dAccum, sizeof(float4) * N1));
-    SKH_CHECK(dev_alloc(c, c->dDiffuse, sizeof(float4) * N1));
-    SKH_CHECK(dev_alloc(c, c->dSpecular, sizeof(float4) * N1));
-    SKH_CHECK(dev_alloc(c, c->dDiffCnt, sizeof(uint16_t) * N1));
-    SKH_CHECK(dev_alloc(c, c->dSpecCnt, sizeof(uint16_t) * N1));
-    SKH_CHECK(dev_alloc(c, c->dSums, sizeof(float) * 11 * N1));
-    SKH_CHECK(dev_alloc(c, c->dPath, sizeof(float) * SKH_PATH_FLOATS * N));
-    SKH_CHECK(dev_alloc(c, c->dRayQ[0], sizeof(float) * 9 * NQ));
-    SKH_CHECK(dev_alloc(c, c->dRayQ[1], sizeof(float) * 9 * NQ));
-    SKH_CHECK(dev_alloc(c, c->dHits, sizeof(float) * 8 * NQ));
-    SKH_CHECK(dev_alloc(c, c->dShadowQ, sizeof(float) * 9 * NQ));
-    SKH_CHECK(dev_alloc(c, c->dContrib, sizeof(float4) * NQ));
-    c->queueConstFilled = false;
-    SKH_CHECK(dev_alloc(c, c->dCounts, sizeof(uint32_t) * frame_count_words(c)));
-    c->traceBlocks = (uint32_t)c->numCUs * c->wavesPerCU;
-    SKH_CHECK(dev_alloc(c, c->dOvf, sizeof(int) * (size_t)(SKH_STACK_OVF + SKH_TAIL_EXTRA) * (uint32_t)c->numCUs * std::max(std::max(c->wavesPerCU, c->wavesPerCUWorld), std::max(c->wavesPerCUShadow, c->wavesPerCUShadowWorld)) * SKH_TRACE_BLOCK));
-    SKH_CHECK(dev_alloc(c, c->dOvf2, sizeof(int) * (size_t)(SKH_STACK_OVF + SKH_TAIL_EXTRA) * (uint32_t)c->numCUs * std::max(std::max(c->wavesPerCU, c->wavesPerCUWorld), std::max(c->wavesPerCUShadow, c->wavesPerCUShadowWorld)) * SKH_TRACE_BLOCK));
-    SKH_TRY(c, hipMemsetAsync(c->dAccum.p, 0, sizeof(float4) * N1, c->stream));
-    SKH_TRY(c, hipMemsetAsync(c->dDiffuse.p, 0, sizeof(float4) * N1, c->stream));
-    SKH_TRY(c, hipMemsetAsync(c->dSpecular.p, 0, sizeof(float4) * N1, c->stream));
-    SKH_TRY(c, hipMemsetAsync(c->dDiffCnt.p, 0, sizeof(uint16_t) * N1, c->stream));
-    SKH_TRY(c, hipMemsetAsync(c->dSpecCnt.p, 0, sizeof(uint16_t) * N1, c->stream));
-    SKH_TRY(c, hipStreamSynchronize(c->stream));
+    SKH_CHECK(dev_alloc(c, c->frame.dAccum, sizeof(float4) * N1));
+    SKH_CHECK(dev_alloc(c, c->frame.dDiffuse, sizeof(float4) * N1));
+    SKH_CHECK(dev_alloc(c, c->frame.dSpecular, sizeof(float4) * N1));
+    SKH_CHECK(dev_alloc(c, c->frame.dDiffCnt, sizeof(uint16_t) * N1));
+    SKH_CHECK(dev_alloc(c, c->frame.dSpecCnt, sizeof(uint16_t) * N1));
+    SKH_CHECK(dev_alloc(c, c->frame.dSums, sizeof(float) * 11 * N1));
+    SKH_CHECK(dev_alloc(c, c->frame.dPath, sizeof(float) * SKH_PATH_FLOATS * N));
+    SKH_CHECK(dev_alloc(c, c->frame.dRayQ[0], sizeof(float) * 9 * NQ));
+    SKH_CHECK(dev_alloc(c, c->frame.dRayQ[1], sizeof(float) * 9 * NQ));
+    SKH_CHECK(dev_alloc(c, c->frame.dHits, sizeof(float) * 8 * NQ));
+    SKH_CHECK(dev_alloc(c, c->frame.dShadowQ, sizeof(float) * 9 * NQ));
+    SKH_CHECK(dev_alloc(c, c->frame.dContrib, sizeof(float4) * NQ));
+    c->frame.queueConstFilled = false;
+    SKH_CHECK(dev_alloc(c, c->frame.dCounts, sizeof(uint32_t) * frame_count_words(c)));
+    c->frame.traceBlocks = (uint32_t)c->dev.numCUs * c->opt.wavesPerCU;
+    SKH_CHECK(dev_alloc(c, c->frame.dOvf, sizeof(int) * (size_t)(SKH_STACK_OVF + SKH_TAIL_EXTRA) * (uint32_t)c->dev.numCUs * std::max(std::max(c->opt.wavesPerCU, c->opt.wavesPerCUWorld), std::max(c->opt.wavesPerCUShadow, c->opt.wavesPerCUShadowWorld)) * SKH_TRACE_BLOCK));
+    SKH_CHECK(dev_alloc(c, c->frame.dOvf2, sizeof(int) * (size_t)(SKH_STACK_OVF + SKH_TAIL_EXTRA) * (uint32_t)c->dev.numCUs * std::max(std::max(c->opt.wavesPerCU, c->opt.wavesPerCUWorld), std::max(c->opt.wavesPerCUShadow, c->opt.wavesPerCUShadowWorld)) * SKH_TRACE_BLOCK));
+    SKH_TRY(c, hipMemsetAsync(c->frame.dAccum.p, 0, sizeof(float4) * N1, c->dev.stream));
+    SKH_TRY(c, hipMemsetAsync(c->frame.dDiffuse.p, 0, sizeof(float4) * N1, c->dev.stream));
+    SKH_TRY(c, hipMemsetAsync(c->frame.dSpecular.p, 0, sizeof(float4) * N1, c->dev.stream));
+    SKH_TRY(c, hipMemsetAsync(c->frame.dDiffCnt.p, 0, sizeof(uint16_t) * N1, c->dev.stream));
+    SKH_TRY(c, hipMemsetAsync(c->frame.dSpecCnt.p, 0, sizeof(uint16_t) * N1, c->dev.stream));
+    SKH_TRY(c, hipStreamSynchronize(c->dev.stream));
     return SKH_OK;
 }
 
@@ -660,9 +652,9 @@ skh_status skh_resize(skh_context* c, uint32_t width, uint32_t height)
     if (!c || width == 0 || height == 0)
         return SKH_INVALID_ARGUMENT;
     spec_drop(c);
-    (void)hipSetDevice(c->device);
-    c->width = width;
-    c->height = height;
+    (void)hipSetDevice(c->dev.device);
+    c->frame.width = width;
+    c->frame.height = height;
     return alloc_frame(c);
 }
 
@@ -671,15 +663,15 @@ skh_status skh_set_tiles(skh_context* c, uint32_t tile_size, const uint32_t* til
     if (!c || tile_size < 8 || tile_size > 256 || (tile_size & (tile_size - 1)))
         return SKH_INVALID_ARGUMENT;
     spec_drop(c);
-    (void)hipSetDevice(c->device);
-    c->tileSize = tile_size;
-    c->tileShift = 0;
-    while ((1u << c->tileShift) < tile_size)
-        ++c->tileShift;
-    c->customTiles = tile_xy != nullptr;
+    (void)hipSetDevice(c->dev.device);
+    c->frame.tileSize = tile_size;
+    c->frame.tileShift = 0;
+    while ((1u << c->frame.tileShift) < tile_size)
+        ++c->frame.tileShift;
+    c->frame.customTiles = tile_xy != nullptr;
     if (tile_xy)
-        c->tileXY.assign(tile_xy, tile_xy + 2 * (size_t)n_tiles);
-    if (c->width && c->height)
+        c->frame.tileXY.assign(tile_xy, tile_xy + 2 * (size_t)n_tiles);
+    if (c->frame.width && c->frame.height)
         return alloc_frame(c);
     return SKH_OK;
 }
@@ -687,13 +679,13 @@ skh_status skh_set_tiles(skh_context* c, uint32_t tile_size, const uint32_t* til
 // ---- timing helpers ----
 static hipEvent_t next_event(skh_context* c)
 {
-    if (c->eventsUsed == c->eventPool.size())
+    if (c->timing.eventsUsed == c->timing.eventPool.size())
     {
         hipEvent_t e;
         (void)hipEventCreate(&e);
-        c->eventPool.push_back(e);
+        c->timing.eventPool.push_back(e);
     }
-    return c->eventPool[c->eventsUsed++];
+    return c->timing.eventPool[c->timing.eventsUsed++];
 }
 struct SpanGuard
 {
@@ -701,10 +693,10 @@ struct SpanGuard
     int cls;
     hipEvent_t a = nullptr;
     hipStream_t st;
-    SpanGuard(skh_context* c_, int cls_, hipStream_t st_ = nullptr) : c(c_), cls(cls_), st(st_ ? st_ : c_->stream)
+    SpanGuard(skh_context* c_, int cls_, hipStream_t st_ = nullptr) : c(c_), cls(cls_), st(st_ ? st_ : c_->dev.stream)
     {
-        c->launches[cls]++;
-        if (c->timing)
+        c->timing.launches[cls]++;
+        if (c->opt.timing)
         {
             a = next_event(c);
             (void)hipEventRecord(a, st);
@@ -712,75 +704,75 @@ struct SpanGuard
     }
     ~SpanGuard()
     {
-        if (c->timing)
+        if (c->opt.timing)
         {
             hipEvent_t b = next_event(c);
             (void)hipEventRecord(b, st);
-            c->spans.push_back(TimedSpan{ cls, a, b });
+            c->timing.spans.push_back(TimedSpan{ cls, a, b });
         }
     }
 };
 static void harvest_spans(skh_context* c)
 {
-    for (const TimedSpan& s : c->spans)
+    for (const TimedSpan& s : c->timing.spans)
     {
         float ms = 0.0f;
         if (hipEventElapsedTime(&ms, s.a, s.b) == hipSuccess)
         {
-            c->msClass[s.cls] += ms;
+            c->timing.msClass[s.cls] += ms;
             if (getenv("SKH_DEBUG_SPANS"))
                 fprintf(stderr, "[span] class %d %.3f ms\n", s.cls, ms);
         }
     }
-    c->spans.clear();
-    c->eventsUsed = 0;
+    c->timing.spans.clear();
+    c->timing.eventsUsed = 0;
 }
 
 static DevScene make_dev_scene(const skh_context* c)
 {
     DevScene sc;
-    sc.tlasNodes = c->dTlasNodes.as<Node4>();
-    sc.tlasInst = c->dTlasInst.as<uint32_t>();
-    sc.tlasRoot = c->tlasRoot;
-    sc.numWorldCurves = c->numWorldCurves;
-    sc.worldCurveIdentLast = c->worldCurveIdentLast;
-    sc.worldCurveMerged = c->worldCurveMerged;
+    sc.tlasNodes = c->accel.dTlasNodes.as<Node4>();
+    sc.tlasInst = c->accel.dTlasInst.as<uint32_t>();
+    sc.tlasRoot = c->accel.tlasRoot;
+    sc.numWorldCurves = c->accel.numWorldCurves;
+    sc.worldCurveIdentLast = c->accel.worldCurveIdentLast;
+    sc.worldCurveMerged = c->accel.worldCurveMerged;
     for (uint32_t k = 0; k < SKH_WORLD_CURVES; ++k)
-        sc.worldCurveRoot[k] = k < c->numWorldCurves ? c->worldCurveRoot[k] : SKH_REF_INVALID, sc.worldCurveInst[k] = k < c->numWorldCurves ? c->worldCurveInst[k] : 0u;
-    sc.numInstances = c->nInstances;
-    sc.inst = c->dDevInst.as<DevInstance>();
-    sc.tinst = c->dTravInst.as<DevInstance>();
-    sc.triNodes = c->dTriNodes.as<Node4>();
-    sc.tris = c->dTris.as<float4>();
-    sc.segNodes = c->dSegNodes.as<Node4>();
-    sc.segs = c->dSegs.as<float4>();
-    sc.curveSplit = c->curveSplitBuilt;
-    sc.worldRoot = c->worldRoot;
-    sc.lightRoot = c->lightRoot;
-    sc.instances = c->dShadeInst.as<HostInstance>();
-    sc.shadeTris = c->dShadeTris.as<float4>();
-    sc.verts = c->dVerts.as<uint8_t>();
-    sc.indices = c->dIndices.as<uint32_t>();
-    sc.meshes = c->dMeshes.as<uint4>();
-    sc.curveSegBase = c->dCurveSegBase.as<uint32_t>();
-    sc.segStartAll = c->dSegStartAll.as<uint32_t>();
-    sc.cpoints = c->dPoints.as<float>();
-    sc.cradii = c->dRadii.as<float>();
-    sc.lights = c->dLights.as<Light>();
-    sc.numLights = c->nLights;
-    sc.materials = c->dMaterials.as<Material>();
-    sc.hairConst = c->dHairConst.as<HairConst>();
-    sc.numMaterials = c->nMaterials;
-    sc.texels = c->dTexels.as<uint32_t>();
-    sc.texDesc = c->dTexDesc.as<uint4>();
-    sc.numTextures = c->nTextures;
-    sc.profile = c->dStats.as<StatsDev>();
-    sc.overflowFlag = c->hOverflow; // (hipHostMallocMapped memory: the host pointer is valid on the device)
+        sc.worldCurveRoot[k] = k < c->accel.numWorldCurves ? c->accel.worldCurveRoot[k] : SKH_REF_INVALID, sc.worldCurveInst[k] = k < c->accel.numWorldCurves ? c->accel.worldCurveInst[k] : 0u;
+    sc.numInstances = c->scene.nInstances;
+    sc.inst = c->accel.dDevInst.as<DevInstance>();
+    sc.tinst = c->accel.dTravInst.as<DevInstance>();
+    sc.triNodes = c->accel.dTriNodes.as<Node4>();
+    sc.tris = c->accel.dTris.as<float4>();
+    sc.segNodes = c->accel.dSegNodes.as<Node4>();
+    sc.segs = c->accel.dSegs.as<float4>();
+    sc.curveSplit = c->accel.curveSplitBuilt;
+    sc.worldRoot = c->accel.worldRoot;
+    sc.lightRoot = c->accel.lightRoot;
+    sc.instances = c->accel.dShadeInst.as<HostInstance>();
+    sc.shadeTris = c->accel.dShadeTris.as<float4>();
+    sc.verts = c->scene.dVerts.as<uint8_t>();
+    sc.indices = c->scene.dIndices.as<uint32_t>();
+    sc.meshes = c->scene.dMeshes.as<uint4>();
+    sc.curveSegBase = c->accel.dCurveSegBase.as<uint32_t>();
+    sc.segStartAll = c->accel.dSegStartAll.as<uint32_t>();
+    sc.cpoints = c->scene.dPoints.as<float>();
+    sc.cradii = c->scene.dRadii.as<float>();
+    sc.lights = c->scene.dLights.as<Light>();
+    sc.numLights = c->scene.nLights;
+    sc.materials = c->scene.dMaterials.as<Material>();
+    sc.hairConst = c->scene.dHairConst.as<HairConst>();
+    sc.numMaterials = c->scene.nMaterials;
+    sc.texels = c->scene.dTexels.as<uint32_t>();
+    sc.texDesc = c->scene.dTexDesc.as<uint4>();
+    sc.numTextures = c->scene.nTextures;
+    sc.profile = c->timing.dStats.as<StatsDev>();
+    sc.overflowFlag = c->dev.hOverflow; // (hipHostMallocMapped memory: the host pointer is valid on the device)
     return sc;
 }
 
 // What the probes (tests' doors to single device functions) share: the inputs up (an input without bytes is left out), the output allocated, `launch(dIn, dOut)`
-// on c->stream, the launch checked, the stream waited for, the output back.
+// on c->dev.stream, the launch checked, the stream waited for, the output back.
 struct ProbeIn
 {
     const void* src;
@@ -796,7 +788,7 @@ static skh_status probe_roundtrip(skh_context* c, const ProbeIn (&in)[N], void* 
     SKH_CHECK(dev_alloc(c, dOut, outBytes));
     launch(dIn, dOut);
     SKH_TRY(c, hipGetLastError());
-    SKH_TRY(c, hipStreamSynchronize(c->stream));
+    SKH_TRY(c, hipStreamSynchronize(c->dev.stream));
     SKH_TRY(c, hipMemcpy(out, dOut.p, outBytes, hipMemcpyDeviceToHost));
     return SKH_OK;
 }
@@ -805,9 +797,9 @@ static skh_status probe_roundtrip(skh_context* c, const ProbeIn (&in)[N], void* 
 // an entry binds a texture that exists: the k_shade builds with MTEX in them run (anything else -- no table, all ids 0 or beyond the list -- runs the others)
 static bool mtex_active(const skh_context* c)
 {
-    for (const skh_material_textures& e : c->mtex)
+    for (const skh_material_textures& e : c->mtex.table)
         for (uint32_t id : { e.roughness_texture, e.metallic_texture, e.emission_texture })
-            if (id != 0u && id <= c->nTextures)
+            if (id != 0u && id <= c->scene.nTextures)
                 return true;
     return false;
 }
@@ -817,21 +809,21 @@ static MtexP make_mtex(const skh_context* c)
     MtexP m;
     m.table = nullptr, m.count = 0;
     if (mtex_active(c))
-        m.table = c->dMtex.as<uint4>(), m.count = (uint32_t)c->mtex.size();
+        m.table = c->mtex.dTable.as<uint4>(), m.count = (uint32_t)c->mtex.table.size();
     return m;
 }
 
 // What the per-material table setters share.  Removal (no entries) is a no-op on a context that has none: nothing traced ahead is thrown away for it.  `check` validates
-// the entries, leaves the message of a refusal, and may point `src` / `bytes` at a packed form of the table; `stale`: the derived state to mark, if any.
+// the entries, leaves the message of a refusal, and may point `src` / `bytes` at a packed form of the table; `changed`: the input this table is (skh_stale.h).
 template <typename T, typename Check>
-static skh_status set_material_table(skh_context* c, const char* fn, const T* entries, uint32_t n, std::vector<T>& kept, DevBuf& dev, bool* stale, Check&& check)
+static skh_status set_material_table(skh_context* c, const char* fn, const T* entries, uint32_t n, std::vector<T>& kept, DevBuf& dev, skh_stale::Input changed, Check&& check)
 {
-    (void)hipSetDevice(c->device);
+    (void)hipSetDevice(c->dev.device);
     const void* src = entries;
     size_t bytes = sizeof(T) * (size_t)n;
-    if (entries && n > c->nMaterials)
+    if (entries && n > c->scene.nMaterials)
     {
-        c->err = std::string(fn) + ": " + std::to_string(n) + " entries for " + std::to_string(c->nMaterials) + " materials (call skh_set_materials first)";
+        c->dev.err = std::string(fn) + ": " + std::to_string(n) + " entries for " + std::to_string(c->scene.nMaterials) + " materials (call skh_set_materials first)";
         return SKH_INVALID_ARGUMENT;
     }
     if (!entries || n == 0)
@@ -842,7 +834,7 @@ static skh_status set_material_table(skh_context* c, const char* fn, const T* en
     else
         SKH_CHECK(check(src, bytes));
     spec_drop(c);
-    SKH_TRY(c, hipStreamSynchronize(c->stream)); // (the table is about to be replaced)
+    SKH_TRY(c, hipStreamSynchronize(c->dev.stream)); // (the table is about to be replaced)
     DevBuf d;
     if (entries && n)
     {
@@ -852,8 +844,7 @@ static skh_status set_material_table(skh_context* c, const char* fn, const T* en
     else
         kept.clear();
     dev = std::move(d);
-    if (stale)
-        *stale = true;
+    touched(c, changed);
     return SKH_OK;
 }
 
@@ -862,14 +853,14 @@ skh_status skh_set_material_textures(skh_context* c, const skh_material_textures
     static_assert(sizeof(skh_material_textures) == 48 && sizeof(skh_material_textures) == sizeof(MtexEntry), "skh_material_textures");
     if (!c)
         return SKH_INVALID_ARGUMENT;
-    return set_material_table(c, "skh_set_material_textures", entries, n, c->mtex, c->dMtex, nullptr, [&](const void*&, size_t&) {
+    return set_material_table(c, "skh_set_material_textures", entries, n, c->mtex.table, c->mtex.dTable, skh_stale::IN_MATERIAL_TEXTURES, [&](const void*&, size_t&) {
         for (uint32_t k = 0; k < n; ++k)
         {
             const skh_material_textures& e = entries[k];
             if (e.roughness_channel > 3u || e.metallic_channel > 3u || e.emission_channel > 4u || !std::isfinite(e.roughness_scale) || !std::isfinite(e.roughness_bias) ||
                 !std::isfinite(e.metallic_scale) || !std::isfinite(e.metallic_bias) || e.reserved[0] != 0u || e.reserved[1] != 0u)
             {
-                c->err = "skh_set_material_textures: entry " + std::to_string(k) + ": a channel out of range (0..3, emission 0..4), a scale or bias that is not finite, or a non-zero reserved word";
+                c->dev.err = "skh_set_material_textures: entry " + std::to_string(k) + ": a channel out of range (0..3, emission 0..4), a scale or bias that is not finite, or a non-zero reserved word";
                 return SKH_INVALID_ARGUMENT;
             }
         }
@@ -883,24 +874,24 @@ skh_status skh_material_probe(skh_context* c, uint32_t n, const uint32_t* materi
         return SKH_INVALID_ARGUMENT;
     if (n && (!material || !uv || !out))
     {
-        c->err = "skh_material_probe: a missing input / output pointer";
+        c->dev.err = "skh_material_probe: a missing input / output pointer";
         return SKH_INVALID_ARGUMENT;
     }
-    if (c->nMaterials == 0)
+    if (c->scene.nMaterials == 0)
     {
-        c->err = "skh_material_probe: the context has no materials (call skh_set_materials first)";
+        c->dev.err = "skh_material_probe: the context has no materials (call skh_set_materials first)";
         return SKH_INVALID_ARGUMENT;
     }
     if (n == 0)
         return SKH_OK;
-    (void)hipSetDevice(c->device);
-    std::vector<float> le(4 * (size_t)c->nMaterials, 0.0f); // (materials beyond the emission list do not emit)
-    for (uint32_t m = 0; m < c->nMaterials && 3 * (size_t)m + 2 < c->emission.size(); ++m)
-        memcpy(&le[4 * (size_t)m], &c->emission[3 * (size_t)m], 3 * sizeof(float));
+    (void)hipSetDevice(c->dev.device);
+    std::vector<float> le(4 * (size_t)c->scene.nMaterials, 0.0f); // (materials beyond the emission list do not emit)
+    for (uint32_t m = 0; m < c->scene.nMaterials && 3 * (size_t)m + 2 < c->emit.emission.size(); ++m)
+        memcpy(&le[4 * (size_t)m], &c->emit.emission[3 * (size_t)m], 3 * sizeof(float));
     const ProbeIn in[] = { { le.data(), le.size() * sizeof(float) }, { material, sizeof(uint32_t) * (size_t)n }, { uv, 2 * sizeof(float) * (size_t)n } };
     return probe_roundtrip(c, in, out, 8 * sizeof(float) * (size_t)n, [&](const DevBuf* d, const DevBuf& dOut) {
-        k_material_probe<<<(n + 255) / 256, 256, 0, c->stream>>>(make_mtex(c), c->dMaterials.as<Material>(), c->nMaterials, d[0].as<float4>(), c->dTexels.as<uint32_t>(),
-                                                                 c->dTexDesc.as<uint4>(), c->nTextures, d[1].as<uint32_t>(), d[2].as<float>(), n, dOut.as<float>());
+        k_material_probe<<<(n + 255) / 256, 256, 0, c->dev.stream>>>(make_mtex(c), c->scene.dMaterials.as<Material>(), c->scene.nMaterials, d[0].as<float4>(), c->scene.dTexels.as<uint32_t>(),
+                                                                 c->scene.dTexDesc.as<uint4>(), c->scene.nTextures, d[1].as<uint32_t>(), d[2].as<float>(), n, dOut.as<float>());
     });
 }
 
@@ -912,14 +903,14 @@ skh_status skh_set_material_cutouts(skh_context* c, const skh_material_cutout* e
 {
     if (!c)
         return SKH_INVALID_ARGUMENT;
-    return set_material_table(c, "skh_set_material_cutouts", entries, n, c->cutouts, c->dCutouts, &c->cutStale, [&](const void*&, size_t&) {
+    return set_material_table(c, "skh_set_material_cutouts", entries, n, c->cut.cutouts, c->cut.dCutouts, skh_stale::IN_MATERIAL_CUTOUTS, [&](const void*&, size_t&) {
         for (uint32_t k = 0; k < n; ++k)
         {
             const skh_material_cutout& e = entries[k];
             if (e.opacity_channel > 3u || !std::isfinite(e.opacity_scale) || !std::isfinite(e.opacity_bias) || !(e.threshold >= 0.0f && e.threshold <= 1.0f) ||
                 e.reserved[0] != 0u || e.reserved[1] != 0u || e.reserved[2] != 0u)
             {
-                c->err = "skh_set_material_cutouts: entry " + std::to_string(k) + ": a channel above 3, a scale or bias that is not finite, a threshold outside [0, 1] or a non-zero reserved word";
+                c->dev.err = "skh_set_material_cutouts: entry " + std::to_string(k) + ": a channel above 3, a scale or bias that is not finite, a threshold outside [0, 1] or a non-zero reserved word";
                 return SKH_INVALID_ARGUMENT;
             }
         }
@@ -935,7 +926,7 @@ skh_status skh_set_material_blend(skh_context* c, const skh_material_blend* entr
     if (!c)
         return SKH_INVALID_ARGUMENT;
     std::vector<uint4> packed; // what the device reads: one uint4 per material (BlendP)
-    return set_material_table(c, "skh_set_material_blend", entries, n, c->blends, c->dBlend, &c->cutStale, [&](const void*& src, size_t& bytes) {
+    return set_material_table(c, "skh_set_material_blend", entries, n, c->cut.blends, c->cut.dBlend, skh_stale::IN_MATERIAL_BLEND, [&](const void*& src, size_t& bytes) {
         packed.resize(n);
         for (uint32_t k = 0; k < n; ++k)
         {
@@ -943,7 +934,7 @@ skh_status skh_set_material_blend(skh_context* c, const skh_material_blend* entr
             if (e.opacity_channel > 3u || !std::isfinite(e.opacity_scale) || !std::isfinite(e.opacity_bias) || e.active > 1u || e.reserved[0] != 0u || e.reserved[1] != 0u ||
                 e.reserved[2] != 0u)
             {
-                c->err = "skh_set_material_blend: material " + std::to_string(k) + ": a channel above 3, a scale or bias that is not finite, active above 1 or a non-zero reserved word";
+                c->dev.err = "skh_set_material_blend: material " + std::to_string(k) + ": a channel above 3, a scale or bias that is not finite, active above 1 or a non-zero reserved word";
                 return SKH_INVALID_ARGUMENT;
             }
             uint32_t sb, bb;
@@ -960,13 +951,13 @@ skh_status skh_set_material_blend(skh_context* c, const skh_material_blend* entr
 static inline uint32_t instance_material(const skh_context* c, const skh_instance& in)
 {
     const uint32_t mid = in.material_id == 0xffffffffu ? 0u : in.material_id;
-    return mid < c->nMaterials ? mid : 0u;
+    return mid < c->scene.nMaterials ? mid : 0u;
 }
 
 // does material k emit (skh_set_emission)?
 static inline bool material_emits(const skh_context* c, size_t k)
 {
-    return 3 * k + 2 < c->emission.size() && (c->emission[3 * k] > 0.0f || c->emission[3 * k + 1] > 0.0f || c->emission[3 * k + 2] > 0.0f);
+    return 3 * k + 2 < c->emit.emission.size() && (c->emit.emission[3 * k] > 0.0f || c->emit.emission[3 * k + 1] > 0.0f || c->emit.emission[3 * k + 2] > 0.0f);
 }
 
 // the active entries among the first n of a per-material table, and the mesh instances that use one
@@ -977,43 +968,43 @@ static void count_in_use(const skh_context* c, uint32_t n, Active&& active, uint
     for (uint32_t k = 0; k < n; ++k)
         entries += active(k) ? 1u : 0u;
     if (entries)
-        for (const skh_instance& in : c->instances)
+        for (const skh_instance& in : c->scene.instances)
             users += (in.type == SKH_INSTANCE_MESH && instance_material(c, in) < n && active(instance_material(c, in))) ? 1u : 0u;
 }
 
 // Is a cutout in use (derived: an active entry on a material that a mesh instance uses)?  And the one combination that is refused: a material that emits and is cut.
 static skh_status cut_ensure(skh_context* c)
 {
-    if (c->cutStale)
+    if (c->cut.stale)
     {
-        const uint32_t nTab = (uint32_t)std::min<size_t>(c->cutouts.size(), c->nMaterials);
-        count_in_use(c, nTab, [&](uint32_t k) { return c->cutouts[k].threshold > 0.0f; }, c->cutActiveMaterials, c->cutInstances);
+        const uint32_t nTab = (uint32_t)std::min<size_t>(c->cut.cutouts.size(), c->scene.nMaterials);
+        count_in_use(c, nTab, [&](uint32_t k) { return c->cut.cutouts[k].threshold > 0.0f; }, c->cut.activeMaterials, c->cut.instances);
         // fractional opacity: the same derivation over the blend table
-        const uint32_t nBl = (uint32_t)std::min<size_t>(c->blends.size(), c->nMaterials);
-        count_in_use(c, nBl, [&](uint32_t k) { return c->blends[k].active != 0u; }, c->blendActiveMaterials, c->blendInstances);
-        c->cutStale = false;
+        const uint32_t nBl = (uint32_t)std::min<size_t>(c->cut.blends.size(), c->scene.nMaterials);
+        count_in_use(c, nBl, [&](uint32_t k) { return c->cut.blends[k].active != 0u; }, c->cut.blendActiveMaterials, c->cut.blendInstances);
+        c->cut.stale = false;
     }
-    if (c->blendActiveMaterials)
-        for (uint32_t k = 0; k < c->blends.size() && k < c->nMaterials; ++k)
+    if (c->cut.blendActiveMaterials)
+        for (uint32_t k = 0; k < c->cut.blends.size() && k < c->scene.nMaterials; ++k)
         {
-            if (!c->blends[k].active)
+            if (!c->cut.blends[k].active)
                 continue;
-            if (k < c->cutouts.size() && c->cutouts[k].threshold > 0.0f)
+            if (k < c->cut.cutouts.size() && c->cut.cutouts[k].threshold > 0.0f)
             {
-                c->err = "material " + std::to_string(k) + " has both an active cutout (skh_set_material_cutouts) and an active blend entry (skh_set_material_blend): one opacity rule per material";
+                c->dev.err = "material " + std::to_string(k) + " has both an active cutout (skh_set_material_cutouts) and an active blend entry (skh_set_material_blend): one opacity rule per material";
                 return SKH_INVALID_ARGUMENT;
             }
             if (material_emits(c, k))
             {
-                c->err = "material " + std::to_string(k) + " both emits (skh_set_emission) and has an active blend entry (skh_set_material_blend): blended emitters are not supported";
+                c->dev.err = "material " + std::to_string(k) + " both emits (skh_set_emission) and has an active blend entry (skh_set_material_blend): blended emitters are not supported";
                 return SKH_INVALID_ARGUMENT;
             }
         }
-    if (c->cutActiveMaterials && !c->emission.empty())
-        for (uint32_t k = 0; k < c->cutouts.size() && k < c->nMaterials; ++k)
-            if (c->cutouts[k].threshold > 0.0f && material_emits(c, k))
+    if (c->cut.activeMaterials && !c->emit.emission.empty())
+        for (uint32_t k = 0; k < c->cut.cutouts.size() && k < c->scene.nMaterials; ++k)
+            if (c->cut.cutouts[k].threshold > 0.0f && material_emits(c, k))
             {
-                c->err = "material " + std::to_string(k) + " both emits (skh_set_emission) and has an active cutout (skh_set_material_cutouts): cut-away emitters are not supported";
+                c->dev.err = "material " + std::to_string(k) + " both emits (skh_set_emission) and has an active cutout (skh_set_material_cutouts): cut-away emitters are not supported";
                 return SKH_INVALID_ARGUMENT;
             }
     return SKH_OK;
@@ -1022,14 +1013,14 @@ static skh_status cut_ensure(skh_context* c)
 // does the stage between trace and shade run: is a cutout or a blend entry in use?
 static inline bool cut_stage_on(const skh_context* c)
 {
-    return c->cutInstances != 0u || c->blendInstances != 0u;
+    return c->cut.instances != 0u || c->cut.blendInstances != 0u;
 }
 
 static CutoutP make_cutout(const skh_context* c)
 {
     CutoutP p;
-    p.table = c->dCutouts.as<uint4>();
-    p.count = (uint32_t)std::min<size_t>(c->cutouts.size(), c->nMaterials);
+    p.table = c->cut.dCutouts.as<uint4>();
+    p.count = (uint32_t)std::min<size_t>(c->cut.cutouts.size(), c->scene.nMaterials);
     return p;
 }
 
@@ -1038,10 +1029,10 @@ static BlendP make_blend(const skh_context* c)
 {
     BlendP p;
     memset(&p, 0, sizeof(p));
-    if (c->blendInstances)
+    if (c->cut.blendInstances)
     {
-        p.table = c->dBlend.as<uint4>();
-        p.count = (uint32_t)std::min<size_t>(c->blends.size(), c->nMaterials);
+        p.table = c->cut.dBlend.as<uint4>();
+        p.count = (uint32_t)std::min<size_t>(c->cut.blends.size(), c->scene.nMaterials);
     }
     return p;
 }
@@ -1050,7 +1041,7 @@ static size_t frame_count_words(const skh_context* c)
 {
     const size_t base = (size_t)SKH_COUNT_STRIDE * SKH_SHARDS * 2 * SKH_MAX_LAUNCH_ROUNDS + (size_t)16 * SKH_FETCH_STRIDE * SKH_MAX_LAUNCH_ROUNDS;
     // behind them, in a context with a cutout in use: per bounce and side (closest, shadow) cutout_rounds x {length words, fetch cursors}
-    return base + (cut_stage_on(c) ? (size_t)SKH_MAX_LAUNCH_ROUNDS * 2 * c->cutoutRounds * SKH_CUT_WORDS : 0u);
+    return base + (cut_stage_on(c) ? (size_t)SKH_MAX_LAUNCH_ROUNDS * 2 * c->opt.cutoutRounds * SKH_CUT_WORDS : 0u);
 }
 
 // the cutout stage's frame buffers: allocated when a cutout is in use (and only then), freed when none is any more
@@ -1058,38 +1049,48 @@ static skh_status cut_alloc_frame(skh_context* c)
 {
     if (!cut_stage_on(c))
     {
-        if (c->dCutQ[0].p)
+        if (c->cut.dQ[0].p)
         {
-            SKH_TRY(c, hipStreamSynchronize(c->stream));
+            SKH_TRY(c, hipStreamSynchronize(c->dev.stream));
             for (int k = 0; k < 2; ++k)
-                dev_free(c->dCutQ[k]), dev_free(c->dCutShadowQ[k]), dev_free(c->dCutShadowHits[k]);
-            dev_free(c->dCutHits);
+                dev_free(c->cut.dQ[k]), dev_free(c->cut.dShadowQ[k]), dev_free(c->cut.dShadowHits[k]);
+            dev_free(c->cut.dHits);
         }
         return SKH_OK;
     }
-    if (!c->width)
+    if (!c->frame.width)
         return SKH_OK;
-    const size_t NQ = (size_t)SKH_SHARDS * c->queueRegion;
+    const size_t NQ = (size_t)SKH_SHARDS * c->frame.queueRegion;
     const size_t qBytes = sizeof(float) * 9 * NQ, hBytes = sizeof(float) * 8 * NQ, cBytes = sizeof(uint32_t) * frame_count_words(c);
-    if (c->dCutQ[0].bytes >= qBytes && c->dCutQ[0].bytes <= 2 * qBytes + 4096 && c->dCounts.bytes >= cBytes)
+    if (c->cut.dQ[0].bytes >= qBytes && c->cut.dQ[0].bytes <= 2 * qBytes + 4096 && c->frame.dCounts.bytes >= cBytes)
         return SKH_OK;
-    SKH_TRY(c, hipStreamSynchronize(c->stream));
+    SKH_TRY(c, hipStreamSynchronize(c->dev.stream));
     for (int k = 0; k < 2; ++k)
     {
-        SKH_CHECK(dev_alloc(c, c->dCutQ[k], qBytes));
-        SKH_CHECK(dev_alloc(c, c->dCutShadowQ[k], qBytes));
-        SKH_CHECK(dev_alloc(c, c->dCutShadowHits[k], hBytes));
+        SKH_CHECK(dev_alloc(c, c->cut.dQ[k], qBytes));
+        SKH_CHECK(dev_alloc(c, c->cut.dShadowQ[k], qBytes));
+        SKH_CHECK(dev_alloc(c, c->cut.dShadowHits[k], hBytes));
     }
-    SKH_CHECK(dev_alloc(c, c->dCutHits, hBytes));
-    if (c->dCounts.bytes < cBytes)
-        SKH_CHECK(dev_alloc(c, c->dCounts, cBytes));
+    SKH_CHECK(dev_alloc(c, c->cut.dHits, hBytes));
+    if (c->frame.dCounts.bytes < cBytes)
+        SKH_CHECK(dev_alloc(c, c->frame.dCounts, cBytes));
     return SKH_OK;
 }
 
 // bytes of the cutout stage's frame buffers
 static uint64_t cut_stage_bytes(const skh_context* c)
 {
-    return c->dCutQ[0].bytes + c->dCutQ[1].bytes + c->dCutHits.bytes + c->dCutShadowQ[0].bytes + c->dCutShadowQ[1].bytes + c->dCutShadowHits[0].bytes + c->dCutShadowHits[1].bytes;
+    return c->cut.dQ[0].bytes + c->cut.dQ[1].bytes + c->cut.dHits.bytes + c->cut.dShadowQ[0].bytes + c->cut.dShadowQ[1].bytes + c->cut.dShadowHits[0].bytes + c->cut.dShadowHits[1].bytes;
+}
+
+// what skh_get_cutout_info and skh_get_blend_info share: the in-use counts brought up to date, the stage's counters read back
+static skh_status cut_read_stats(skh_context* c, CutStatsDev& sd)
+{
+    (void)hipSetDevice(c->dev.device);
+    SKH_CHECK(cut_ensure(c));
+    SKH_TRY(c, hipStreamSynchronize(c->dev.stream));
+    SKH_TRY(c, hipMemcpy(&sd, c->cut.dStats.p, sizeof(sd), hipMemcpyDeviceToHost));
+    return SKH_OK;
 }
 
 skh_status skh_get_cutout_info(skh_context* c, skh_cutout_info* out)
@@ -1097,12 +1098,9 @@ skh_status skh_get_cutout_info(skh_context* c, skh_cutout_info* out)
     if (!c || !out)
         return SKH_INVALID_ARGUMENT;
     memset(out, 0, sizeof(*out));
-    (void)hipSetDevice(c->device);
-    SKH_CHECK(cut_ensure(c));
     CutStatsDev sd;
-    SKH_TRY(c, hipStreamSynchronize(c->stream));
-    SKH_TRY(c, hipMemcpy(&sd, c->dCutStats.p, sizeof(sd), hipMemcpyDeviceToHost));
-    out->active_materials = c->cutActiveMaterials, out->instances = c->cutInstances;
+    SKH_CHECK(cut_read_stats(c, sd));
+    out->active_materials = c->cut.activeMaterials, out->instances = c->cut.instances;
     out->continued_closest = sd.continued[0], out->continued_shadow = sd.continued[1];
     out->accepted_by_cap = sd.capped[0] + sd.capped[1];
     out->bytes = cut_stage_bytes(c);
@@ -1114,12 +1112,9 @@ skh_status skh_get_blend_info(skh_context* c, skh_blend_info* out)
     if (!c || !out)
         return SKH_INVALID_ARGUMENT;
     memset(out, 0, sizeof(*out));
-    (void)hipSetDevice(c->device);
-    SKH_CHECK(cut_ensure(c));
     CutStatsDev sd;
-    SKH_TRY(c, hipStreamSynchronize(c->stream));
-    SKH_TRY(c, hipMemcpy(&sd, c->dCutStats.p, sizeof(sd), hipMemcpyDeviceToHost));
-    out->active_materials = c->blendActiveMaterials, out->instances = c->blendInstances;
+    SKH_CHECK(cut_read_stats(c, sd));
+    out->active_materials = c->cut.blendActiveMaterials, out->instances = c->cut.blendInstances;
     out->passed_radiance = sd.blendPassed, out->crossed_shadow = sd.blendCrossed, out->accepted_by_cap = sd.blendCapped;
     out->bytes = cut_stage_bytes(c);
     return SKH_OK;
@@ -1131,10 +1126,10 @@ skh_status skh_blend_probe(skh_context* c, uint32_t n, const uint32_t* in, float
         return SKH_INVALID_ARGUMENT;
     if (!n)
         return SKH_OK;
-    (void)hipSetDevice(c->device);
+    (void)hipSetDevice(c->dev.device);
     const ProbeIn pin[] = { { in, sizeof(uint32_t) * 6 * (size_t)n } };
     return probe_roundtrip(c, pin, xi, sizeof(float) * (size_t)n,
-                           [&](const DevBuf* d, const DevBuf& dOut) { k_blend_probe<<<(n + 255) / 256, 256, 0, c->stream>>>(n, d[0].as<uint32_t>(), dOut.as<float>()); });
+                           [&](const DevBuf* d, const DevBuf& dOut) { k_blend_probe<<<(n + 255) / 256, 256, 0, c->dev.stream>>>(n, d[0].as<uint32_t>(), dOut.as<float>()); });
 }
 
 static skh_status ensure_ready(skh_context* c);
@@ -1153,39 +1148,39 @@ static uint32_t lshape_flags_for(uint32_t flags, int32_t type)
 // for lights beyond the caller's table -- exists only when one is.
 static skh_status lshape_ensure(skh_context* c)
 {
-    if (!c->lshapeStale)
+    if (!c->lshape.stale)
         return SKH_OK;
-    const uint32_t n = (uint32_t)std::min<size_t>(c->lshapes.size(), c->nLights);
+    const uint32_t n = (uint32_t)std::min<size_t>(c->lshape.table.size(), c->scene.nLights);
     uint32_t discs = 0, cones = 0;
-    std::vector<float> table(8 * (size_t)c->nLights, 0.0f);
+    std::vector<float> table(8 * (size_t)c->scene.nLights, 0.0f);
     for (uint32_t k = 0; k < n; ++k)
     {
-        const skh_light_shape& e = c->lshapes[k];
-        const uint32_t f = lshape_flags_for(e.flags, c->lightTypes[k]);
+        const skh_light_shape& e = c->lshape.table[k];
+        const uint32_t f = lshape_flags_for(e.flags, c->scene.lightTypes[k]);
         discs += (f & SKH_LIGHT_SHAPE_SAMPLE_DISC) ? 1u : 0u, cones += (f & SKH_LIGHT_SHAPE_CONE) ? 1u : 0u;
         float* o = &table[8 * (size_t)k];
         memcpy(o, &f, 4);
         o[1] = e.cos_outer, o[2] = e.cos_inner, o[3] = e.focus, o[4] = e.axis[0], o[5] = e.axis[1], o[6] = e.axis[2];
     }
-    if (c->dLshape.p || discs || cones)
-        SKH_TRY(c, hipStreamSynchronize(c->stream)); // (the table is about to be replaced or freed)
+    if (c->lshape.dTable.p || discs || cones)
+        SKH_TRY(c, hipStreamSynchronize(c->dev.stream)); // (the table is about to be replaced or freed)
     if (discs || cones)
     {
         DevBuf d;
         SKH_CHECK(dev_upload(c, d, table.data(), table.size() * sizeof(float)));
-        c->dLshape = std::move(d);
+        c->lshape.dTable = std::move(d);
     }
     else
-        dev_free(c->dLshape);
-    c->lshapeDiscs = discs, c->lshapeCones = cones;
-    c->lshapeStale = false;
+        dev_free(c->lshape.dTable);
+    c->lshape.discs = discs, c->lshape.cones = cones;
+    c->lshape.stale = false;
     return SKH_OK;
 }
 
 static LshapeP make_lshape(const skh_context* c)
 {
     LshapeP p;
-    p.table = (c->lshapeDiscs || c->lshapeCones) ? c->dLshape.as<float4>() : nullptr;
+    p.table = (c->lshape.discs || c->lshape.cones) ? c->lshape.dTable.as<float4>() : nullptr;
     return p;
 }
 
@@ -1193,20 +1188,20 @@ skh_status skh_set_light_shapes(skh_context* c, const skh_light_shape* entries, 
 {
     if (!c)
         return SKH_INVALID_ARGUMENT;
-    (void)hipSetDevice(c->device);
+    (void)hipSetDevice(c->dev.device);
     if (!entries || n == 0)
     {
         // remove: a no-op on a context that has none (nothing traced ahead is thrown away for it)
-        if (c->lshapes.empty())
+        if (c->lshape.table.empty())
             return SKH_OK;
         spec_drop(c);
-        c->lshapes.clear();
-        c->lshapeStale = true;
+        c->lshape.table.clear();
+        touched(c, skh_stale::IN_LIGHT_SHAPES);
         return SKH_OK;
     }
-    if (n > c->nLights)
+    if (n > c->scene.nLights)
     {
-        c->err = "skh_set_light_shapes: " + std::to_string(n) + " entries for " + std::to_string(c->nLights) + " lights (call skh_set_lights first)";
+        c->dev.err = "skh_set_light_shapes: " + std::to_string(n) + " entries for " + std::to_string(c->scene.nLights) + " lights (call skh_set_lights first)";
         return SKH_INVALID_ARGUMENT;
     }
     for (uint32_t k = 0; k < n; ++k)
@@ -1221,15 +1216,15 @@ skh_status skh_set_light_shapes(skh_context* c, const skh_light_shape* entries, 
         }
         if (!ok)
         {
-            c->err = "skh_set_light_shapes: light " + std::to_string(k) +
+            c->dev.err = "skh_set_light_shapes: light " + std::to_string(k) +
                      ": flags above 3, a cosine outside [-1, 1] or not finite, cos_inner < cos_outer, a focus that is negative or not finite, a cone axis that is not "
                      "finite or not of unit length, or a non-zero reserved word";
             return SKH_INVALID_ARGUMENT;
         }
     }
     spec_drop(c);
-    c->lshapes.assign(entries, entries + n);
-    c->lshapeStale = true;
+    c->lshape.table.assign(entries, entries + n);
+    touched(c, skh_stale::IN_LIGHT_SHAPES);
     return SKH_OK;
 }
 
@@ -1238,9 +1233,9 @@ skh_status skh_get_light_shape_info(skh_context* c, skh_light_shape_info* out)
     if (!c || !out)
         return SKH_INVALID_ARGUMENT;
     memset(out, 0, sizeof(*out));
-    (void)hipSetDevice(c->device);
+    (void)hipSetDevice(c->dev.device);
     SKH_CHECK(lshape_ensure(c));
-    out->sampled_discs = c->lshapeDiscs, out->cones = c->lshapeCones;
+    out->sampled_discs = c->lshape.discs, out->cones = c->lshape.cones;
     return SKH_OK;
 }
 
@@ -1250,26 +1245,26 @@ skh_status skh_light_shape_probe(skh_context* c, uint32_t kind, const void* in, 
         return SKH_INVALID_ARGUMENT;
     if (kind > SKH_LSHAPE_PROBE_PDF || (n && (!in || !out)))
     {
-        c->err = "skh_light_shape_probe: unknown kind, or a missing input / output pointer";
+        c->dev.err = "skh_light_shape_probe: unknown kind, or a missing input / output pointer";
         return SKH_INVALID_ARGUMENT;
     }
-    (void)hipSetDevice(c->device);
+    (void)hipSetDevice(c->dev.device);
     SKH_CHECK(lshape_ensure(c));
     if (n == 0)
         return SKH_OK;
     const size_t inBytes = (kind == SKH_LSHAPE_PROBE_SAMPLE ? 6u : 7u) * sizeof(uint32_t), outBytes = (kind == SKH_LSHAPE_PROBE_SAMPLE ? 13u : 2u) * sizeof(float);
     const ProbeIn pin[] = { { in, inBytes * n } };
     return probe_roundtrip(c, pin, out, outBytes * n, [&](const DevBuf* d, const DevBuf& dOut) {
-        k_lshape_probe<<<(n + 255) / 256, 256, 0, c->stream>>>(c->dLights.as<Light>(), c->nLights, make_lshape(c), 0u, kind, d[0].as<uint32_t>(), n, dOut.as<float>());
+        k_lshape_probe<<<(n + 255) / 256, 256, 0, c->dev.stream>>>(c->scene.dLights.as<Light>(), c->scene.nLights, make_lshape(c), 0u, kind, d[0].as<uint32_t>(), n, dOut.as<float>());
     });
 }
 
 // ---- emissive meshes: skh_set_emission, the emitter table (skh_emit.h) ----
 static void emit_clear(skh_context* c)
 {
-    dev_free(c->dEmitEntries), dev_free(c->dEmitCdf), dev_free(c->dEmitGuide), dev_free(c->dEmitLe), dev_free(c->dEmitInstOffset);
-    c->emitCount = c->emitInstances = c->emitGuideBits = 0;
-    c->emitSumW = 0.0;
+    dev_free(c->emit.dEntries), dev_free(c->emit.dCdf), dev_free(c->emit.dGuide), dev_free(c->emit.dLe), dev_free(c->emit.dInstOffset);
+    c->emit.count = c->emit.instances = c->emit.guideBits = 0;
+    c->emit.sumW = 0.0;
 }
 
 static float lum709(const float* rgb)
@@ -1280,39 +1275,39 @@ static float lum709(const float* rgb)
 // Builds the table when it is stale.  Needs the geometry, the instances and the material count, no acceleration structure.
 static skh_status emit_ensure(skh_context* c)
 {
-    if (!c->emitStale)
+    if (!c->emit.stale)
         return SKH_OK;
-    if (c->emission.empty())
+    if (c->emit.emission.empty())
     {
         // (nothing emits: no device work, no synchronisation -- a context that was never told pays one test per call)
-        if (c->emitCount || c->dEmitLe.p)
+        if (c->emit.count || c->emit.dLe.p)
         {
-            SKH_TRY(c, hipStreamSynchronize(c->stream));
+            SKH_TRY(c, hipStreamSynchronize(c->dev.stream));
             emit_clear(c);
         }
-        c->emitMsBuild = 0.0;
-        c->emitStale = false;
+        c->emit.msBuild = 0.0;
+        c->emit.stale = false;
         return SKH_OK;
     }
     const auto t0 = std::chrono::steady_clock::now();
-    SKH_TRY(c, hipStreamSynchronize(c->stream)); // (the tables are about to be replaced)
-    const uint32_t nMat = std::max(1u, c->nMaterials), nMeshes = (uint32_t)c->meshes.size(), nInst = (uint32_t)c->instances.size();
+    SKH_TRY(c, hipStreamSynchronize(c->dev.stream)); // (the tables are about to be replaced)
+    const uint32_t nMat = std::max(1u, c->scene.nMaterials), nMeshes = (uint32_t)c->scene.meshes.size(), nInst = (uint32_t)c->scene.instances.size();
     std::vector<float> le(4 * (size_t)nMat, 0.0f); // {r, g, b, luminance}; materials beyond the emission list do not emit
-    for (uint32_t m = 0; m < nMat && 3 * (size_t)m + 2 < c->emission.size(); ++m)
+    for (uint32_t m = 0; m < nMat && 3 * (size_t)m + 2 < c->emit.emission.size(); ++m)
     {
-        memcpy(&le[4 * (size_t)m], &c->emission[3 * (size_t)m], 3 * sizeof(float));
-        le[4 * (size_t)m + 3] = lum709(&c->emission[3 * (size_t)m]);
+        memcpy(&le[4 * (size_t)m], &c->emit.emission[3 * (size_t)m], 3 * sizeof(float));
+        le[4 * (size_t)m + 3] = lum709(&c->emit.emission[3 * (size_t)m]);
     }
     std::vector<uint32_t> emitInst, emitBase, instOffset(std::max(1u, nInst), 0xffffffffu);
     uint64_t total = 0;
     for (uint32_t i = 0; i < nInst; ++i)
     {
-        const skh_instance& in = c->instances[i];
+        const skh_instance& in = c->scene.instances[i];
         if (in.type != SKH_INSTANCE_MESH || in.geom_id >= nMeshes)
             continue;
         const uint32_t mid = instance_material(c, in);
         float w2o[12];
-        const uint32_t tris = c->meshes[in.geom_id].index_count / 3u;
+        const uint32_t tris = c->scene.meshes[in.geom_id].index_count / 3u;
         if (!(le[4 * (size_t)mid + 3] > 0.0f) || tris == 0 || !invert_affine(in.transform, w2o)) // (a singular instance is disabled: no ray reaches it)
             continue;
         emitInst.push_back(i);
@@ -1321,7 +1316,7 @@ static skh_status emit_ensure(skh_context* c)
         total += tris;
         if (total > SKH_EMIT_MAX_ENTRIES)
         {
-            c->err = "emitter table: more than 2^24 emissive triangles (SKH_EMIT_MAX_ENTRIES)";
+            c->dev.err = "emitter table: more than 2^24 emissive triangles (SKH_EMIT_MAX_ENTRIES)";
             return SKH_INVALID_ARGUMENT;
         }
     }
@@ -1329,8 +1324,8 @@ static skh_status emit_ensure(skh_context* c)
     if (n == 0)
     {
         emit_clear(c);
-        c->emitMsBuild = 0.0;
-        c->emitStale = false;
+        c->emit.msBuild = 0.0;
+        c->emit.stale = false;
         return SKH_OK;
     }
     emitBase.push_back(n);
@@ -1350,9 +1345,9 @@ static skh_status emit_ensure(skh_context* c)
     SKH_CHECK(dev_upload(c, dBase, emitBase.data(), emitBase.size() * sizeof(uint32_t)));
     double* tileSum = dTmp.as<double>();
     double* sumW = tileSum + nTiles;
-    hipStream_t st = c->stream;
-    k_emit_gather<<<(n + SKH_EMIT_BLOCK - 1u) / SKH_EMIT_BLOCK, SKH_EMIT_BLOCK, 0, st>>>(c->dVerts.as<uint8_t>(), c->dIndices.as<uint32_t>(), c->dMeshes.as<uint4>(),
-                                                                                       c->dInstances.as<uint32_t>(), dLe.as<float4>(), nMat, dInst.as<uint32_t>(),
+    hipStream_t st = c->dev.stream;
+    k_emit_gather<<<(n + SKH_EMIT_BLOCK - 1u) / SKH_EMIT_BLOCK, SKH_EMIT_BLOCK, 0, st>>>(c->scene.dVerts.as<uint8_t>(), c->scene.dIndices.as<uint32_t>(), c->scene.dMeshes.as<uint4>(),
+                                                                                       c->scene.dInstances.as<uint32_t>(), dLe.as<float4>(), nMat, dInst.as<uint32_t>(),
                                                                                        dBase.as<uint32_t>(), nEmit, n, dEntries.as<float4>(), dWeight.as<float>());
     k_emit_tile_sums<<<nTiles, SKH_EMIT_BLOCK, 0, st>>>(dWeight.as<float>(), n, tileSum);
     k_emit_scan_tiles<<<1, SKH_EMIT_BLOCK, 0, st>>>(tileSum, nTiles, sumW);
@@ -1362,11 +1357,11 @@ static skh_status emit_ensure(skh_context* c)
     double totalW = 0.0;
     SKH_TRY(c, hipMemcpyAsync(&totalW, sumW, sizeof(double), hipMemcpyDeviceToHost, st));
     SKH_TRY(c, hipStreamSynchronize(st));
-    c->dEmitEntries = std::move(dEntries), c->dEmitCdf = std::move(dCdf), c->dEmitGuide = std::move(dGuide), c->dEmitLe = std::move(dLe), c->dEmitInstOffset = std::move(dOff);
-    c->emitCount = n, c->emitInstances = nEmit, c->emitGuideBits = bits;
-    c->emitSumW = totalW;
-    c->emitMsBuild = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
-    c->emitStale = false;
+    c->emit.dEntries = std::move(dEntries), c->emit.dCdf = std::move(dCdf), c->emit.dGuide = std::move(dGuide), c->emit.dLe = std::move(dLe), c->emit.dInstOffset = std::move(dOff);
+    c->emit.count = n, c->emit.instances = nEmit, c->emit.guideBits = bits;
+    c->emit.sumW = totalW;
+    c->emit.msBuild = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    c->emit.stale = false;
     return SKH_OK;
 }
 
@@ -1374,16 +1369,16 @@ static EmitP make_emit(const skh_context* c)
 {
     EmitP e;
     memset(&e, 0, sizeof(e));
-    if (!(c->emitSumW > 0.0))
+    if (!(c->emit.sumW > 0.0))
         return e;
-    e.entries = c->dEmitEntries.as<float4>();
-    e.cdf = c->dEmitCdf.as<float>();
-    e.guide = c->dEmitGuide.as<uint32_t>();
-    e.Le = c->dEmitLe.as<float4>();
-    e.instOffset = c->dEmitInstOffset.as<uint32_t>();
-    e.count = c->emitCount, e.guideBits = c->emitGuideBits, e.numMaterials = std::max(1u, c->nMaterials);
-    e.nee = c->emitNee;
-    e.invSumW = (float)(1.0 / c->emitSumW);
+    e.entries = c->emit.dEntries.as<float4>();
+    e.cdf = c->emit.dCdf.as<float>();
+    e.guide = c->emit.dGuide.as<uint32_t>();
+    e.Le = c->emit.dLe.as<float4>();
+    e.instOffset = c->emit.dInstOffset.as<uint32_t>();
+    e.count = c->emit.count, e.guideBits = c->emit.guideBits, e.numMaterials = std::max(1u, c->scene.nMaterials);
+    e.nee = c->opt.emitNee;
+    e.invSumW = (float)(1.0 / c->emit.sumW);
     return e;
 }
 
@@ -1391,27 +1386,26 @@ skh_status skh_set_emission(skh_context* c, const float* rgb, uint32_t n)
 {
     if (!c)
         return SKH_INVALID_ARGUMENT;
-    (void)hipSetDevice(c->device);
+    (void)hipSetDevice(c->dev.device);
     if (!rgb || n == 0)
     {
         // remove: a no-op on a context that has none (nothing traced ahead is thrown away for it)
-        if (c->emission.empty())
+        if (c->emit.emission.empty())
             return SKH_OK;
         spec_drop(c);
-        c->emission.clear();
-        c->emitStale = true;
-        c->cutStale = true;
+        c->emit.emission.clear();
+        touched(c, skh_stale::IN_EMISSION);
         return SKH_OK;
     }
-    if (n > c->nMaterials)
+    if (n > c->scene.nMaterials)
     {
-        c->err = "skh_set_emission: " + std::to_string(n) + " radiances for " + std::to_string(c->nMaterials) + " materials (call skh_set_materials first)";
+        c->dev.err = "skh_set_emission: " + std::to_string(n) + " radiances for " + std::to_string(c->scene.nMaterials) + " materials (call skh_set_materials first)";
         return SKH_INVALID_ARGUMENT;
     }
     for (size_t k = 0; k < 3 * (size_t)n; ++k)
         if (!(rgb[k] >= 0.0f) || std::isinf(rgb[k])) // (a NaN fails >=)
         {
-            c->err = "skh_set_emission: the radiances must be finite and >= 0";
+            c->dev.err = "skh_set_emission: the radiances must be finite and >= 0";
             return SKH_INVALID_ARGUMENT;
         }
     spec_drop(c);
@@ -1419,11 +1413,10 @@ skh_status skh_set_emission(skh_context* c, const float* rgb, uint32_t n)
     for (size_t k = 0; k < 3 * (size_t)n; ++k)
         any = any || rgb[k] > 0.0f;
     if (any)
-        c->emission.assign(rgb, rgb + 3 * (size_t)n);
+        c->emit.emission.assign(rgb, rgb + 3 * (size_t)n);
     else
-        c->emission.clear(); // (all black: the context of one that was never told)
-    c->emitStale = true;
-    c->cutStale = true;
+        c->emit.emission.clear(); // (all black: the context of one that was never told)
+    touched(c, skh_stale::IN_EMISSION);
     return SKH_OK;
 }
 
@@ -1432,12 +1425,12 @@ skh_status skh_get_emitter_info(skh_context* c, skh_emitter_info* out)
     if (!c || !out)
         return SKH_INVALID_ARGUMENT;
     memset(out, 0, sizeof(*out));
-    (void)hipSetDevice(c->device);
+    (void)hipSetDevice(c->dev.device);
     SKH_CHECK(emit_ensure(c));
-    out->triangles = c->emitCount, out->instances = c->emitInstances;
-    out->sum_w = c->emitSumW;
-    out->ms_build = c->emitMsBuild;
-    out->bytes = c->emitCount ? c->dEmitEntries.bytes + c->dEmitCdf.bytes + c->dEmitGuide.bytes + c->dEmitLe.bytes + c->dEmitInstOffset.bytes : 0u;
+    out->triangles = c->emit.count, out->instances = c->emit.instances;
+    out->sum_w = c->emit.sumW;
+    out->ms_build = c->emit.msBuild;
+    out->bytes = c->emit.count ? c->emit.dEntries.bytes + c->emit.dCdf.bytes + c->emit.dGuide.bytes + c->emit.dLe.bytes + c->emit.dInstOffset.bytes : 0u;
     return SKH_OK;
 }
 
@@ -1447,14 +1440,14 @@ skh_status skh_emitter_probe(skh_context* c, uint32_t kind, const void* in, uint
         return SKH_INVALID_ARGUMENT;
     if (kind > SKH_EMIT_PROBE_PDF || (n && (!in || !out)))
     {
-        c->err = "skh_emitter_probe: unknown kind, or a missing input / output pointer";
+        c->dev.err = "skh_emitter_probe: unknown kind, or a missing input / output pointer";
         return SKH_INVALID_ARGUMENT;
     }
-    (void)hipSetDevice(c->device);
+    (void)hipSetDevice(c->dev.device);
     SKH_CHECK(emit_ensure(c));
-    if (!(c->emitSumW > 0.0))
+    if (!(c->emit.sumW > 0.0))
     {
-        c->err = "skh_emitter_probe: the context has no emitter (no emissive material on a mesh instance)";
+        c->dev.err = "skh_emitter_probe: the context has no emitter (no emissive material on a mesh instance)";
         return SKH_INVALID_ARGUMENT;
     }
     if (n == 0)
@@ -1467,21 +1460,21 @@ skh_status skh_emitter_probe(skh_context* c, uint32_t kind, const void* in, uint
     const ProbeIn pin[] = { { in, inBytes * n } };
     return probe_roundtrip(c, pin, out, outBytes * n, [&](const DevBuf* d, const DevBuf& dOut) {
         if (withMaps)
-            k_emit_probe_mtex<<<(n + 255) / 256, 256, 0, c->stream>>>(make_emit(c), make_mtex(c), make_dev_scene(c), d[0].as<float>(), n, dOut.as<uint32_t>());
+            k_emit_probe_mtex<<<(n + 255) / 256, 256, 0, c->dev.stream>>>(make_emit(c), make_mtex(c), make_dev_scene(c), d[0].as<float>(), n, dOut.as<uint32_t>());
         else
-            k_emit_probe<<<(n + 255) / 256, 256, 0, c->stream>>>(make_emit(c), (uint32_t)c->instances.size(), kind, d[0].as<uint32_t>(), n, dOut.as<uint32_t>());
+            k_emit_probe<<<(n + 255) / 256, 256, 0, c->dev.stream>>>(make_emit(c), (uint32_t)c->scene.instances.size(), kind, d[0].as<uint32_t>(), n, dOut.as<uint32_t>());
     });
 }
 
 static skh_status ensure_ready(skh_context* c)
 {
-    if (!c->accelBuilt)
+    if (!c->accel.built)
     {
         skh_status s = skh_build_accel(c, SKH_BUILD_LBVH);
         if (s != SKH_OK)
             return s;
     }
-    if (c->nMaterials == 0)
+    if (c->scene.nMaterials == 0)
     {
         // material 0 = default.mdl::default_material (OptixRender.cpp:1090-1097)
         skh_material m;
@@ -1521,13 +1514,13 @@ static const TraceKernel kTraceKernels[TB_COUNT][2 /* ANY */][2 /* COUNT */] = {
 // The build this context's launches run.  `split`: the pass asks for the SPLIT build (tail_split -1: render_one).
 static TraceBuild trace_build(const skh_context* c, bool split)
 {
-    const bool noTopLevel = c->tlasRoot == SKH_REF_INVALID && c->worldKernel;
-    if (!c->nSegs && noTopLevel && (c->worldRoot != SKH_REF_INVALID || c->lightRoot != SKH_REF_INVALID))
-        return (c->tailSplit == 2 || (c->tailSplit == 1 && c->hierNodes > 16384u) || split) ? TB_WORLD_SPLIT : TB_WORLD;
-    if (c->nSegs && noTopLevel && c->numWorldCurves > 0)
+    const bool noTopLevel = c->accel.tlasRoot == SKH_REF_INVALID && c->opt.worldKernel;
+    if (!c->accel.nSegs && noTopLevel && (c->accel.worldRoot != SKH_REF_INVALID || c->accel.lightRoot != SKH_REF_INVALID))
+        return (c->opt.tailSplit == 2 || (c->opt.tailSplit == 1 && c->accel.hierNodes > 16384u) || split) ? TB_WORLD_SPLIT : TB_WORLD;
+    if (c->accel.nSegs && noTopLevel && c->accel.numWorldCurves > 0)
         return TB_WORLD_CURVES;
     // scenes without curve instances run the build of the kernel that has no curve intersector in it (fewer VGPRs)
-    return c->nSegs ? TB_GENERAL_CURVES : TB_GENERAL;
+    return c->accel.nSegs ? TB_GENERAL_CURVES : TB_GENERAL;
 }
 
 // Everything one launch of the persistent trace kernel depends on beside the scene and the context's options.
@@ -1550,43 +1543,43 @@ static void launch_trace(skh_context* c, const DevScene& sc, const TraceLaunch& 
 {
     const bool any = t.any;
     const TraceBuild build = trace_build(c, t.split);
-    const bool curveBuild = c->nSegs != 0;
+    const bool curveBuild = c->accel.nSegs != 0;
     // (small overlapped passes, triangle scenes: a closest-hit wave asks for rays when 48 instead of 32 of its lanes are idle -- 1-spp 1080p call 3.11 -> 3.01 ms; 40 / 56: 3.04 / 3.04; lower
     // thresholds lose: 24 / 16 / 8: 3.20 / 3.29 / 3.44; the any-hit threshold stays: 32 / 56 of 64: 3.16 / 3.12 against 3.11 at 48.  An explicit fetch_min_closest applies everywhere.)
-    const uint32_t fetchMinClosest = (t.smallGrid && !curveBuild && !c->fetchMinClosestSet) ? c->fetchMinClosestSmall : (curveBuild ? c->curveFetchMinClosest : c->fetchMinClosest);
-    const uint32_t fetchMin = any ? (curveBuild ? c->curveFetchMinShadow : c->fetchMinShadow) : fetchMinClosest;
-    const uint32_t nodeBreak = any ? (curveBuild ? c->curveNodeBreakShadow : c->nodeBreakShadow) : (curveBuild ? c->curveNodeBreakClosest : c->nodeBreakClosest);
+    const uint32_t fetchMinClosest = (t.smallGrid && !curveBuild && !c->opt.fetchMinClosestSet) ? c->opt.fetchMinClosestSmall : (curveBuild ? c->opt.curveFetchMinClosest : c->opt.fetchMinClosest);
+    const uint32_t fetchMin = any ? (curveBuild ? c->opt.curveFetchMinShadow : c->opt.fetchMinShadow) : fetchMinClosest;
+    const uint32_t nodeBreak = any ? (curveBuild ? c->opt.curveNodeBreakShadow : c->opt.nodeBreakShadow) : (curveBuild ? c->opt.curveNodeBreakClosest : c->opt.nodeBreakClosest);
     // (the world-only kernel with the curve block -- curve instances under identity transforms -- wants the triangle kernels' node-loop exits and
     // an earlier curve block: hair stand-in 1 862 -> 1 937 Mray/s with 32 / 28 / 32 against the two-level curve build's 20 / 20 / 48, gpurun_out/r5t)
     const bool worldCurves = build == TB_WORLD_CURVES;
-    const uint32_t nodeBreakW = worldCurves ? (any ? c->nodeBreakShadow : c->nodeBreakClosest) : nodeBreak;
-    const uint32_t fm = fetchMin | ((worldCurves ? c->worldCurveMin : c->curveMin) << 8) | (nodeBreakW << 16) | (c->leafMin << 24);
+    const uint32_t nodeBreakW = worldCurves ? (any ? c->opt.nodeBreakShadow : c->opt.nodeBreakClosest) : nodeBreak;
+    const uint32_t fm = fetchMin | ((worldCurves ? c->opt.worldCurveMin : c->opt.curveMin) << 8) | (nodeBreakW << 16) | (c->opt.leafMin << 24);
     hipStream_t st = t.stream;
-    int* ovf = st == c->stream ? c->dOvf.as<int>() : c->dOvf2.as<int>(); // (two trace kernels may be in flight)
-    StatsDev* sd = c->dStats.as<StatsDev>();
+    int* ovf = st == c->dev.stream ? c->frame.dOvf.as<int>() : c->frame.dOvf2.as<int>(); // (two trace kernels may be in flight)
+    StatsDev* sd = c->timing.dStats.as<StatsDev>();
     const bool worldOnly = build == TB_WORLD || build == TB_WORLD_SPLIT;
     // (the world-only triangle builds run 8 waves per SIMD)
-    const uint32_t fullGrid = (any && !c->nSegs) ? (uint32_t)c->numCUs * (worldOnly ? c->wavesPerCUShadowWorld : c->wavesPerCUShadow)
-                                                 : (worldOnly ? (uint32_t)c->numCUs * c->wavesPerCUWorld : c->traceBlocks);
+    const uint32_t fullGrid = (any && !c->accel.nSegs) ? (uint32_t)c->dev.numCUs * (worldOnly ? c->opt.wavesPerCUShadowWorld : c->opt.wavesPerCUShadow)
+                                                 : (worldOnly ? (uint32_t)c->dev.numCUs * c->opt.wavesPerCUWorld : c->frame.traceBlocks);
     // (overlapped small passes: small_waves_* are shares of a 32-wave CU; a build that fits fewer waves -- the curve builds: 24 -- takes the same share of what it fits,
     // so that the two concurrent launches still fit side by side: hair 1-spp calls 651 -> ~680 Mray/s against an unscaled 20 / 12)
-    const uint32_t scaledGrid = (uint32_t)((uint64_t)t.smallGrid * fullGrid / (32u * (uint32_t)c->numCUs));
-    const uint32_t blocks = t.smallGrid ? std::max((uint32_t)c->numCUs, std::min(scaledGrid, fullGrid)) : fullGrid;
+    const uint32_t scaledGrid = (uint32_t)((uint64_t)t.smallGrid * fullGrid / (32u * (uint32_t)c->dev.numCUs));
+    const uint32_t blocks = t.smallGrid ? std::max((uint32_t)c->dev.numCUs, std::min(scaledGrid, fullGrid)) : fullGrid;
     // A hierarchy that fits the L2 many times over (Cornell: 30 triangles) makes rays so cheap that the launch is bound by the eight queue cursors'
     // atomics (~88 M per second and address): such scenes reserve 128 positions per atomic (Cornell 13.5 -> 14.8 Gray/s).  Larger scenes lose by it
     // (neighbouring rays are then traced at different times by one wave instead of together by neighbouring waves: kitchen -1 %, hair -2 %;
     // docs/LOG.md, round 5); only the world-only triangle builds carry the code.
-    const uint32_t chunk = c->fetchChunk >= 0 ? (uint32_t)c->fetchChunk : (c->hierNodes <= 16384u ? 128u : 0u);
+    const uint32_t chunk = c->opt.fetchChunk >= 0 ? (uint32_t)c->opt.fetchChunk : (c->accel.hierNodes <= 16384u ? 128u : 0u);
 #ifdef SKH_TAIL_PROFILE
     (void)hipMemsetAsync(&sd->launchT0[any ? 1 : 0], 0xff, sizeof(unsigned long long), st);
 #endif
-    kTraceKernels[build][any ? 1 : 0][c->countTraversal ? 1 : 0]<<<blocks, SKH_TRACE_BLOCK, 0, st>>>(sc, t.rq, t.counts, t.fetch, fm, t.hq, t.ps, t.contrib, ovf, sd, c->lightBox, chunk);
+    kTraceKernels[build][any ? 1 : 0][c->opt.countTraversal ? 1 : 0]<<<blocks, SKH_TRACE_BLOCK, 0, st>>>(sc, t.rq, t.counts, t.fetch, fm, t.hq, t.ps, t.contrib, ovf, sd, c->accel.lightBox, chunk);
 }
 
 // what the closest-hit launches of SHADOW rays walk: not the baked light proxies' tree (shadow rays do not see lights)
 static DevScene shadow_scene(const skh_context* c, DevScene sc)
 {
-    if (c->worldRoot != SKH_REF_INVALID || c->tlasRoot != SKH_REF_INVALID)
+    if (c->accel.worldRoot != SKH_REF_INVALID || c->accel.tlasRoot != SKH_REF_INVALID)
         sc.lightRoot = SKH_REF_INVALID;
     return sc;
 }
@@ -1613,10 +1606,10 @@ static void run_cutout_chain(skh_context* c, const DevScene& sc, const DevScene&
     BlendP bl = cr.bl;
     const auto kernel = kCutoutKernels[shadow ? 1 : 0][bl.count != 0u ? 1 : 0];
     bl.pathIds = reinterpret_cast<const uint32_t*>(t.rq.base + (size_t)8 * t.rq.stride);
-    CutStatsDev* cst = c->dCutStats.as<CutStatsDev>();
+    CutStatsDev* cst = c->cut.dStats.as<CutStatsDev>();
     const uint32_t perShard = (((cr.rays + SKH_SHARDS - 1u) / SKH_SHARDS) + 63u) & ~63u;
     const dim3 grid(SKH_SHARDS * ((std::min(perShard, t.rq.region) + SKH_CUTOUT_BLOCK - 1) / SKH_CUTOUT_BLOCK));
-    const uint32_t R = c->cutoutRounds, QW = SKH_COUNT_STRIDE * SKH_SHARDS;
+    const uint32_t R = c->opt.cutoutRounds, QW = SKH_COUNT_STRIDE * SKH_SHARDS;
     bl.round = 0u;
     kernel<<<grid, SKH_CUTOUT_BLOCK, 0, t.stream>>>(sc, cutp, t.rq, t.counts, t.hq, 1u, 0u, t.hq, cr.rawOut, t.ps, contrib, cr.q[0], cr.words, cst, bl);
     TraceLaunch next = t; // (any = false, contrib = nullptr: trace_step)
@@ -1652,11 +1645,11 @@ static void trace_step(skh_context* c, const DevScene& sc, TraceLaunch t, bool s
 // After a synchronisation: did any traversal of the calls since the last check drop a stack entry (its result may miss hits)?
 static skh_status check_stack_overflow(skh_context* c, const char* where)
 {
-    if (!*c->hOverflow)
+    if (!*c->dev.hOverflow)
         return SKH_OK;
-    *c->hOverflow = 0u;
-    c->stackOverflows++;
-    c->err = std::string(where) + ": a traversal stack overflowed its " + std::to_string(SKH_STACK_LDS) + " LDS + " + std::to_string(SKH_STACK_OVF) +
+    *c->dev.hOverflow = 0u;
+    c->timing.stackOverflows++;
+    c->dev.err = std::string(where) + ": a traversal stack overflowed its " + std::to_string(SKH_STACK_LDS) + " LDS + " + std::to_string(SKH_STACK_OVF) +
              " global entries and dropped a subtree: hits may be missing (degenerate hierarchy?)";
     return SKH_FAIL;
 }
@@ -1677,19 +1670,18 @@ skh_status skh_set_adaptive(skh_context* c, const skh_adaptive* a)
     if (!c || (a && skh_adaptive_check(a) != SKH_OK))
     {
         if (c)
-            c->err = "skh_set_adaptive: threshold finite and >= 0, dark_level finite and > 0, min_samples >= 2, interval >= 1, reserved words 0";
+            c->dev.err = "skh_set_adaptive: threshold finite and >= 0, dark_level finite and > 0, min_samples >= 2, interval >= 1, reserved words 0";
         return SKH_INVALID_ARGUMENT;
     }
-    (void)hipSetDevice(c->device);
+    (void)hipSetDevice(c->dev.device);
     spec_drop(c); // (also: the adaptive frame starts again)
     c->adapt.on = a != nullptr;
     if (a)
         c->adapt.cfg = *a;
     else
     {
-        SKH_TRY(c, hipStreamSynchronize(c->stream));
-        dev_free(c->dTileXYRender), dev_free(c->dRaygenBaseRender), dev_free(c->dAdaptState), dev_free(c->dAdaptTileQ), dev_free(c->dAdaptFrozenAt);
-        c->adapt = skh_context::Adaptive();
+        SKH_TRY(c, hipStreamSynchronize(c->dev.stream));
+        c->adapt = skh_context::Adaptive(); // (frees the feature's five buffers)
     }
     return SKH_OK;
 }
@@ -1707,22 +1699,22 @@ static skh_status adapt_prepare(skh_context* c, const skh_frame_params& p)
     skh_context::Adaptive& ad = c->adapt;
     if (ad.ready && p.subframe_index != 0)
         return SKH_OK;
-    const size_t N1 = std::max(1u, c->numSlots), nt = std::max(1u, c->numTiles);
-    const size_t baseBytes = sizeof(uint32_t) * std::max(1u, c->raygenBlocksPerSub);
-    SKH_CHECK(dev_alloc(c, c->dTileXYRender, sizeof(uint32_t) * 2 * nt));
-    SKH_CHECK(dev_alloc(c, c->dRaygenBaseRender, baseBytes));
-    SKH_CHECK(dev_alloc(c, c->dAdaptState, sizeof(float4) * N1));
-    SKH_CHECK(dev_alloc(c, c->dAdaptTileQ, sizeof(float) * nt));
-    SKH_CHECK(dev_alloc(c, c->dAdaptFrozenAt, sizeof(uint32_t) * nt));
-    SKH_TRY(c, hipMemcpyAsync(c->dTileXYRender.p, c->dTileXY.p, sizeof(uint32_t) * 2 * c->numTiles, hipMemcpyDeviceToDevice, c->stream));
-    SKH_TRY(c, hipMemcpyAsync(c->dRaygenBaseRender.p, c->dRaygenBase.p, baseBytes, hipMemcpyDeviceToDevice, c->stream));
-    SKH_TRY(c, hipMemsetAsync(c->dAdaptState.p, 0, sizeof(float4) * N1, c->stream));
-    SKH_TRY(c, hipMemsetAsync(c->dAdaptTileQ.p, 0, sizeof(float) * nt, c->stream));
-    SKH_TRY(c, hipMemsetAsync(c->dAdaptFrozenAt.p, 0, sizeof(uint32_t) * nt, c->stream));
-    ad.frozenAt.assign(c->numTiles, 0u);
+    const size_t N1 = std::max(1u, c->frame.numSlots), nt = std::max(1u, c->frame.numTiles);
+    const size_t baseBytes = sizeof(uint32_t) * std::max(1u, c->frame.raygenBlocksPerSub);
+    SKH_CHECK(dev_alloc(c, c->adapt.dTileXYRender, sizeof(uint32_t) * 2 * nt));
+    SKH_CHECK(dev_alloc(c, c->adapt.dRaygenBaseRender, baseBytes));
+    SKH_CHECK(dev_alloc(c, c->adapt.dState, sizeof(float4) * N1));
+    SKH_CHECK(dev_alloc(c, c->adapt.dTileQ, sizeof(float) * nt));
+    SKH_CHECK(dev_alloc(c, c->adapt.dFrozenAt, sizeof(uint32_t) * nt));
+    SKH_TRY(c, hipMemcpyAsync(c->adapt.dTileXYRender.p, c->frame.dTileXY.p, sizeof(uint32_t) * 2 * c->frame.numTiles, hipMemcpyDeviceToDevice, c->dev.stream));
+    SKH_TRY(c, hipMemcpyAsync(c->adapt.dRaygenBaseRender.p, c->frame.dRaygenBase.p, baseBytes, hipMemcpyDeviceToDevice, c->dev.stream));
+    SKH_TRY(c, hipMemsetAsync(c->adapt.dState.p, 0, sizeof(float4) * N1, c->dev.stream));
+    SKH_TRY(c, hipMemsetAsync(c->adapt.dTileQ.p, 0, sizeof(float) * nt, c->dev.stream));
+    SKH_TRY(c, hipMemsetAsync(c->adapt.dFrozenAt.p, 0, sizeof(uint32_t) * nt, c->dev.stream));
+    ad.frozenAt.assign(c->frame.numTiles, 0u);
     ad.delivered = ad.checks = 0;
-    ad.activeTiles = c->numTiles;
-    ad.raygenValid = c->raygenValidPerSub;
+    ad.activeTiles = c->frame.numTiles;
+    ad.raygenValid = c->frame.raygenValidPerSub;
     ad.pixelObs = ad.pixelObsSaved = 0;
     ad.ready = true;
     return SKH_OK;
@@ -1740,7 +1732,7 @@ static inline uint32_t adapt_to_next_check(const skh_context* c)
 // the fields of FrameP that describe the frame's geometry
 static void frame_geometry(const skh_context* c, FrameP& fp)
 {
-    fp.width = c->width, fp.height = c->height, fp.tileSize = c->tileSize, fp.tileShift = c->tileShift, fp.numTiles = c->numTiles, fp.numSlots = c->numSlots;
+    fp.width = c->frame.width, fp.height = c->frame.height, fp.tileSize = c->frame.tileSize, fp.tileShift = c->frame.tileShift, fp.numTiles = c->frame.numTiles, fp.numSlots = c->frame.numSlots;
 }
 
 static FrameP adapt_frame(const skh_context* c, const skh_frame_params& p)
@@ -1759,27 +1751,27 @@ static skh_status adapt_after_pass(skh_context* c, const skh_frame_params& p, ui
     skh_context::Adaptive& ad = c->adapt;
     ad.delivered += launches;
     ad.pixelObs += (uint64_t)ad.raygenValid * launches;
-    ad.pixelObsSaved += (uint64_t)(c->raygenValidPerSub - ad.raygenValid) * launches;
-    if (ad.delivered < ad.cfg.min_samples || (ad.delivered - ad.cfg.min_samples) % ad.cfg.interval != 0u || c->numTiles == 0u)
+    ad.pixelObsSaved += (uint64_t)(c->frame.raygenValidPerSub - ad.raygenValid) * launches;
+    if (ad.delivered < ad.cfg.min_samples || (ad.delivered - ad.cfg.min_samples) % ad.cfg.interval != 0u || c->frame.numTiles == 0u)
         return SKH_OK;
     const float thr2 = ad.cfg.threshold * ad.cfg.threshold;
     {
         SpanGuard g(c, KC_ACCUM);
-        k_adapt_tiles<<<c->numTiles, 256, 0, c->stream>>>(adapt_frame(c, p), c->dTileXYRender.as<uint32_t>(), c->dAdaptState.as<float4>(), ad.delivered, thr2,
-                                                          ad.cfg.dark_level, c->dAdaptTileQ.as<float>(), c->dAdaptFrozenAt.as<uint32_t>());
+        k_adapt_tiles<<<c->frame.numTiles, 256, 0, c->dev.stream>>>(adapt_frame(c, p), c->adapt.dTileXYRender.as<uint32_t>(), c->adapt.dState.as<float4>(), ad.delivered, thr2,
+                                                          ad.cfg.dark_level, c->adapt.dTileQ.as<float>(), c->adapt.dFrozenAt.as<uint32_t>());
     }
     ad.checks++;
-    SKH_TRY(c, hipMemcpyAsync(ad.frozenAt.data(), c->dAdaptFrozenAt.p, sizeof(uint32_t) * c->numTiles, hipMemcpyDeviceToHost, c->stream));
-    SKH_TRY(c, hipStreamSynchronize(c->stream));
+    SKH_TRY(c, hipMemcpyAsync(ad.frozenAt.data(), c->adapt.dFrozenAt.p, sizeof(uint32_t) * c->frame.numTiles, hipMemcpyDeviceToHost, c->dev.stream));
+    SKH_TRY(c, hipStreamSynchronize(c->dev.stream));
     uint32_t active = 0;
-    for (uint32_t t = 0; t < c->numTiles; ++t)
+    for (uint32_t t = 0; t < c->frame.numTiles; ++t)
         active += ad.frozenAt[t] == 0u ? 1u : 0u;
     if (active != ad.activeTiles)
     {
         std::vector<uint32_t> base;
         raygen_tables(c, ad.frozenAt.data(), base, ad.raygenValid);
-        SKH_TRY(c, hipMemcpyAsync(c->dRaygenBaseRender.p, base.data(), sizeof(uint32_t) * base.size(), hipMemcpyHostToDevice, c->stream));
-        SKH_TRY(c, hipStreamSynchronize(c->stream)); // (`base` goes out of scope)
+        SKH_TRY(c, hipMemcpyAsync(c->adapt.dRaygenBaseRender.p, base.data(), sizeof(uint32_t) * base.size(), hipMemcpyHostToDevice, c->dev.stream));
+        SKH_TRY(c, hipStreamSynchronize(c->dev.stream)); // (`base` goes out of scope)
         ad.activeTiles = active;
     }
     return SKH_OK;
@@ -1788,11 +1780,11 @@ static skh_status adapt_after_pass(skh_context* c, const skh_frame_params& p, ui
 // the frozen tiles' pixels of a call's d_image
 static void adapt_fill(skh_context* c, const skh_frame_params& p, void* d_image)
 {
-    if (!d_image || c->adapt.activeTiles == c->numTiles || c->numSlots == 0u)
+    if (!d_image || c->adapt.activeTiles == c->frame.numTiles || c->frame.numSlots == 0u)
         return;
     SpanGuard g(c, KC_ACCUM);
-    k_adapt_fill<<<(c->numSlots + 255) / 256, 256, 0, c->stream>>>(adapt_frame(c, p), c->dTileXY.as<uint32_t>(), c->dAdaptFrozenAt.as<uint32_t>(),
-                                                                 c->dAccum.as<float4>(), reinterpret_cast<float4*>(d_image));
+    k_adapt_fill<<<(c->frame.numSlots + 255) / 256, 256, 0, c->dev.stream>>>(adapt_frame(c, p), c->frame.dTileXY.as<uint32_t>(), c->adapt.dFrozenAt.as<uint32_t>(),
+                                                                 c->frame.dAccum.as<float4>(), reinterpret_cast<float4*>(d_image));
 }
 
 skh_status skh_get_adaptive_info(skh_context* c, skh_adaptive_info* out)
@@ -1802,19 +1794,19 @@ skh_status skh_get_adaptive_info(skh_context* c, skh_adaptive_info* out)
     const skh_context::Adaptive& ad = c->adapt;
     memset(out, 0, sizeof(*out));
     out->enabled = ad.on ? 1u : 0u;
-    out->tiles = c->numTiles;
-    out->active_tiles = c->numTiles;
+    out->tiles = c->frame.numTiles;
+    out->active_tiles = c->frame.numTiles;
     if (!ad.on || !ad.ready)
         return SKH_OK; // (the frame has not begun: every tile active, nothing observed)
     out->active_tiles = ad.activeTiles;
     out->checks = ad.checks;
     uint32_t lo = 0xffffffffu, hi = 0;
-    for (uint32_t t = 0; t < c->numTiles; ++t)
+    for (uint32_t t = 0; t < c->frame.numTiles; ++t)
     {
         const uint32_t n = ad.frozenAt[t] ? ad.frozenAt[t] : ad.delivered;
         lo = std::min(lo, n), hi = std::max(hi, n);
     }
-    out->min_observations = c->numTiles ? lo : 0u;
+    out->min_observations = c->frame.numTiles ? lo : 0u;
     out->max_observations = hi;
     out->pixel_observations = ad.pixelObs;
     out->pixel_observations_saved = ad.pixelObsSaved;
@@ -1884,18 +1876,18 @@ static void fill_queue_constants(skh_context* c, const RenderPass& rp)
     uint32_t bits[2];
     memcpy(&bits[0], &rp.fp.materialTmin, 4);
     memcpy(&bits[1], &rp.fp.shadowTmin, 4);
-    if (c->queueConstFilled && bits[0] == c->queueConstBits[0] && bits[1] == c->queueConstBits[1])
+    if (c->frame.queueConstFilled && bits[0] == c->frame.queueConstBits[0] && bits[1] == c->frame.queueConstBits[1])
         return;
-    const uint32_t fb = (uint32_t)c->numCUs * 8u;
+    const uint32_t fb = (uint32_t)c->dev.numCUs * 8u;
     for (int k = 0; k < 2; ++k)
     {
         k_fill_f32<<<fb, 256, 0, rp.st>>>(rp.rq[k].base + (size_t)6 * NQ, NQ, rp.fp.materialTmin);
         k_fill_f32<<<fb, 256, 0, rp.st>>>(rp.rq[k].base + (size_t)7 * NQ, NQ, 1e16f);
     }
     k_fill_f32<<<fb, 256, 0, rp.st>>>(rp.shq.base + (size_t)6 * NQ, NQ, rp.fp.shadowTmin);
-    c->queueConstFilled = true;
-    c->queueConstBits[0] = bits[0];
-    c->queueConstBits[1] = bits[1];
+    c->frame.queueConstFilled = true;
+    c->frame.queueConstBits[0] = bits[0];
+    c->frame.queueConstBits[1] = bits[1];
 }
 
 // k_shade for bounce b of sample s: the build by HAIR x ENV x EMIT x MTEX (index 8 4 2 1); every one has a twin with light shapes in it, launched only when a shape
@@ -1917,15 +1909,15 @@ static void launch_shade(skh_context* c, const RenderPass& rp, uint32_t s, uint3
     // workgroup b on shard b & 7; those past the end of their shard leave at once
     const uint32_t perShard = (((rp.NP + SKH_SHARDS - 1u) / SKH_SHARDS) + 63u) & ~63u;
     const dim3 sg(SKH_SHARDS * ((perShard + SKH_SHADE_BLOCK - 1) / SKH_SHADE_BLOCK));
-    const uint32_t build = (c->hasHairMaterial ? 8u : 0u) | (c->envW ? 4u : 0u) | (rp.emitp.count ? 2u : 0u) | (rp.mtexp.count ? 1u : 0u), QW = rp.QW;
+    const uint32_t build = (c->scene.hasHairMaterial ? 8u : 0u) | (c->env.w ? 4u : 0u) | (rp.emitp.count ? 2u : 0u) | (rp.mtexp.count ? 1u : 0u), QW = rp.QW;
     uint32_t* counts = rp.counts;
     if (rp.lshp.table)
         kShadeLshapeKernels[build]<<<sg, SKH_SHADE_BLOCK, 0, rp.st>>>(rp.sc, rp.fp, s, b, rp.tiles, rp.rq[b & 1], counts + 2 * b * QW, rp.hq, rp.ps, rp.rq[(b + 1) & 1],
-                                                                      counts + 2 * (b + 1) * QW, rp.shq, c->dContrib.as<float4>(), counts + (2 * b + 1) * QW, rp.envp,
+                                                                      counts + 2 * (b + 1) * QW, rp.shq, c->frame.dContrib.as<float4>(), counts + (2 * b + 1) * QW, rp.envp,
                                                                       rp.emitp, rp.mtexp, rp.lshp);
     else
         kShadeKernels[build]<<<sg, SKH_SHADE_BLOCK, 0, rp.st>>>(rp.sc, rp.fp, s, b, rp.tiles, rp.rq[b & 1], counts + 2 * b * QW, rp.hq, rp.ps, rp.rq[(b + 1) & 1],
-                                                                counts + 2 * (b + 1) * QW, rp.shq, c->dContrib.as<float4>(), counts + (2 * b + 1) * QW, rp.envp, rp.emitp,
+                                                                counts + 2 * (b + 1) * QW, rp.shq, c->frame.dContrib.as<float4>(), counts + (2 * b + 1) * QW, rp.envp, rp.emitp,
                                                                 rp.mtexp);
 }
 
@@ -1943,32 +1935,32 @@ static void render_bounce(skh_context* c, const RenderPass& rp, uint32_t s, uint
     {
         SpanGuard g(c, KC_TRACE_CLOSEST);
         t.rq = rp.rq[b & 1], t.counts = rp.counts + 2 * b * rp.QW, t.fetch = rp.fetch + 16 * b * SKH_FETCH_STRIDE, t.hq = rp.hq, t.contrib = nullptr, t.stream = st;
-        t.smallGrid = smallGrids ? ((b == 0 && c->smallWavesFirst) ? c->smallWavesFirst : c->smallWavesClosest ? c->smallWavesClosest : (c->nSegs ? 16u : 20u)) * (uint32_t)c->numCUs : 0u;
+        t.smallGrid = smallGrids ? ((b == 0 && c->opt.smallWavesFirst) ? c->opt.smallWavesFirst : c->opt.smallWavesClosest ? c->opt.smallWavesClosest : (c->accel.nSegs ? 16u : 20u)) * (uint32_t)c->dev.numCUs : 0u;
         const CutRounds cr{ { rp.cutQ[0], rp.cutQ[1] }, rp.hq, rp.cutH, nullptr, words, rp.NP, blp };
         trace_step(c, rp.sc, t, false, rp.cutOn ? &cr : nullptr);
     }
     if (rp.useOverlap && b > 0)
-        (void)hipStreamWaitEvent(st, c->evShadow, 0); // shade[b] reads the radiance shadow[b-1] adds to and reuses its queue
+        (void)hipStreamWaitEvent(st, c->dev.evShadow, 0); // shade[b] reads the radiance shadow[b-1] adds to and reuses its queue
     {
         SpanGuard g(c, KC_SHADE);
         launch_shade(c, rp, s, b);
     }
-    hipStream_t sst = rp.useOverlap ? c->stream2 : st;
+    hipStream_t sst = rp.useOverlap ? c->dev.stream2 : st;
     if (rp.useOverlap)
     {
-        (void)hipEventRecord(c->evShade, st);
-        (void)hipStreamWaitEvent(sst, c->evShade, 0);
+        (void)hipEventRecord(c->dev.evShade, st);
+        (void)hipStreamWaitEvent(sst, c->dev.evShade, 0);
     }
     {
         SpanGuard g(c, KC_TRACE_SHADOW, sst);
-        t.rq = rp.shq, t.counts = rp.counts + (2 * b + 1) * rp.QW, t.fetch = rp.fetch + (16 * b + 8) * SKH_FETCH_STRIDE, t.hq = HitQ{ nullptr, 0 }, t.contrib = c->dContrib.as<float4>(), t.stream = sst;
-        t.smallGrid = smallGrids ? ((b + 1 == rp.rounds && (c->smallWavesLast || (!c->smallWavesShadow && !c->nSegs))) ? (c->smallWavesLast ? c->smallWavesLast : 20u) : c->smallWavesShadow ? c->smallWavesShadow : (c->nSegs ? 16u : 12u)) * (uint32_t)c->numCUs : 0u;
+        t.rq = rp.shq, t.counts = rp.counts + (2 * b + 1) * rp.QW, t.fetch = rp.fetch + (16 * b + 8) * SKH_FETCH_STRIDE, t.hq = HitQ{ nullptr, 0 }, t.contrib = c->frame.dContrib.as<float4>(), t.stream = sst;
+        t.smallGrid = smallGrids ? ((b + 1 == rp.rounds && (c->opt.smallWavesLast || (!c->opt.smallWavesShadow && !c->accel.nSegs))) ? (c->opt.smallWavesLast ? c->opt.smallWavesLast : 20u) : c->opt.smallWavesShadow ? c->opt.smallWavesShadow : (c->accel.nSegs ? 16u : 12u)) * (uint32_t)c->dev.numCUs : 0u;
         // (a cutout in use) the shadow rays' NEAREST hits, tested and continued like the radiance rays'; a ray that ends in a miss adds its contribution (k_cutout)
-        const CutRounds cr{ { rp.cutSQ[0], rp.cutSQ[1] }, rp.cutSH0, rp.cutSH1, nullptr, rp.cutOn ? words + c->cutoutRounds * SKH_CUT_WORDS : nullptr, rp.NP, blp };
+        const CutRounds cr{ { rp.cutSQ[0], rp.cutSQ[1] }, rp.cutSH0, rp.cutSH1, nullptr, rp.cutOn ? words + c->opt.cutoutRounds * SKH_CUT_WORDS : nullptr, rp.NP, blp };
         trace_step(c, rp.sc, t, true, rp.cutOn ? &cr : nullptr);
     }
     if (rp.useOverlap)
-        (void)hipEventRecord(c->evShadow, sst);
+        (void)hipEventRecord(c->dev.evShadow, sst);
 }
 
 // the accumulation steps of a pass into the frame's accumulators (and the call's d_image)
@@ -1976,22 +1968,22 @@ static void render_accumulate(skh_context* c, const RenderPass& rp, const Render
 {
     if (!plan.finalize)
         return;
-    const uint32_t gridSlots = (c->numSlots + 255) / 256;
+    const uint32_t gridSlots = (c->frame.numSlots + 255) / 256;
     const bool fromPaths = plan.batch > 1 || oneSampleDirect;
     hipStream_t fs = plan.finStream ? plan.finStream : rp.st;
     {
         SpanGuard g(c, KC_ACCUM, fs);
         if (fromPaths)
-            k_finalize_batch<<<gridSlots, 256, 0, fs>>>(rp.fp, rp.tiles, rp.ps, c->dAccum.as<float4>(), c->dDiffuse.as<float4>(), c->dSpecular.as<float4>(),
-                                                        c->dDiffCnt.as<uint16_t>(), c->dSpecCnt.as<uint16_t>(), reinterpret_cast<float4*>(d_image));
+            k_finalize_batch<<<gridSlots, 256, 0, fs>>>(rp.fp, rp.tiles, rp.ps, c->frame.dAccum.as<float4>(), c->frame.dDiffuse.as<float4>(), c->frame.dSpecular.as<float4>(),
+                                                        c->frame.dDiffCnt.as<uint16_t>(), c->frame.dSpecCnt.as<uint16_t>(), reinterpret_cast<float4*>(d_image));
         else
-            k_finalize<<<gridSlots, 256, 0, fs>>>(rp.fp, rp.tiles, c->dSums.as<float>(), c->dAccum.as<float4>(), c->dDiffuse.as<float4>(), c->dSpecular.as<float4>(),
-                                                  c->dDiffCnt.as<uint16_t>(), c->dSpecCnt.as<uint16_t>(), reinterpret_cast<float4*>(d_image));
+            k_finalize<<<gridSlots, 256, 0, fs>>>(rp.fp, rp.tiles, c->frame.dSums.as<float>(), c->frame.dAccum.as<float4>(), c->frame.dDiffuse.as<float4>(), c->frame.dSpecular.as<float4>(),
+                                                  c->frame.dDiffCnt.as<uint16_t>(), c->frame.dSpecCnt.as<uint16_t>(), reinterpret_cast<float4*>(d_image));
     }
     if (plan.adaptive)
     {
         SpanGuard g(c, KC_ACCUM, fs);
-        k_adapt_moments<<<gridSlots, 256, 0, fs>>>(rp.fp, rp.tiles, rp.ps, c->dSums.as<float>(), fromPaths ? 0u : 1u, c->dAdaptState.as<float4>());
+        k_adapt_moments<<<gridSlots, 256, 0, fs>>>(rp.fp, rp.tiles, rp.ps, c->frame.dSums.as<float>(), fromPaths ? 0u : 1u, c->adapt.dState.as<float4>());
     }
 }
 
@@ -1999,11 +1991,11 @@ static skh_status render_one(skh_context* c, const skh_frame_params* p, const Re
 {
     if (p->max_depth > 128 || p->samples_this_launch == 0)
     {
-        c->err = "skh_render_subframe: max_depth must be <= 128 (MAX_BOUNCES, RandomSampler.h:35) and samples_this_launch >= 1";
+        c->dev.err = "skh_render_subframe: max_depth must be <= 128 (MAX_BOUNCES, RandomSampler.h:35) and samples_this_launch >= 1";
         return SKH_INVALID_ARGUMENT;
     }
     RenderPass rp;
-    hipStream_t st = rp.st = c->stream;
+    hipStream_t st = rp.st = c->dev.stream;
     const FrameP& fp = rp.fp = frame_params(c, p, plan);
     const uint32_t batch = plan.batch;
     rp.sc = make_dev_scene(c);
@@ -2011,35 +2003,35 @@ static skh_status render_one(skh_context* c, const skh_frame_params* p, const Re
     rp.emitp = make_emit(c);
     rp.mtexp = make_mtex(c);
     rp.lshp = make_lshape(c);
-    const uint32_t N = c->numSlots * c->batchCapacity; // plane stride of the path-state buffer
-    const uint32_t NQ = SKH_SHARDS * c->queueRegion; // plane stride of every queue (rays, hits, shadow contributions)
-    const uint32_t NP = rp.NP = c->numSlots * batch; // paths in this pass
+    const uint32_t N = c->frame.numSlots * c->frame.batchCapacity; // plane stride of the path-state buffer
+    const uint32_t NQ = SKH_SHARDS * c->frame.queueRegion; // plane stride of every queue (rays, hits, shadow contributions)
+    const uint32_t NP = rp.NP = c->frame.numSlots * batch; // paths in this pass
     if (NP == 0)
         return SKH_OK;
-    rp.tiles = plan.adaptive ? c->dTileXYRender.as<uint32_t>() : c->dTileXY.as<uint32_t>();
-    const uint32_t* raygenBase = plan.adaptive ? c->dRaygenBaseRender.as<uint32_t>() : c->dRaygenBase.as<uint32_t>();
-    const uint32_t raygenValid = plan.adaptive ? c->adapt.raygenValid : c->raygenValidPerSub;
-    rp.ps = PathS{ plan.pathSel ? c->dPathB.as<float>() : c->dPath.as<float>(), plan.pathSel ? c->pathBStride : N };
-    const auto queue = [&](const DevBuf& b) { return RayQ{ b.as<float>(), NQ, c->queueRegion }; };
-    rp.rq[0] = queue(c->dRayQ[0]), rp.rq[1] = queue(c->dRayQ[1]), rp.shq = queue(c->dShadowQ);
-    HitQ hq{ c->dHits.as<float>(), NQ };
+    rp.tiles = plan.adaptive ? c->adapt.dTileXYRender.as<uint32_t>() : c->frame.dTileXY.as<uint32_t>();
+    const uint32_t* raygenBase = plan.adaptive ? c->adapt.dRaygenBaseRender.as<uint32_t>() : c->frame.dRaygenBase.as<uint32_t>();
+    const uint32_t raygenValid = plan.adaptive ? c->adapt.raygenValid : c->frame.raygenValidPerSub;
+    rp.ps = PathS{ plan.pathSel ? c->spec.dPathB.as<float>() : c->frame.dPath.as<float>(), plan.pathSel ? c->spec.pathBStride : N };
+    const auto queue = [&](const DevBuf& b) { return RayQ{ b.as<float>(), NQ, c->frame.queueRegion }; };
+    rp.rq[0] = queue(c->frame.dRayQ[0]), rp.rq[1] = queue(c->frame.dRayQ[1]), rp.shq = queue(c->frame.dShadowQ);
+    HitQ hq{ c->frame.dHits.as<float>(), NQ };
     {
         // 16-byte hit records where they are possible: the world-only triangle kernels (every mesh hit names its shading record) and an instance
         // count and a record count that share 32 bits with the all-ones word left for a miss
         const bool worldKernels = trace_build(c, false) >= TB_WORLD;
-        const uint32_t range = std::max(1u, c->hitPrimRange); // shading records (or mesh-local indices), light proxies' triangles, curve segments: skh_build_accel
+        const uint32_t range = std::max(1u, c->accel.hitPrimRange); // shading records (or mesh-local indices), light proxies' triangles, curve segments: skh_build_accel
         uint32_t B = 1;
         while (B < 31u && (1u << B) < range)
             ++B;
-        hq.primBits = (c->compactHits && worldKernels && c->nShadeRecords != 0u && (uint64_t)c->nInstances <= (1ull << (32u - B)) - 1ull && (1ull << B) >= range) ? B : 0u;
-        hq.direct = c->directRecords;
-        hq.recClamp = c->nShadeRecords ? c->nShadeRecords - 1u : 0u;
+        hq.primBits = (c->opt.compactHits && worldKernels && c->accel.nShadeRecords != 0u && (uint64_t)c->scene.nInstances <= (1ull << (32u - B)) - 1ull && (1ull << B) >= range) ? B : 0u;
+        hq.direct = c->accel.directRecords;
+        hq.recClamp = c->accel.nShadeRecords ? c->accel.nShadeRecords - 1u : 0u;
     }
     rp.hq = hq;
     fill_queue_constants(c, rp);
     // dCounts: 260 queues (2 per bounce) x SKH_SHARDS queue-length words, then the ray-fetch cursors (8 per trace launch); every word
     // that is the target of atomics has a 128-byte line of its own (returning atomics on one line serialise at ~88 per microsecond)
-    uint32_t* counts = rp.counts = c->dCounts.as<uint32_t>();
+    uint32_t* counts = rp.counts = c->frame.dCounts.as<uint32_t>();
     const uint32_t QW = rp.QW = SKH_COUNT_STRIDE * SKH_SHARDS; // words per queue's lengths
     rp.fetch = counts + QW * 2 * SKH_MAX_LAUNCH_ROUNDS;
     // shadow[b] on a second stream: it depends on shade[b] only, and so does closest[b+1]; each fills the other's tail.  Ray
@@ -2049,22 +2041,22 @@ static skh_status render_one(skh_context* c, const skh_frame_params* p, const Re
     // full grids, where the second kernel's blocks simply take the slots the first one's finishing waves leave (1/8 share of a 1080p
     // frame: 24.26 -> 23.87 ms, 93.3 -> 94.9 % of 1/8 of the full frame; 1/4: 97.0 -> 97.8 %).  The full single-GPU frame (64 M paths
     // per pass) gains 0.5 % and stays on one stream so that its per-kernel hipEvent spans do not overlap.  overlap 2: always, reduced grids.
-    rp.smallPass = NP <= (1u << 23) || c->overlap == 2;
-    rp.useOverlap = (c->overlap == 2 || (c->overlap == 1 && NP <= (1u << 25))) && fp.debug != 1;
+    rp.smallPass = NP <= (1u << 23) || c->opt.overlap == 2;
+    rp.useOverlap = (c->opt.overlap == 2 || (c->opt.overlap == 1 && NP <= (1u << 25))) && fp.debug != 1;
     const uint32_t rounds = rp.rounds = fp.maxDepth;
     // Cutouts (skh_set_material_cutouts), only in a context where one is in use: k_cutout and its continuation rounds between a bounce's closest-hit launch and k_shade, and
     // a closest-hit launch with the same rounds behind it in the any-hit launch's place.  Per bounce and side cutout_rounds x SKH_CUT_WORDS words, behind the fetch cursors.
     const bool cutOn = rp.cutOn = cut_stage_on(c);
-    rp.cutBounceWords = 2u * c->cutoutRounds * SKH_CUT_WORDS;
+    rp.cutBounceWords = 2u * c->opt.cutoutRounds * SKH_CUT_WORDS;
     rp.cutWords = rp.fetch + 16 * SKH_FETCH_STRIDE * (rounds + 1);
-    rp.cutQ[0] = queue(c->dCutQ[0]), rp.cutQ[1] = queue(c->dCutQ[1]), rp.cutSQ[0] = queue(c->dCutShadowQ[0]), rp.cutSQ[1] = queue(c->dCutShadowQ[1]);
+    rp.cutQ[0] = queue(c->cut.dQ[0]), rp.cutQ[1] = queue(c->cut.dQ[1]), rp.cutSQ[0] = queue(c->cut.dShadowQ[0]), rp.cutSQ[1] = queue(c->cut.dShadowQ[1]);
     rp.cutH = rp.cutSH0 = rp.cutSH1 = hq; // (records as the closest-hit launches of this pass write them)
-    rp.cutH.base = c->dCutHits.as<float>(), rp.cutSH0.base = c->dCutShadowHits[0].as<float>(), rp.cutSH1.base = c->dCutShadowHits[1].as<float>();
+    rp.cutH.base = c->cut.dHits.as<float>(), rp.cutSH0.base = c->cut.dShadowHits[0].as<float>(), rp.cutSH1.base = c->cut.dShadowHits[1].as<float>();
     // fractional opacity (skh_set_material_blend), where it is in use: what the draw's path identity needs of the frame, and the contribution records, writable
     rp.blp = make_blend(c);
     rp.blp.tileXY = rp.tiles, rp.blp.sppTotal = fp.sppTotal, rp.blp.numSlots = fp.numSlots, rp.blp.tileShift = fp.tileShift;
-    rp.blp.contrib = c->dContrib.as<float4>();
-    rp.split = c->tailSplit < 0 && rp.smallPass && NP >= (1u << 17);
+    rp.blp.contrib = c->frame.dContrib.as<float4>();
+    rp.split = c->opt.tailSplit < 0 && rp.smallPass && NP >= (1u << 17);
     // One sub-frame of one sample, accumulated in this call (the reference caller's pattern): its sums ARE the path's radiance and event word -- the batch kernel reads
     // them where they lie (0.0f + radiance, / 1.0f: the same operations), and the k_collect launch and its 11 planes of sums are not needed.
     const bool oneSampleDirect = batch == 1 && fp.samplesThisLaunch == 1 && plan.finalize && fp.finalFirst == 0 && fp.finalCount == 1;
@@ -2075,7 +2067,7 @@ static skh_status render_one(skh_context* c, const skh_frame_params* p, const Re
         rp.blp.sampleBase = fp.subframeIndex + s;
         {
             SpanGuard g(c, KC_RAYGEN);
-            k_raygen<<<c->raygenBlocksPerSub * fp.batch, 512, 0, st>>>(fp, rp.tiles, s, rp.rq[0], counts, rp.ps, raygenBase, c->raygenBlocksPerSub, raygenValid);
+            k_raygen<<<c->frame.raygenBlocksPerSub * fp.batch, 512, 0, st>>>(fp, rp.tiles, s, rp.rq[0], counts, rp.ps, raygenBase, c->frame.raygenBlocksPerSub, raygenValid);
         }
         for (uint32_t b = 0; b < rounds; ++b)
         {
@@ -2084,19 +2076,19 @@ static skh_status render_one(skh_context* c, const skh_frame_params* p, const Re
                 break;
         }
         if (rp.useOverlap)
-            (void)hipStreamWaitEvent(st, c->evShadow, 0);
+            (void)hipStreamWaitEvent(st, c->dev.evShadow, 0);
         {
             SpanGuard g(c, KC_ACCUM);
-            k_add_stats<<<1, 64, 0, st>>>(counts, rounds, c->dStats.as<StatsDev>());
+            k_add_stats<<<1, 64, 0, st>>>(counts, rounds, c->timing.dStats.as<StatsDev>());
             if (batch == 1 && !oneSampleDirect)
-                k_collect<<<(c->numSlots + 255) / 256, 256, 0, st>>>(fp, rp.tiles, s, rp.ps, c->dSums.as<float>());
+                k_collect<<<(c->frame.numSlots + 255) / 256, 256, 0, st>>>(fp, rp.tiles, s, rp.ps, c->frame.dSums.as<float>());
         }
     }
     render_accumulate(c, rp, plan, oneSampleDirect, d_image);
     hipError_t e = hipGetLastError();
     if (e != hipSuccess)
     {
-        c->err = std::string("render launch: ") + hipGetErrorString(e);
+        c->dev.err = std::string("render launch: ") + hipGetErrorString(e);
         return SKH_FAIL;
     }
     return SKH_OK;
@@ -2106,10 +2098,10 @@ skh_status skh_render_subframes(skh_context* c, const skh_frame_params* params, 
 {
     if (!c || !params)
         return SKH_INVALID_ARGUMENT;
-    (void)hipSetDevice(c->device);
-    if (c->width == 0)
+    (void)hipSetDevice(c->dev.device);
+    if (c->frame.width == 0)
     {
-        c->err = "skh_render_subframe: call skh_resize first";
+        c->dev.err = "skh_render_subframe: call skh_resize first";
         return SKH_INVALID_ARGUMENT;
     }
     skh_status s = ensure_ready(c);
@@ -2121,7 +2113,7 @@ skh_status skh_render_subframes(skh_context* c, const skh_frame_params* params, 
         spec_drop(c, true);
     skh_frame_params p = *params;
     // single-sample sub-frames are traced `batchCapacity` at a time when that gives the GPU more rays per launch
-    const uint32_t cap = (p.samples_this_launch == 1 && p.debug != 1) ? c->batchCapacity : 1u;
+    const uint32_t cap = (p.samples_this_launch == 1 && p.debug != 1) ? c->frame.batchCapacity : 1u;
     const bool adaptive = adapt_applies(c, p) && n_subframes != 0u;
     if (adaptive && (s = adapt_prepare(c, p)) != SKH_OK)
         return s;
@@ -2130,7 +2122,7 @@ skh_status skh_render_subframes(skh_context* c, const skh_frame_params* params, 
         if (adaptive && c->adapt.activeTiles == 0u)
         {
             // every tile is frozen: the rest of the call traces nothing
-            c->adapt.pixelObsSaved += (uint64_t)c->raygenValidPerSub * (n_subframes - k);
+            c->adapt.pixelObsSaved += (uint64_t)c->frame.raygenValidPerSub * (n_subframes - k);
             break;
         }
         uint32_t b = std::min(cap, n_subframes - k);
@@ -2146,8 +2138,8 @@ skh_status skh_render_subframes(skh_context* c, const skh_frame_params* params, 
     }
     if (adaptive)
         adapt_fill(c, p, d_image);
-    SKH_TRY(c, hipStreamSynchronize(c->stream)); // the reference's render() is synchronous (OptixRender.cpp:1012)
-    if (c->timing)
+    SKH_TRY(c, hipStreamSynchronize(c->dev.stream)); // the reference's render() is synchronous (OptixRender.cpp:1012)
+    if (c->opt.timing)
         harvest_spans(c);
     return check_stack_overflow(c, "skh_render_subframes");
 }
@@ -2162,27 +2154,27 @@ static bool same_frame(const skh_frame_params& a, const skh_frame_params& b, uin
     return memcmp(&x, &y, sizeof(x)) == 0;
 }
 
-// speculate_async: start tracing the pass that follows the one being consumed.  Nothing is in flight and c->stream is idle here.
+// speculate_async: start tracing the pass that follows the one being consumed.  Nothing is in flight and c->dev.stream is idle here.
 static skh_status spec_launch_next(skh_context* c)
 {
     skh_context::Speculation& sp = c->spec;
-    if (!c->speculateAsync || !sp.valid || sp.nextInFlight || c->timing)
+    if (!c->opt.speculateAsync || !sp.valid || sp.nextInFlight || c->opt.timing)
         return SKH_OK; // (per-kernel hipEvent spans are harvested at every call: timing runs keep the synchronous scheme)
     const uint32_t nextStart = sp.params.subframe_index + sp.count;
     if (nextStart >= sp.params.spp_total)
         return SKH_OK;
-    const uint32_t cap = std::min(c->speculateMax, c->batchCapacity);
-    const uint32_t n = std::min(std::min(std::max(2u, sp.count * c->speculateGrow), cap), sp.params.spp_total - nextStart);
+    const uint32_t cap = std::min(c->opt.speculateMax, c->frame.batchCapacity);
+    const uint32_t n = std::min(std::min(std::max(2u, sp.count * c->opt.speculateGrow), cap), sp.params.spp_total - nextStart);
     const uint32_t other = sp.buf ^ 1u;
     if (other == 1u)
     {
-        const uint32_t stride = c->numSlots * cap;
-        skh_status s = dev_alloc(c, c->dPathB, sizeof(float) * SKH_PATH_FLOATS * (size_t)stride);
+        const uint32_t stride = c->frame.numSlots * cap;
+        skh_status s = dev_alloc(c, c->spec.dPathB, sizeof(float) * SKH_PATH_FLOATS * (size_t)stride);
         if (s != SKH_OK)
             return s;
-        c->pathBStride = stride;
+        c->spec.pathBStride = stride;
     }
-    SKH_TRY(c, hipMemcpy(sp.statsMark, c->dStats.p, sizeof(sp.statsMark), hipMemcpyDeviceToHost));
+    SKH_TRY(c, hipMemcpy(sp.statsMark, c->timing.dStats.p, sizeof(sp.statsMark), hipMemcpyDeviceToHost));
     sp.nextParams = sp.params;
     sp.nextParams.subframe_index = nextStart;
     sp.nextCount = n;
@@ -2200,21 +2192,21 @@ skh_status skh_render_subframe(skh_context* c, const skh_frame_params* params, v
     if (!c || !params)
         return SKH_INVALID_ARGUMENT;
     skh_context::Speculation& sp = c->spec;
-    const bool eligible = c->speculateMax > 1 && params->samples_this_launch == 1 && params->debug == 0 && c->width != 0 && c->batchCapacity > 1 &&
+    const bool eligible = c->opt.speculateMax > 1 && params->samples_this_launch == 1 && params->debug == 0 && c->frame.width != 0 && c->frame.batchCapacity > 1 &&
                           !c->adapt.on; // (an adaptive context traces nothing ahead: a pass that begins at a check cannot start before the check has run)
     if (!eligible)
     {
         spec_drop(c, false, true);
         return skh_render_subframes(c, params, 1, d_image);
     }
-    (void)hipSetDevice(c->device);
+    (void)hipSetDevice(c->dev.device);
     skh_status s;
     if (sp.nextInFlight && sp.valid && sp.consumed >= sp.count && same_frame(sp.nextParams, *params, 0))
     {
         // the caller has collected the whole pass and continues into the one in flight: wait for it, make it the current pass
         unsigned long long after[2] = { 0, 0 };
-        SKH_TRY(c, hipStreamSynchronize(c->stream));
-        SKH_TRY(c, hipMemcpy(after, c->dStats.p, sizeof(after), hipMemcpyDeviceToHost));
+        SKH_TRY(c, hipStreamSynchronize(c->dev.stream));
+        SKH_TRY(c, hipMemcpy(after, c->timing.dStats.p, sizeof(after), hipMemcpyDeviceToHost));
         sp.nextInFlight = false;
         sp.passRadiance = after[0] - sp.statsMark[0];
         sp.passShadow = after[1] - sp.statsMark[1];
@@ -2230,7 +2222,7 @@ skh_status skh_render_subframe(skh_context* c, const skh_frame_params* params, v
     {
         // this sub-frame was traced ahead: its radiances wait in the path state, only its accumulation step is left (beside a pass in
         // flight it runs on its own stream)
-        hipStream_t fin = sp.nextInFlight ? c->stream3 : c->stream;
+        hipStream_t fin = side_stream(c);
         RenderPlan plan; // the accumulation step of sub-frame sp.consumed of the pass
         plan.batch = sp.count, plan.trace = false, plan.finalFirst = sp.consumed, plan.finalCount = 1, plan.pathSel = sp.buf, plan.finStream = fin;
         if ((s = render_one(c, &sp.params, plan, d_image)) != SKH_OK)
@@ -2240,7 +2232,7 @@ skh_status skh_render_subframe(skh_context* c, const skh_frame_params* params, v
         sp.haveLast = true;
         sp.streak++;
         SKH_TRY(c, hipStreamSynchronize(fin));
-        if (c->timing && !sp.nextInFlight)
+        if (c->opt.timing && !sp.nextInFlight)
             harvest_spans(c);
         if (sp.consumed == 1)
             return spec_launch_next(c); // (first delivery of a pass that was itself traced in flight)
@@ -2252,7 +2244,7 @@ skh_status skh_render_subframe(skh_context* c, const skh_frame_params* params, v
     sp.streak = continues ? sp.streak + 1 : 0;
     uint32_t ahead = 1;
     if (continues && params->spp_total > params->subframe_index)
-        ahead = std::min(std::min(std::max(2u, sp.lastBatch * c->speculateGrow), std::min(c->speculateMax, c->batchCapacity)), params->spp_total - params->subframe_index);
+        ahead = std::min(std::min(std::max(2u, sp.lastBatch * c->opt.speculateGrow), std::min(c->opt.speculateMax, c->frame.batchCapacity)), params->spp_total - params->subframe_index);
     spec_drop(c, true);
     if ((s = ensure_ready(c)) != SKH_OK)
         return s;
@@ -2264,13 +2256,13 @@ skh_status skh_render_subframe(skh_context* c, const skh_frame_params* params, v
         return skh_render_subframes(c, params, 1, d_image);
     }
     unsigned long long before[2] = { 0, 0 }, after[2] = { 0, 0 }; // (StatsDev starts with raysRadiance, raysShadow; the stream is idle here)
-    SKH_TRY(c, hipMemcpy(before, c->dStats.p, sizeof(before), hipMemcpyDeviceToHost));
+    SKH_TRY(c, hipMemcpy(before, c->timing.dStats.p, sizeof(before), hipMemcpyDeviceToHost));
     RenderPlan plan; // `ahead` sub-frames traced, the first one delivered
     plan.batch = ahead, plan.finalCount = 1;
     if ((s = render_one(c, params, plan, d_image)) != SKH_OK)
         return s;
-    SKH_TRY(c, hipStreamSynchronize(c->stream));
-    SKH_TRY(c, hipMemcpy(after, c->dStats.p, sizeof(after), hipMemcpyDeviceToHost));
+    SKH_TRY(c, hipStreamSynchronize(c->dev.stream));
+    SKH_TRY(c, hipMemcpy(after, c->timing.dStats.p, sizeof(after), hipMemcpyDeviceToHost));
     sp.passRadiance = after[0] - before[0];
     sp.passShadow = after[1] - before[1];
     sp.valid = true;
@@ -2281,8 +2273,8 @@ skh_status skh_render_subframe(skh_context* c, const skh_frame_params* params, v
     sp.lastBatch = ahead;
     sp.last = *params;
     sp.haveLast = true;
-    SKH_TRY(c, hipStreamSynchronize(c->stream));
-    if (c->timing)
+    SKH_TRY(c, hipStreamSynchronize(c->dev.stream));
+    if (c->opt.timing)
         harvest_spans(c);
     if ((s = check_stack_overflow(c, "skh_render_subframe")) != SKH_OK)
         return s;
@@ -2293,9 +2285,9 @@ skh_status skh_tonemap(skh_context* c, void* d_image, uint32_t width, uint32_t h
 {
     if (!c || !d_image || !exposure)
         return SKH_INVALID_ARGUMENT;
-    (void)hipSetDevice(c->device);
+    (void)hipSetDevice(c->dev.device);
     const uint32_t n = width * height; // the reference's kernels test `> n` (Tonemappers.cu:20); this build uses >= n
-    hipStream_t st = c->spec.nextInFlight ? c->stream3 : c->stream; // (beside a pass traced ahead: not behind it)
+    hipStream_t st = side_stream(c); // (beside a pass traced ahead: not behind it)
     k_tonemap<<<(n + 255) / 256, 256, 0, st>>>(reinterpret_cast<float4*>(d_image), n, type, exposure[0], exposure[1], exposure[2], gamma);
     SKH_TRY(c, hipStreamSynchronize(st));
     return SKH_OK;
@@ -2305,7 +2297,7 @@ skh_status skh_buffer_alloc(skh_context* c, size_t bytes, void** out)
 {
     if (!c || !out)
         return SKH_INVALID_ARGUMENT;
-    (void)hipSetDevice(c->device);
+    (void)hipSetDevice(c->dev.device);
     *out = nullptr;
     SKH_TRY(c, hipMalloc(out, bytes ? bytes : 16));
     SKH_TRY(c, hipMemset(*out, 0, bytes ? bytes : 16));
@@ -2315,7 +2307,7 @@ skh_status skh_buffer_free(skh_context* c, void* p)
 {
     if (!c)
         return SKH_INVALID_ARGUMENT;
-    (void)hipSetDevice(c->device);
+    (void)hipSetDevice(c->dev.device);
     if (p)
         SKH_TRY(c, hipFree(p));
     return SKH_OK;
@@ -2324,26 +2316,26 @@ skh_status skh_buffer_download(skh_context* c, const void* d, void* host, size_t
 {
     if (!c || !d || !host)
         return SKH_INVALID_ARGUMENT;
-    (void)hipSetDevice(c->device);
+    (void)hipSetDevice(c->dev.device);
     if (c->spec.nextInFlight)
     {
-        // (the image was written by an accumulation step on stream3, which has completed; c->stream is busy with the pass traced
+        // (the image was written by an accumulation step on stream3, which has completed; c->dev.stream is busy with the pass traced
         // ahead and a null-stream copy would wait for it)
-        SKH_TRY(c, hipMemcpyAsync(host, d, bytes, hipMemcpyDeviceToHost, c->stream3));
-        SKH_TRY(c, hipStreamSynchronize(c->stream3));
+        SKH_TRY(c, hipMemcpyAsync(host, d, bytes, hipMemcpyDeviceToHost, c->dev.stream3));
+        SKH_TRY(c, hipStreamSynchronize(c->dev.stream3));
         return SKH_OK;
     }
-    SKH_TRY(c, hipStreamSynchronize(c->stream));
+    SKH_TRY(c, hipStreamSynchronize(c->dev.stream));
     SKH_TRY(c, hipMemcpy(host, d, bytes, hipMemcpyDeviceToHost));
     return SKH_OK;
 }
-// (the same choice of stream: beside a pass traced ahead, else behind whatever c->stream still does with the buffer)
+// (the same choice of stream: beside a pass traced ahead, else behind whatever c->dev.stream still does with the buffer)
 skh_status skh_buffer_upload(skh_context* c, void* d, const void* host, size_t bytes)
 {
     if (!c || !d || !host)
         return SKH_INVALID_ARGUMENT;
-    (void)hipSetDevice(c->device);
-    hipStream_t st = c->spec.nextInFlight ? c->stream3 : c->stream;
+    (void)hipSetDevice(c->dev.device);
+    hipStream_t st = side_stream(c);
     SKH_TRY(c, hipMemcpyAsync(d, host, bytes, hipMemcpyHostToDevice, st));
     SKH_TRY(c, hipStreamSynchronize(st));
     return SKH_OK;
@@ -2353,7 +2345,7 @@ skh_status skh_host_register(skh_context* c, void* host, size_t bytes)
 {
     if (!c || !host || !bytes)
         return SKH_INVALID_ARGUMENT;
-    (void)hipSetDevice(c->device);
+    (void)hipSetDevice(c->dev.device);
     SKH_TRY(c, hipHostRegister(host, bytes, hipHostRegisterDefault));
     return SKH_OK;
 }
@@ -2361,61 +2353,61 @@ skh_status skh_host_unregister(skh_context* c, void* host)
 {
     if (!c || !host)
         return SKH_INVALID_ARGUMENT;
-    (void)hipSetDevice(c->device);
+    (void)hipSetDevice(c->dev.device);
     SKH_TRY(c, hipHostUnregister(host));
     return SKH_OK;
 }
 
 static skh_status detile_to(skh_context* c, const DevBuf& src, void* d_dst)
 {
-    k_detile<<<(c->numSlots + 255) / 256, 256, 0, c->stream>>>(src.as<float4>(), c->dTileXY.as<uint32_t>(), c->numSlots, c->tileShift,
-                                                              c->width, c->height, reinterpret_cast<float4*>(d_dst));
+    k_detile<<<(c->frame.numSlots + 255) / 256, 256, 0, c->dev.stream>>>(src.as<float4>(), c->frame.dTileXY.as<uint32_t>(), c->frame.numSlots, c->frame.tileShift,
+                                                              c->frame.width, c->frame.height, reinterpret_cast<float4*>(d_dst));
     return SKH_OK;
 }
 
 static skh_status read_slots(skh_context* c, const DevBuf& src, float* host)
 {
-    if (!c || !host || !c->width)
+    if (!c || !host || !c->frame.width)
         return SKH_INVALID_ARGUMENT;
-    (void)hipSetDevice(c->device);
-    const size_t bytes = sizeof(float4) * (size_t)c->width * c->height;
-    skh_status s = dev_alloc(c, c->dScratchImage, bytes);
+    (void)hipSetDevice(c->dev.device);
+    const size_t bytes = sizeof(float4) * (size_t)c->frame.width * c->frame.height;
+    skh_status s = dev_alloc(c, c->frame.dScratchImage, bytes);
     if (s != SKH_OK)
         return s;
-    SKH_TRY(c, hipMemsetAsync(c->dScratchImage.p, 0, bytes, c->stream));
-    detile_to(c, src, c->dScratchImage.p);
-    SKH_TRY(c, hipMemcpyAsync(host, c->dScratchImage.p, bytes, hipMemcpyDeviceToHost, c->stream));
-    SKH_TRY(c, hipStreamSynchronize(c->stream));
+    SKH_TRY(c, hipMemsetAsync(c->frame.dScratchImage.p, 0, bytes, c->dev.stream));
+    detile_to(c, src, c->frame.dScratchImage.p);
+    SKH_TRY(c, hipMemcpyAsync(host, c->frame.dScratchImage.p, bytes, hipMemcpyDeviceToHost, c->dev.stream));
+    SKH_TRY(c, hipStreamSynchronize(c->dev.stream));
     return SKH_OK;
 }
 skh_status skh_read_accum(skh_context* c, float* host_rgba)
 {
-    return read_slots(c, c->dAccum, host_rgba);
+    return read_slots(c, c->frame.dAccum, host_rgba);
 }
 skh_status skh_read_adaptive(skh_context* c, float* host_rgba)
 {
-    if (!c || !host_rgba || !c->width)
+    if (!c || !host_rgba || !c->frame.width)
         return SKH_INVALID_ARGUMENT;
     if (!c->adapt.on || !c->adapt.ready)
     {
-        memset(host_rgba, 0, sizeof(float) * 4 * (size_t)c->width * c->height); // (no frame has begun: nothing observed)
+        memset(host_rgba, 0, sizeof(float) * 4 * (size_t)c->frame.width * c->frame.height); // (no frame has begun: nothing observed)
         return SKH_OK;
     }
-    return read_slots(c, c->dAdaptState, host_rgba);
+    return read_slots(c, c->adapt.dState, host_rgba);
 }
 skh_status skh_read_aov(skh_context* c, uint32_t which, float* host_rgba)
 {
     if (!c)
         return SKH_INVALID_ARGUMENT;
-    return read_slots(c, which == 0 ? c->dDiffuse : c->dSpecular, host_rgba);
+    return read_slots(c, which == 0 ? c->frame.dDiffuse : c->frame.dSpecular, host_rgba);
 }
 skh_status skh_copy_accum(skh_context* c, void* d_dst)
 {
     if (!c || !d_dst)
         return SKH_INVALID_ARGUMENT;
-    (void)hipSetDevice(c->device);
-    detile_to(c, c->dAccum, d_dst);
-    SKH_TRY(c, hipStreamSynchronize(c->stream));
+    (void)hipSetDevice(c->dev.device);
+    detile_to(c, c->frame.dAccum, d_dst);
+    SKH_TRY(c, hipStreamSynchronize(c->dev.stream));
     return SKH_OK;
 }
 // the diffuse / specular AOV accumulators to a device image: what render() hands back once all samples are done and the debug view
@@ -2424,23 +2416,23 @@ skh_status skh_copy_aov(skh_context* c, uint32_t which, void* d_dst)
 {
     if (!c || !d_dst || which > 1u)
         return SKH_INVALID_ARGUMENT;
-    (void)hipSetDevice(c->device);
-    if (c->width == 0)
+    (void)hipSetDevice(c->dev.device);
+    if (c->frame.width == 0)
     {
-        c->err = "skh_copy_aov: call skh_resize first";
+        c->dev.err = "skh_copy_aov: call skh_resize first";
         return SKH_INVALID_ARGUMENT;
     }
-    detile_to(c, which == 0 ? c->dDiffuse : c->dSpecular, d_dst);
-    SKH_TRY(c, hipStreamSynchronize(c->stream));
+    detile_to(c, which == 0 ? c->frame.dDiffuse : c->frame.dSpecular, d_dst);
+    SKH_TRY(c, hipStreamSynchronize(c->dev.stream));
     return SKH_OK;
 }
 skh_status skh_copy_accum_tiles(skh_context* c, void* d_dst)
 {
     if (!c || !d_dst)
         return SKH_INVALID_ARGUMENT;
-    (void)hipSetDevice(c->device);
-    SKH_TRY(c, hipMemcpyAsync(d_dst, c->dAccum.p, sizeof(float4) * (size_t)c->numSlots, hipMemcpyDeviceToDevice, c->stream));
-    SKH_TRY(c, hipStreamSynchronize(c->stream));
+    (void)hipSetDevice(c->dev.device);
+    SKH_TRY(c, hipMemcpyAsync(d_dst, c->frame.dAccum.p, sizeof(float4) * (size_t)c->frame.numSlots, hipMemcpyDeviceToDevice, c->dev.stream));
+    SKH_TRY(c, hipStreamSynchronize(c->dev.stream));
     return SKH_OK;
 }
 skh_status skh_scatter_tiles(skh_context* c, const void* d_src_tiles, const uint32_t* tile_xy, uint32_t n_tiles, uint32_t tile_size,
@@ -2448,22 +2440,22 @@ skh_status skh_scatter_tiles(skh_context* c, const void* d_src_tiles, const uint
 {
     if (!c || !d_src_tiles || !tile_xy || !d_dst || (tile_size & (tile_size - 1)))
         return SKH_INVALID_ARGUMENT;
-    (void)hipSetDevice(c->device);
+    (void)hipSetDevice(c->dev.device);
     // (tile list kept in a context buffer: no allocation per call; tiles whose origin lies outside the image -- the padding
     // of a gathered multi-rank tile set -- write nothing)
-    skh_status s = dev_upload(c, c->dScatterXY, tile_xy, sizeof(uint32_t) * 2 * (size_t)n_tiles);
+    skh_status s = dev_upload(c, c->multi.dScatterXY, tile_xy, sizeof(uint32_t) * 2 * (size_t)n_tiles);
     if (s != SKH_OK)
         return s;
     uint32_t shift = 0;
     while ((1u << shift) < tile_size)
         ++shift;
     const uint32_t slots = n_tiles * tile_size * tile_size;
-    k_detile<<<(slots + 255) / 256, 256, 0, c->stream>>>(reinterpret_cast<const float4*>(d_src_tiles), c->dScatterXY.as<uint32_t>(), slots, shift,
+    k_detile<<<(slots + 255) / 256, 256, 0, c->dev.stream>>>(reinterpret_cast<const float4*>(d_src_tiles), c->multi.dScatterXY.as<uint32_t>(), slots, shift,
                                                         width, height, reinterpret_cast<float4*>(d_dst));
-    hipError_t e = hipStreamSynchronize(c->stream);
+    hipError_t e = hipStreamSynchronize(c->dev.stream);
     if (e != hipSuccess)
     {
-        c->err = std::string("skh_scatter_tiles: ") + hipGetErrorString(e);
+        c->dev.err = std::string("skh_scatter_tiles: ") + hipGetErrorString(e);
         return SKH_FAIL;
     }
     return SKH_OK;
@@ -2559,26 +2551,26 @@ skh_status skh_comm_init(skh_context* c, const void* id, int world_size, int ran
 {
     if (!c || !id || world_size < 1 || rank < 0 || rank >= world_size)
         return SKH_INVALID_ARGUMENT;
-    (void)hipSetDevice(c->device);
+    (void)hipSetDevice(c->dev.device);
     RcclApi* r = rccl();
     if (!r)
     {
-        c->err = "skh_comm_init: RCCL is not available (librccl.so.1)";
+        c->dev.err = "skh_comm_init: RCCL is not available (librccl.so.1)";
         return SKH_FAIL;
     }
-    if (c->comm)
+    if (c->multi.comm)
         (void)skh_comm_destroy(c);
     ncclUniqueId uid;
     memcpy(&uid, id, sizeof(uid));
-    const ncclResult_t e = r->CommInitRank(&c->comm, world_size, uid, rank);
+    const ncclResult_t e = r->CommInitRank(&c->multi.comm, world_size, uid, rank);
     if (e != ncclSuccess)
     {
-        c->comm = nullptr;
-        c->err = std::string("skh_comm_init: ncclCommInitRank: ") + (r->GetErrorString ? r->GetErrorString(e) : "error");
+        c->multi.comm = nullptr;
+        c->dev.err = std::string("skh_comm_init: ncclCommInitRank: ") + (r->GetErrorString ? r->GetErrorString(e) : "error");
         return SKH_FAIL;
     }
-    c->commWorld = world_size;
-    c->commRank = rank;
+    c->multi.world = world_size;
+    c->multi.rank = rank;
     return SKH_OK;
 }
 
@@ -2587,15 +2579,15 @@ skh_status skh_comm_info(skh_context* c, int* out_world, int* out_rank, int* out
     if (!c)
         return SKH_INVALID_ARGUMENT;
     if (out_world)
-        *out_world = c->commWorld;
+        *out_world = c->multi.world;
     if (out_rank)
-        *out_rank = c->commRank;
+        *out_rank = c->multi.rank;
     if (out_rccl_ranks)
     {
         // what RCCL itself says about the communicator (ncclCommCount): 0 = no communicator (world size 1, or the caller gathers another way)
         int n = 0;
-        RcclApi* r = c->comm ? rccl() : nullptr;
-        if (r && r->CommCount && r->CommCount(c->comm, &n) != ncclSuccess)
+        RcclApi* r = c->multi.comm ? rccl() : nullptr;
+        if (r && r->CommCount && r->CommCount(c->multi.comm, &n) != ncclSuccess)
             n = -1;
         *out_rccl_ranks = n;
     }
@@ -2606,66 +2598,66 @@ skh_status skh_comm_destroy(skh_context* c)
 {
     if (!c)
         return SKH_INVALID_ARGUMENT;
-    (void)hipSetDevice(c->device);
-    if (c->comm)
+    (void)hipSetDevice(c->dev.device);
+    if (c->multi.comm)
     {
-        (void)hipStreamSynchronize(c->stream);
+        (void)hipStreamSynchronize(c->dev.stream);
         RcclApi* r = rccl();
         if (r)
-            (void)r->CommDestroy(c->comm);
-        c->comm = nullptr;
+            (void)r->CommDestroy(c->multi.comm);
+        c->multi.comm = nullptr;
     }
-    c->commWorld = 1;
-    c->commRank = 0;
+    c->multi.world = 1;
+    c->multi.rank = 0;
     return SKH_OK;
 }
 
 skh_status skh_gather_tiles(skh_context* c, uint32_t max_tiles, void* d_recv, int root)
 {
-    if (!c || root < 0 || root >= c->commWorld || max_tiles < c->numTiles || (c->commRank == root && !d_recv))
+    if (!c || root < 0 || root >= c->multi.world || max_tiles < c->frame.numTiles || (c->multi.rank == root && !d_recv))
         return SKH_INVALID_ARGUMENT;
-    (void)hipSetDevice(c->device);
-    if (c->commWorld > 1 && !c->comm)
+    (void)hipSetDevice(c->dev.device);
+    if (c->multi.world > 1 && !c->multi.comm)
     {
-        c->err = "skh_gather_tiles: call skh_comm_init first";
+        c->dev.err = "skh_gather_tiles: call skh_comm_init first";
         return SKH_INVALID_ARGUMENT;
     }
-    const size_t tilePixels = (size_t)c->tileSize * c->tileSize;
+    const size_t tilePixels = (size_t)c->frame.tileSize * c->frame.tileSize;
     const size_t chunk = (size_t)max_tiles * tilePixels; // float4 per rank
-    const size_t mine = (size_t)c->numTiles * tilePixels;
-    const bool isRoot = c->commRank == root;
+    const size_t mine = (size_t)c->frame.numTiles * tilePixels;
+    const bool isRoot = c->multi.rank == root;
     // the root's own share goes straight into its slot of the receive buffer; a sender stages its tiles (zero-padded) once
     float4* dst = isRoot ? reinterpret_cast<float4*>(d_recv) + (size_t)root * chunk : nullptr;
     if (!isRoot)
     {
-        skh_status s = dev_alloc(c, c->dTileSend, sizeof(float4) * chunk);
+        skh_status s = dev_alloc(c, c->multi.dTileSend, sizeof(float4) * chunk);
         if (s != SKH_OK)
             return s;
-        dst = c->dTileSend.as<float4>();
+        dst = c->multi.dTileSend.as<float4>();
     }
-    SKH_TRY(c, hipMemcpyAsync(dst, c->dAccum.p, sizeof(float4) * mine, hipMemcpyDeviceToDevice, c->stream));
+    SKH_TRY(c, hipMemcpyAsync(dst, c->frame.dAccum.p, sizeof(float4) * mine, hipMemcpyDeviceToDevice, c->dev.stream));
     if (chunk > mine)
-        SKH_TRY(c, hipMemsetAsync(dst + mine, 0, sizeof(float4) * (chunk - mine), c->stream));
-    if (c->commWorld > 1)
+        SKH_TRY(c, hipMemsetAsync(dst + mine, 0, sizeof(float4) * (chunk - mine), c->dev.stream));
+    if (c->multi.world > 1)
     {
         RcclApi* r = rccl();
         ncclResult_t e = r->GroupStart();
         if (isRoot)
         {
-            for (int k = 0; k < c->commWorld && e == ncclSuccess; ++k)
+            for (int k = 0; k < c->multi.world && e == ncclSuccess; ++k)
                 if (k != root)
-                    e = r->Recv(reinterpret_cast<float4*>(d_recv) + (size_t)k * chunk, chunk * 4, ncclFloat, k, c->comm, c->stream);
+                    e = r->Recv(reinterpret_cast<float4*>(d_recv) + (size_t)k * chunk, chunk * 4, ncclFloat, k, c->multi.comm, c->dev.stream);
         }
         else if (e == ncclSuccess)
-            e = r->Send(dst, chunk * 4, ncclFloat, root, c->comm, c->stream);
+            e = r->Send(dst, chunk * 4, ncclFloat, root, c->multi.comm, c->dev.stream);
         const ncclResult_t e2 = r->GroupEnd();
         if (e != ncclSuccess || e2 != ncclSuccess)
         {
-            c->err = std::string("skh_gather_tiles: ") + (r->GetErrorString ? r->GetErrorString(e != ncclSuccess ? e : e2) : "RCCL error");
+            c->dev.err = std::string("skh_gather_tiles: ") + (r->GetErrorString ? r->GetErrorString(e != ncclSuccess ? e : e2) : "RCCL error");
             return SKH_FAIL;
         }
     }
-    SKH_TRY(c, hipStreamSynchronize(c->stream));
+    SKH_TRY(c, hipStreamSynchronize(c->dev.stream));
     return SKH_OK;
 }
 
@@ -2722,7 +2714,7 @@ static skh_status trace_device_as(skh_context* c, const void* d_rays, uint32_t n
 {
     if (!c || (n_rays && (!d_rays || !d_hits)) || mode > 1)
         return SKH_INVALID_ARGUMENT;
-    (void)hipSetDevice(c->device);
+    (void)hipSetDevice(c->dev.device);
     skh_status s = ensure_ready(c);
     if (s != SKH_OK || n_rays == 0)
         return s;
@@ -2736,7 +2728,7 @@ static skh_status trace_device_as(skh_context* c, const void* d_rays, uint32_t n
     SKH_CHECK(dev_alloc(c, h, sizeof(float) * 8 * NQ));
     // a cutout in use (skh_set_material_cutouts): the continuation rounds run on the internal records, before k_hits_soa_to_aos; their words lie behind the fetch cursors
     const bool cutOn = cut_stage_on(c);
-    const size_t cutWordCount = cutOn ? (size_t)c->cutoutRounds * SKH_CUT_WORDS : 0u;
+    const size_t cutWordCount = cutOn ? (size_t)c->opt.cutoutRounds * SKH_CUT_WORDS : 0u;
     DevBuf cq0, cq1, h2, h0;
     SKH_CHECK(dev_alloc(c, cnt, sizeof(uint32_t) * (SKH_SHARDS * SKH_COUNT_STRIDE + 8 * SKH_FETCH_STRIDE + cutWordCount)));
     if (cutOn)
@@ -2747,9 +2739,9 @@ static skh_status trace_device_as(skh_context* c, const void* d_rays, uint32_t n
         if (mode == SKH_TRACE_SHADOW)
             SKH_CHECK(dev_alloc(c, h0, sizeof(float) * 8 * NQ));
     }
-    if (!c->traceBlocks)
-        c->traceBlocks = (uint32_t)c->numCUs * c->wavesPerCU;
-    SKH_CHECK(dev_alloc(c, c->dOvf, sizeof(int) * (size_t)(SKH_STACK_OVF + SKH_TAIL_EXTRA) * (uint32_t)c->numCUs * std::max(std::max(c->wavesPerCU, c->wavesPerCUWorld), std::max(c->wavesPerCUShadow, c->wavesPerCUShadowWorld)) * SKH_TRACE_BLOCK));
+    if (!c->frame.traceBlocks)
+        c->frame.traceBlocks = (uint32_t)c->dev.numCUs * c->opt.wavesPerCU;
+    SKH_CHECK(dev_alloc(c, c->frame.dOvf, sizeof(int) * (size_t)(SKH_STACK_OVF + SKH_TAIL_EXTRA) * (uint32_t)c->dev.numCUs * std::max(std::max(c->opt.wavesPerCU, c->opt.wavesPerCUWorld), std::max(c->opt.wavesPerCUShadow, c->opt.wavesPerCUShadowWorld)) * SKH_TRACE_BLOCK));
     RayQ rq{ q.as<float>(), (uint32_t)NQ, per };
     HitQ hq{ h.as<float>(), (uint32_t)NQ };
     PathS ps{ nullptr, 0 };
@@ -2758,30 +2750,30 @@ static skh_status trace_device_as(skh_context* c, const void* d_rays, uint32_t n
     uint32_t hcount[SKH_SHARDS * SKH_COUNT_STRIDE] = { 0 };
     for (uint32_t g = 0; g < SKH_SHARDS; ++g)
         hcount[g * SKH_COUNT_STRIDE] = std::min(per, n_rays - std::min(n_rays, g * per));
-    SKH_TRY(c, hipMemcpyAsync(dcount, hcount, sizeof(hcount), hipMemcpyHostToDevice, c->stream));
-    SKH_TRY(c, hipStreamSynchronize(c->stream)); // (hcount lives on this stack frame)
+    SKH_TRY(c, hipMemcpyAsync(dcount, hcount, sizeof(hcount), hipMemcpyHostToDevice, c->dev.stream));
+    SKH_TRY(c, hipStreamSynchronize(c->dev.stream)); // (hcount lives on this stack frame)
     const DevScene sc = make_dev_scene(c);
-    k_rays_aos_to_soa<<<(n_rays + 255) / 256, 256, 0, c->stream>>>(reinterpret_cast<const skh_ray*>(d_rays), n_rays, per, rq);
+    k_rays_aos_to_soa<<<(n_rays + 255) / 256, 256, 0, c->dev.stream>>>(reinterpret_cast<const skh_ray*>(d_rays), n_rays, per, rq);
     for (uint32_t r = 0; r < std::max(1u, repeat); ++r)
     {
-        (void)hipMemsetAsync(dfetch, 0, sizeof(uint32_t) * (8 * SKH_FETCH_STRIDE + cutWordCount), c->stream);
+        (void)hipMemsetAsync(dfetch, 0, sizeof(uint32_t) * (8 * SKH_FETCH_STRIDE + cutWordCount), c->dev.stream);
         SpanGuard g(c, cls);
         const bool shadow = mode == SKH_TRACE_SHADOW;
-        const TraceLaunch t{ rq, dcount, dfetch, hq, ps, nullptr, c->stream, shadow, 0u, false };
+        const TraceLaunch t{ rq, dcount, dfetch, hq, ps, nullptr, c->dev.stream, shadow, 0u, false };
         // (a cutout in use) no sample: a blend hit counts iff a > 0; a shadow query's result is one float per ray
         CutRounds cr{ { RayQ{ cq0.as<float>(), (uint32_t)NQ, per }, RayQ{ cq1.as<float>(), (uint32_t)NQ, per } }, HitQ{ h0.as<float>(), (uint32_t)NQ }, HitQ{ h2.as<float>(), (uint32_t)NQ },
                       shadow ? hq.base : nullptr, dfetch + 8 * SKH_FETCH_STRIDE, n_rays, make_blend(c) };
         cr.bl.raw = 1u;
         trace_step(c, sc, t, shadow, cutOn ? &cr : nullptr);
     }
-    k_hits_soa_to_aos<<<(n_rays + 255) / 256, 256, 0, c->stream>>>(hq, n_rays, per, per, mode, reinterpret_cast<skh_hit*>(d_hits), c->dShadeInst.as<skh_instance>());
-    hipError_t e = hipStreamSynchronize(c->stream);
+    k_hits_soa_to_aos<<<(n_rays + 255) / 256, 256, 0, c->dev.stream>>>(hq, n_rays, per, per, mode, reinterpret_cast<skh_hit*>(d_hits), c->accel.dShadeInst.as<skh_instance>());
+    hipError_t e = hipStreamSynchronize(c->dev.stream);
     if (e != hipSuccess || (e = hipGetLastError()) != hipSuccess)
     {
-        c->err = std::string("skh_trace: ") + hipGetErrorString(e);
+        c->dev.err = std::string("skh_trace: ") + hipGetErrorString(e);
         return SKH_FAIL;
     }
-    if (c->timing)
+    if (c->opt.timing)
         harvest_spans(c);
     return check_stack_overflow(c, "skh_trace");
 }
@@ -2795,7 +2787,7 @@ skh_status skh_trace(skh_context* c, const skh_ray* rays, uint32_t n_rays, uint3
 {
     if (!c || (n_rays && (!rays || !hits)))
         return SKH_INVALID_ARGUMENT;
-    (void)hipSetDevice(c->device);
+    (void)hipSetDevice(c->dev.device);
     if (n_rays == 0)
         return SKH_OK;
     DevBuf dr, dh;
@@ -2807,7 +2799,7 @@ skh_status skh_trace(skh_context* c, const skh_ray* rays, uint32_t n_rays, uint3
         hipError_t e = hipMemcpy(hits, dh.p, sizeof(skh_hit) * (size_t)n_rays, hipMemcpyDeviceToHost);
         if (e != hipSuccess)
         {
-            c->err = std::string("skh_trace readback: ") + hipGetErrorString(e);
+            c->dev.err = std::string("skh_trace readback: ") + hipGetErrorString(e);
             s = SKH_FAIL;
         }
     }
@@ -2849,7 +2841,7 @@ skh_status skh_render_aovs(skh_context* c, const skh_aov_params* p, uint32_t pla
 {
     if (!c)
         return SKH_INVALID_ARGUMENT;
-    const char* why = aov_refusal(p, c->width, c->height);
+    const char* why = aov_refusal(p, c->frame.width, c->frame.height);
     if (!why && (planes == 0u || (planes >> SKH_AOV_COUNT) != 0u))
         why = "no plane asked for, or a bit at or above SKH_AOV_COUNT";
     if (!why && !d_planes)
@@ -2859,10 +2851,10 @@ skh_status skh_render_aovs(skh_context* c, const skh_aov_params* p, uint32_t pla
             why = "a plane asked for without a buffer";
     if (why)
     {
-        c->err = std::string("skh_render_aovs: ") + why;
+        c->dev.err = std::string("skh_render_aovs: ") + why;
         return SKH_INVALID_ARGUMENT;
     }
-    (void)hipSetDevice(c->device);
+    (void)hipSetDevice(c->dev.device);
     const auto t0 = std::chrono::steady_clock::now();
     SKH_CHECK(ensure_ready(c)); // (the scene record below is the built one's)
     AovP ap;
@@ -2870,12 +2862,12 @@ skh_status skh_render_aovs(skh_context* c, const skh_aov_params* p, uint32_t pla
     memcpy(ap.clipToView, p->clip_to_view, sizeof(ap.clipToView));
     memcpy(ap.worldToClip, p->world_to_clip, sizeof(ap.worldToClip));
     const bool whole = p->width == 0u && p->height == 0u;
-    ap.imageW = c->width, ap.imageH = c->height;
-    ap.x0 = p->x0, ap.y0 = p->y0, ap.width = whole ? c->width : p->width;
-    const uint32_t regionH = whole ? c->height : p->height;
+    ap.imageW = c->frame.width, ap.imageH = c->frame.height;
+    ap.x0 = p->x0, ap.y0 = p->y0, ap.width = whole ? c->frame.width : p->width;
+    const uint32_t regionH = whole ? c->frame.height : p->height;
     ap.sampleIndex = p->sample_index, ap.sppTotal = p->spp_total, ap.tmin = p->tmin;
     const uint64_t total = (uint64_t)ap.width * regionH;
-    const uint32_t band = (uint32_t)std::min<uint64_t>(total, c->aovBand);
+    const uint32_t band = (uint32_t)std::min<uint64_t>(total, c->opt.aovBand);
     DevBuf rays, hits; // (of one band; gone when the call returns)
     SKH_CHECK(dev_alloc(c, rays, sizeof(skh_ray) * (size_t)band));
     SKH_CHECK(dev_alloc(c, hits, sizeof(skh_hit) * (size_t)band));
@@ -2885,7 +2877,7 @@ skh_status skh_render_aovs(skh_context* c, const skh_aov_params* p, uint32_t pla
         ap.first = (uint32_t)first, ap.count = (uint32_t)std::min<uint64_t>(band, total - first);
         {
             SpanGuard g(c, KC_AOV);
-            k_aov_raygen<<<(ap.count + 255) / 256, 256, 0, c->stream>>>(ap, rays.as<float4>());
+            k_aov_raygen<<<(ap.count + 255) / 256, 256, 0, c->dev.stream>>>(ap, rays.as<float4>());
         }
         SKH_CHECK(trace_device_as(c, rays.p, ap.count, SKH_TRACE_CLOSEST, hits.p, 1, KC_AOV));
         AovPlanes out;
@@ -2893,17 +2885,17 @@ skh_status skh_render_aovs(skh_context* c, const skh_aov_params* p, uint32_t pla
             out.p[k] = ((planes >> k) & 1u) ? reinterpret_cast<uint4*>(d_planes[k]) + first : nullptr;
         {
             SpanGuard g(c, KC_AOV);
-            k_aov_resolve<<<(ap.count + 255) / 256, 256, 0, c->stream>>>(make_dev_scene(c), mtexp, ap, planes, rays.as<float4>(), hits.as<skh_hit>(), out);
+            k_aov_resolve<<<(ap.count + 255) / 256, 256, 0, c->dev.stream>>>(make_dev_scene(c), mtexp, ap, planes, rays.as<float4>(), hits.as<skh_hit>(), out);
         }
         SKH_TRY(c, hipGetLastError());
-        SKH_TRY(c, hipStreamSynchronize(c->stream)); // (the band's buffers are reused)
+        SKH_TRY(c, hipStreamSynchronize(c->dev.stream)); // (the band's buffers are reused)
     }
-    if (c->timing)
+    if (c->opt.timing)
         harvest_spans(c);
-    c->aovInfo.calls++;
-    c->aovInfo.rays += total;
-    c->aovInfo.ms_last = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
-    c->aovInfo.bytes_last = 16ull * total * (uint64_t)__builtin_popcount(planes);
+    c->aov.info.calls++;
+    c->aov.info.rays += total;
+    c->aov.info.ms_last = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    c->aov.info.bytes_last = 16ull * total * (uint64_t)__builtin_popcount(planes);
     return SKH_OK;
 }
 
@@ -2911,7 +2903,7 @@ skh_status skh_get_aov_info(skh_context* c, skh_aov_info* out)
 {
     if (!c || !out)
         return SKH_INVALID_ARGUMENT;
-    *out = c->aovInfo;
+    *out = c->aov.info;
     return SKH_OK;
 }
 
@@ -2947,7 +2939,7 @@ skh_status skh_denoise_check(const skh_denoise_params* p)
 
 static uint64_t denoise_scratch_bytes(const skh_context* c)
 {
-    return (uint64_t)c->dDnColor[0].bytes + c->dDnColor[1].bytes + c->dDnG0.bytes + c->dDnG1.bytes;
+    return (uint64_t)c->dn.dColor[0].bytes + c->dn.dColor[1].bytes + c->dn.dG0.bytes + c->dn.dG1.bytes;
 }
 
 skh_status skh_denoise(skh_context* c, const skh_denoise_params* p, const void* d_color, const void* d_ids, const void* d_normal, const void* d_position,
@@ -2955,10 +2947,10 @@ skh_status skh_denoise(skh_context* c, const skh_denoise_params* p, const void* 
 {
     if (!c)
         return SKH_INVALID_ARGUMENT;
-    (void)hipSetDevice(c->device);
+    (void)hipSetDevice(c->dev.device);
     if (!p) // free the scratch
     {
-        dev_free(c->dDnColor[0]), dev_free(c->dDnColor[1]), dev_free(c->dDnG0), dev_free(c->dDnG1);
+        dev_free(c->dn.dColor[0]), dev_free(c->dn.dColor[1]), dev_free(c->dn.dG0), dev_free(c->dn.dG1);
         return SKH_OK;
     }
     const char* why = denoise_refusal(p);
@@ -2968,43 +2960,43 @@ skh_status skh_denoise(skh_context* c, const skh_denoise_params* p, const void* 
         why = "a flag that needs the albedo plane, and no albedo plane";
     if (why)
     {
-        c->err = std::string("skh_denoise: ") + why;
+        c->dev.err = std::string("skh_denoise: ") + why;
         return SKH_INVALID_ARGUMENT;
     }
     const auto t0 = std::chrono::steady_clock::now();
     const size_t n = (size_t)p->width * p->height;
-    SKH_CHECK(dev_alloc(c, c->dDnColor[0], 16 * n));
+    SKH_CHECK(dev_alloc(c, c->dn.dColor[0], 16 * n));
     if (p->levels > 1u)
-        SKH_CHECK(dev_alloc(c, c->dDnColor[1], 16 * n));
-    SKH_CHECK(dev_alloc(c, c->dDnG0, 16 * n));
-    SKH_CHECK(dev_alloc(c, c->dDnG1, 8 * n));
-    hipStream_t st = c->spec.nextInFlight ? c->stream3 : c->stream; // (beside a pass traced ahead, not behind it: skh_tonemap's choice)
+        SKH_CHECK(dev_alloc(c, c->dn.dColor[1], 16 * n));
+    SKH_CHECK(dev_alloc(c, c->dn.dG0, 16 * n));
+    SKH_CHECK(dev_alloc(c, c->dn.dG1, 8 * n));
+    hipStream_t st = side_stream(c); // (beside a pass traced ahead, not behind it: skh_tonemap's choice)
     DnP dp;
     dp.width = p->width, dp.height = p->height, dp.step = 1u, dp.kc = 0.0f;
     dp.kn = 1.0f / (p->sigma_normal * p->sigma_normal), dp.kp = 1.0f / (p->sigma_plane * p->sigma_plane);
     dp.albedoFloor = p->albedo_floor, dp.flags = p->flags;
     k_dn_pack<<<(uint32_t)((n + 255) / 256), 256, 0, st>>>(dp, reinterpret_cast<const float4*>(d_color), reinterpret_cast<const uint4*>(d_ids),
                                                           reinterpret_cast<const float4*>(d_normal), reinterpret_cast<const float4*>(d_position),
-                                                          reinterpret_cast<const float4*>(d_albedo), c->dDnColor[0].as<float4>(), c->dDnG0.as<float4>(),
-                                                          c->dDnG1.as<float2>());
+                                                          reinterpret_cast<const float4*>(d_albedo), c->dn.dColor[0].as<float4>(), c->dn.dG0.as<float4>(),
+                                                          c->dn.dG1.as<float2>());
     const dim3 grid(((p->width + 63u) / 64u) * ((p->height + 3u) / 4u)), block(64, 4); // (<= 2^24 + 2^20 tiles of 64 x 4 pixels, row-major)
     for (uint32_t k = 0; k < p->levels; ++k)
     {
         const uint32_t level = p->first_level + k;
         const float sc = p->sigma_color * (1.0f / (float)(1u << level)); // (exact: a power of two)
         dp.step = 1u << level, dp.kc = 1.0f / (sc * sc);
-        const float4* cin = c->dDnColor[k & 1u].as<float4>();
+        const float4* cin = c->dn.dColor[k & 1u].as<float4>();
         if (k + 1u < p->levels)
-            k_dn_level<false><<<grid, block, 0, st>>>(dp, cin, c->dDnG0.as<float4>(), c->dDnG1.as<float2>(), c->dDnColor[(k + 1u) & 1u].as<float4>(), nullptr, nullptr, nullptr);
+            k_dn_level<false><<<grid, block, 0, st>>>(dp, cin, c->dn.dG0.as<float4>(), c->dn.dG1.as<float2>(), c->dn.dColor[(k + 1u) & 1u].as<float4>(), nullptr, nullptr, nullptr);
         else
-            k_dn_level<true><<<grid, block, 0, st>>>(dp, cin, c->dDnG0.as<float4>(), c->dDnG1.as<float2>(), nullptr, reinterpret_cast<const uint4*>(d_color),
+            k_dn_level<true><<<grid, block, 0, st>>>(dp, cin, c->dn.dG0.as<float4>(), c->dn.dG1.as<float2>(), nullptr, reinterpret_cast<const uint4*>(d_color),
                                                     reinterpret_cast<const float4*>(d_albedo), reinterpret_cast<uint4*>(d_out));
     }
     SKH_TRY(c, hipGetLastError());
     SKH_TRY(c, hipStreamSynchronize(st));
-    c->dnInfo.calls++;
-    c->dnInfo.pixels += n;
-    c->dnInfo.ms_last = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    c->dn.info.calls++;
+    c->dn.info.pixels += n;
+    c->dn.info.ms_last = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
     return SKH_OK;
 }
 
@@ -3012,7 +3004,7 @@ skh_status skh_get_denoise_info(skh_context* c, skh_denoise_info* out)
 {
     if (!c || !out)
         return SKH_INVALID_ARGUMENT;
-    *out = c->dnInfo;
+    *out = c->dn.info;
     out->scratch_bytes = denoise_scratch_bytes(c);
     return SKH_OK;
 }
@@ -3033,23 +3025,23 @@ struct OptRow
     OptEffect effect;
     void (*store)(skh_context*, int64_t);
     bool needsSegNode = false;            // value 1 is refused by a library compiled without segment-node support (skh_kernels.h SKH_SEGNODE)
-    bool skh_context::*counters = nullptr; // timing / count_traversal: speculation is dropped only when the flag CHANGES (and the last parameters are kept)
+    bool skh_context::Options::*counters = nullptr; // timing / count_traversal: speculation is dropped only when the flag CHANGES (and the last parameters are kept)
 };
 static const int64_t kOptMin = INT64_MIN, kOptMax = INT64_MAX; // (kOptMin .. kOptMax: any value, read as value != 0)
-#define OPT_U32(field) [](skh_context* c, int64_t v) { c->field = (uint32_t)v; }
-#define OPT_I32(field) [](skh_context* c, int64_t v) { c->field = (int32_t)v; }
-#define OPT_FLAG(field) [](skh_context* c, int64_t v) { c->field = v != 0; }
+#define OPT_U32(field) [](skh_context* c, int64_t v) { c->opt.field = (uint32_t)v; }
+#define OPT_I32(field) [](skh_context* c, int64_t v) { c->opt.field = (int32_t)v; }
+#define OPT_FLAG(field) [](skh_context* c, int64_t v) { c->opt.field = v != 0; }
 static const OptRow kOptions[] = {
     // a pass traced ahead with the OTHER setting must not be delivered under this one: its traversal counters would be missing from the
     // per-ray figures while its rays count; the pass in flight is waited for and dropped too
-    { "count_traversal", kOptMin, kOptMax, OPT_NONE, OPT_FLAG(countTraversal), false, &skh_context::countTraversal },
-    { "timing", kOptMin, kOptMax, OPT_NONE, OPT_FLAG(timing), false, &skh_context::timing },
+    { "count_traversal", kOptMin, kOptMax, OPT_NONE, OPT_FLAG(countTraversal), false, &skh_context::Options::countTraversal },
+    { "timing", kOptMin, kOptMax, OPT_NONE, OPT_FLAG(timing), false, &skh_context::Options::timing },
     // (an explicitly set value applies to the curve build too: its own defaults hold until then)
-    { "fetch_min_closest", 1, 64, OPT_NONE, [](skh_context* c, int64_t v) { c->fetchMinClosestSet = true, c->fetchMinClosest = c->curveFetchMinClosest = (uint32_t)v; } },
-    { "fetch_min_shadow", 1, 64, OPT_NONE, [](skh_context* c, int64_t v) { c->fetchMinShadow = c->curveFetchMinShadow = (uint32_t)v; } },
-    { "node_break_closest", 0, 64, OPT_NONE, [](skh_context* c, int64_t v) { c->nodeBreakClosest = c->curveNodeBreakClosest = (uint32_t)v; } },
-    { "node_break_shadow", 0, 64, OPT_NONE, [](skh_context* c, int64_t v) { c->nodeBreakShadow = c->curveNodeBreakShadow = (uint32_t)v; } },
-    { "curve_min", 1, 64, OPT_NONE, [](skh_context* c, int64_t v) { c->curveMin = c->worldCurveMin = (uint32_t)v; } },
+    { "fetch_min_closest", 1, 64, OPT_NONE, [](skh_context* c, int64_t v) { c->opt.fetchMinClosestSet = true, c->opt.fetchMinClosest = c->opt.curveFetchMinClosest = (uint32_t)v; } },
+    { "fetch_min_shadow", 1, 64, OPT_NONE, [](skh_context* c, int64_t v) { c->opt.fetchMinShadow = c->opt.curveFetchMinShadow = (uint32_t)v; } },
+    { "node_break_closest", 0, 64, OPT_NONE, [](skh_context* c, int64_t v) { c->opt.nodeBreakClosest = c->opt.curveNodeBreakClosest = (uint32_t)v; } },
+    { "node_break_shadow", 0, 64, OPT_NONE, [](skh_context* c, int64_t v) { c->opt.nodeBreakShadow = c->opt.curveNodeBreakShadow = (uint32_t)v; } },
+    { "curve_min", 1, 64, OPT_NONE, [](skh_context* c, int64_t v) { c->opt.curveMin = c->opt.worldCurveMin = (uint32_t)v; } },
     { "fetch_min_closest_small", 1, 64, OPT_NONE, OPT_U32(fetchMinClosestSmall) },
     { "fetch_chunk", -1, 4096, OPT_NONE, OPT_I32(fetchChunk) },
     { "leaf_min", 0, 64, OPT_NONE, OPT_U32(leafMin) },
@@ -3065,7 +3057,7 @@ static const OptRow kOptions[] = {
     { "aov_band", 64, 1 << 26, OPT_NONE, OPT_U32(aovBand) },
     { "speculate", 0, 64, OPT_NONE, OPT_U32(speculateMax) },
     { "speculate_grow", 2, 64, OPT_NONE, OPT_U32(speculateGrow) },
-    { "speculate_async", 0, 1, OPT_NONE, [](skh_context* c, int64_t v) { spec_drop(c), c->speculateAsync = (uint32_t)v; } },
+    { "speculate_async", 0, 1, OPT_NONE, [](skh_context* c, int64_t v) { spec_drop(c), c->opt.speculateAsync = (uint32_t)v; } },
     { "world_kernel", kOptMin, kOptMax, OPT_NONE, OPT_FLAG(worldKernel) }, // (the build reads it -- worldCurveKernel -- and setting it has never invalidated the build)
     // the frame's buffers
     { "subframe_batch", 0, 64, OPT_FRAME, OPT_U32(subframeBatch) },
@@ -3075,7 +3067,7 @@ static const OptRow kOptions[] = {
     { "waves_per_cu_shadow_world", 1, 32, OPT_FRAME, OPT_U32(wavesPerCUShadowWorld) },
     // what skh_build_accel reads
     { "compact_hits", 0, 1, OPT_REBUILD, OPT_U32(compactHits) }, // (skh_build_accel decides with it which word a baked triangle's hit carries)
-    { "direct_records", -1, 1, OPT_REBUILD, OPT_I32(directRecordsOpt) },
+    { "direct_records", -1, 1, OPT_REBUILD, OPT_I32(directRecords) },
     { "merge_light_proxies", 0, 1, OPT_REBUILD, OPT_U32(mergeLightProxies) },
     { "tight_instance_boxes", kOptMin, kOptMax, OPT_REBUILD, OPT_FLAG(tightInstanceBoxes) },
     { "curve_leaf", 1, 4, OPT_REBUILD, OPT_U32(curveLeaf) },
@@ -3112,19 +3104,19 @@ skh_status skh_set_option(skh_context* c, const char* name, int64_t value)
             row = &r;
     if (!row || !row->counters)
         spec_drop(c);
-    else if (c->*(row->counters) != (value != 0))
+    else if (c->opt.*(row->counters) != (value != 0))
         spec_drop(c, true);
     if (!row)
     {
-        c->err = std::string("skh_set_option: unknown option ") + name;
+        c->dev.err = std::string("skh_set_option: unknown option ") + name;
         return SKH_INVALID_ARGUMENT;
     }
     if (value < row->lo || value > row->hi || (row->needsSegNode && value == 1 && !SKH_SEGNODE))
         return SKH_INVALID_ARGUMENT;
     row->store(c, value);
     if (row->effect == OPT_REBUILD)
-        c->accelBuilt = false, c->refitReady = false;
-    if (row->effect == OPT_FRAME && c->width)
+        touched(c, skh_stale::IN_REBUILD_OPTION);
+    if (row->effect == OPT_FRAME && c->frame.width)
         return alloc_frame(c);
     return SKH_OK;
 }
@@ -3134,7 +3126,7 @@ skh_status skh_get_device_info(skh_context* c, skh_device_info* out)
     if (!c || !out)
         return SKH_INVALID_ARGUMENT;
     hipDeviceProp_t prop;
-    SKH_TRY(c, hipGetDeviceProperties(&prop, c->device));
+    SKH_TRY(c, hipGetDeviceProperties(&prop, c->dev.device));
     memset(out, 0, sizeof(*out));
     out->compute_units = (uint32_t)prop.multiProcessorCount;
     out->simds_per_cu = 4;
@@ -3151,8 +3143,8 @@ skh_status skh_get_build_info(skh_context* c, skh_build_info* out)
 {
     if (!c || !out)
         return SKH_INVALID_ARGUMENT;
-    *out = c->buildInfo;
-    out->ms_build = c->msBuild;
+    *out = c->accel.buildInfo;
+    out->ms_build = c->accel.msBuild;
     return SKH_OK;
 }
 
@@ -3160,14 +3152,14 @@ skh_status skh_get_stats(skh_context* c, skh_stats* out)
 {
     if (!c || !out)
         return SKH_INVALID_ARGUMENT;
-    (void)hipSetDevice(c->device);
+    (void)hipSetDevice(c->dev.device);
     StatsDev sd;
-    SKH_TRY(c, hipStreamSynchronize(c->stream));
-    SKH_TRY(c, hipMemcpy(&sd, c->dStats.p, sizeof(sd), hipMemcpyDeviceToHost));
+    SKH_TRY(c, hipStreamSynchronize(c->dev.stream));
+    SKH_TRY(c, hipMemcpy(&sd, c->timing.dStats.p, sizeof(sd), hipMemcpyDeviceToHost));
     memset(out, 0, sizeof(*out));
     // rays count when their sub-frame is DELIVERED: what was traced ahead and thrown away (spec_drop) is out, and so is what is still
     // waiting to be collected -- the rest of the current pass and the whole pass in flight (complete after the synchronize above)
-    uint64_t outR = c->discardedRadiance, outS = c->discardedShadow;
+    uint64_t outR = c->spec.discardedRadiance, outS = c->spec.discardedShadow;
     {
         const skh_context::Speculation& sp = c->spec;
         if (sp.valid && sp.consumed < sp.count && sp.count > 0)
@@ -3183,7 +3175,7 @@ skh_status skh_get_stats(skh_context* c, skh_stats* out)
     }
     out->rays_radiance = sd.raysRadiance - std::min<uint64_t>(sd.raysRadiance, outR);
     out->rays_shadow = sd.raysShadow - std::min<uint64_t>(sd.raysShadow, outS);
-    out->speculated_discarded = c->discardedSubframes;
+    out->speculated_discarded = c->spec.discardedSubframes;
     for (int k = 0; k < 2; ++k)
     {
         out->nodes_visited[k] = sd.nodes[k];
@@ -3250,18 +3242,18 @@ skh_status skh_get_stats(skh_context* c, skh_stats* out)
                         100.0 * (double)sd.afterDryHist[k][j] / (double)waves);
     }
 #endif
-    out->ms_trace_closest = c->msClass[KC_TRACE_CLOSEST];
-    out->ms_trace_shadow = c->msClass[KC_TRACE_SHADOW];
-    out->ms_shade = c->msClass[KC_SHADE];
-    out->ms_raygen = c->msClass[KC_RAYGEN];
-    out->ms_accumulate = c->msClass[KC_ACCUM];
-    out->ms_sort = c->msClass[KC_SORT];
-    out->ms_build = c->msBuild;
-    out->launches_trace_closest = c->launches[KC_TRACE_CLOSEST];
-    out->launches_trace_shadow = c->launches[KC_TRACE_SHADOW];
-    out->launches_shade = c->launches[KC_SHADE];
-    out->launches_other = c->launches[KC_RAYGEN] + c->launches[KC_ACCUM];
-    out->stack_overflows = c->stackOverflows;
+    out->ms_trace_closest = c->timing.msClass[KC_TRACE_CLOSEST];
+    out->ms_trace_shadow = c->timing.msClass[KC_TRACE_SHADOW];
+    out->ms_shade = c->timing.msClass[KC_SHADE];
+    out->ms_raygen = c->timing.msClass[KC_RAYGEN];
+    out->ms_accumulate = c->timing.msClass[KC_ACCUM];
+    out->ms_sort = c->timing.msClass[KC_SORT];
+    out->ms_build = c->accel.msBuild;
+    out->launches_trace_closest = c->timing.launches[KC_TRACE_CLOSEST];
+    out->launches_trace_shadow = c->timing.launches[KC_TRACE_SHADOW];
+    out->launches_shade = c->timing.launches[KC_SHADE];
+    out->launches_other = c->timing.launches[KC_RAYGEN] + c->timing.launches[KC_ACCUM];
+    out->stack_overflows = c->timing.stackOverflows;
     return SKH_OK;
 }
 
@@ -3269,20 +3261,20 @@ skh_status skh_reset_stats(skh_context* c)
 {
     if (!c)
         return SKH_INVALID_ARGUMENT;
-    (void)hipSetDevice(c->device);
+    (void)hipSetDevice(c->dev.device);
     spec_drop(c, true); // (what was traced ahead belongs to the counters being cleared)
-    SKH_TRY(c, hipStreamSynchronize(c->stream));
-    SKH_TRY(c, hipMemset(c->dStats.p, 0, sizeof(StatsDev)));
-    SKH_TRY(c, hipMemset(c->dCutStats.p, 0, sizeof(CutStatsDev)));
-    c->stackOverflows = 0;
-    c->discardedRadiance = c->discardedShadow = 0;
-    c->discardedSubframes = 0;
-    c->aovInfo.calls = c->aovInfo.rays = 0;
-    c->dnInfo.calls = c->dnInfo.pixels = 0;
+    SKH_TRY(c, hipStreamSynchronize(c->dev.stream));
+    SKH_TRY(c, hipMemset(c->timing.dStats.p, 0, sizeof(StatsDev)));
+    SKH_TRY(c, hipMemset(c->cut.dStats.p, 0, sizeof(CutStatsDev)));
+    c->timing.stackOverflows = 0;
+    c->spec.discardedRadiance = c->spec.discardedShadow = 0;
+    c->spec.discardedSubframes = 0;
+    c->aov.info.calls = c->aov.info.rays = 0;
+    c->dn.info.calls = c->dn.info.pixels = 0;
     for (int k = 0; k < KC_COUNT; ++k)
     {
-        c->msClass[k] = 0.0;
-        c->launches[k] = 0;
+        c->timing.msClass[k] = 0.0;
+        c->timing.launches[k] = 0;
     }
     return SKH_OK;
 }
@@ -3291,13 +3283,13 @@ skh_status skh_synchronize(skh_context* c)
 {
     if (!c)
         return SKH_INVALID_ARGUMENT;
-    (void)hipSetDevice(c->device);
-    SKH_TRY(c, hipStreamSynchronize(c->stream));
+    (void)hipSetDevice(c->dev.device);
+    SKH_TRY(c, hipStreamSynchronize(c->dev.stream));
     return SKH_OK;
 }
 
 void* skh_get_stream(skh_context* c)
 {
-    return c ? (void*)c->stream : nullptr;
+    return c ? (void*)c->dev.stream : nullptr;
 }
 
