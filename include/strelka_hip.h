@@ -631,7 +631,8 @@ skh_status skh_read_adaptive(skh_context* ctx, float* host_rgba);
  *            acceleration structure the call builds one, as skh_trace does.
  *   cost     the region is processed in bands of at most option aov_band rays (2^22; 64 ... 2^26): a 32-byte ray and a 20-byte hit record per ray of a band,
  *            freed before the call returns.  With option timing its spans are a class of their own: ms_trace_closest does not move.
- * Not part of it: accumulated or anti-aliased planes, motion vectors, authored face ids (prim_id is the triangle), the eye-space normal, multi-rank gathering. */
+ * Not part of it: accumulated or anti-aliased planes, authored face ids (prim_id is the triangle), the eye-space normal, multi-rank gathering.
+ * Motion vectors come from skh_temporal (its d_motion plane), which reprojects these planes into the previous frame. */
 #define SKH_AOV_IDS         0u /* uint32 x 4: instance_id, prim_id, material, kind */
 #define SKH_AOV_HIT         1u /* float  x 4: t, u, v (skh_hit's), depth */
 #define SKH_AOV_NORMAL      2u /* float  x 4: N.xyz, facing */
@@ -693,7 +694,8 @@ skh_status skh_get_aov_info(skh_context* ctx, skh_aov_info* out);
  *            finite; a flag bit other than the two; a non-zero reserved word -- and a NULL image that the call needs.
  *   cost     scratch owned by the context, 56 bytes per pixel (two colour images, one guide record), grown when a larger image comes, freed by skh_destroy and
  *            by skh_denoise(ctx, NULL, ...).  A context that never calls it allocates and launches nothing for it.
- * Not part of it: variance guidance (SVGF), temporal accumulation or reprojection, separate diffuse / specular filtering, firefly clamping, a denoised accumulator. */
+ * Not part of it: variance guidance (SVGF), separate diffuse / specular filtering, firefly clamping, a denoised accumulator.  Temporal accumulation and
+ * reprojection are a pass of their own: skh_temporal, below. */
 #define SKH_DENOISE_DEMODULATE 1u
 #define SKH_DENOISE_REMODULATE 2u
 #define SKH_DENOISE_MAX_LEVEL  8u /* first_level + levels <= 8: steps up to 128 */
@@ -721,6 +723,71 @@ typedef struct skh_denoise_info
     uint64_t scratch_bytes;  /* device bytes the context holds for the filter now */
 } skh_denoise_info;
 skh_status skh_get_denoise_info(skh_context* ctx, skh_denoise_info* out);
+
+/* ---- Temporal accumulation: the previous frame's history, reprojected through the first-hit planes and blended with the new frame (new; DESIGN.md
+ *      section 2, "Temporal accumulation").  A pure function of caller-owned device planes, one pass, one kernel (skh_temporal.h).
+ *   inputs   caller-owned device images of width x height records of 16 bytes, row-major, in the layout of skh_render_aovs.  Of the current frame: the colour C
+ *            (float rgba) and the planes IDS (instance_id and kind are used), NORMAL (xyz), POSITION (xyz), ALBEDO (rgb).  Of the previous frame: IDS, NORMAL,
+ *            POSITION and a HISTORY record {illumination.rgb, n} per pixel, n the history length as a float.
+ *   surface  skh_denoise's rule: kind 1 or 2 and finite r, g, b in C.  For every other pixel d_out is C bit for bit, d_history_out is {0, 0, 0, 0} and d_motion
+ *            is {0, 0, 0, 0}.  The alpha word of d_out is C's, bit for bit, for every pixel.
+ *   input    c = C.rgb; with SKH_TEMPORAL_DEMODULATE c = C.rgb / m per channel, m = albedo > albedo_floor ? albedo : albedo_floor (skh_denoise's rule: a NaN
+ *            albedo gives the floor).  The history is kept in these units.
+ *   project  clip = mul44(prev_world_to_clip, (P, 1)), P = POSITION(p).xyz, each row ((m0 P.x + m1 P.y) + m2 P.z) + m3 1;
+ *            fx = ((clip.x / clip.w) 0.5 + 0.5) W - 0.5, fy = ((clip.y / clip.w) 0.5 + 0.5) H - 0.5: the inverse of generate_camera_ray's
+ *            ndc = (px + 0.5) / W 2 - 1, no y flip.  The pixel PROJECTS iff clip.w > 0 and fx, fy are finite with -1 <= fx <= W and -1 <= fy <= H; the range
+ *            test comes before any conversion to an integer.
+ *   taps     ix = floor(fx), tx = fx - ix, likewise in y; q_k = (ix + dx, iy + dy) for (dx, dy) = (0,0), (1,0), (0,1), (1,1), with the weights
+ *            (1 - tx)(1 - ty), tx (1 - ty), (1 - tx) ty, tx ty.  Tap k is ACCEPTED iff it lies in the image, its weight is > 0, the previous IDS there has the
+ *            kind and the instance_id of the current pixel, the previous history there has finite rgb and a finite n >= 1,
+ *            (N'(q).x N(p).x + N'(q).y N(p).y) + N'(q).z N(p).z >= normal_min, and |d| <= plane_tolerance with g = P'(q) - P(p) per component and
+ *            d = (N(p).x g.x + N(p).y g.y) + N(p).z g.z (skh_denoise's d).  Every comparison is written so that a NaN rejects.  A rejected tap is selected
+ *            out, never multiplied by zero; an address outside the image is clamped to a legal one before the load.
+ *   blend    with an accepted tap, in tap order: sw = sum w, h = sum (w hist.rgb) / sw, nh = sum (w hist.n) / sw, n' = min(nh + 1, max_history),
+ *            alpha = 1 / n', ill = h + (c - h) alpha per channel.  Otherwise (the pixel does not project, or no tap is accepted) ill = c, n' = initial_length.
+ *            d_history_out = {ill, n'};  d_out.rgb = ill m with DEMODULATE, else ill.
+ *            Every product, sum and quotient is a rounded float32 operation: no fma.  The order is fixed, so the bits are a function of the inputs alone.
+ *   motion   d_motion, when not NULL: {fx - px, fy - py, sw, mask}, mask a float holding bit k for an accepted tap k (0 ... 15).  A surface pixel that does not
+ *            project writes {0, 0, 0, 0}; one that projects without an accepted tap writes its motion with sw = 0, mask = 0.
+ *   no prev  d_prev_history == NULL: there is no previous frame.  The other three previous-frame pointers and the matrix's use are dropped, and every surface
+ *            pixel takes the branch without history: how a host seeds a history of a known length (initial_length).
+ *   call     synchronous, on the stream skh_denoise uses.  d_out == d_color is allowed (a pixel reads only its own C) and gives the bits of the out-of-place
+ *            call; d_history_out == d_prev_history is refused (taps read neighbours).  d_albedo may be NULL without DEMODULATE.
+ *   effects  none on the frame: the accumulator, the AOV accumulators, the adaptive statistics and the ray counts are not read or written; tile ownership plays
+ *            no part; sub-frames traced ahead are not dropped.  No scratch memory: a context that never calls it allocates and launches nothing for it.
+ *   refused  with SKH_INVALID_ARGUMENT, nothing written, the previous state kept: what skh_temporal_check refuses -- width or height 0 or width * height >
+ *            2^26; a matrix entry that is not finite; normal_min outside [-1, 1] or NaN; plane_tolerance <= 0 or NaN (+inf is legal and turns the test off);
+ *            max_history not finite or < 1; initial_length not finite, < 1 or > max_history; an albedo_floor that is <= 0 or not finite; a flag bit other than
+ *            DEMODULATE; a non-zero reserved word -- and a NULL image that the call needs, and the alias above.
+ * Not part of it: object motion (a moved instance loses its history through the plane test; a move smaller than the tolerance ghosts), neighbourhood colour
+ * clamping for lighting changes, luminance moments or variance guidance for the spatial filter, separate diffuse / specular histories, what is seen in mirrors
+ * and through glass (the guides describe the first surface). */
+#define SKH_TEMPORAL_DEMODULATE 1u
+
+typedef struct skh_temporal_params
+{
+    uint32_t width, height;       /* >= 1, width * height <= 2^26 */
+    float prev_world_to_clip[16]; /* row-major: the world_to_clip of the skh_aov_params the previous guide planes were rendered with */
+    float normal_min;             /* in [-1, 1]: the least dot of the two normals */
+    float plane_tolerance;        /* > 0 (+inf: off); scene units */
+    float max_history;            /* finite, >= 1: alpha never falls below 1 / max_history */
+    float initial_length;         /* finite, in [1, max_history]: the n' of a pixel without history */
+    float albedo_floor;           /* finite, > 0 */
+    uint32_t flags;               /* SKH_TEMPORAL_* */
+    uint32_t reserved[8];         /* 0 */
+} skh_temporal_params;
+
+/* SKH_OK when *p is a setting skh_temporal accepts (needs no context and no GPU, as skh_denoise_check) */
+skh_status skh_temporal_check(const skh_temporal_params* p);
+skh_status skh_temporal(skh_context* ctx, const skh_temporal_params* p, const void* d_color, const void* d_ids, const void* d_normal, const void* d_position,
+                        const void* d_albedo, const void* d_prev_history, const void* d_prev_ids, const void* d_prev_normal, const void* d_prev_position,
+                        void* d_out, void* d_history_out, void* d_motion /* may be NULL */);
+typedef struct skh_temporal_info
+{
+    uint64_t calls, pixels; /* since the last skh_reset_stats */
+    double ms_last;         /* wall time of the last call, its synchronisation included */
+} skh_temporal_info;
+skh_status skh_get_temporal_info(skh_context* ctx, skh_temporal_info* out);
 
 /* ---- the tonemap() + gammaCorrection post pass (postprocessing/Tonemappers.cu:111-135), in place on a
  *      device float4 image.  type: 0 none, 1 Reinhard, 2 ACES fitted, 3 ACES film; gamma <= 0 = off ---- */

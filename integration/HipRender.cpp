@@ -259,8 +259,14 @@ void HipRender::freeGuides()
             skh_buffer_free(mCtx, g);
         g = nullptr;
     }
+    for (void** g : { &mPrevGuide[0], &mPrevGuide[1], &mPrevGuide[2], &mHistory[0], &mHistory[1] })
+    {
+        if (mCtx && *g)
+            skh_buffer_free(mCtx, *g);
+        *g = nullptr;
+    }
     mGuideWidth = mGuideHeight = 0;
-    mGuidesValid = false;
+    mGuidesValid = mPrevGuidesValid = mHistoryValid = false;
 }
 
 bool HipRender::setDenoiser(bool on, const HipDenoise* params)
@@ -268,7 +274,8 @@ bool HipRender::setDenoiser(bool on, const HipDenoise* params)
     if (!on)
     {
         mDenoise = false;
-        freeGuides();
+        if (!mTemporal)
+            freeGuides();
         memset(&mDenoiseApplied, 0, sizeof(mDenoiseApplied));
         return !mCtx || check(skh_denoise(mCtx, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr), "skh_denoise"); // (the library's scratch goes too)
     }
@@ -286,20 +293,60 @@ bool HipRender::setDenoiser(bool on, const HipDenoise* params)
     return true;
 }
 
-// the four guide planes of the whole image through the pixel centres, into buffers of this object
+bool HipRender::setTemporal(bool on, const HipTemporal* params)
+{
+    const HipTemporal t = params ? *params : HipTemporal();
+    // (checked here with an image and a scene that pass: the real ones are render()'s)
+    const skh_temporal_params probe = hipTemporalParams(t, 1u, 1u, nullptr, 1.0f, 1.0f);
+    if (on && skh_temporal_check(&probe) != SKH_OK)
+    {
+        mError = "setTemporal: the setting was refused (normalMin in [-1, 1], a positive tolerance, finite maxHistory >= 1 and positive floor)";
+        return false;
+    }
+    dropHistory(); // (a history kept under another setting is not this one's)
+    mPrevGuidesValid = false;
+    memset(&mTemporalApplied, 0, sizeof(mTemporalApplied));
+    if (!on)
+    {
+        mTemporal = false;
+        if (!mDenoise)
+            freeGuides();
+        return true;
+    }
+    if (!mTemporal)
+        mGuidesValid = false; // (the buffers this feature adds come with the next guide pass)
+    mTemporal = true;
+    mTemporalSetting = t;
+    return true;
+}
+
+// the four guide planes of the whole image through the pixel centres, into buffers of this object.  With temporal accumulation on, the set rendered last
+// (ids, normal, position) and its world_to_clip first become the previous frame's.
 bool HipRender::renderGuides()
 {
-    if (mGuideWidth != mWidth || mGuideHeight != mHeight)
+    if (mGuideWidth != mWidth || mGuideHeight != mHeight || (mTemporal && !mHistory[0]))
     {
         freeGuides();
         for (void*& g : mGuide)
             if (!check(skh_buffer_alloc(mCtx, (size_t)16 * mWidth * mHeight, &g), "skh_buffer_alloc"))
                 return false;
+        if (mTemporal)
+            for (void** g : { &mPrevGuide[0], &mPrevGuide[1], &mPrevGuide[2], &mHistory[0], &mHistory[1] })
+                if (!check(skh_buffer_alloc(mCtx, (size_t)16 * mWidth * mHeight, g), "skh_buffer_alloc"))
+                    return false;
         mGuideWidth = mWidth, mGuideHeight = mHeight;
     }
     skh_aov_params ap;
     if (!aovParams(ap, nullptr, false))
         return false;
+    if (mTemporal)
+    {
+        for (int k = 0; k < 3; ++k)
+            std::swap(mGuide[k], mPrevGuide[k]);
+        memcpy(mPrevWorldToClip, mGuideWorldToClip, sizeof(mPrevWorldToClip));
+        mPrevGuidesValid = mGuidesValid;
+        memcpy(mGuideWorldToClip, ap.world_to_clip, sizeof(mGuideWorldToClip));
+    }
     void* d[SKH_AOV_COUNT] = {};
     d[SKH_AOV_IDS] = mGuide[0], d[SKH_AOV_NORMAL] = mGuide[1], d[SKH_AOV_POSITION] = mGuide[2], d[SKH_AOV_ALBEDO] = mGuide[3];
     const uint32_t planes = (1u << SKH_AOV_IDS) | (1u << SKH_AOV_NORMAL) | (1u << SKH_AOV_POSITION) | (1u << SKH_AOV_ALBEDO);
@@ -608,11 +655,13 @@ void HipRender::render(Buffer* output)
     {
         sh.mSubframeIndex = 0; // other lights: the accumulated image is of the old ones
         mLightShapesChanged = false;
+        dropHistory();
     }
     if (mEnvironmentChanged)
     {
         sh.mSubframeIndex = 0; // a new sky: the accumulated image is of the old one
         mEnvironmentChanged = false;
+        dropHistory();
     }
     if (sh.mFrameNumber == 0)
         uploadScene(); // scene is uploaded once (OptixRender.cpp:876-888); later edits are ignored, like the reference, except ...
@@ -626,6 +675,7 @@ void HipRender::render(Buffer* output)
     {
         sh.mSubframeIndex = 0;
         sh.mSettingsManager->setAs<bool>("render/pt/isResized", true);
+        dropHistory();
         applyTiles(width, height);
         check(skh_resize(mCtx, width, height), "skh_resize");
         mWidth = width;
@@ -634,7 +684,8 @@ void HipRender::render(Buffer* output)
     Camera& camera = mScene->getCamera(0);
     camera.updateAspectRatio(width / (float)height);
     camera.updateViewMatrix();
-    if (camera.matrices.perspective != mPrevPerspective || camera.matrices.view != mPrevView)
+    const bool cameraChanged = camera.matrices.perspective != mPrevPerspective || camera.matrices.view != mPrevView;
+    if (cameraChanged)
         sh.mSubframeIndex = 0; // need reset (OptixRender.cpp:903-908)
 
     SettingsManager& settings = *sh.mSettingsManager;
@@ -651,7 +702,10 @@ void HipRender::render(Buffer* output)
     const float gamma = settings.getAs<float>("render/post/gamma");
     const uint32_t tonemapperType = settings.getAs<uint32_t>("render/pt/tonemapperType");
     if (settingsChanged)
+    {
         sh.mSubframeIndex = 0;
+        dropHistory();
+    }
 
     skh_frame_params p;
     memset(&p, 0, sizeof(p));
@@ -690,9 +744,19 @@ void HipRender::render(Buffer* output)
         samplesThisLaunch = 1;
         enableAccumulation = false;
     }
+    // temporal accumulation: a moving camera's frame is one raw sample of the sequence, another one every time (HipRender.h, rotateSamples)
+    const bool temporalFrame = mTemporal && p.debug == 0 && (!mSharing || mRank == 0);
+    const bool startCall = sh.mSubframeIndex == 0;
+    if (mTemporal && mTemporalSetting.rotateSamples && !mSharing && p.debug == 0 && enableAccumulation && startCall && cameraChanged && mRendered && totalSpp != 0u)
+    {
+        p.subframe_index = mRotation++ % totalSpp;
+        samplesThisLaunch = std::min(samplesPerLaunch, totalSpp - p.subframe_index);
+        enableAccumulation = false; // (below: mSubframeIndex stays 0, the first still call starts a normal accumulation at sample 0)
+    }
     p.samples_this_launch = samplesThisLaunch;
     p.enable_accumulation = enableAccumulation;
     p.spp_total = totalSpp;
+    mLastSubframeIndex = p.subframe_index, mLastEnableAccumulation = p.enable_accumulation;
 
     void* dImage = static_cast<HipBuffer*>(output)->getNativePtr();
     const bool adaptiveFrame = mAdaptive && enableAccumulation && p.debug == 0;
@@ -708,7 +772,7 @@ void HipRender::render(Buffer* output)
         mConverged = false;
     // the denoiser's guide planes belong to the accumulation: rendered when it (re)starts or the image size changed, before the frame's own work
     const bool denoiseFrame = mDenoise && p.debug == 0 && (!mSharing || mRank == 0);
-    if (denoiseFrame && (sh.mSubframeIndex == 0 || !mGuidesValid || mGuideWidth != width || mGuideHeight != height))
+    if ((denoiseFrame || temporalFrame) && (startCall || !mGuidesValid || mGuideWidth != width || mGuideHeight != height))
         renderGuides();
     if (samplesThisLaunch != 0 && !mConverged)
     {
@@ -739,6 +803,38 @@ void HipRender::render(Buffer* output)
             check(skh_scatter_tiles(mCtx, mGatherBuf, mAllTileXY.data(), (uint32_t)(mAllTileXY.size() / 2), mTileSize, dImage, width, height),
                   "skh_scatter_tiles");
     }
+    if (temporalFrame && mGuidesValid)
+    {
+        // the output image -- linear here --; the accumulator is not touched
+        const int next = 1 - mHistoryStored;
+        if (startCall)
+        {
+            // the stored history, reprojected into the new frame and blended with it, in place; the new history takes the stored one's place
+            const bool had = mHistoryValid && mPrevGuidesValid;
+            const skh_temporal_params tp = hipTemporalParams(mTemporalSetting, width, height, had ? mPrevWorldToClip : nullptr, 1.0f, mSceneDiagonal);
+            if (check(skh_temporal(mCtx, &tp, dImage, mGuide[0], mGuide[1], mGuide[2], mGuide[3], had ? mHistory[mHistoryStored] : nullptr, mPrevGuide[0], mPrevGuide[1],
+                                   mPrevGuide[2], dImage, mHistory[next], nullptr),
+                      "skh_temporal"))
+            {
+                mHistoryStored = next, mHistoryValid = true;
+                mTemporalApplied = tp, mTemporalHadPrevious = had;
+            }
+        }
+        else
+        {
+            // an accumulation in progress: its image is shown as it is, and becomes the history with its true length (the call's image output goes to the
+            // history buffer that is not the stored one, and is discarded)
+            skh_temporal_params tp = hipTemporalParams(mTemporalSetting, width, height, nullptr, 1.0f, mSceneDiagonal);
+            tp.initial_length = std::min((float)sh.mSubframeIndex, tp.max_history); // (the samples in the accumulator: >= 1 here)
+            if (check(skh_temporal(mCtx, &tp, dImage, mGuide[0], mGuide[1], mGuide[2], mGuide[3], nullptr, nullptr, nullptr, nullptr, mHistory[next],
+                                   mHistory[mHistoryStored], nullptr),
+                      "skh_temporal"))
+            {
+                mHistoryValid = true;
+                mTemporalApplied = tp, mTemporalHadPrevious = false;
+            }
+        }
+    }
     if (denoiseFrame && mGuidesValid)
     {
         // the output image -- linear here --, in place; the accumulator is not touched
@@ -752,6 +848,7 @@ void HipRender::render(Buffer* output)
     sh.mFrameNumber++;
     mPrevView = camera.matrices.view;
     mPrevPerspective = camera.matrices.perspective;
+    mRendered = true;
 }
 
 #ifndef SKH_WITH_STRELKA_HEADERS

@@ -86,6 +86,34 @@ inline skh_denoise_params hipDenoiseParams(const HipDenoise& d, uint32_t width, 
     return p;
 }
 
+struct HipTemporal // HipRender::setTemporal: a field that is 0 takes its default
+{
+    float normalMin = 0.0f;      // 0.9; another value is taken as it is (-1 turns the test off)
+    float planeTolerance = 0.0f; // scene units; default (also for a negative value): planeFraction x the diagonal of the scene's bounding box
+    float planeFraction = 0.0f;  // 0.005, the denoiser's fraction
+    float maxHistory = 0.0f;     // 32
+    float albedoFloor = 0.0f;    // 0.05
+    bool rotateSamples = true;   // a moving camera's frames take successive samples of the sequence instead of sample 0 every time
+};
+
+// the skh_temporal_params render() hands to skh_temporal for a HipTemporal setting: DEMODULATE; prevWorldToClip nullptr = no previous frame (the identity, which
+// the check accepts); initialLength 0 = 1
+inline skh_temporal_params hipTemporalParams(const HipTemporal& t, uint32_t width, uint32_t height, const float* prevWorldToClip, float initialLength, float sceneDiagonal)
+{
+    skh_temporal_params p = {};
+    p.width = width, p.height = height;
+    for (int k = 0; k < 16; ++k)
+        p.prev_world_to_clip[k] = prevWorldToClip ? prevWorldToClip[k] : (k % 5 == 0 ? 1.0f : 0.0f);
+    p.normal_min = t.normalMin != 0.0f ? t.normalMin : 0.9f;
+    const float plane = t.planeTolerance > 0.0f ? t.planeTolerance : (t.planeFraction > 0.0f ? t.planeFraction : 0.005f) * sceneDiagonal;
+    p.plane_tolerance = plane > 0.0f ? plane : HUGE_VALF; // (no mesh instance to measure: the test is off)
+    p.max_history = t.maxHistory > 0.0f ? t.maxHistory : 32.0f;
+    p.initial_length = initialLength > 0.0f ? initialLength : 1.0f;
+    p.albedo_floor = t.albedoFloor > 0.0f ? t.albedoFloor : 0.05f;
+    p.flags = SKH_TEMPORAL_DEMODULATE;
+    return p;
+}
+
 class HipRender : public Render
 {
 public:
@@ -170,6 +198,35 @@ public:
         p = mDenoiseApplied;
         return mDenoiseApplied.width != 0u;
     }
+    // Temporal accumulation (skh_temporal; new: in the reference every camera move starts from one sample), OFF by default.  With it on, render() with debug == 0
+    // ends with exactly one skh_temporal call on the OUTPUT image -- after the gather, before skh_denoise when that is on, before the tonemap; the accumulator is
+    // never touched.  This object owns two history buffers and a second set of ids / normal / position guide buffers; the guide pass is the denoiser's
+    // renderGuides(), once per accumulation whichever of the two features is on.
+    //   a call that starts an accumulation       reprojects the stored history into the new frame, stores the new history, and the guide sets change places
+    //   a call that continues one                shows the accumulator's image as before and stores it as the history, with its true length
+    //                                            min(samples accumulated, maxHistory): skh_temporal without a previous frame, its image output discarded
+    //   the history is dropped after             a resize, setLightShapes / setEnvironment changes, the settings changes that restart the accumulation, setTemporal.
+    //                                            Moved instances keep it: the plane test answers for the geometry (their shadows lag)
+    //   rotateSamples                            a start call whose camera differs from the previous call's is traced with enable_accumulation = 0 and
+    //                                            subframe_index = (a counter advanced per such call) % sppTotal: the raw sample of that index, so that consecutive
+    //                                            moving frames do not repeat sample 0's random numbers.  mSubframeIndex stays 0: the first still call starts a
+    //                                            normal accumulation.  Not with tile sharing (a raw sample is not gathered).
+    // With tile sharing rank 0 makes the call on the gathered image.  params == nullptr: every default.  false: the setting was refused (skh_temporal_check; the
+    // previous one stays).  With it off, render() makes the calls it made before.
+    bool setTemporal(bool on, const HipTemporal* params = nullptr);
+    // what the last render() handed to skh_temporal (false: none yet); hadPrevious: whether that call reprojected a stored history
+    bool temporalParams(skh_temporal_params& p, bool* hadPrevious = nullptr) const
+    {
+        p = mTemporalApplied;
+        if (hadPrevious)
+            *hadPrevious = mTemporalHadPrevious;
+        return mTemporalApplied.width != 0u;
+    }
+    // the frame parameters' sample choice of the last render(): subframe_index and enable_accumulation as handed to skh_render_subframe
+    void lastSample(uint32_t& subframeIndex, uint32_t& enableAccumulation) const
+    {
+        subframeIndex = mLastSubframeIndex, enableAccumulation = mLastEnableAccumulation;
+    }
 
 private:
     skh_context* mCtx = nullptr;
@@ -210,6 +267,23 @@ private:
     void measureScene(const std::vector<skh_instance>& inst);
     bool renderGuides();
     void freeGuides();
+    bool mTemporal = false;
+    HipTemporal mTemporalSetting;
+    skh_temporal_params mTemporalApplied = {};
+    bool mTemporalHadPrevious = false;
+    void* mHistory[2] = {};    // {illumination.rgb, n} per pixel; mHistory[mHistoryStored] is the stored one, the other the next call's output
+    int mHistoryStored = 0;
+    bool mHistoryValid = false; // false: the next call has no previous frame
+    void* mPrevGuide[3] = {};  // ids | normal | position the stored history belonged to when the guide sets last changed places
+    bool mPrevGuidesValid = false;
+    float mGuideWorldToClip[16] = {}, mPrevWorldToClip[16] = {}; // of mGuide / mPrevGuide
+    uint32_t mRotation = 0;    // moving start calls so far (rotateSamples)
+    bool mRendered = false;    // a render() has been made: mPrevView is a camera
+    uint32_t mLastSubframeIndex = 0, mLastEnableAccumulation = 0;
+    void dropHistory()
+    {
+        mHistoryValid = false;
+    }
     void uploadMaterials(); // MaterialDescription list -> skh_material blocks + textures (OptixRender.cpp:1270-1433)
 };
 

@@ -34,7 +34,8 @@ SYMBOLS = ["skh_create", "skh_destroy", "skh_last_error", "skh_abi_version", "sk
            "skh_set_light_shapes", "skh_get_light_shape_info", "skh_light_shape_probe",
            "skh_adaptive_check", "skh_set_adaptive", "skh_get_adaptive_info", "skh_read_adaptive",
            "skh_aov_check", "skh_render_aovs", "skh_get_aov_info",
-           "skh_denoise_check", "skh_denoise", "skh_get_denoise_info", "skh_buffer_upload"]
+           "skh_denoise_check", "skh_denoise", "skh_get_denoise_info", "skh_buffer_upload",
+           "skh_temporal_check", "skh_temporal", "skh_get_temporal_info"]
 
 BUILD_INFO = np.dtype([("triangles", np.uint32), ("nodes", np.uint32), ("reinsert_rounds", np.uint32), ("reinsert_moves", np.uint32),
                        ("reinsert_min_size", np.uint32), ("refit", np.uint32), ("cost_before", np.float64), ("cost_after", np.float64),
@@ -58,6 +59,9 @@ assert AOV_INFO.itemsize == 32
 DENOISE_INFO = np.dtype([("calls", np.uint64), ("pixels", np.uint64), ("ms_last", np.float64), ("scratch_bytes", np.uint64)])
 assert DENOISE_INFO.itemsize == 32
 DENOISE_GUIDES = ("ids", "normal", "position", "albedo")  # the planes skh_denoise reads, in its argument order
+TEMPORAL_INFO = np.dtype([("calls", np.uint64), ("pixels", np.uint64), ("ms_last", np.float64)])
+assert TEMPORAL_INFO.itemsize == 24
+TEMPORAL_PREV = ("history", "ids", "normal", "position")  # the previous-frame images skh_temporal reads, in its argument order
 # skh_light_shape_probe: kind -> (number, words in, words out) per record
 LSHAPE_PROBES = {"sample": (0, 6, 13), "pdf": (1, 7, 2)}
 # skh_emitter_probe: kind -> (number, words in, words out) per record
@@ -134,6 +138,9 @@ def load():
     lib.skh_denoise_check.argtypes = [vp]
     lib.skh_denoise.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp]
     lib.skh_get_denoise_info.argtypes = [vp, vp]
+    lib.skh_temporal_check.argtypes = [vp]
+    lib.skh_temporal.argtypes = [vp] * 14
+    lib.skh_get_temporal_info.argtypes = [vp, vp]
     lib.skh_buffer_upload.argtypes = [vp, vp, vp, C.c_size_t]
     lib.skh_resize.argtypes = [vp, u32, u32]
     lib.skh_set_tiles.argtypes = [vp, u32, vp, u32]
@@ -198,6 +205,12 @@ def denoise_check(params):
     """skh_denoise_check: would skh_denoise accept these S.DENOISE_PARAMS?  (needs no context and no GPU)"""
     p = np.ascontiguousarray(params, dtype=S.DENOISE_PARAMS)
     return load().skh_denoise_check(_p(p)) == 0
+
+
+def temporal_check(params):
+    """skh_temporal_check: would skh_temporal accept these S.TEMPORAL_PARAMS?  (needs no context and no GPU)"""
+    p = np.ascontiguousarray(params, dtype=S.TEMPORAL_PARAMS)
+    return load().skh_temporal_check(_p(p)) == 0
 
 
 def adaptive_dark_level(radiance, exposure):
@@ -558,6 +571,57 @@ class Context:
         d = np.zeros((), DENOISE_INFO)
         self._ck(self.lib.skh_get_denoise_info(self.h, _p(d)), "skh_get_denoise_info")
         return {k: (float(d[k]) if d[k].dtype.kind == "f" else int(d[k])) for k in DENOISE_INFO.names}
+
+    def temporal_device(self, params, d_color, d_ids, d_normal, d_position, d_albedo, d_prev_history, d_prev_ids, d_prev_normal, d_prev_position, d_out, d_history_out,
+                        d_motion=None):
+        """skh_temporal on caller-owned device images (d_out may be d_color; d_albedo may be None without DEMODULATE; d_prev_history None = no previous frame;
+        d_motion None = no motion plane)"""
+        p = np.ascontiguousarray(params, dtype=S.TEMPORAL_PARAMS)
+        self._ck(self.lib.skh_temporal(self.h, _p(p), d_color, d_ids, d_normal, d_position, d_albedo, d_prev_history, d_prev_ids, d_prev_normal, d_prev_position,
+                                       d_out, d_history_out, d_motion), "skh_temporal")
+
+    def temporal(self, image, guides, prev, params):
+        """skh_temporal, numpy in and numpy out: `image` an (h, w, 4) float32 colour image, `guides` {"ids", "normal", "position", "albedo"} of the current frame as
+        render_guides returns them ("albedo" may be missing without DEMODULATE), `prev` None (no previous frame) or {"history", "ids", "normal", "position"} of the
+        previous one, `params` S.temporal_params -> {"image", "history", "motion"}, (h, w, 4) float32 each.  Device buffers come from skh_buffer_alloc and are freed here."""
+        img = np.ascontiguousarray(image, np.float32)
+        p = np.array(params, dtype=S.TEMPORAL_PARAMS)
+        h, w = int(p["height"]), int(p["width"])
+        if img.shape != (h, w, 4):
+            raise ValueError(f"the image must be ({h}, {w}, 4)")
+        planes = {"color": img}
+        for n in DENOISE_GUIDES:
+            if guides.get(n) is not None:
+                planes[n] = np.ascontiguousarray(guides[n], np.uint32 if n == "ids" else np.float32)
+        if prev is not None:
+            for n in TEMPORAL_PREV:
+                planes["prev_" + n] = np.ascontiguousarray(prev[n], np.uint32 if n == "ids" else np.float32)
+        for n, a in planes.items():
+            if a.shape != (h, w, 4):
+                raise ValueError(f"{n} must be ({h}, {w}, 4)")
+        bufs = {}
+        try:
+            for n, a in planes.items():
+                bufs[n] = self.buffer_alloc(a.nbytes)
+                self.buffer_upload(bufs[n], a)
+            for n in ("image", "history", "motion"):
+                bufs[n] = self.buffer_alloc(img.nbytes)
+            self.temporal_device(p, bufs["color"], bufs.get("ids"), bufs.get("normal"), bufs.get("position"), bufs.get("albedo"), bufs.get("prev_history"),
+                                 bufs.get("prev_ids"), bufs.get("prev_normal"), bufs.get("prev_position"), bufs["image"], bufs["history"], bufs["motion"])
+            out = {}
+            for n in ("image", "history", "motion"):
+                out[n] = np.zeros_like(img)
+                self.buffer_download(bufs[n], out[n])
+            return out
+        finally:
+            for d in bufs.values():
+                self.buffer_free(d)
+
+    def temporal_info(self):
+        """skh_get_temporal_info: calls and pixels since the last reset_stats, the last call's wall time"""
+        d = np.zeros((), TEMPORAL_INFO)
+        self._ck(self.lib.skh_get_temporal_info(self.h, _p(d)), "skh_get_temporal_info")
+        return {k: (float(d[k]) if d[k].dtype.kind == "f" else int(d[k])) for k in TEMPORAL_INFO.names}
 
     def render_subframe(self, params, d_image=None):
         p = np.ascontiguousarray(params, dtype=S.FRAME_PARAMS)

@@ -81,7 +81,7 @@ struct TimedSpan
 
 // The context: one member struct per subject, every member in exactly one of them.  `scene` is what the skh_set_* calls stored, `opt` what skh_set_option stored;
 // everything else is derived from those two -- `accel` by the builders, the feature groups (`env`, `emit`, `mtex`, `cut`, `lshape`) by their setters and
-// *_ensure functions, `frame` by alloc_frame -- or is state of the calls in progress (`spec`, `adapt`, `timing`, `aov`, `dn`).  Which change of an input
+// *_ensure functions, `frame` by alloc_frame -- or is state of the calls in progress (`spec`, `adapt`, `timing`, `aov`, `dn`, `tp`).  Which change of an input
 // invalidates which derived state: skh_stale.h.  No group is ever reset wholesale while the context lives, except `adapt` by skh_set_adaptive(NULL): the
 // buffers are kept and reused by dev_alloc's size window.
 struct skh_context
@@ -399,6 +399,12 @@ struct skh_context
         DevBuf dColor[2], dG0, dG1;
         skh_denoise_info info = {};
     } dn;
+
+    // temporal accumulation (skh_temporal; skh_temporal.h): no scratch, nothing but this lives between two calls
+    struct Temporal
+    {
+        skh_temporal_info info = {};
+    } tp;
 };
 
 // A caller changed `in`: every derived state that depends on it is invalidated (the table: skh_stale.h).

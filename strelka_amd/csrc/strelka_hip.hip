@@ -38,6 +38,7 @@ static_assert(sizeof(skh_hit) == 20 && sizeof(Light) == 112 && sizeof(Material) 
 #include "skh_host.h"
 #include "skh_aov.h"
 #include "skh_denoise.h"
+#include "skh_temporal.h"
 
 // Sobol generator matrices for the 5 dimensions the reference tabulates (RandomSampler.h:139-164), produced from the
 // Joe-Kuo recurrences (d=2: s=1 a=0 m={1}; d=3: s=2 a=1 m={1,3}; d=4: s=3 a=1 m={1,3,1}; d=5: s=3 a=2 m={1,1,1}).
@@ -3009,6 +3010,94 @@ skh_status skh_get_denoise_info(skh_context* c, skh_denoise_info* out)
     return SKH_OK;
 }
 
+// ---- temporal accumulation (skh_temporal.h): skh_temporal_check, skh_temporal, skh_get_temporal_info ----
+static_assert(sizeof(skh_temporal_params) == 128 && sizeof(skh_temporal_info) == 24, "ABI layout");
+
+// why *p is refused, or nullptr
+static const char* temporal_refusal(const skh_temporal_params* p)
+{
+    if (!p)
+        return "no parameters";
+    if (p->width == 0u || p->height == 0u || (uint64_t)p->width * p->height > (1ull << 26))
+        return "an empty image, or one of more than 2^26 pixels";
+    for (float m : p->prev_world_to_clip)
+        if (!std::isfinite(m))
+            return "a matrix entry that is not finite";
+    if (!(p->normal_min >= -1.0f && p->normal_min <= 1.0f)) // (a NaN too)
+        return "a normal_min outside [-1, 1] or NaN";
+    if (!(p->plane_tolerance > 0.0f))
+        return "a plane_tolerance that is <= 0 or NaN";
+    if (!std::isfinite(p->max_history) || !(p->max_history >= 1.0f))
+        return "a max_history that is < 1 or not finite";
+    if (!std::isfinite(p->initial_length) || !(p->initial_length >= 1.0f) || !(p->initial_length <= p->max_history))
+        return "an initial_length that is < 1, above max_history or not finite";
+    if (!std::isfinite(p->albedo_floor) || !(p->albedo_floor > 0.0f))
+        return "an albedo_floor that is <= 0 or not finite";
+    if (p->flags & ~SKH_TEMPORAL_DEMODULATE)
+        return "an unknown flag bit";
+    for (uint32_t r : p->reserved)
+        if (r != 0u)
+            return "a non-zero reserved word";
+    return nullptr;
+}
+
+skh_status skh_temporal_check(const skh_temporal_params* p)
+{
+    return temporal_refusal(p) ? SKH_INVALID_ARGUMENT : SKH_OK;
+}
+
+skh_status skh_temporal(skh_context* c, const skh_temporal_params* p, const void* d_color, const void* d_ids, const void* d_normal, const void* d_position,
+                        const void* d_albedo, const void* d_prev_history, const void* d_prev_ids, const void* d_prev_normal, const void* d_prev_position,
+                        void* d_out, void* d_history_out, void* d_motion)
+{
+    if (!c)
+        return SKH_INVALID_ARGUMENT;
+    (void)hipSetDevice(c->dev.device);
+    const char* why = temporal_refusal(p);
+    if (!why && (!d_color || !d_ids || !d_normal || !d_position || !d_out || !d_history_out))
+        why = "a NULL image";
+    if (!why && (p->flags & SKH_TEMPORAL_DEMODULATE) && !d_albedo)
+        why = "a flag that needs the albedo plane, and no albedo plane";
+    if (!why && d_prev_history && (!d_prev_ids || !d_prev_normal || !d_prev_position))
+        why = "a previous history without its guide planes";
+    if (!why && d_prev_history && d_history_out == d_prev_history)
+        why = "d_history_out == d_prev_history (taps read neighbours)";
+    if (why)
+    {
+        c->dev.err = std::string("skh_temporal: ") + why;
+        return SKH_INVALID_ARGUMENT;
+    }
+    const auto t0 = std::chrono::steady_clock::now();
+    const size_t n = (size_t)p->width * p->height;
+    hipStream_t st = side_stream(c); // (skh_denoise's stream: beside a pass traced ahead, not behind it)
+    TpP tp;
+    tp.width = p->width, tp.height = p->height;
+    for (int k = 0; k < 16; ++k)
+        tp.prevWorldToClip[k] = p->prev_world_to_clip[k];
+    tp.normalMin = p->normal_min, tp.planeTolerance = p->plane_tolerance, tp.maxHistory = p->max_history, tp.initialLength = p->initial_length;
+    tp.albedoFloor = p->albedo_floor, tp.flags = p->flags, tp.hasPrev = d_prev_history ? 1u : 0u;
+    const dim3 grid(((p->width + 63u) / 64u) * ((p->height + 3u) / 4u)), block(64, 4); // (<= 2^24 + 2^20 tiles of 64 x 4 pixels, row-major)
+    k_tp_reproject<<<grid, block, 0, st>>>(tp, reinterpret_cast<const uint4*>(d_color), reinterpret_cast<const uint4*>(d_ids), reinterpret_cast<const float4*>(d_normal),
+                                           reinterpret_cast<const float4*>(d_position), reinterpret_cast<const float4*>(d_albedo),
+                                           reinterpret_cast<const float4*>(d_prev_history), reinterpret_cast<const uint4*>(d_prev_ids),
+                                           reinterpret_cast<const float4*>(d_prev_normal), reinterpret_cast<const float4*>(d_prev_position),
+                                           reinterpret_cast<uint4*>(d_out), reinterpret_cast<float4*>(d_history_out), reinterpret_cast<float4*>(d_motion));
+    SKH_TRY(c, hipGetLastError());
+    SKH_TRY(c, hipStreamSynchronize(st));
+    c->tp.info.calls++;
+    c->tp.info.pixels += n;
+    c->tp.info.ms_last = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    return SKH_OK;
+}
+
+skh_status skh_get_temporal_info(skh_context* c, skh_temporal_info* out)
+{
+    if (!c || !out)
+        return SKH_INVALID_ARGUMENT;
+    *out = c->tp.info;
+    return SKH_OK;
+}
+
 // ---- skh_set_option: one row per name ----
 // What setting an option costs beyond the store.  OPT_REBUILD: a hierarchy depends on it -- the build is invalidated, and with it skh_update_accel's in-place
 // path (include/strelka_hip.h).  OPT_FRAME: the frame's buffers are sized by it -- they are allocated again when a frame exists.
@@ -3271,6 +3360,7 @@ skh_status skh_reset_stats(skh_context* c)
     c->spec.discardedSubframes = 0;
     c->aov.info.calls = c->aov.info.rays = 0;
     c->dn.info.calls = c->dn.info.pixels = 0;
+    c->tp.info.calls = c->tp.info.pixels = 0;
     for (int k = 0; k < KC_COUNT; ++k)
     {
         c->timing.msClass[k] = 0.0;

@@ -698,6 +698,33 @@ def denoise_params(width, height, levels=5, sigma_color=None, sigma_normal=DENOI
     return p
 
 
+TEMPORAL_PARAMS = np.dtype([("width", np.uint32), ("height", np.uint32), ("prev_world_to_clip", np.float32, 16), ("normal_min", np.float32),
+                            ("plane_tolerance", np.float32), ("max_history", np.float32), ("initial_length", np.float32), ("albedo_floor", np.float32),
+                            ("flags", np.uint32), ("reserved", np.uint32, 8)])  # skh_temporal_params, 128 B
+assert TEMPORAL_PARAMS.itemsize == 128
+TEMPORAL_DEMODULATE = 1
+# the defaults of temporal_params (DESIGN.md section 2 "Temporal accumulation" gives the reasons)
+TEMPORAL_NORMAL_MIN = 0.9     # cos 26 degrees: the two pixel-centre normals of one smooth surface a camera move apart, not a crease
+TEMPORAL_MAX_HISTORY = 32.0   # alpha never below 1/32
+
+
+def temporal_params(width, height, prev_aov_params=None, normal_min=TEMPORAL_NORMAL_MIN, plane_tolerance=None, max_history=TEMPORAL_MAX_HISTORY, initial_length=1.0,
+                    albedo_floor=DENOISE_ALBEDO_FLOOR, demodulate=True, scene=None):
+    """skh_temporal_params.  `prev_aov_params` (aov_params' record the previous guide planes were rendered with) supplies prev_world_to_clip; None: the identity,
+    for a call without a previous frame.  plane_tolerance is in scene units; None: DENOISE_PLANE_FRACTION of scene_diagonal(`scene`) (`scene`: Scene.arrays()),
+    the denoiser's rule for its sigma_plane."""
+    p = np.zeros((), TEMPORAL_PARAMS)
+    p["width"], p["height"] = width, height
+    p["prev_world_to_clip"] = np.eye(4, dtype=np.float32).reshape(16) if prev_aov_params is None else np.asarray(prev_aov_params["world_to_clip"], np.float32).reshape(16)
+    if plane_tolerance is None:
+        if scene is None:
+            raise ValueError("plane_tolerance is in scene units: give it, or give `scene` to take it as a fraction of the bounding-box diagonal")
+        plane_tolerance = DENOISE_PLANE_FRACTION * scene_diagonal(scene)
+    p["normal_min"], p["plane_tolerance"], p["max_history"], p["initial_length"], p["albedo_floor"] = normal_min, plane_tolerance, max_history, initial_length, albedo_floor
+    p["flags"] = TEMPORAL_DEMODULATE if demodulate else 0
+    return p
+
+
 def default_exposure(filmIso=100.0, cm2_factor=1.0, fStop=4.0, shutterSpeed=100.0):
     """exposureValue of OptiXRender::render (OptixRender.cpp:961-987), fp32 arithmetic."""
     f = np.float32
