@@ -694,8 +694,8 @@ skh_status skh_get_aov_info(skh_context* ctx, skh_aov_info* out);
  *            finite; a flag bit other than the two; a non-zero reserved word -- and a NULL image that the call needs.
  *   cost     scratch owned by the context, 56 bytes per pixel (two colour images, one guide record), grown when a larger image comes, freed by skh_destroy and
  *            by skh_denoise(ctx, NULL, ...).  A context that never calls it allocates and launches nothing for it.
- * Not part of it: variance guidance (SVGF), separate diffuse / specular filtering, firefly clamping, a denoised accumulator.  Temporal accumulation and
- * reprojection are a pass of their own: skh_temporal, below. */
+ * Not part of it: separate diffuse / specular filtering, firefly clamping, a denoised accumulator.  Temporal accumulation and reprojection are a pass of their
+ * own: skh_temporal, below; variance guidance (SVGF) is a call of its own: skh_denoise_variance, further below. */
 #define SKH_DENOISE_DEMODULATE 1u
 #define SKH_DENOISE_REMODULATE 2u
 #define SKH_DENOISE_MAX_LEVEL  8u /* first_level + levels <= 8: steps up to 128 */
@@ -760,7 +760,7 @@ skh_status skh_get_denoise_info(skh_context* ctx, skh_denoise_info* out);
  *            max_history not finite or < 1; initial_length not finite, < 1 or > max_history; an albedo_floor that is <= 0 or not finite; a flag bit other than
  *            DEMODULATE; a non-zero reserved word -- and a NULL image that the call needs, and the alias above.
  * Not part of it: object motion (a moved instance loses its history through the plane test; a move smaller than the tolerance ghosts), neighbourhood colour
- * clamping for lighting changes, luminance moments or variance guidance for the spatial filter, separate diffuse / specular histories, what is seen in mirrors
+ * clamping for lighting changes, separate diffuse / specular histories (luminance moments and variance guidance: skh_moments, below), what is seen in mirrors
  * and through glass (the guides describe the first surface). */
 #define SKH_TEMPORAL_DEMODULATE 1u
 
@@ -788,6 +788,86 @@ typedef struct skh_temporal_info
     double ms_last;         /* wall time of the last call, its synchronisation included */
 } skh_temporal_info;
 skh_status skh_get_temporal_info(skh_context* ctx, skh_temporal_info* out);
+
+/* ---- Variance guidance: luminance moments carried through skh_temporal's reprojection, and an a-trous filter whose luminance edge-stop is scaled by the
+ *      local standard deviation (new; DESIGN.md section 2, "Variance guidance").  Schied et al., HPG 2017 (SVGF).  Two pure functions of caller-owned device
+ *      planes (skh_variance.h); records, row order, rounding (every product, sum, quotient and square root one rounded float32 operation, no fma; sqrtf is
+ *      correctly rounded), the fixed summation order, selection of skipped taps, clamped addresses and NaN-failing comparisons are skh_denoise's and
+ *      skh_temporal's.  lum(c) = (0.2126f c.x + 0.7152f c.y) + 0.0722f c.z.  SURFACE is skh_denoise's rule, m its albedo floor rule.
+ *
+ *   skh_moments   MOMENTS record {mu1, mu2, variance, nm}, nm the moments' own history length as a float.  p is the struct given to skh_temporal for this
+ *            frame (checked by skh_temporal_check; normal_min and plane_tolerance are not used); d_color .. d_albedo are the current frame's as handed to
+ *            skh_temporal (the RAW colour, not its output); d_motion is the motion plane that call wrote.
+ *              a pixel that is no surface pixel writes {0, 0, 0, 0}
+ *              l = lum(c), c = C.rgb, or C.rgb / m with SKH_TEMPORAL_DEMODULATE
+ *              with a previous frame (d_motion and d_prev_moments given): fx, fy, PROJECTS, the four taps and their weights are skh_temporal's, recomputed from
+ *              POSITION(p) and p->prev_world_to_clip; mask = (motion.w >= 0 && motion.w <= 15) ? (uint)motion.w : 0.  Tap k is USED iff the pixel projects, bit k
+ *              of mask is set, the tap lies in the image, its weight is > 0, and the previous MOMENTS there has finite mu1, mu2 and a finite nm >= 1.
+ *              with a used tap, in tap order: sw = sum w, m1 = sum (w mu1) / sw, m2 = sum (w mu2) / sw, nh = sum (w nm) / sw, nm' = min(nh + 1, max_history),
+ *              alpha = 1 / nm', mu1' = m1 + (l - m1) alpha, mu2' = m2 + (l l - m2) alpha.  Otherwise mu1' = l, mu2' = l l, nm' = initial_length.
+ *              v = mu2' - mu1' mu1'; variance = v > 0 ? v : 0.
+ *            Refused as skh_temporal refuses, and: d_moments_out == d_prev_moments, or exactly one of d_motion / d_prev_moments NULL.  No scratch, no effect
+ *            on the frame, synchronous on skh_denoise's stream.
+ *
+ *   skh_denoise_variance   skh_denoise with the colour term replaced by a luminance term and the variance filtered along.  d_moments is a MOMENTS plane.
+ *     input variance  v0(p) = z when z = MOMENTS(p).variance is finite and > 0, else 0.  With SKH_VDENOISE_ESTIMATE a surface pixel whose nm is not >= min_history
+ *            takes the spatial estimate instead: over dy = -3 .. 3 outer, dx = -3 .. 3 inner, step 1, the taps that lie in the image, are surface pixels and have
+ *            finite mu1, mu2: w = exp(-(a <= 64 ? a : 64)), a = tn + tp (skh_denoise's normal and plane terms), s0 += w, s1 += w mu1(q), s2 += w mu2(q);
+ *            e1 = s1 / s0, e2 = s2 / s0, v = e2 - e1 e1, v = v > 0 ? v : 0, k = min_history / (nm >= 1 ? nm : 1), v0 = v k.  No used tap gives 0.
+ *     level l  step 1 << l.  For a surface pixel p, from the level's input colour c and variance v:
+ *              vbar(p) = the 3 x 3 Gaussian {1/16, 1/8, 1/16; 1/8, 1/4, 1/8; 1/16, 1/8, 1/16} of v over the surface taps in the image at offsets -1 .. 1 (not
+ *              dilated), dy outer, dx inner: sum (k v(q)) / sum k over the taps taken
+ *              kl = 1 / (sigma_luminance sqrtf(vbar) + epsilon)
+ *              per tap of skh_denoise's 5 x 5: tl = fabsf(lum(c(q)) - lum(c(p))) kl (with sigma_luminance == +inf tl is 0: selected, not computed as inf 0);
+ *              a = (tl + tn) + tp; an a that is not <= 64 counts as 64; w = (h[dx] h[dy]) exp(-a)
+ *              sw += w, sc += w c(q) per channel, sv += (w w) v(q);  out = sc / sw, v_out = sv / (sw sw): the next level's c and v
+ *     flags    DEMODULATE / REMODULATE as in skh_denoise; the variance is in the first level's (demodulated) units throughout and is never remodulated.
+ *            Pixels that are no surface pixels and every alpha word are copied bit for bit.
+ *     d_moments_out  when not NULL: {mu1, mu2, v_out of the last level, nm} on surface pixels, mu1, mu2, nm copied from d_moments; {0, 0, 0, 0} elsewhere.
+ *            Feeding it to the next call without ESTIMATE makes the levels of one call equal chained one-level calls, bit for bit, on both outputs.
+ *            d_out == d_color and d_moments_out == d_moments are allowed.
+ *     refused  what skh_vdenoise_check refuses -- skh_denoise's clauses for the shared fields, an epsilon that is <= 0 or not finite, a min_history that is < 1
+ *            or not finite, an unknown flag bit, a non-zero reserved word -- and a NULL image that the call needs, d_moments among them.
+ *     cost     the scratch is skh_denoise's allocation (56 bytes per pixel, the variance rides in the colour record's fourth word): both calls grow it, both free
+ *            it with params == NULL, skh_get_denoise_info and skh_get_vdenoise_info report the same bytes.
+ * Not part of it: separate diffuse / specular histories, neighbourhood colour clamping, feeding the first level's output back into the history, variance for a
+ * still camera's accumulator, multi-rank handling beyond "rank 0 on the gathered image". */
+#define SKH_VDENOISE_ESTIMATE 4u
+
+skh_status skh_moments(skh_context* ctx, const skh_temporal_params* p, const void* d_color, const void* d_ids, const void* d_position, const void* d_albedo,
+                       const void* d_motion /* NULL = no previous frame */, const void* d_prev_moments /* NULL = no previous frame */, void* d_moments_out);
+typedef struct skh_moments_info
+{
+    uint64_t calls, pixels; /* since the last skh_reset_stats */
+    double ms_last;         /* wall time of the last call, its synchronisation included */
+} skh_moments_info;
+skh_status skh_get_moments_info(skh_context* ctx, skh_moments_info* out);
+
+typedef struct skh_vdenoise_params
+{
+    uint32_t width, height;       /* as skh_denoise_params */
+    uint32_t first_level, levels; /* as skh_denoise_params */
+    float sigma_luminance;        /* > 0 (+inf: the term is off); in standard deviations of the luminance */
+    float sigma_normal;           /* > 0 (+inf: off) */
+    float sigma_plane;            /* > 0 (+inf: off); scene units */
+    float albedo_floor;           /* finite, > 0 */
+    float epsilon;                /* finite, > 0; luminance units */
+    float min_history;            /* finite, >= 1 */
+    uint32_t flags;               /* SKH_DENOISE_DEMODULATE | SKH_DENOISE_REMODULATE | SKH_VDENOISE_ESTIMATE */
+    uint32_t reserved[5];         /* 0 */
+} skh_vdenoise_params;
+
+/* SKH_OK when *p is a setting skh_denoise_variance accepts (needs no context and no GPU, as skh_denoise_check) */
+skh_status skh_vdenoise_check(const skh_vdenoise_params* p);
+skh_status skh_denoise_variance(skh_context* ctx, const skh_vdenoise_params* p, const void* d_color, const void* d_ids, const void* d_normal,
+                                const void* d_position, const void* d_albedo, const void* d_moments, void* d_out, void* d_moments_out /* may be NULL */);
+typedef struct skh_vdenoise_info
+{
+    uint64_t calls, pixels;  /* since the last skh_reset_stats */
+    double ms_last;          /* wall time of the last call, its synchronisation included */
+    uint64_t scratch_bytes;  /* device bytes the context holds for the filter now (skh_denoise_info's) */
+} skh_vdenoise_info;
+skh_status skh_get_vdenoise_info(skh_context* ctx, skh_vdenoise_info* out);
 
 /* ---- the tonemap() + gammaCorrection post pass (postprocessing/Tonemappers.cu:111-135), in place on a
  *      device float4 image.  type: 0 none, 1 Reinhard, 2 ACES fitted, 3 ACES film; gamma <= 0 = off ---- */

@@ -259,14 +259,14 @@ void HipRender::freeGuides()
             skh_buffer_free(mCtx, g);
         g = nullptr;
     }
-    for (void** g : { &mPrevGuide[0], &mPrevGuide[1], &mPrevGuide[2], &mHistory[0], &mHistory[1] })
+    for (void** g : { &mPrevGuide[0], &mPrevGuide[1], &mPrevGuide[2], &mHistory[0], &mHistory[1], &mVarianceImage, &mMotion, &mMoments[0], &mMoments[1] })
     {
         if (mCtx && *g)
             skh_buffer_free(mCtx, *g);
         *g = nullptr;
     }
     mGuideWidth = mGuideHeight = 0;
-    mGuidesValid = mPrevGuidesValid = mHistoryValid = false;
+    mGuidesValid = mPrevGuidesValid = mHistoryValid = mMomentsValid = false;
 }
 
 bool HipRender::setDenoiser(bool on, const HipDenoise* params)
@@ -317,6 +317,32 @@ bool HipRender::setTemporal(bool on, const HipTemporal* params)
         mGuidesValid = false; // (the buffers this feature adds come with the next guide pass)
     mTemporal = true;
     mTemporalSetting = t;
+    return true;
+}
+
+bool HipRender::setVarianceGuidance(bool on, const HipVariance* params)
+{
+    const HipVariance v = params ? *params : HipVariance();
+    // (checked here with an image, an exposure and a scene that pass: the real ones are render()'s)
+    const float one[3] = { 1.0f, 1.0f, 1.0f };
+    const skh_vdenoise_params probe = hipVarianceParams(v, HipDenoise(), 1u, 1u, one, 1.0f);
+    if (on && skh_vdenoise_check(&probe) != SKH_OK)
+    {
+        mError = "setVarianceGuidance: the setting was refused (a positive sigmaLuminance, finite positive epsilon, finite minHistory >= 1)";
+        return false;
+    }
+    mMomentsValid = false; // (moments kept under another setting are not this one's)
+    memset(&mVarianceApplied, 0, sizeof(mVarianceApplied));
+    mVariance = on;
+    if (on)
+        mVarianceSetting = v;
+    else
+        for (void** g : { &mVarianceImage, &mMotion, &mMoments[0], &mMoments[1] })
+        {
+            if (mCtx && *g)
+                skh_buffer_free(mCtx, *g);
+            *g = nullptr;
+        }
     return true;
 }
 
@@ -803,7 +829,40 @@ void HipRender::render(Buffer* output)
             check(skh_scatter_tiles(mCtx, mGatherBuf, mAllTileXY.data(), (uint32_t)(mAllTileXY.size() / 2), mTileSize, dImage, width, height),
                   "skh_scatter_tiles");
     }
-    if (temporalFrame && mGuidesValid)
+    // variance guidance replaces this call's skh_temporal + skh_denoise pair by skh_temporal + skh_moments + skh_denoise_variance: only with both features on, only
+    // on a call that starts an accumulation, and only once its four buffers exist
+    bool guided = mVariance && temporalFrame && denoiseFrame && mGuidesValid && startCall;
+    if (guided && !mVarianceImage)
+        for (void** g : { &mVarianceImage, &mMotion, &mMoments[0], &mMoments[1] })
+            guided = guided && check(skh_buffer_alloc(mCtx, (size_t)16 * width * height, g), "skh_buffer_alloc");
+    if (guided)
+    {
+        const int next = 1 - mHistoryStored, nextMoments = 1 - mMomentsStored;
+        const bool had = mHistoryValid && mPrevGuidesValid, hadMoments = had && mMomentsValid;
+        const skh_temporal_params tp = hipTemporalParams(mTemporalSetting, width, height, had ? mPrevWorldToClip : nullptr, 1.0f, mSceneDiagonal);
+        const skh_vdenoise_params vp = hipVarianceParams(mVarianceSetting, mDenoiseSetting, width, height, p.exposure, mSceneDiagonal);
+        // the blended image goes to this object's buffer: the output image keeps the raw sample for skh_moments, then takes the filtered result
+        if (check(skh_temporal(mCtx, &tp, dImage, mGuide[0], mGuide[1], mGuide[2], mGuide[3], had ? mHistory[mHistoryStored] : nullptr, mPrevGuide[0], mPrevGuide[1],
+                               mPrevGuide[2], mVarianceImage, mHistory[next], mMotion),
+                  "skh_temporal"))
+        {
+            mHistoryStored = next, mHistoryValid = true;
+            mTemporalApplied = tp, mTemporalHadPrevious = had;
+            if (check(skh_moments(mCtx, &tp, dImage, mGuide[0], mGuide[2], mGuide[3], hadMoments ? mMotion : nullptr, hadMoments ? mMoments[mMomentsStored] : nullptr,
+                                  mMoments[nextMoments]),
+                      "skh_moments"))
+            {
+                mMomentsStored = nextMoments, mMomentsValid = true;
+                mMomentsHadPrevious = hadMoments;
+                if (check(skh_denoise_variance(mCtx, &vp, mVarianceImage, mGuide[0], mGuide[1], mGuide[2], mGuide[3], mMoments[mMomentsStored], dImage, nullptr),
+                          "skh_denoise_variance"))
+                    mVarianceApplied = vp;
+            }
+            else
+                mMomentsValid = false;
+        }
+    }
+    if (!guided && temporalFrame && mGuidesValid)
     {
         // the output image -- linear here --; the accumulator is not touched
         const int next = 1 - mHistoryStored;
@@ -835,7 +894,7 @@ void HipRender::render(Buffer* output)
             }
         }
     }
-    if (denoiseFrame && mGuidesValid)
+    if (!guided && denoiseFrame && mGuidesValid)
     {
         // the output image -- linear here --, in place; the accumulator is not touched
         const skh_denoise_params dn = hipDenoiseParams(mDenoiseSetting, width, height, p.exposure, mSceneDiagonal);

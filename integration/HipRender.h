@@ -114,6 +114,30 @@ inline skh_temporal_params hipTemporalParams(const HipTemporal& t, uint32_t widt
     return p;
 }
 
+struct HipVariance // HipRender::setVarianceGuidance: a field that is 0 (or negative) takes its default
+{
+    float sigmaLuminance = 0.0f; // 0.25: the luminance term is 1 at a quarter of the local per-sample standard deviation (docs/LOG.md has the table)
+    float epsilon = 0.0f;        // luminance; default: 0.01 / the mean of the frame's three exposure factors -- a hundredth of HipDenoise's default sigmaColor
+    float minHistory = 0.0f;     // 4: moments younger than this take the spatial estimate
+};
+
+// the skh_vdenoise_params render() hands to skh_denoise_variance: the levels, sigmaNormal, sigmaPlane and albedoFloor of the HipDenoise setting (hipDenoiseParams'
+// defaults), the three fields of the HipVariance setting, all three flags
+inline skh_vdenoise_params hipVarianceParams(const HipVariance& v, const HipDenoise& d, uint32_t width, uint32_t height, const float exposure[3], float sceneDiagonal)
+{
+    const skh_denoise_params dn = hipDenoiseParams(d, width, height, exposure, sceneDiagonal);
+    skh_vdenoise_params p = {};
+    p.width = width, p.height = height;
+    p.first_level = dn.first_level, p.levels = dn.levels;
+    p.sigma_luminance = v.sigmaLuminance > 0.0f ? v.sigmaLuminance : 0.25f;
+    p.sigma_normal = dn.sigma_normal, p.sigma_plane = dn.sigma_plane, p.albedo_floor = dn.albedo_floor;
+    const float meanExposure = (exposure[0] + exposure[1] + exposure[2]) / 3.0f;
+    p.epsilon = v.epsilon > 0.0f ? v.epsilon : 0.01f / meanExposure;
+    p.min_history = v.minHistory > 0.0f ? v.minHistory : 4.0f;
+    p.flags = SKH_DENOISE_DEMODULATE | SKH_DENOISE_REMODULATE | SKH_VDENOISE_ESTIMATE;
+    return p;
+}
+
 class HipRender : public Render
 {
 public:
@@ -222,6 +246,21 @@ public:
             *hadPrevious = mTemporalHadPrevious;
         return mTemporalApplied.width != 0u;
     }
+    // Variance guidance (skh_moments + skh_denoise_variance; new), OFF by default.  It acts only when setTemporal and setDenoiser are both on, and only on a call
+    // that starts an accumulation (a moving camera's frame).  On such a call skh_temporal writes into an image buffer of this object, with a motion buffer of this
+    // object; skh_moments then runs on the raw output image; skh_denoise_variance filters from the object's buffer into the output image with all three flags, in
+    // skh_denoise's place.  Two moments buffers change places as the histories do and are dropped whenever the history is.  A call that continues an accumulation
+    // makes exactly the calls it makes without the setting and leaves the moments alone.  params == nullptr: every default.  false: the setting was refused
+    // (skh_vdenoise_check; the previous one stays).  With it off, render() makes the calls it made before.
+    bool setVarianceGuidance(bool on, const HipVariance* params = nullptr);
+    // what the last guided render() handed to skh_denoise_variance (false: none yet); hadPrevious: whether that call's skh_moments had previous moments
+    bool varianceParams(skh_vdenoise_params& p, bool* hadPrevious = nullptr) const
+    {
+        p = mVarianceApplied;
+        if (hadPrevious)
+            *hadPrevious = mMomentsHadPrevious;
+        return mVarianceApplied.width != 0u;
+    }
     // the frame parameters' sample choice of the last render(): subframe_index and enable_accumulation as handed to skh_render_subframe
     void lastSample(uint32_t& subframeIndex, uint32_t& enableAccumulation) const
     {
@@ -280,9 +319,19 @@ private:
     uint32_t mRotation = 0;    // moving start calls so far (rotateSamples)
     bool mRendered = false;    // a render() has been made: mPrevView is a camera
     uint32_t mLastSubframeIndex = 0, mLastEnableAccumulation = 0;
+    bool mVariance = false;
+    HipVariance mVarianceSetting;
+    skh_vdenoise_params mVarianceApplied = {};
+    bool mMomentsHadPrevious = false;
+    void* mVarianceImage = nullptr; // skh_temporal's image output on a guided call: skh_denoise_variance's input
+    void* mMotion = nullptr;        // skh_temporal's motion plane on a guided call
+    void* mMoments[2] = {};         // {mu1, mu2, variance, nm} per pixel; mMoments[mMomentsStored] is the stored one
+    int mMomentsStored = 0;
+    bool mMomentsValid = false;     // false: the next guided call has no previous moments
     void dropHistory()
     {
         mHistoryValid = false;
+        mMomentsValid = false;
     }
     void uploadMaterials(); // MaterialDescription list -> skh_material blocks + textures (OptixRender.cpp:1270-1433)
 };

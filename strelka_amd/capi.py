@@ -35,7 +35,8 @@ SYMBOLS = ["skh_create", "skh_destroy", "skh_last_error", "skh_abi_version", "sk
            "skh_adaptive_check", "skh_set_adaptive", "skh_get_adaptive_info", "skh_read_adaptive",
            "skh_aov_check", "skh_render_aovs", "skh_get_aov_info",
            "skh_denoise_check", "skh_denoise", "skh_get_denoise_info", "skh_buffer_upload",
-           "skh_temporal_check", "skh_temporal", "skh_get_temporal_info"]
+           "skh_temporal_check", "skh_temporal", "skh_get_temporal_info",
+           "skh_moments", "skh_get_moments_info", "skh_vdenoise_check", "skh_denoise_variance", "skh_get_vdenoise_info"]
 
 BUILD_INFO = np.dtype([("triangles", np.uint32), ("nodes", np.uint32), ("reinsert_rounds", np.uint32), ("reinsert_moves", np.uint32),
                        ("reinsert_min_size", np.uint32), ("refit", np.uint32), ("cost_before", np.float64), ("cost_after", np.float64),
@@ -62,6 +63,10 @@ DENOISE_GUIDES = ("ids", "normal", "position", "albedo")  # the planes skh_denoi
 TEMPORAL_INFO = np.dtype([("calls", np.uint64), ("pixels", np.uint64), ("ms_last", np.float64)])
 assert TEMPORAL_INFO.itemsize == 24
 TEMPORAL_PREV = ("history", "ids", "normal", "position")  # the previous-frame images skh_temporal reads, in its argument order
+MOMENTS_INFO = np.dtype([("calls", np.uint64), ("pixels", np.uint64), ("ms_last", np.float64)])
+assert MOMENTS_INFO.itemsize == 24
+VDENOISE_INFO = np.dtype([("calls", np.uint64), ("pixels", np.uint64), ("ms_last", np.float64), ("scratch_bytes", np.uint64)])
+assert VDENOISE_INFO.itemsize == 32
 # skh_light_shape_probe: kind -> (number, words in, words out) per record
 LSHAPE_PROBES = {"sample": (0, 6, 13), "pdf": (1, 7, 2)}
 # skh_emitter_probe: kind -> (number, words in, words out) per record
@@ -141,6 +146,11 @@ def load():
     lib.skh_temporal_check.argtypes = [vp]
     lib.skh_temporal.argtypes = [vp] * 14
     lib.skh_get_temporal_info.argtypes = [vp, vp]
+    lib.skh_moments.argtypes = [vp] * 9
+    lib.skh_get_moments_info.argtypes = [vp, vp]
+    lib.skh_vdenoise_check.argtypes = [vp]
+    lib.skh_denoise_variance.argtypes = [vp] * 10
+    lib.skh_get_vdenoise_info.argtypes = [vp, vp]
     lib.skh_buffer_upload.argtypes = [vp, vp, vp, C.c_size_t]
     lib.skh_resize.argtypes = [vp, u32, u32]
     lib.skh_set_tiles.argtypes = [vp, u32, vp, u32]
@@ -211,6 +221,17 @@ def temporal_check(params):
     """skh_temporal_check: would skh_temporal accept these S.TEMPORAL_PARAMS?  (needs no context and no GPU)"""
     p = np.ascontiguousarray(params, dtype=S.TEMPORAL_PARAMS)
     return load().skh_temporal_check(_p(p)) == 0
+
+
+def moments_check(params):
+    """would skh_moments accept these S.TEMPORAL_PARAMS?  It takes the struct skh_temporal took, and skh_temporal_check is its check."""
+    return temporal_check(params)
+
+
+def vdenoise_check(params):
+    """skh_vdenoise_check: would skh_denoise_variance accept these S.VDENOISE_PARAMS?  (needs no context and no GPU)"""
+    p = np.ascontiguousarray(params, dtype=S.VDENOISE_PARAMS)
+    return load().skh_vdenoise_check(_p(p)) == 0
 
 
 def adaptive_dark_level(radiance, exposure):
@@ -622,6 +643,77 @@ class Context:
         d = np.zeros((), TEMPORAL_INFO)
         self._ck(self.lib.skh_get_temporal_info(self.h, _p(d)), "skh_get_temporal_info")
         return {k: (float(d[k]) if d[k].dtype.kind == "f" else int(d[k])) for k in TEMPORAL_INFO.names}
+
+    def _info(self, fn, dtype):
+        d = np.zeros((), dtype)
+        self._ck(getattr(self.lib, fn)(self.h, _p(d)), fn)
+        return {k: (float(d[k]) if d[k].dtype.kind == "f" else int(d[k])) for k in dtype.names}
+
+    def _with_planes(self, planes, h, w, outputs, call):
+        """uploads the (h, w, 4) arrays of `planes` (None entries are left out), allocates `outputs`, runs call(bufs) and downloads the outputs as float32"""
+        planes = {n: a for n, a in planes.items() if a is not None}
+        for n, a in planes.items():
+            if a.shape != (h, w, 4):
+                raise ValueError(f"{n} must be ({h}, {w}, 4)")
+        bufs = {}
+        try:
+            for n, a in planes.items():
+                bufs[n] = self.buffer_alloc(a.nbytes)
+                self.buffer_upload(bufs[n], a)
+            for n in outputs:
+                bufs[n] = self.buffer_alloc(16 * h * w)
+            call(bufs)
+            out = {}
+            for n in outputs:
+                out[n] = np.zeros((h, w, 4), np.float32)
+                self.buffer_download(bufs[n], out[n])
+            return out
+        finally:
+            for d in bufs.values():
+                self.buffer_free(d)
+
+    def moments_device(self, params, d_color, d_ids, d_position, d_albedo, d_motion, d_prev_moments, d_moments_out):
+        """skh_moments on caller-owned device images: `params` the S.TEMPORAL_PARAMS skh_temporal took for this frame, d_color the RAW colour it took, d_motion the
+        motion plane it wrote; d_motion and d_prev_moments both None = no previous frame; d_albedo may be None without DEMODULATE"""
+        p = np.ascontiguousarray(params, dtype=S.TEMPORAL_PARAMS)
+        self._ck(self.lib.skh_moments(self.h, _p(p), d_color, d_ids, d_position, d_albedo, d_motion, d_prev_moments, d_moments_out), "skh_moments")
+
+    def moments(self, image, guides, motion, prev_moments, params):
+        """skh_moments, numpy in and numpy out: `image` the raw (h, w, 4) colour, `guides` {"ids", "position", "albedo"} of the current frame, `motion` the motion plane
+        temporal() returned and `prev_moments` the previous MOMENTS plane (both None: no previous frame), `params` S.temporal_params -> (h, w, 4) float32 MOMENTS"""
+        p = np.array(params, dtype=S.TEMPORAL_PARAMS)
+        h, w = int(p["height"]), int(p["width"])
+        f32 = lambda a: None if a is None else np.ascontiguousarray(a, np.float32)
+        planes = {"color": f32(image), "ids": None if guides.get("ids") is None else np.ascontiguousarray(guides["ids"], np.uint32),
+                  "position": f32(guides.get("position")), "albedo": f32(guides.get("albedo")), "motion": f32(motion), "prev_moments": f32(prev_moments)}
+        return self._with_planes(planes, h, w, ("moments",), lambda b: self.moments_device(
+            p, b.get("color"), b.get("ids"), b.get("position"), b.get("albedo"), b.get("motion"), b.get("prev_moments"), b["moments"]))["moments"]
+
+    def moments_info(self):
+        """skh_get_moments_info: calls and pixels since the last reset_stats, the last call's wall time"""
+        return self._info("skh_get_moments_info", MOMENTS_INFO)
+
+    def denoise_variance_device(self, params, d_color, d_ids, d_normal, d_position, d_albedo, d_moments, d_out, d_moments_out=None):
+        """skh_denoise_variance on caller-owned device images (d_out may be d_color, d_moments_out may be d_moments or None; d_albedo may be None when neither
+        modulation flag is set); params None frees the scratch"""
+        p = None if params is None else np.ascontiguousarray(params, dtype=S.VDENOISE_PARAMS)
+        self._ck(self.lib.skh_denoise_variance(self.h, _p(p), d_color, d_ids, d_normal, d_position, d_albedo, d_moments, d_out, d_moments_out), "skh_denoise_variance")
+
+    def denoise_variance(self, image, guides, moments, params, moments_out=True):
+        """skh_denoise_variance, numpy in and numpy out: `image` and `guides` as denoise(), `moments` an (h, w, 4) MOMENTS plane, `params` S.vdenoise_params ->
+        {"image", "moments"} ((h, w, 4) float32; without `moments_out` the call gets no d_moments_out and "moments" is missing)"""
+        p = np.array(params, dtype=S.VDENOISE_PARAMS)
+        h, w = int(p["height"]), int(p["width"])
+        f32 = lambda a: None if a is None else np.ascontiguousarray(a, np.float32)
+        planes = {"color": f32(image), "ids": None if guides.get("ids") is None else np.ascontiguousarray(guides["ids"], np.uint32),
+                  "normal": f32(guides.get("normal")), "position": f32(guides.get("position")), "albedo": f32(guides.get("albedo")), "moments_in": f32(moments)}
+        outputs = ("image", "moments") if moments_out else ("image",)
+        return self._with_planes(planes, h, w, outputs, lambda b: self.denoise_variance_device(
+            p, b.get("color"), b.get("ids"), b.get("normal"), b.get("position"), b.get("albedo"), b.get("moments_in"), b["image"], b.get("moments")))
+
+    def vdenoise_info(self):
+        """skh_get_vdenoise_info: calls and pixels since the last reset_stats, the last call's wall time, the scratch bytes the context holds (the denoiser's)"""
+        return self._info("skh_get_vdenoise_info", VDENOISE_INFO)
 
     def render_subframe(self, params, d_image=None):
         p = np.ascontiguousarray(params, dtype=S.FRAME_PARAMS)

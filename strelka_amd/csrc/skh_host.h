@@ -405,6 +405,16 @@ struct skh_context
     {
         skh_temporal_info info = {};
     } tp;
+
+    // variance guidance (skh_moments, skh_denoise_variance; skh_variance.h): the filter's scratch is the denoiser's, nothing but this lives between two calls
+    struct Moments
+    {
+        skh_moments_info info = {};
+    } mo;
+    struct VarianceDenoiser
+    {
+        skh_vdenoise_info info = {};
+    } vd;
 };
 
 // A caller changed `in`: every derived state that depends on it is invalidated (the table: skh_stale.h).

@@ -39,6 +39,7 @@ static_assert(sizeof(skh_hit) == 20 && sizeof(Light) == 112 && sizeof(Material) 
 #include "skh_aov.h"
 #include "skh_denoise.h"
 #include "skh_temporal.h"
+#include "skh_variance.h"
 
 // Sobol generator matrices for the 5 dimensions the reference tabulates (RandomSampler.h:139-164), produced from the
 // Joe-Kuo recurrences (d=2: s=1 a=0 m={1}; d=3: s=2 a=1 m={1,3}; d=4: s=3 a=1 m={1,3,1}; d=5: s=3 a=2 m={1,1,1}).
@@ -3098,6 +3099,160 @@ skh_status skh_get_temporal_info(skh_context* c, skh_temporal_info* out)
     return SKH_OK;
 }
 
+// ---- variance guidance (skh_variance.h): skh_moments, skh_get_moments_info, skh_vdenoise_check, skh_denoise_variance, skh_get_vdenoise_info ----
+static_assert(sizeof(skh_moments_info) == 24 && sizeof(skh_vdenoise_params) == 64 && sizeof(skh_vdenoise_info) == 32, "ABI layout");
+
+skh_status skh_moments(skh_context* c, const skh_temporal_params* p, const void* d_color, const void* d_ids, const void* d_position, const void* d_albedo,
+                       const void* d_motion, const void* d_prev_moments, void* d_moments_out)
+{
+    if (!c)
+        return SKH_INVALID_ARGUMENT;
+    (void)hipSetDevice(c->dev.device);
+    const char* why = temporal_refusal(p);
+    if (!why && (!d_color || !d_ids || !d_position || !d_moments_out))
+        why = "a NULL image";
+    if (!why && (p->flags & SKH_TEMPORAL_DEMODULATE) && !d_albedo)
+        why = "a flag that needs the albedo plane, and no albedo plane";
+    if (!why && (d_motion == nullptr) != (d_prev_moments == nullptr))
+        why = "exactly one of d_motion and d_prev_moments";
+    if (!why && d_prev_moments && d_moments_out == d_prev_moments)
+        why = "d_moments_out == d_prev_moments (taps read neighbours)";
+    if (why)
+    {
+        c->dev.err = std::string("skh_moments: ") + why;
+        return SKH_INVALID_ARGUMENT;
+    }
+    const auto t0 = std::chrono::steady_clock::now();
+    const size_t n = (size_t)p->width * p->height;
+    hipStream_t st = side_stream(c); // (skh_temporal's stream)
+    TpP tp;
+    tp.width = p->width, tp.height = p->height;
+    for (int k = 0; k < 16; ++k)
+        tp.prevWorldToClip[k] = p->prev_world_to_clip[k];
+    tp.normalMin = p->normal_min, tp.planeTolerance = p->plane_tolerance, tp.maxHistory = p->max_history, tp.initialLength = p->initial_length;
+    tp.albedoFloor = p->albedo_floor, tp.flags = p->flags, tp.hasPrev = d_prev_moments ? 1u : 0u;
+    const dim3 grid(((p->width + 63u) / 64u) * ((p->height + 3u) / 4u)), block(64, 4);
+    k_vr_moments<<<grid, block, 0, st>>>(tp, reinterpret_cast<const float4*>(d_color), reinterpret_cast<const uint4*>(d_ids),
+                                         reinterpret_cast<const float4*>(d_position), reinterpret_cast<const float4*>(d_albedo),
+                                         reinterpret_cast<const float4*>(d_motion), reinterpret_cast<const float4*>(d_prev_moments),
+                                         reinterpret_cast<float4*>(d_moments_out));
+    SKH_TRY(c, hipGetLastError());
+    SKH_TRY(c, hipStreamSynchronize(st));
+    c->mo.info.calls++;
+    c->mo.info.pixels += n;
+    c->mo.info.ms_last = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    return SKH_OK;
+}
+
+skh_status skh_get_moments_info(skh_context* c, skh_moments_info* out)
+{
+    if (!c || !out)
+        return SKH_INVALID_ARGUMENT;
+    *out = c->mo.info;
+    return SKH_OK;
+}
+
+// why *p is refused, or nullptr
+static const char* vdenoise_refusal(const skh_vdenoise_params* p)
+{
+    if (!p)
+        return "no parameters";
+    if (p->width == 0u || p->height == 0u || (uint64_t)p->width * p->height > (1ull << 26))
+        return "an empty image, or one of more than 2^26 pixels";
+    if (p->levels == 0u || p->first_level > SKH_DENOISE_MAX_LEVEL || p->levels > SKH_DENOISE_MAX_LEVEL || p->first_level + p->levels > SKH_DENOISE_MAX_LEVEL)
+        return "no level, or a level beyond first_level + levels <= 8";
+    for (float s : { p->sigma_luminance, p->sigma_normal, p->sigma_plane })
+        if (!(s > 0.0f)) // (a NaN too)
+            return "a sigma that is <= 0 or NaN";
+    if (!std::isfinite(p->albedo_floor) || !(p->albedo_floor > 0.0f))
+        return "an albedo_floor that is <= 0 or not finite";
+    if (!std::isfinite(p->epsilon) || !(p->epsilon > 0.0f))
+        return "an epsilon that is <= 0 or not finite";
+    if (!std::isfinite(p->min_history) || !(p->min_history >= 1.0f))
+        return "a min_history that is < 1 or not finite";
+    if (p->flags & ~(SKH_DENOISE_DEMODULATE | SKH_DENOISE_REMODULATE | SKH_VDENOISE_ESTIMATE))
+        return "an unknown flag bit";
+    for (uint32_t r : p->reserved)
+        if (r != 0u)
+            return "a non-zero reserved word";
+    return nullptr;
+}
+
+skh_status skh_vdenoise_check(const skh_vdenoise_params* p)
+{
+    return vdenoise_refusal(p) ? SKH_INVALID_ARGUMENT : SKH_OK;
+}
+
+skh_status skh_denoise_variance(skh_context* c, const skh_vdenoise_params* p, const void* d_color, const void* d_ids, const void* d_normal,
+                                const void* d_position, const void* d_albedo, const void* d_moments, void* d_out, void* d_moments_out)
+{
+    if (!c)
+        return SKH_INVALID_ARGUMENT;
+    if (!p) // free the scratch: skh_denoise's
+        return skh_denoise(c, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr);
+    (void)hipSetDevice(c->dev.device);
+    const char* why = vdenoise_refusal(p);
+    if (!why && (!d_color || !d_ids || !d_normal || !d_position || !d_moments || !d_out))
+        why = "a NULL image";
+    if (!why && (p->flags & (SKH_DENOISE_DEMODULATE | SKH_DENOISE_REMODULATE)) && !d_albedo)
+        why = "a flag that needs the albedo plane, and no albedo plane";
+    if (why)
+    {
+        c->dev.err = std::string("skh_denoise_variance: ") + why;
+        return SKH_INVALID_ARGUMENT;
+    }
+    const auto t0 = std::chrono::steady_clock::now();
+    const size_t n = (size_t)p->width * p->height;
+    const uint32_t est = (p->flags & SKH_VDENOISE_ESTIMATE) ? 1u : 0u;
+    SKH_CHECK(dev_alloc(c, c->dn.dColor[0], 16 * n));
+    if (p->levels + est > 1u)
+        SKH_CHECK(dev_alloc(c, c->dn.dColor[1], 16 * n));
+    SKH_CHECK(dev_alloc(c, c->dn.dG0, 16 * n));
+    SKH_CHECK(dev_alloc(c, c->dn.dG1, 8 * n));
+    hipStream_t st = side_stream(c);
+    VrP vp;
+    vp.width = p->width, vp.height = p->height, vp.step = 1u;
+    vp.lumOff = std::isinf(p->sigma_luminance) ? 1u : 0u;
+    vp.sigmaLuminance = vp.lumOff ? 0.0f : p->sigma_luminance, vp.epsilon = p->epsilon;
+    vp.kn = 1.0f / (p->sigma_normal * p->sigma_normal), vp.kp = 1.0f / (p->sigma_plane * p->sigma_plane);
+    vp.albedoFloor = p->albedo_floor, vp.minHistory = p->min_history, vp.flags = p->flags;
+    const float4* g0 = c->dn.dG0.as<float4>();
+    const float2* g1 = c->dn.dG1.as<float2>();
+    const float4* mom = reinterpret_cast<const float4*>(d_moments);
+    k_vr_pack<<<(uint32_t)((n + 255) / 256), 256, 0, st>>>(vp, reinterpret_cast<const float4*>(d_color), reinterpret_cast<const uint4*>(d_ids),
+                                                          reinterpret_cast<const float4*>(d_normal), reinterpret_cast<const float4*>(d_position),
+                                                          reinterpret_cast<const float4*>(d_albedo), mom, c->dn.dColor[0].as<float4>(), c->dn.dG0.as<float4>(),
+                                                          c->dn.dG1.as<float2>());
+    const dim3 grid(((p->width + 63u) / 64u) * ((p->height + 3u) / 4u)), block(64, 4); // (<= 2^24 + 2^20 tiles of 64 x 4 pixels, row-major)
+    if (est)
+        k_vr_estimate<<<grid, block, 0, st>>>(vp, c->dn.dColor[0].as<float4>(), g0, g1, mom, c->dn.dColor[1].as<float4>());
+    for (uint32_t k = 0; k < p->levels; ++k)
+    {
+        vp.step = 1u << (p->first_level + k);
+        const float4* cin = c->dn.dColor[(k + est) & 1u].as<float4>();
+        if (k + 1u < p->levels)
+            k_vr_level<false><<<grid, block, 0, st>>>(vp, cin, g0, g1, c->dn.dColor[(k + est + 1u) & 1u].as<float4>(), nullptr, nullptr, nullptr, nullptr, nullptr);
+        else
+            k_vr_level<true><<<grid, block, 0, st>>>(vp, cin, g0, g1, nullptr, reinterpret_cast<const uint4*>(d_color), reinterpret_cast<const float4*>(d_albedo),
+                                                    reinterpret_cast<uint4*>(d_out), mom, reinterpret_cast<float4*>(d_moments_out));
+    }
+    SKH_TRY(c, hipGetLastError());
+    SKH_TRY(c, hipStreamSynchronize(st));
+    c->vd.info.calls++;
+    c->vd.info.pixels += n;
+    c->vd.info.ms_last = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    return SKH_OK;
+}
+
+skh_status skh_get_vdenoise_info(skh_context* c, skh_vdenoise_info* out)
+{
+    if (!c || !out)
+        return SKH_INVALID_ARGUMENT;
+    *out = c->vd.info;
+    out->scratch_bytes = denoise_scratch_bytes(c);
+    return SKH_OK;
+}
+
 // ---- skh_set_option: one row per name ----
 // What setting an option costs beyond the store.  OPT_REBUILD: a hierarchy depends on it -- the build is invalidated, and with it skh_update_accel's in-place
 // path (include/strelka_hip.h).  OPT_FRAME: the frame's buffers are sized by it -- they are allocated again when a frame exists.
@@ -3361,6 +3516,8 @@ skh_status skh_reset_stats(skh_context* c)
     c->aov.info.calls = c->aov.info.rays = 0;
     c->dn.info.calls = c->dn.info.pixels = 0;
     c->tp.info.calls = c->tp.info.pixels = 0;
+    c->mo.info.calls = c->mo.info.pixels = 0;
+    c->vd.info.calls = c->vd.info.pixels = 0;
     for (int k = 0; k < KC_COUNT; ++k)
     {
         c->timing.msClass[k] = 0.0;

@@ -725,6 +725,62 @@ def temporal_params(width, height, prev_aov_params=None, normal_min=TEMPORAL_NOR
     return p
 
 
+VDENOISE_PARAMS = np.dtype([("width", np.uint32), ("height", np.uint32), ("first_level", np.uint32), ("levels", np.uint32), ("sigma_luminance", np.float32),
+                            ("sigma_normal", np.float32), ("sigma_plane", np.float32), ("albedo_floor", np.float32), ("epsilon", np.float32),
+                            ("min_history", np.float32), ("flags", np.uint32), ("reserved", np.uint32, 5)])  # skh_vdenoise_params, 64 B
+assert VDENOISE_PARAMS.itemsize == 64
+VDENOISE_ESTIMATE = 4
+# the defaults of vdenoise_params (DESIGN.md section 2 "Variance guidance" gives the reasons)
+VDENOISE_SIGMA_LUMINANCE = 0.25   # the luminance term is 1 at a quarter of the local per-sample standard deviation: the best on the Cornell orbit (docs/LOG.md); Schied et al. use 4
+VDENOISE_MIN_HISTORY = 4.0        # moments younger than this take the spatial estimate
+VDENOISE_EPSILON_FRACTION = 1e-2  # epsilon as a fraction of the image's mean demodulated luminance
+
+
+def luminance(c):
+    c = np.asarray(c, np.float64)
+    return 0.2126 * c[..., 0] + 0.7152 * c[..., 1] + 0.0722 * c[..., 2]
+
+
+def vdenoise_epsilon(image, guides=None, albedo_floor=DENOISE_ALBEDO_FLOOR, demodulate=True):
+    """the default epsilon for an (h, w, 4) image: VDENOISE_EPSILON_FRACTION x the mean luminance of the filter's first-level input over the pixels it works on
+    (denoise_sigma_color's selection of pixels and units)"""
+    with np.errstate(invalid="ignore"):
+        c = np.asarray(image, np.float64)[..., :3]
+    ok = np.isfinite(c).all(axis=-1)
+    if guides is not None and guides.get("ids") is not None:
+        kind = np.asarray(guides["ids"])[..., 3]
+        ok &= (kind == 1) | (kind == 2)
+    if demodulate and guides is not None and guides.get("albedo") is not None:
+        a = np.asarray(guides["albedo"], np.float64)[..., :3]
+        with np.errstate(all="ignore"):
+            c = c / np.where(a > albedo_floor, a, albedo_floor)
+    level = float(np.abs(luminance(c[ok])).mean()) if ok.any() else 0.0
+    return VDENOISE_EPSILON_FRACTION * level if level > 0.0 and np.isfinite(level) else VDENOISE_EPSILON_FRACTION
+
+
+def vdenoise_params(width, height, levels=5, sigma_luminance=VDENOISE_SIGMA_LUMINANCE, sigma_normal=DENOISE_SIGMA_NORMAL, sigma_plane=None, first_level=0,
+                    albedo_floor=DENOISE_ALBEDO_FLOOR, epsilon=None, min_history=VDENOISE_MIN_HISTORY, demodulate=True, remodulate=True, estimate=True, image=None,
+                    guides=None, exposure=None, scene=None):
+    """skh_vdenoise_params.  sigma_normal, sigma_plane and albedo_floor are denoise_params' (sigma_plane None: DENOISE_PLANE_FRACTION of scene_diagonal(`scene`)).
+    epsilon None: vdenoise_epsilon(`image`, `guides`) when the image to be filtered is given, else VDENOISE_EPSILON_FRACTION of 1 / the mean exposure factor, the
+    level denoise_params assumes for an image it never sees."""
+    p = np.zeros((), VDENOISE_PARAMS)
+    p["width"], p["height"], p["first_level"], p["levels"] = width, height, first_level, levels
+    if epsilon is None and image is not None:
+        epsilon = vdenoise_epsilon(image, guides, albedo_floor, demodulate)
+    if epsilon is None:
+        e = np.asarray(default_exposure() if exposure is None else exposure, np.float64).reshape(-1)
+        epsilon = VDENOISE_EPSILON_FRACTION / float(e.mean())
+    if sigma_plane is None:
+        if scene is None:
+            raise ValueError("sigma_plane is in scene units: give it, or give `scene` to take it as a fraction of the bounding-box diagonal")
+        sigma_plane = DENOISE_PLANE_FRACTION * scene_diagonal(scene)
+    p["sigma_luminance"], p["sigma_normal"], p["sigma_plane"], p["albedo_floor"] = sigma_luminance, sigma_normal, sigma_plane, albedo_floor
+    p["epsilon"], p["min_history"] = epsilon, min_history
+    p["flags"] = (DENOISE_DEMODULATE if demodulate else 0) | (DENOISE_REMODULATE if remodulate else 0) | (VDENOISE_ESTIMATE if estimate else 0)
+    return p
+
+
 def default_exposure(filmIso=100.0, cm2_factor=1.0, fStop=4.0, shutterSpeed=100.0):
     """exposureValue of OptiXRender::render (OptixRender.cpp:961-987), fp32 arithmetic."""
     f = np.float32
