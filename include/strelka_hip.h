@@ -1007,6 +1007,9 @@ skh_status skh_unit_probe(skh_context* ctx, uint32_t unit, uint32_t param, const
  *                 compact_hits (1: render passes of scenes the world-only kernels trace, whose instance count and primitive range share 32 bits, keep 16-byte hit records {t, u, v, instance | record or segment}; 0: 32-byte records always),
  *                 direct_records (-1 = by the counts: a baked mesh triangle's hit names its shading record, unless only (instance, mesh-local primitive) fits a 16-byte hit record; 0 / 1 forced),
  *                 fetch_chunk (-1 = auto: 128 when the triangle + curve trees hold <= 16384 nodes, else 0; queue positions a trace wave reserves per atomic on its shard's cursor),
+ *                 queue_order (1: a pass of several sub-frames queues its camera rays cell by cell, all sub-frames of a cell together, the cells dealt round-robin to the
+ *                 queue's shards along a Morton curve over the tiles; 0: in slot order, sub-frame after sub-frame.  A one-sub-frame pass is the same under both),
+ *                 cell_blocks (0 = auto: -1; -1: a cell is one 64-slot chunk, an 8 x 8 pixel block; n >= 1: n 512-slot blocks, 2 = a 32 x 32 tile),
  *                 node_break_closest / node_break_shadow (32 / 28, curves 20 / 20 until one is set explicitly: leave the node loop below x/64 descending rays),
  *                 leaf_min (16: lanes for the minority kind of leaf work), curve_min (48: lanes parked in front of the
  *                 curve intersector before it runs), subframe_batch (0 = auto: ~64 M paths per pass), aov_band (2^22; 64 ... 2^26: rays per band of skh_render_aovs),

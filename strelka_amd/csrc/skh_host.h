@@ -3,6 +3,7 @@
 #pragma once
 #include "../../include/strelka_hip.h"
 #include "skh_kernels.h"
+#include "skh_order.h"
 #include "skh_stale.h"
 
 #include <string>
@@ -162,6 +163,9 @@ struct skh_context
                                 // stand-in: 16: 712, 32: 907, 40: 958, 48: 984, 56: 971, 64: 887; round 2 counted parked LANES whose owners ran their own runs: 48: 334)
         uint32_t leafMin = 16; // postpone the minority kind of leaf work unless it has this many lanes (0 = never postpone; measured +1.5 % at 16)
         uint32_t subframeBatch = 0; // option subframe_batch: 0 = auto (frame.batchCapacity)
+        uint32_t queueOrder = 1; // option queue_order: where k_raygen puts a pass's camera rays in the first queue (skh_order.h).  0 = slot order, sub-frame after sub-frame; 1 = cell by
+                                 // cell, all sub-frames of a cell together.  A pass of one sub-frame is the same under both
+        int32_t cellBlocks = 0;  // option cell_blocks: 512-slot raygen blocks per cell of queue_order 1; -1 = an eighth of a block (one 64-slot chunk, a wave of k_raygen); 0 = automatic
         bool worldKernel = true; // option world_kernel: scenes with an empty top level run the world-only build of k_trace (0 = the general build: A/B, tests)
         // -- what skh_build_accel reads --
         uint32_t reinsertRounds = 8; // option reinsert_rounds: rounds of parallel reinsertion over the PLOC tree of the triangle build (skh_bvh.h k_ri_*)
@@ -324,6 +328,17 @@ struct skh_context
         DevBuf dTileXY, dAccum, dDiffuse, dSpecular, dDiffCnt, dSpecCnt, dSums, dPath, dRayQ[2], dHits, dShadowQ, dContrib, dCounts, dOvf, dOvf2, dScratchImage;
         DevBuf dRaygenBase;
         uint32_t raygenBlocksPerSub = 0, raygenValidPerSub = 0;
+        // queue_order 1: k_raygen's tables of the cell order (skh_order.h), per pass size -- they depend on `batch` --, cell size and tile set; built by the first pass that
+        // needs them (raygen_order).  alloc_frame drops them; an adaptive pass's are those of the frozen set numbered adapt.orderGen
+        struct CellTables
+        {
+            uint32_t batch = 0, gen = 0;
+            int32_t cellBlocks = 0;
+            bool adaptive = false;
+            DevBuf dQBase, dSubStride;
+        };
+        std::vector<CellTables> cellTables;
+        uint32_t cellTablesNext = 0; // the entry the next new key overwrites once the few there are hold other keys
         std::vector<uint32_t> chunkValid; // valid pixels per 64-slot chunk (an 8 x 8 pixel block) of the home list: what the ray-generation tables are summed from
         uint32_t queueConstBits[2] = { 0, 0 }; // materialTmin / shadowTmin the constant planes of the ray queues hold (bit patterns)
         bool queueConstFilled = false; // ... and whether they hold them at all (alloc_frame resets it)
@@ -369,6 +384,7 @@ struct skh_context
         bool ready = false;      // buffers allocated for this frame geometry and the frame's state initialised (cleared by every reset)
         uint32_t delivered = 0;  // observations since the frame began
         uint32_t checks = 0, activeTiles = 0, raygenValid = 0;
+        uint32_t orderGen = 0; // counts the frozen sets: frame.cellTables of an older one are stale
         uint64_t pixelObs = 0, pixelObsSaved = 0;
         std::vector<uint32_t> frozenAt; // per tile: 0 = active, else its observation count when it froze
         DevBuf dTileXYRender, dRaygenBaseRender, dState, dTileQ, dFrozenAt;

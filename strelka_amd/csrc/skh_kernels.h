@@ -705,17 +705,25 @@ SKH_DI void block_compact2(bool emitA, uint32_t* counterA, bool emitB, uint32_t*
 
 // Ray generation without atomics: which slots of a tile set fall inside the image is known on the host, so the first queue
 // position of every 512-slot block (`blockBase`, exclusive prefix of the per-block valid counts) and the number of valid
-// pixels per sub-frame (`validPerSub`) are tables; inside a block the rank comes from ballots.  The queue order is the slot
-// order (tile-major, Morton inside a tile), sub-frame after sub-frame -- and one returning atomic per block less (a single
-// queue-tail word takes ~88 of those per microsecond: a 64 M-path launch was bound by exactly that).
+// pixels per sub-frame (`validPerSub`) are tables; inside a block the rank comes from ballots -- one returning atomic per block
+// less (a single queue-tail word takes ~88 of those per microsecond: a 64 M-path launch was bound by exactly that).
+// WHERE in the first queue a ray goes is the host's choice (skh_order.h): position = qBase[u] + sub * subStride[u] + rank, u the
+// block, or with `perWave` the wave's 64-slot chunk.  subStride == NULL is the slot order (tile-major, Morton inside a tile),
+// sub-frame after sub-frame: every stride is validPerSub.  The cell order puts all sub-frames of a few blocks back to back.
+// Only the position depends on the order; the path index does not.  The grid walks `launchCell` blocks through all sub-frames
+// before it moves on (launchCell = blocksPerSub: sub-frame after sub-frame), so neighbouring workgroups write neighbouring runs.
 __global__ void __launch_bounds__(512) k_raygen(FrameP fp, const uint32_t* __restrict__ tileXY, uint32_t sampleOffset, RayQ rq,
-                                               uint32_t* __restrict__ counter, PathS ps, const uint32_t* __restrict__ blockBase,
-                                               uint32_t blocksPerSub, uint32_t validPerSub)
+                                               uint32_t* __restrict__ counter, PathS ps, const uint32_t* __restrict__ qBase,
+                                               const uint32_t* __restrict__ subStride, uint32_t blocksPerSub, uint32_t validPerSub,
+                                               uint32_t launchCell, uint32_t perWave)
 {
     __shared__ uint32_t s_wave[SKH_COMPACT_MAX_WAVES + 1];
     // several sub-frames can be in flight at once (fp.batch): path = sub * numSlots + slot.  Paths of different
     // sub-frames are independent; only the accumulation (k_finalize_batch) has to respect their order.
-    const uint32_t sub = blockIdx.x / blocksPerSub, bi = blockIdx.x - sub * blocksPerSub;
+    // (the last launch cell may hold fewer blocks: the grid's surplus there comes out as sub >= fp.batch)
+    const uint32_t span = launchCell * fp.batch, lc = blockIdx.x / span, inSpan = blockIdx.x - lc * span;
+    const uint32_t nb = min(launchCell, blocksPerSub - lc * launchCell);
+    const uint32_t sub = inSpan / nb, bi = lc * launchCell + (inSpan - sub * nb);
     const uint32_t slot = bi * blockDim.x + threadIdx.x;
     const uint32_t path = sub * fp.numSlots + slot;
     uint32_t px = 0, py = 0;
@@ -737,10 +745,11 @@ __global__ void __launch_bounds__(512) k_raygen(FrameP fp, const uint32_t* __res
         s_wave[wave] = (uint32_t)__popcll(m);
     __syncthreads();
     uint32_t before = 0;
-    for (uint32_t w = 0; w < wave; ++w)
+    for (uint32_t w = 0; w < wave && !perWave; ++w)
         before += s_wave[w];
-    // dense index in slot order -> shard: the queue is cut into SKH_SHARDS equal runs of `per` rays (the last one shorter)
-    const uint32_t dense = sub * validPerSub + blockBase[bi] + before + rank_below(m);
+    // dense index in queue order -> shard: the queue is cut into SKH_SHARDS equal runs of `per` rays (the last one shorter)
+    const uint32_t u = perWave ? bi * 8u + wave : bi;
+    const uint32_t dense = qBase[u] + sub * (subStride ? subStride[u] : validPerSub) + before + rank_below(m);
     const uint32_t total = validPerSub * fp.batch;
     const uint32_t per = (((total + SKH_SHARDS - 1u) / SKH_SHARDS) + 63u) & ~63u;
     const uint32_t shard = per ? dense / per : 0u;

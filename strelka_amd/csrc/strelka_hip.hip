@@ -569,9 +569,82 @@ static void raygen_tables(const skh_context* c, const uint32_t* frozenAt, std::v
     }
 }
 
+// What k_raygen is given beside the frame: the two position tables, and how its grid walks the blocks.
+struct RaygenOrder
+{
+    const uint32_t *qBase = nullptr, *subStride = nullptr; // (subStride NULL: the slot order)
+    uint32_t launchCell = 1, perWave = 0;
+};
+
+// The cell size of queue_order 1 in raygen blocks (-1: a 64-slot chunk).  Automatic: the chunk -- the smallest cell was the fastest on the kitchen (docs/LOG.md
+// "Queue order": 1/8, 1, 2, 4, 8, 16 blocks: -1.6, -1.0, -1.4, -0.7, -1.2, -0.3 % of the frame), and a cell of 64 pixels x 64 samples already fills four trace workgroups.
+static int32_t cell_blocks(const skh_context* c)
+{
+    return c->opt.cellBlocks ? c->opt.cellBlocks : -1;
+}
+
+// k_raygen's order for a pass of `batch` sub-frames.  The slot order's tables are alloc_frame's (an adaptive pass's: adapt_after_pass's); the cell order's depend on the
+// pass size and are built here the first time a pass of that size needs them: from the same per-chunk valid counts, with the same frozen tiles left out, so both
+// orders fill exactly the positions [0, valid * batch).  A one-sub-frame pass has nothing to interleave: both options give it the slot order.
+static skh_status raygen_order(skh_context* c, bool adaptive, uint32_t batch, RaygenOrder& out)
+{
+    skh_context::Frame& f = c->frame;
+    out = RaygenOrder{};
+    out.qBase = adaptive ? c->adapt.dRaygenBaseRender.as<uint32_t>() : f.dRaygenBase.as<uint32_t>();
+    out.launchCell = std::max(1u, f.raygenBlocksPerSub);
+    if (c->opt.queueOrder == 0u || batch <= 1u)
+        return SKH_OK;
+    const int32_t cb = cell_blocks(c);
+    const uint32_t gen = adaptive ? c->adapt.orderGen : 0u;
+    out.perWave = cb < 0 ? 1u : 0u;
+    out.launchCell = cb < 0 ? 1u : std::min((uint32_t)cb, std::max(1u, f.raygenBlocksPerSub));
+    skh_context::Frame::CellTables* e = nullptr;
+    for (skh_context::Frame::CellTables& t : f.cellTables)
+        if (t.batch == batch && t.cellBlocks == cb && t.adaptive == adaptive && t.gen == gen)
+            e = &t;
+    if (!e)
+    {
+        // the units: blocks, or their 64-slot chunks (padded to whole blocks); valid slots and first pixel of each, from the HOME list (a frozen tile counts nothing)
+        const uint32_t perUnit = cb < 0 ? 1u : 8u, chunks = (uint32_t)f.chunkValid.size(), shift2 = 2 * f.tileShift, mask = (1u << shift2) - 1u;
+        const uint32_t nUnits = f.raygenBlocksPerSub * (cb < 0 ? 8u : 1u);
+        const uint32_t* frozenAt = adaptive ? c->adapt.frozenAt.data() : nullptr;
+        std::vector<uint32_t> valid(nUnits, 0u), origin(2 * (size_t)nUnits, 0u);
+        for (uint32_t u = 0; u < nUnits; ++u)
+        {
+            const uint32_t j0 = u * perUnit;
+            if (j0 >= chunks)
+                continue;
+            const uint32_t tile = (j0 * 64u) >> shift2, m = (j0 * 64u) & mask;
+            origin[2 * (size_t)u] = f.tileXY[2 * tile] + skh_order::even_bits(m), origin[2 * (size_t)u + 1] = f.tileXY[2 * tile + 1] + skh_order::even_bits(m >> 1);
+            for (uint32_t j = j0; j < std::min(chunks, j0 + perUnit); ++j)
+                if (!frozenAt || frozenAt[(j * 64u) >> shift2] == 0u)
+                    valid[u] += f.chunkValid[j];
+        }
+        skh_order::Tables t;
+        skh_order::cell_order(valid.data(), origin.data(), nUnits, batch, cb < 0 ? 1u : (uint32_t)cb, SKH_SHARDS, t);
+        if (t.validPerSub != (adaptive ? c->adapt.raygenValid : f.raygenValidPerSub))
+        {
+            c->dev.err = "raygen_order: the cell order counts other slots than the slot order";
+            return SKH_FAIL;
+        }
+        // a few pass sizes at most are alive at a time (the full batch, the tail of a call, the look-ahead's 2 / 4 / 8): beyond eight keys the oldest entry goes
+        if (f.cellTables.size() < 8u)
+            f.cellTables.emplace_back(), e = &f.cellTables.back();
+        else
+            e = &f.cellTables[f.cellTablesNext++ % 8u];
+        e->batch = 0; // (not a key until both tables are up: dev_upload orders the copy behind the launches that read the old ones, and waits for it)
+        SKH_CHECK(dev_upload(c, e->dQBase, t.qBase.data(), sizeof(uint32_t) * t.qBase.size()));
+        SKH_CHECK(dev_upload(c, e->dSubStride, t.subStride.data(), sizeof(uint32_t) * t.subStride.size()));
+        e->batch = batch, e->cellBlocks = cb, e->adaptive = adaptive, e->gen = gen;
+    }
+    out.qBase = e->dQBase.as<uint32_t>(), out.subStride = e->dSubStride.as<uint32_t>();
+    return SKH_OK;
+}
+
 static skh_status alloc_frame(skh_context* c)
 {
     const uint32_t T = c->frame.tileSize;
+    c->frame.cellTables.clear(); // (of the frame that was)
     if (!c->frame.customTiles)
     {
         c->frame.tileXY.clear();
@@ -1717,6 +1790,7 @@ static skh_status adapt_prepare(skh_context* c, const skh_frame_params& p)
     ad.delivered = ad.checks = 0;
     ad.activeTiles = c->frame.numTiles;
     ad.raygenValid = c->frame.raygenValidPerSub;
+    ad.orderGen++; // (the cell order's tables of the last frame's frozen sets are stale)
     ad.pixelObs = ad.pixelObsSaved = 0;
     ad.ready = true;
     return SKH_OK;
@@ -1775,6 +1849,7 @@ static skh_status adapt_after_pass(skh_context* c, const skh_frame_params& p, ui
         SKH_TRY(c, hipMemcpyAsync(c->adapt.dRaygenBaseRender.p, base.data(), sizeof(uint32_t) * base.size(), hipMemcpyHostToDevice, c->dev.stream));
         SKH_TRY(c, hipStreamSynchronize(c->dev.stream)); // (`base` goes out of scope)
         ad.activeTiles = active;
+        ad.orderGen++; // (... and the cell order's, which the next pass builds when it needs them: raygen_order)
     }
     return SKH_OK;
 }
@@ -2011,7 +2086,9 @@ static skh_status render_one(skh_context* c, const skh_frame_params* p, const Re
     if (NP == 0)
         return SKH_OK;
     rp.tiles = plan.adaptive ? c->adapt.dTileXYRender.as<uint32_t>() : c->frame.dTileXY.as<uint32_t>();
-    const uint32_t* raygenBase = plan.adaptive ? c->adapt.dRaygenBaseRender.as<uint32_t>() : c->frame.dRaygenBase.as<uint32_t>();
+    RaygenOrder order;
+    if (plan.trace)
+        SKH_CHECK(raygen_order(c, plan.adaptive, batch, order));
     const uint32_t raygenValid = plan.adaptive ? c->adapt.raygenValid : c->frame.raygenValidPerSub;
     rp.ps = PathS{ plan.pathSel ? c->spec.dPathB.as<float>() : c->frame.dPath.as<float>(), plan.pathSel ? c->spec.pathBStride : N };
     const auto queue = [&](const DevBuf& b) { return RayQ{ b.as<float>(), NQ, c->frame.queueRegion }; };
@@ -2069,7 +2146,9 @@ static skh_status render_one(skh_context* c, const skh_frame_params* p, const Re
         rp.blp.sampleBase = fp.subframeIndex + s;
         {
             SpanGuard g(c, KC_RAYGEN);
-            k_raygen<<<c->frame.raygenBlocksPerSub * fp.batch, 512, 0, st>>>(fp, rp.tiles, s, rp.rq[0], counts, rp.ps, raygenBase, c->frame.raygenBlocksPerSub, raygenValid);
+            const uint32_t launchCells = (c->frame.raygenBlocksPerSub + order.launchCell - 1u) / order.launchCell;
+            k_raygen<<<launchCells * order.launchCell * fp.batch, 512, 0, st>>>(fp, rp.tiles, s, rp.rq[0], counts, rp.ps, order.qBase, order.subStride, c->frame.raygenBlocksPerSub, raygenValid,
+                                                                                 order.launchCell, order.perWave);
         }
         for (uint32_t b = 0; b < rounds; ++b)
         {
@@ -3305,6 +3384,9 @@ static const OptRow kOptions[] = {
     { "world_kernel", kOptMin, kOptMax, OPT_NONE, OPT_FLAG(worldKernel) }, // (the build reads it -- worldCurveKernel -- and setting it has never invalidated the build)
     // the frame's buffers
     { "subframe_batch", 0, 64, OPT_FRAME, OPT_U32(subframeBatch) },
+    // where the camera rays go in the first queue (skh_order.h): read by the next pass, which builds the tables it finds missing
+    { "queue_order", 0, 1, OPT_NONE, OPT_U32(queueOrder) },
+    { "cell_blocks", -1, 64, OPT_NONE, OPT_I32(cellBlocks) },
     { "waves_per_cu", 1, 32, OPT_FRAME, OPT_U32(wavesPerCU) },
     { "waves_per_cu_shadow", 1, 32, OPT_FRAME, OPT_U32(wavesPerCUShadow) },
     { "waves_per_cu_world", 1, 32, OPT_FRAME, OPT_U32(wavesPerCUWorld) },
