@@ -759,8 +759,9 @@ skh_status skh_get_denoise_info(skh_context* ctx, skh_denoise_info* out);
  *            2^26; a matrix entry that is not finite; normal_min outside [-1, 1] or NaN; plane_tolerance <= 0 or NaN (+inf is legal and turns the test off);
  *            max_history not finite or < 1; initial_length not finite, < 1 or > max_history; an albedo_floor that is <= 0 or not finite; a flag bit other than
  *            DEMODULATE; a non-zero reserved word -- and a NULL image that the call needs, and the alias above.
- * Not part of it: object motion (a moved instance loses its history through the plane test; a move smaller than the tolerance ghosts), neighbourhood colour
- * clamping for lighting changes, separate diffuse / specular histories (luminance moments and variance guidance: skh_moments, below), what is seen in mirrors
+ * Object motion: the call projects P as if nothing in the world had moved.  For moved instances hand it, as d_normal and d_position, the planes that
+ * skh_rewind_guides (further below) writes.
+ * Not part of it: neighbourhood colour clamping for lighting changes, separate diffuse / specular histories (luminance moments and variance guidance: skh_moments, below), what is seen in mirrors
  * and through glass (the guides describe the first surface). */
 #define SKH_TEMPORAL_DEMODULATE 1u
 
@@ -868,6 +869,73 @@ typedef struct skh_vdenoise_info
     uint64_t scratch_bytes;  /* device bytes the context holds for the filter now (skh_denoise_info's) */
 } skh_vdenoise_info;
 skh_status skh_get_vdenoise_info(skh_context* ctx, skh_vdenoise_info* out);
+
+/* ---- Object motion: the current frame's POSITION and NORMAL planes rewound into the previous frame's world, so that skh_temporal and skh_moments follow
+ *      instances whose transforms changed between the two frames (new; DESIGN.md section 2, "Object motion").  skh_temporal uses the current POSITION and NORMAL
+ *      for the projection, the normal test against N'(q) and the plane test against P'(q); skh_moments uses POSITION for the projection.  Handed where the
+ *      surface point WAS and how it FACED, each of those uses is right as it stands.  One pass, one kernel (skh_motion.h), and the table that drives it.
+ *
+ *   table    skh_instance_motion per instance, indexed by IDS.instance_id.  to_prev maps a current world position of the instance to its previous one,
+ *            normal_to_prev a current world normal to a positive multiple of its previous one.  SKH_MOTION_MOVED: the matrices apply; without it the entry
+ *            is skipped and its matrix words are not looked at.  SKH_MOTION_DROP (with MOVED): the instance's pixels get no history.
+ *   skh_instance_motion_from_transforms   the single place an entry is derived: from the instance's 3 x 4 row-major transforms (object to world, as
+ *            skh_set_instances takes them) of the previous frame, A = [A_lin | a], and of the current one, B = [B_lin | b].  Host only; needs no context and
+ *            no GPU.  When the twelve words of A and B are equal bit for bit: flags = 0, identity matrices.  Otherwise, in double, each operation rounded once,
+ *            in this order:
+ *              inv(M), M 3 x 3:  c00 = m11 m22 - m12 m21, c01 = m12 m20 - m10 m22, c02 = m10 m21 - m11 m20, det = (m00 c00 + m01 c01) + m02 c02;
+ *                       the adjugate's entry (i, j) = m[j+1][i+1] m[j+2][i+2] - m[j+1][i+2] m[j+2][i+1] with the indices taken modulo 3 (c00, c01, c02 are its
+ *                       first column); inv(M)(i, j) = adjugate(i, j) / det
+ *              Bi = inv(B_lin), Ai = inv(A_lin)
+ *              L(i, j) = (A_lin(i, 0) Bi(0, j) + A_lin(i, 1) Bi(1, j)) + A_lin(i, 2) Bi(2, j)
+ *              t(i) = a(i) - ((L(i, 0) b(0) + L(i, 1) b(1)) + L(i, 2) b(2))
+ *              K(i, j) = (Ai(0, i) B_lin(j, 0) + Ai(1, i) B_lin(j, 1)) + Ai(2, i) B_lin(j, 2): transpose(inv(A_lin)) transpose(B_lin), the inverse transpose of
+ *                       L itself and not its cofactor matrix, so that a mirror keeps its sign
+ *            to_prev = [L | t] and normal_to_prev = K, each entry rounded once to float32; flags = MOVED.  When either determinant is 0, or an input word or a
+ *            rounded word is not finite: flags = MOVED | DROP and identity matrices.  SKH_INVALID_ARGUMENT for a NULL pointer, nothing else fails.
+ *   skh_instance_motion_check   refuses a flag bit other than the two, DROP without MOVED, a non-zero reserved word, a matrix word that is not finite in an
+ *            entry that is MOVED and not DROP, and table == NULL with n > 0.  Needs no context and no GPU.
+ *   skh_set_instance_motion   checks the table and uploads it into a device table the context owns; the table grows when a larger one comes and is freed by
+ *            n == 0 and by skh_destroy.  It is an input of its own: no scene setter touches it and it touches no derived state (it is no entry of the
+ *            staleness table).  A refused table leaves the previous one in force.
+ *   skh_rewind_guides   a pure function of caller-owned planes in the layout of skh_render_aovs; records, row order and rounding are skh_temporal's: every
+ *            product, sum, quotient and square root is one rounded float32 operation, no fma.  Per pixel, id = IDS, P = POSITION, N = NORMAL; the entry
+ *            e = table[id.instance_id] APPLIES iff id.kind is 1 or 2, id.instance_id < n and e.flags & MOVED.  With m = e.to_prev, k = e.normal_to_prev:
+ *              applies, no DROP   P*.x = ((m0 P.x + m1 P.y) + m2 P.z) + m3, rows y (m4 ..) and z (m8 ..) likewise
+ *                                 v.x = (k0 N.x + k1 N.y) + k2 N.z, rows y (k3 ..) and z (k6 ..) likewise; s = (v.x v.x + v.y v.y) + v.z v.z; N* = v / sqrtf(s)
+ *                                 per component.  No special case: a zero or NaN normal gives a NaN N*, which skh_temporal's NaN-failing comparisons reject
+ *                                 (a NaN that an operation produces has no defined payload; a copied word keeps its bits).
+ *              applies, DROP      P*.xyz = the quiet NaN 0x7fc00000 (skh_temporal and skh_moments find that the pixel does not project); N* = N
+ *              the .w words of both planes pass through
+ *              every other pixel  both records copied bit for bit
+ *            d_position_out == d_position and d_normal_out == d_normal are allowed (a pixel reads only its own records) and give the bits of the out-of-place
+ *            call.  Synchronous, on the stream skh_denoise uses.  No effect on the frame, sub-frames traced ahead are not dropped, no scratch beyond the table.
+ *            Refused with SKH_INVALID_ARGUMENT, nothing written: width or height 0 or width * height > 2^26, a NULL plane, no table set.
+ *   use      rewind the current frame's planes, hand the rewound pair to skh_temporal (d_normal, d_position) and to skh_moments (d_position); its motion plane
+ *            then follows the instance too.  skh_denoise, skh_denoise_variance and the NEXT frame's previous guides keep the true planes.
+ * Not part of it: the shadow (or reflection, or bounce light) a moved object casts on OTHER surfaces lags as any lighting change does; deforming meshes (vertex
+ * edits followed by skh_refit_accel have no per-instance motion); what is seen in mirrors and through glass (the guides describe the first surface). */
+#define SKH_MOTION_MOVED 1u /* the entry's matrices apply */
+#define SKH_MOTION_DROP 2u  /* with MOVED: the instance's pixels get no history (replaced, teleported, singular transform) */
+typedef struct skh_instance_motion /* 96 bytes, six float4 */
+{
+    float to_prev[12];       /* row-major 3x4: P_prev = to_prev (P, 1) */
+    float normal_to_prev[9]; /* row-major 3x3: N_prev ~ normal_to_prev N (any positive scale) */
+    uint32_t flags;          /* SKH_MOTION_* */
+    uint32_t reserved[2];    /* 0 */
+} skh_instance_motion;
+
+skh_status skh_instance_motion_from_transforms(const float prev[12], const float cur[12], skh_instance_motion* out);
+skh_status skh_instance_motion_check(const skh_instance_motion* table, uint32_t n);
+skh_status skh_set_instance_motion(skh_context* ctx, const skh_instance_motion* table, uint32_t n);
+skh_status skh_rewind_guides(skh_context* ctx, uint32_t width, uint32_t height, const void* d_ids, const void* d_position, const void* d_normal,
+                             void* d_position_out, void* d_normal_out);
+typedef struct skh_rewind_info
+{
+    uint64_t calls, pixels; /* since the last skh_reset_stats */
+    double ms_last;         /* wall time of the last call, its synchronisation included */
+    uint64_t entries;       /* entries of the table in force (0: none) */
+} skh_rewind_info;
+skh_status skh_get_rewind_info(skh_context* ctx, skh_rewind_info* out);
 
 /* ---- the tonemap() + gammaCorrection post pass (postprocessing/Tonemappers.cu:111-135), in place on a
  *      device float4 image.  type: 0 none, 1 Reinhard, 2 ACES fitted, 3 ACES film; gamma <= 0 = off ---- */

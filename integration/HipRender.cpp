@@ -259,7 +259,8 @@ void HipRender::freeGuides()
             skh_buffer_free(mCtx, g);
         g = nullptr;
     }
-    for (void** g : { &mPrevGuide[0], &mPrevGuide[1], &mPrevGuide[2], &mHistory[0], &mHistory[1], &mVarianceImage, &mMotion, &mMoments[0], &mMoments[1] })
+    for (void** g : { &mPrevGuide[0], &mPrevGuide[1], &mPrevGuide[2], &mHistory[0], &mHistory[1], &mVarianceImage, &mMotion, &mMoments[0], &mMoments[1],
+                      &mRewound[0], &mRewound[1] })
     {
         if (mCtx && *g)
             skh_buffer_free(mCtx, *g);
@@ -346,6 +347,54 @@ bool HipRender::setVarianceGuidance(bool on, const HipVariance* params)
     return true;
 }
 
+void HipRender::setInstanceMotion(bool on)
+{
+    mInstanceMotion = on;
+    if (on)
+        return;
+    mGuideInstances.clear(), mPrevGuideInstances.clear();
+    for (void*& g : mRewound)
+    {
+        if (mCtx && g)
+            skh_buffer_free(mCtx, g);
+        g = nullptr;
+    }
+    if (mCtx)
+        check(skh_set_instance_motion(mCtx, nullptr, 0), "skh_set_instance_motion"); // (the library's table goes too)
+}
+
+// With object motion on, when the instance tables of the two guide sets differ in a transform: the current set's position and normal planes, rewound into the
+// previous frame's world, in mRewound.  false: nothing moved (or the feature is off, or a call failed) -- the caller hands on the true planes.
+bool HipRender::rewindGuides(uint32_t width, uint32_t height)
+{
+    if (!mInstanceMotion || mGuideInstances.empty() || mPrevGuideInstances.empty())
+        return false;
+    const size_t n = mGuideInstances.size(), nPrev = mPrevGuideInstances.size();
+    bool differ = n != nPrev;
+    for (size_t i = 0; i < n && !differ; ++i)
+        differ = memcmp(mGuideInstances[i].transform, mPrevGuideInstances[i].transform, sizeof(mGuideInstances[i].transform)) != 0;
+    if (!differ)
+        return false;
+    std::vector<skh_instance_motion> table(n);
+    for (size_t i = 0; i < n; ++i)
+    {
+        if (i < nPrev)
+            skh_instance_motion_from_transforms(mPrevGuideInstances[i].transform, mGuideInstances[i].transform, &table[i]);
+        else
+        {
+            // an instance the previous frame did not have: no history
+            skh_instance_motion_from_transforms(mGuideInstances[i].transform, mGuideInstances[i].transform, &table[i]);
+            table[i].flags = SKH_MOTION_MOVED | SKH_MOTION_DROP;
+        }
+    }
+    if (!check(skh_set_instance_motion(mCtx, table.data(), (uint32_t)n), "skh_set_instance_motion"))
+        return false;
+    for (void*& g : mRewound)
+        if (!g && !check(skh_buffer_alloc(mCtx, (size_t)16 * width * height, &g), "skh_buffer_alloc"))
+            return false;
+    return check(skh_rewind_guides(mCtx, width, height, mGuide[0], mGuide[2], mGuide[1], mRewound[0], mRewound[1]), "skh_rewind_guides");
+}
+
 // the four guide planes of the whole image through the pixel centres, into buffers of this object.  With temporal accumulation on, the set rendered last
 // (ids, normal, position) and its world_to_clip first become the previous frame's.
 bool HipRender::renderGuides()
@@ -372,6 +421,11 @@ bool HipRender::renderGuides()
         memcpy(mPrevWorldToClip, mGuideWorldToClip, sizeof(mPrevWorldToClip));
         mPrevGuidesValid = mGuidesValid;
         memcpy(mGuideWorldToClip, ap.world_to_clip, sizeof(mGuideWorldToClip));
+        if (mInstanceMotion)
+        {
+            std::swap(mGuideInstances, mPrevGuideInstances);
+            mGuideInstances = mSentInstances;
+        }
     }
     void* d[SKH_AOV_COUNT] = {};
     d[SKH_AOV_IDS] = mGuide[0], d[SKH_AOV_NORMAL] = mGuide[1], d[SKH_AOV_POSITION] = mGuide[2], d[SKH_AOV_ALBEDO] = mGuide[3];
@@ -841,14 +895,18 @@ void HipRender::render(Buffer* output)
         const bool had = mHistoryValid && mPrevGuidesValid, hadMoments = had && mMomentsValid;
         const skh_temporal_params tp = hipTemporalParams(mTemporalSetting, width, height, had ? mPrevWorldToClip : nullptr, 1.0f, mSceneDiagonal);
         const skh_vdenoise_params vp = hipVarianceParams(mVarianceSetting, mDenoiseSetting, width, height, p.exposure, mSceneDiagonal);
+        // moved instances: the reprojection's normal and position are the rewound planes; the filter keeps the true ones
+        const bool rewound = had && rewindGuides(width, height);
+        const void* tNormal = rewound ? mRewound[1] : mGuide[1];
+        const void* tPosition = rewound ? mRewound[0] : mGuide[2];
         // the blended image goes to this object's buffer: the output image keeps the raw sample for skh_moments, then takes the filtered result
-        if (check(skh_temporal(mCtx, &tp, dImage, mGuide[0], mGuide[1], mGuide[2], mGuide[3], had ? mHistory[mHistoryStored] : nullptr, mPrevGuide[0], mPrevGuide[1],
+        if (check(skh_temporal(mCtx, &tp, dImage, mGuide[0], tNormal, tPosition, mGuide[3], had ? mHistory[mHistoryStored] : nullptr, mPrevGuide[0], mPrevGuide[1],
                                mPrevGuide[2], mVarianceImage, mHistory[next], mMotion),
                   "skh_temporal"))
         {
             mHistoryStored = next, mHistoryValid = true;
             mTemporalApplied = tp, mTemporalHadPrevious = had;
-            if (check(skh_moments(mCtx, &tp, dImage, mGuide[0], mGuide[2], mGuide[3], hadMoments ? mMotion : nullptr, hadMoments ? mMoments[mMomentsStored] : nullptr,
+            if (check(skh_moments(mCtx, &tp, dImage, mGuide[0], tPosition, mGuide[3], hadMoments ? mMotion : nullptr, hadMoments ? mMoments[mMomentsStored] : nullptr,
                                   mMoments[nextMoments]),
                       "skh_moments"))
             {
@@ -871,7 +929,9 @@ void HipRender::render(Buffer* output)
             // the stored history, reprojected into the new frame and blended with it, in place; the new history takes the stored one's place
             const bool had = mHistoryValid && mPrevGuidesValid;
             const skh_temporal_params tp = hipTemporalParams(mTemporalSetting, width, height, had ? mPrevWorldToClip : nullptr, 1.0f, mSceneDiagonal);
-            if (check(skh_temporal(mCtx, &tp, dImage, mGuide[0], mGuide[1], mGuide[2], mGuide[3], had ? mHistory[mHistoryStored] : nullptr, mPrevGuide[0], mPrevGuide[1],
+            const bool rewound = had && rewindGuides(width, height); // (moved instances: the rewound normal and position planes)
+            if (check(skh_temporal(mCtx, &tp, dImage, mGuide[0], rewound ? mRewound[1] : mGuide[1], rewound ? mRewound[0] : mGuide[2], mGuide[3],
+                                   had ? mHistory[mHistoryStored] : nullptr, mPrevGuide[0], mPrevGuide[1],
                                    mPrevGuide[2], dImage, mHistory[next], nullptr),
                       "skh_temporal"))
             {

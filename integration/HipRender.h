@@ -261,6 +261,14 @@ public:
             *hadPrevious = mMomentsHadPrevious;
         return mVarianceApplied.width != 0u;
     }
+    // Object motion (skh_rewind_guides; new), OFF by default.  It acts only with setTemporal on.  With it on, a copy of the instance table as it was last sent to
+    // the library is kept beside each of the two guide sets and changes places with them.  A render() that reprojects a stored history compares the two tables'
+    // transforms word by word; when they differ it derives the skh_instance_motion table (skh_instance_motion_from_transforms per instance), hands it to
+    // skh_set_instance_motion, and makes exactly one skh_rewind_guides call from the current guide set into two more buffers of this object, which then stand
+    // in for the normal and position planes of skh_temporal's current frame and, on a guided call, for skh_moments' position plane.  skh_denoise,
+    // skh_denoise_variance and the stored guide sets keep the true planes.  With it off -- and on every call that does not reproject across a transform
+    // change -- render() makes the calls it made before.
+    void setInstanceMotion(bool on);
     // the frame parameters' sample choice of the last render(): subframe_index and enable_accumulation as handed to skh_render_subframe
     void lastSample(uint32_t& subframeIndex, uint32_t& enableAccumulation) const
     {
@@ -328,6 +336,10 @@ private:
     void* mMoments[2] = {};         // {mu1, mu2, variance, nm} per pixel; mMoments[mMomentsStored] is the stored one
     int mMomentsStored = 0;
     bool mMomentsValid = false;     // false: the next guided call has no previous moments
+    bool mInstanceMotion = false;
+    std::vector<skh_instance> mGuideInstances, mPrevGuideInstances; // the instance table as sent when mGuide / mPrevGuide were rendered (setInstanceMotion)
+    void* mRewound[2] = {};  // position | normal of mGuide in the previous frame's world (skh_rewind_guides' outputs)
+    bool rewindGuides(uint32_t width, uint32_t height); // true: mRewound holds this call's rewound planes
     void dropHistory()
     {
         mHistoryValid = false;

@@ -36,7 +36,8 @@ SYMBOLS = ["skh_create", "skh_destroy", "skh_last_error", "skh_abi_version", "sk
            "skh_aov_check", "skh_render_aovs", "skh_get_aov_info",
            "skh_denoise_check", "skh_denoise", "skh_get_denoise_info", "skh_buffer_upload",
            "skh_temporal_check", "skh_temporal", "skh_get_temporal_info",
-           "skh_moments", "skh_get_moments_info", "skh_vdenoise_check", "skh_denoise_variance", "skh_get_vdenoise_info"]
+           "skh_moments", "skh_get_moments_info", "skh_vdenoise_check", "skh_denoise_variance", "skh_get_vdenoise_info",
+           "skh_instance_motion_from_transforms", "skh_instance_motion_check", "skh_set_instance_motion", "skh_rewind_guides", "skh_get_rewind_info"]
 
 BUILD_INFO = np.dtype([("triangles", np.uint32), ("nodes", np.uint32), ("reinsert_rounds", np.uint32), ("reinsert_moves", np.uint32),
                        ("reinsert_min_size", np.uint32), ("refit", np.uint32), ("cost_before", np.float64), ("cost_after", np.float64),
@@ -67,6 +68,8 @@ MOMENTS_INFO = np.dtype([("calls", np.uint64), ("pixels", np.uint64), ("ms_last"
 assert MOMENTS_INFO.itemsize == 24
 VDENOISE_INFO = np.dtype([("calls", np.uint64), ("pixels", np.uint64), ("ms_last", np.float64), ("scratch_bytes", np.uint64)])
 assert VDENOISE_INFO.itemsize == 32
+REWIND_INFO = np.dtype([("calls", np.uint64), ("pixels", np.uint64), ("ms_last", np.float64), ("entries", np.uint64)])
+assert REWIND_INFO.itemsize == 32
 # skh_light_shape_probe: kind -> (number, words in, words out) per record
 LSHAPE_PROBES = {"sample": (0, 6, 13), "pdf": (1, 7, 2)}
 # skh_emitter_probe: kind -> (number, words in, words out) per record
@@ -151,6 +154,11 @@ def load():
     lib.skh_vdenoise_check.argtypes = [vp]
     lib.skh_denoise_variance.argtypes = [vp] * 10
     lib.skh_get_vdenoise_info.argtypes = [vp, vp]
+    lib.skh_instance_motion_from_transforms.argtypes = [vp, vp, vp]
+    lib.skh_instance_motion_check.argtypes = [vp, u32]
+    lib.skh_set_instance_motion.argtypes = [vp, vp, u32]
+    lib.skh_rewind_guides.argtypes = [vp, u32, u32, vp, vp, vp, vp, vp]
+    lib.skh_get_rewind_info.argtypes = [vp, vp]
     lib.skh_buffer_upload.argtypes = [vp, vp, vp, C.c_size_t]
     lib.skh_resize.argtypes = [vp, u32, u32]
     lib.skh_set_tiles.argtypes = [vp, u32, vp, u32]
@@ -226,6 +234,12 @@ def temporal_check(params):
 def moments_check(params):
     """would skh_moments accept these S.TEMPORAL_PARAMS?  It takes the struct skh_temporal took, and skh_temporal_check is its check."""
     return temporal_check(params)
+
+
+def instance_motion_check(table):
+    """skh_instance_motion_check: would skh_set_instance_motion accept this S.INSTANCE_MOTION table?  (needs no context and no GPU)"""
+    t = np.ascontiguousarray(table, dtype=S.INSTANCE_MOTION).reshape(-1)
+    return load().skh_instance_motion_check(_p(t), len(t)) == 0
 
 
 def vdenoise_check(params):
@@ -714,6 +728,29 @@ class Context:
     def vdenoise_info(self):
         """skh_get_vdenoise_info: calls and pixels since the last reset_stats, the last call's wall time, the scratch bytes the context holds (the denoiser's)"""
         return self._info("skh_get_vdenoise_info", VDENOISE_INFO)
+
+    def set_instance_motion(self, table):
+        """skh_set_instance_motion: the S.INSTANCE_MOTION table (scene.instance_motion builds it) that rewind_guides applies, one entry per instance; None or an
+        empty table frees the context's copy"""
+        t = np.zeros(0, S.INSTANCE_MOTION) if table is None else np.ascontiguousarray(table, dtype=S.INSTANCE_MOTION).reshape(-1)
+        self._ck(self.lib.skh_set_instance_motion(self.h, _p(t) if len(t) else None, len(t)), "skh_set_instance_motion")
+
+    def rewind_guides_device(self, width, height, d_ids, d_position, d_normal, d_position_out, d_normal_out):
+        """skh_rewind_guides on caller-owned device planes (an out plane may be its own in plane)"""
+        self._ck(self.lib.skh_rewind_guides(self.h, width, height, d_ids, d_position, d_normal, d_position_out, d_normal_out), "skh_rewind_guides")
+
+    def rewind_guides(self, guides):
+        """skh_rewind_guides, numpy in and numpy out: `guides` {"ids", "position", "normal"} of the current frame as render_guides returns them ->
+        {"position", "normal"}, (h, w, 4) float32: what to hand temporal() and moments() in their place"""
+        ids = np.ascontiguousarray(guides["ids"], np.uint32)
+        h, w = ids.shape[:2]
+        planes = {"ids": ids, "position_in": np.ascontiguousarray(guides["position"], np.float32), "normal_in": np.ascontiguousarray(guides["normal"], np.float32)}
+        return self._with_planes(planes, h, w, ("position", "normal"), lambda b: self.rewind_guides_device(
+            w, h, b["ids"], b["position_in"], b["normal_in"], b["position"], b["normal"]))
+
+    def rewind_info(self):
+        """skh_get_rewind_info: calls and pixels since the last reset_stats, the last call's wall time, the entries of the table in force"""
+        return self._info("skh_get_rewind_info", REWIND_INFO)
 
     def render_subframe(self, params, d_image=None):
         p = np.ascontiguousarray(params, dtype=S.FRAME_PARAMS)

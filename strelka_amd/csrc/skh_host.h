@@ -431,6 +431,15 @@ struct skh_context
     {
         skh_vdenoise_info info = {};
     } vd;
+
+    // object motion (skh_set_instance_motion, skh_rewind_guides; skh_motion.h): the table is an input of its own -- no scene setter touches it, and it is no
+    // entry of skh_stale.h.  It exists from a set with n > 0 until a set with n == 0 or skh_destroy.
+    struct Motion
+    {
+        DevBuf dTable;
+        uint32_t entries = 0;
+        skh_rewind_info info = {};
+    } rw;
 };
 
 // A caller changed `in`: every derived state that depends on it is invalidated (the table: skh_stale.h).

@@ -40,6 +40,7 @@ static_assert(sizeof(skh_hit) == 20 && sizeof(Light) == 112 && sizeof(Material) 
 #include "skh_denoise.h"
 #include "skh_temporal.h"
 #include "skh_variance.h"
+#include "skh_motion.h"
 
 // Sobol generator matrices for the 5 dimensions the reference tabulates (RandomSampler.h:139-164), produced from the
 // Joe-Kuo recurrences (d=2: s=1 a=0 m={1}; d=3: s=2 a=1 m={1,3}; d=4: s=3 a=1 m={1,3,1}; d=5: s=3 a=2 m={1,1,1}).
@@ -3332,6 +3333,168 @@ skh_status skh_get_vdenoise_info(skh_context* c, skh_vdenoise_info* out)
     return SKH_OK;
 }
 
+// ---- object motion (skh_motion.h): skh_instance_motion_from_transforms, skh_instance_motion_check, skh_set_instance_motion, skh_rewind_guides ----
+static_assert(sizeof(skh_instance_motion) == 96 && sizeof(skh_rewind_info) == 32, "ABI layout");
+
+// inverse of the row-major 3 x 3 `m` by adjugate / determinant, in the operation order the header writes out; false when the determinant is 0 or not finite
+static bool motion_inverse(const double m[3][3], double inv[3][3])
+{
+    double adj[3][3];
+    for (int i = 0; i < 3; ++i)
+        for (int j = 0; j < 3; ++j)
+            adj[i][j] = m[(j + 1) % 3][(i + 1) % 3] * m[(j + 2) % 3][(i + 2) % 3] - m[(j + 1) % 3][(i + 2) % 3] * m[(j + 2) % 3][(i + 1) % 3];
+    const double det = (m[0][0] * adj[0][0] + m[0][1] * adj[1][0]) + m[0][2] * adj[2][0];
+    if (det == 0.0 || !std::isfinite(det))
+        return false;
+    for (int i = 0; i < 3; ++i)
+        for (int j = 0; j < 3; ++j)
+            inv[i][j] = adj[i][j] / det;
+    return true;
+}
+
+skh_status skh_instance_motion_from_transforms(const float prev[12], const float cur[12], skh_instance_motion* out)
+{
+    if (!prev || !cur || !out)
+        return SKH_INVALID_ARGUMENT;
+    skh_instance_motion e = {};
+    e.to_prev[0] = e.to_prev[5] = e.to_prev[10] = 1.0f;
+    e.normal_to_prev[0] = e.normal_to_prev[4] = e.normal_to_prev[8] = 1.0f;
+    if (std::memcmp(prev, cur, 12 * sizeof(float)) == 0)
+    {
+        *out = e; // flags 0: the entry is skipped
+        return SKH_OK;
+    }
+    skh_instance_motion moved = e;
+    bool ok = true;
+    double A[3][3], B[3][3], a[3], b[3], Ai[3][3], Bi[3][3];
+    for (int i = 0; i < 3; ++i)
+    {
+        for (int j = 0; j < 3; ++j)
+            A[i][j] = prev[4 * i + j], B[i][j] = cur[4 * i + j];
+        a[i] = prev[4 * i + 3], b[i] = cur[4 * i + 3];
+    }
+    for (int k = 0; k < 12; ++k)
+        ok = ok && std::isfinite(prev[k]) && std::isfinite(cur[k]);
+    ok = ok && motion_inverse(B, Bi) && motion_inverse(A, Ai);
+    if (ok)
+        for (int i = 0; i < 3; ++i)
+        {
+            double L[3];
+            for (int j = 0; j < 3; ++j)
+            {
+                L[j] = (A[i][0] * Bi[0][j] + A[i][1] * Bi[1][j]) + A[i][2] * Bi[2][j];
+                moved.to_prev[4 * i + j] = (float)L[j];
+                const double K = (Ai[0][i] * B[j][0] + Ai[1][i] * B[j][1]) + Ai[2][i] * B[j][2];
+                moved.normal_to_prev[3 * i + j] = (float)K;
+            }
+            moved.to_prev[4 * i + 3] = (float)(a[i] - ((L[0] * b[0] + L[1] * b[1]) + L[2] * b[2]));
+        }
+    for (int k = 0; ok && k < 12; ++k)
+        ok = std::isfinite(moved.to_prev[k]);
+    for (int k = 0; ok && k < 9; ++k)
+        ok = std::isfinite(moved.normal_to_prev[k]);
+    if (ok)
+        moved.flags = SKH_MOTION_MOVED, *out = moved;
+    else
+        e.flags = SKH_MOTION_MOVED | SKH_MOTION_DROP, *out = e;
+    return SKH_OK;
+}
+
+// why the table is refused, or nullptr
+static const char* motion_refusal(const skh_instance_motion* table, uint32_t n)
+{
+    if (n > 0u && !table)
+        return "no table for n > 0";
+    for (uint32_t i = 0; i < n; ++i)
+    {
+        const skh_instance_motion& e = table[i];
+        if (e.flags & ~(SKH_MOTION_MOVED | SKH_MOTION_DROP))
+            return "an unknown flag bit";
+        if ((e.flags & SKH_MOTION_DROP) && !(e.flags & SKH_MOTION_MOVED))
+            return "DROP without MOVED";
+        if (e.reserved[0] != 0u || e.reserved[1] != 0u)
+            return "a non-zero reserved word";
+        if (e.flags == SKH_MOTION_MOVED)
+        {
+            for (float m : e.to_prev)
+                if (!std::isfinite(m))
+                    return "a matrix word that is not finite in a moved entry";
+            for (float m : e.normal_to_prev)
+                if (!std::isfinite(m))
+                    return "a matrix word that is not finite in a moved entry";
+        }
+    }
+    return nullptr;
+}
+
+skh_status skh_instance_motion_check(const skh_instance_motion* table, uint32_t n)
+{
+    return motion_refusal(table, n) ? SKH_INVALID_ARGUMENT : SKH_OK;
+}
+
+skh_status skh_set_instance_motion(skh_context* c, const skh_instance_motion* table, uint32_t n)
+{
+    if (!c)
+        return SKH_INVALID_ARGUMENT;
+    (void)hipSetDevice(c->dev.device);
+    if (const char* why = motion_refusal(table, n))
+    {
+        c->dev.err = std::string("skh_set_instance_motion: ") + why;
+        return SKH_INVALID_ARGUMENT;
+    }
+    if (n == 0u)
+    {
+        dev_free(c->rw.dTable);
+        c->rw.entries = 0;
+        return SKH_OK;
+    }
+    c->rw.entries = 0; // (until the new table is in place: a failed upload leaves none)
+    SKH_CHECK(dev_upload(c, c->rw.dTable, table, sizeof(skh_instance_motion) * (size_t)n));
+    c->rw.entries = n;
+    return SKH_OK;
+}
+
+skh_status skh_rewind_guides(skh_context* c, uint32_t width, uint32_t height, const void* d_ids, const void* d_position, const void* d_normal, void* d_position_out,
+                             void* d_normal_out)
+{
+    if (!c)
+        return SKH_INVALID_ARGUMENT;
+    (void)hipSetDevice(c->dev.device);
+    const char* why = nullptr;
+    if (width == 0u || height == 0u || (uint64_t)width * height > (1ull << 26))
+        why = "an empty image, or one of more than 2^26 pixels";
+    if (!why && (!d_ids || !d_position || !d_normal || !d_position_out || !d_normal_out))
+        why = "a NULL plane";
+    if (!why && (c->rw.entries == 0u || !c->rw.dTable.p))
+        why = "no motion table set (skh_set_instance_motion)";
+    if (why)
+    {
+        c->dev.err = std::string("skh_rewind_guides: ") + why;
+        return SKH_INVALID_ARGUMENT;
+    }
+    const auto t0 = std::chrono::steady_clock::now();
+    hipStream_t st = side_stream(c); // (skh_temporal's stream)
+    const dim3 grid(((width + 63u) / 64u) * ((height + 3u) / 4u)), block(64, 4); // (<= 2^24 + 2^20 tiles of 64 x 4 pixels, row-major)
+    k_mo_rewind<<<grid, block, 0, st>>>(width, height, c->rw.entries, c->rw.dTable.as<float4>(), reinterpret_cast<const uint4*>(d_ids),
+                                        reinterpret_cast<const float4*>(d_position), reinterpret_cast<const float4*>(d_normal),
+                                        reinterpret_cast<float4*>(d_position_out), reinterpret_cast<float4*>(d_normal_out));
+    SKH_TRY(c, hipGetLastError());
+    SKH_TRY(c, hipStreamSynchronize(st));
+    c->rw.info.calls++;
+    c->rw.info.pixels += (uint64_t)width * height;
+    c->rw.info.ms_last = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    return SKH_OK;
+}
+
+skh_status skh_get_rewind_info(skh_context* c, skh_rewind_info* out)
+{
+    if (!c || !out)
+        return SKH_INVALID_ARGUMENT;
+    *out = c->rw.info;
+    out->entries = c->rw.entries;
+    return SKH_OK;
+}
+
 // ---- skh_set_option: one row per name ----
 // What setting an option costs beyond the store.  OPT_REBUILD: a hierarchy depends on it -- the build is invalidated, and with it skh_update_accel's in-place
 // path (include/strelka_hip.h).  OPT_FRAME: the frame's buffers are sized by it -- they are allocated again when a frame exists.
@@ -3600,6 +3763,7 @@ skh_status skh_reset_stats(skh_context* c)
     c->tp.info.calls = c->tp.info.pixels = 0;
     c->mo.info.calls = c->mo.info.pixels = 0;
     c->vd.info.calls = c->vd.info.pixels = 0;
+    c->rw.info.calls = c->rw.info.pixels = 0;
     for (int k = 0; k < KC_COUNT; ++k)
     {
         c->timing.msClass[k] = 0.0;

@@ -725,6 +725,38 @@ def temporal_params(width, height, prev_aov_params=None, normal_min=TEMPORAL_NOR
     return p
 
 
+INSTANCE_MOTION = np.dtype([("to_prev", np.float32, 12), ("normal_to_prev", np.float32, 9), ("flags", np.uint32), ("reserved", np.uint32, 2)])  # skh_instance_motion, 96 B
+assert INSTANCE_MOTION.itemsize == 96
+MOTION_MOVED, MOTION_DROP = 1, 2
+
+
+def instance_motion(prev_instances, instances):
+    """the skh_instance_motion table that takes the current frame's guide planes back to the previous frame: one entry per instance, derived from the two
+    INSTANCE tables' transforms by the library's own skh_instance_motion_from_transforms (host only, no GPU).  An instance the previous table does not have
+    (the current one is longer) gets MOVED | DROP: it has no history."""
+    import ctypes as C
+
+    from . import capi
+
+    lib = capi.load()
+    prev = np.ascontiguousarray(prev_instances, dtype=INSTANCE).reshape(-1)
+    cur = np.ascontiguousarray(instances, dtype=INSTANCE).reshape(-1)
+    table = np.zeros(len(cur), INSTANCE_MOTION)
+    for i in range(len(cur)):
+        if i >= len(prev):
+            table[i]["to_prev"] = np.eye(3, 4, dtype=np.float32).reshape(12)
+            table[i]["normal_to_prev"] = np.eye(3, dtype=np.float32).reshape(9)
+            table[i]["flags"] = MOTION_MOVED | MOTION_DROP
+            continue
+        a, b = np.ascontiguousarray(prev[i]["transform"], np.float32), np.ascontiguousarray(cur[i]["transform"], np.float32)
+        e = np.zeros((), INSTANCE_MOTION)
+        st = lib.skh_instance_motion_from_transforms(a.ctypes.data_as(C.c_void_p), b.ctypes.data_as(C.c_void_p), e.ctypes.data_as(C.c_void_p))
+        if st != 0:
+            raise RuntimeError("skh_instance_motion_from_transforms failed")
+        table[i] = e
+    return table
+
+
 VDENOISE_PARAMS = np.dtype([("width", np.uint32), ("height", np.uint32), ("first_level", np.uint32), ("levels", np.uint32), ("sigma_luminance", np.float32),
                             ("sigma_normal", np.float32), ("sigma_plane", np.float32), ("albedo_floor", np.float32), ("epsilon", np.float32),
                             ("min_history", np.float32), ("flags", np.uint32), ("reserved", np.uint32, 5)])  # skh_vdenoise_params, 64 B

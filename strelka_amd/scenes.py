@@ -136,6 +136,41 @@ def cornell_box():
     return sc
 
 
+CORNELL_BLOCKS_SHORT, CORNELL_BLOCKS_TALL = 3, 4  # cornell_blocks(): the two blocks' instance ids
+
+
+def cornell_blocks():
+    """cornell_box() with the short and the tall block as instances of their own: the shell (floor, ceiling, back wall), the red wall, the green wall, the short
+    block (CORNELL_BLOCKS_SHORT), the tall block (CORNELL_BLOCKS_TALL) and the light proxy = 6 instances.  Each block's mesh is built about the centre of its
+    base; its rotation and translation are the instance's transform, so that a caller animates a block through update_accel (object motion)."""
+    sc = S.Scene()
+    white = sc.addMaterial(S.MAT_DIFFUSE, (0.725, 0.71, 0.68))
+    red = sc.addMaterial(S.MAT_DIFFUSE, (0.63, 0.065, 0.05))
+    green = sc.addMaterial(S.MAT_DIFFUSE, (0.14, 0.45, 0.091))
+    P, T = [], []
+    for q in (_quad((-1, -1, 1), (1, -1, 1), (1, -1, -1), (-1, -1, -1)), _quad((-1, 1, -1), (1, 1, -1), (1, 1, 1), (-1, 1, 1)),
+              _quad((-1, -1, -1), (1, -1, -1), (1, 1, -1), (-1, 1, -1))):  # floor, ceiling, back wall
+        T.append(q[1] + sum(len(p) for p in P))
+        P.append(q[0])
+    m_shell = _add_mesh(sc, np.concatenate(P), np.concatenate(T))
+    m_red = _add_mesh(sc, *_quad((-1, -1, 1), (-1, -1, -1), (-1, 1, -1), (-1, 1, 1)))
+    m_green = _add_mesh(sc, *_quad((1, -1, -1), (1, -1, 1), (1, 1, 1), (1, 1, -1)))
+    m_short = _add_mesh(sc, *_box_mesh((-0.3, 0, -0.3), (0.3, 0.6, 0.3), skip_bottom=True))
+    m_tall = _add_mesh(sc, *_box_mesh((-0.3, 0, -0.3), (0.3, 1.2, 0.3), skip_bottom=True))
+    I = np.eye(4)
+    sc.createInstance(S.INSTANCE_MESH, m_shell, white, I)
+    sc.createInstance(S.INSTANCE_MESH, m_red, red, I)
+    sc.createInstance(S.INSTANCE_MESH, m_green, green, I)
+    sc.createInstance(S.INSTANCE_MESH, m_short, white, S.translate((0.33, -1.0, 0.35)) @ S.rotate((0, 1, 0), math.radians(-17)))
+    sc.createInstance(S.INSTANCE_MESH, m_tall, white, S.translate((-0.33, -1.0, -0.3)) @ S.rotate((0, 1, 0), math.radians(17)))
+    xf = S.translate((0.0, 0.995, 0.0)) @ S.rotate((1, 0, 0), math.radians(-90))
+    sc.createLight({"type": 0, "xform": xf, "useXform": True, "width": 0.52, "height": 0.42, "color": (17.0, 12.0, 4.0), "intensity": 1.0})
+    cam = S.Camera(fov=39.3)
+    cam.lookAt((0.0, 0.0, 3.9), (0.0, 0.0, 0.0))
+    sc.addCamera(cam)
+    return sc
+
+
 def kitchen_standin(seed=1234, n_meshes=150, n_instances=2000, tri_lo=200, tri_hi=50000, target_tris=None):
     """C3 "kitchen stand-in" (SURVEY 8d): room 10 x 6 x 4 units, >= 1.0 M unique triangles in >= 2000 instances of
     >= 150 meshes (sizes log-uniform tri_lo..tri_hi, de-indexed like Mesh.cpp:140-178), 4 rect lights + 1 distant
