@@ -761,7 +761,8 @@ skh_status skh_get_denoise_info(skh_context* ctx, skh_denoise_info* out);
  *            DEMODULATE; a non-zero reserved word -- and a NULL image that the call needs, and the alias above.
  * Object motion: the call projects P as if nothing in the world had moved.  For moved instances hand it, as d_normal and d_position, the planes that
  * skh_rewind_guides (further below) writes.
- * Not part of it: neighbourhood colour clamping for lighting changes, separate diffuse / specular histories (luminance moments and variance guidance: skh_moments, below), what is seen in mirrors
+ * Lighting changes: a tap is accepted on geometry alone; skh_rectify (further below) clamps the history this call wrote to a fast history's window.
+ * Not part of it: separate diffuse / specular histories (luminance moments and variance guidance: skh_moments, below), what is seen in mirrors
  * and through glass (the guides describe the first surface). */
 #define SKH_TEMPORAL_DEMODULATE 1u
 
@@ -936,6 +937,65 @@ typedef struct skh_rewind_info
     uint64_t entries;       /* entries of the table in force (0: none) */
 } skh_rewind_info;
 skh_status skh_get_rewind_info(skh_context* ctx, skh_rewind_info* out);
+
+/* ---- History rectification: the long history skh_temporal wrote, clamped per pixel and channel to the mean +- k standard deviations of a second, short
+ *      ("fast") history over a small window on the same surface (new; DESIGN.md section 2, "History rectification").  skh_temporal accepts a tap on geometry
+ *      alone, so a surface whose LIGHTING changed (the shadow of an instance that moved) keeps the old light for max_history frames.  The fast history is what
+ *      the same skh_temporal writes with a small max_history from a previous fast history; it follows such a change within a few frames, and the long one keeps
+ *      its low noise wherever the two agree.  A pure function of caller-owned device planes, one pass, one kernel (skh_rectify.h).  Records, row order and
+ *      rounding are skh_temporal's: every product, sum, difference, quotient and square root is one rounded float32 operation, no fma; sqrtf is correctly
+ *      rounded; every comparison is written so that a NaN fails it; a skipped tap is selected out, never multiplied by zero; an address outside the image is
+ *      clamped to a legal one before the load.
+ *   inputs   d_image the image skh_temporal wrote (float rgba), IDS (instance_id and kind are used), ALBEDO (rgb; REMODULATE only), HISTORY the long history
+ *            skh_temporal wrote, {ill.rgb, n}, and FAST the fast history, the same record {f.rgb, nf}.
+ *   rectified   pixel p is RECTIFIED iff IDS(p).kind is 1 or 2, HISTORY(p) has finite rgb and a finite n >= 1, and FAST(p) has finite rgb and a finite nf >= 1.
+ *            Every other pixel copies d_image to d_out and d_history to d_history_out bit for bit and writes d_info as {0, 0, 0, 0}.  The alpha word of d_out is
+ *            d_image's, bit for bit, for every pixel.
+ *   window   dy = -radius ... radius outer, dx = -radius ... radius inner, step 1.  Tap q = p + (dx, dy) is TAKEN iff it lies in the image, IDS(q) has the kind and
+ *            the instance_id of IDS(p), and FAST(q) has finite rgb and a finite nf >= 1.  The centre of a rectified pixel is always taken, so s0 >= 1.
+ *   statistics   per channel, f = FAST(q)'s channel, two sweeps over the taken taps in that order:
+ *              first   s0 = s0 + 1, s1 = s1 + f;  mean = s1 / s0
+ *              second  d = f - mean, s2 = s2 + d d;  sd = sqrtf(s2 / s0)
+ *            (two sweeps and not sum f f - mean mean, whose cancellation has no honest error bar; how the second sweep gets at f is the kernel's business)
+ *   clamp    h = HISTORY(p)'s channel.  e = k sd, lo = mean - e, hi = mean + e;  r = h;  r = h < lo ? lo : r;  r = h > hi ? hi : r.  Bit c of mask (c = 0, 1, 2
+ *            for r, g, b) is set where h < lo or h > hi.  With k == +inf neither comparison is made: r = h, mask = 0 (selected, not computed as inf 0).
+ *   length   n' = n;  with SKH_RECTIFY_SHORTEN, mask != 0 and nf(p) < n:  n' = nf(p)
+ *   outputs  d_history_out = {r, n'};  d_out.rgb = r m with SKH_RECTIFY_REMODULATE, else r, m = albedo > albedo_floor ? albedo : albedo_floor (skh_denoise's
+ *            rule).  skh_temporal computes ill m in the same way, so an unclamped pixel's d_out has d_image's bits.
+ *            d_info, when not NULL: {(float)mask, s0, dmax, n'}, dmax = |r - h| of r, then g and b each replacing it where larger (a > comparison).
+ *   call     synchronous, on the stream skh_denoise uses.  d_out == d_image and d_history_out == d_history are allowed (a pixel reads only its own records of
+ *            those planes) and give the bits of the out-of-place call; d_history_out == d_fast and d_out == d_fast are refused (the window reads neighbours).
+ *            d_albedo may be NULL without REMODULATE.
+ *   effects  none on the frame: the accumulator, the AOV accumulators, the adaptive statistics and the ray counts are not read or written; sub-frames traced
+ *            ahead are not dropped.  No scratch memory: a context that never calls it allocates and launches nothing for it.
+ *   refused  with SKH_INVALID_ARGUMENT, nothing written, the previous state kept: what skh_rectify_check refuses -- width or height 0 or width * height >
+ *            2^26; a radius outside 1 ... 3; k <= 0 or NaN; an albedo_floor that is <= 0 or not finite; a flag bit other than the two; a non-zero reserved
+ *            word -- and a NULL image that the call needs, and the two aliases above.
+ * Not part of it: the moments of skh_moments stay unrectified (their variance lags a lighting change as the history did); what is seen in mirrors and through
+ * glass (the guides describe the first surface); deforming meshes. */
+#define SKH_RECTIFY_REMODULATE 1u /* d_out.rgb = r m */
+#define SKH_RECTIFY_SHORTEN 2u    /* a clamped pixel's history is no longer than its fast history */
+
+typedef struct skh_rectify_params
+{
+    uint32_t width, height; /* >= 1, width * height <= 2^26 */
+    uint32_t radius;        /* 1, 2 or 3: a 3 x 3, 5 x 5 or 7 x 7 window */
+    float k;                /* > 0; +inf is legal and clamps nothing */
+    float albedo_floor;     /* finite, > 0 */
+    uint32_t flags;         /* SKH_RECTIFY_* */
+    uint32_t reserved[8];   /* 0 */
+} skh_rectify_params;
+
+/* SKH_OK when *p is a setting skh_rectify accepts (needs no context and no GPU, as skh_temporal_check) */
+skh_status skh_rectify_check(const skh_rectify_params* p);
+skh_status skh_rectify(skh_context* ctx, const skh_rectify_params* p, const void* d_image, const void* d_ids, const void* d_albedo /* may be NULL */,
+                       const void* d_history, const void* d_fast, void* d_out, void* d_history_out, void* d_info /* may be NULL */);
+typedef struct skh_rectify_info
+{
+    uint64_t calls, pixels; /* since the last skh_reset_stats */
+    double ms_last;         /* wall time of the last call, its synchronisation included */
+} skh_rectify_info;
+skh_status skh_get_rectify_info(skh_context* ctx, skh_rectify_info* out);
 
 /* ---- the tonemap() + gammaCorrection post pass (postprocessing/Tonemappers.cu:111-135), in place on a
  *      device float4 image.  type: 0 none, 1 Reinhard, 2 ACES fitted, 3 ACES film; gamma <= 0 = off ---- */

@@ -260,14 +260,14 @@ void HipRender::freeGuides()
         g = nullptr;
     }
     for (void** g : { &mPrevGuide[0], &mPrevGuide[1], &mPrevGuide[2], &mHistory[0], &mHistory[1], &mVarianceImage, &mMotion, &mMoments[0], &mMoments[1],
-                      &mRewound[0], &mRewound[1] })
+                      &mRewound[0], &mRewound[1], &mFast[0], &mFast[1], &mRectifyImage })
     {
         if (mCtx && *g)
             skh_buffer_free(mCtx, *g);
         *g = nullptr;
     }
     mGuideWidth = mGuideHeight = 0;
-    mGuidesValid = mPrevGuidesValid = mHistoryValid = mMomentsValid = false;
+    mGuidesValid = mPrevGuidesValid = mHistoryValid = mMomentsValid = mFastValid = false;
 }
 
 bool HipRender::setDenoiser(bool on, const HipDenoise* params)
@@ -363,6 +363,62 @@ void HipRender::setInstanceMotion(bool on)
         check(skh_set_instance_motion(mCtx, nullptr, 0), "skh_set_instance_motion"); // (the library's table goes too)
 }
 
+bool HipRender::setHistoryRectification(bool on, const HipRectify* params)
+{
+    const HipRectify r = params ? *params : HipRectify();
+    // (checked here with an image that passes: the real one is render()'s; the fast length through the temporal call it is for)
+    float fast = 0.0f;
+    const skh_rectify_params probe = hipRectifyParams(r, 1u, 1u, 0.05f, &fast);
+    skh_temporal_params fastProbe = hipTemporalParams(HipTemporal(), 1u, 1u, nullptr, 1.0f, 1.0f);
+    fastProbe.max_history = fast;
+    if (on && (skh_rectify_check(&probe) != SKH_OK || skh_temporal_check(&fastProbe) != SKH_OK))
+    {
+        mError = "setHistoryRectification: the setting was refused (radius 1 .. 3, k > 0, finite fastHistory >= 1)";
+        return false;
+    }
+    if (!on && !mRectify)
+        return true; // (off already: the history stays)
+    dropHistory(); // (the two histories start together)
+    memset(&mRectifyApplied, 0, sizeof(mRectifyApplied));
+    mRectifyFastApplied = 0.0f;
+    mRectify = on;
+    if (on)
+        mRectifySetting = r;
+    else
+        for (void** g : { &mFast[0], &mFast[1], &mRectifyImage })
+        {
+            if (mCtx && *g)
+                skh_buffer_free(mCtx, *g);
+            *g = nullptr;
+        }
+    return true;
+}
+
+bool HipRender::fastHistory(const skh_temporal_params& tp, const void* dColor, const void* normal, const void* position)
+{
+    if (!mRectify || !mFast[0] || !mFast[1] || !mRectifyImage) // (the three buffers come with the guide buffers: renderGuides)
+        return false;
+    skh_temporal_params tf = tp;
+    hipRectifyParams(mRectifySetting, tp.width, tp.height, tp.albedo_floor, &tf.max_history);
+    tf.initial_length = std::min(tf.initial_length, tf.max_history);
+    // (without a fast history of its own the stored history is both: read under the shorter max_history it has the length min(n, fastHistory))
+    const void* prev = mFastValid ? mFast[mFastStored] : mHistory[mHistoryStored];
+    if (!check(skh_temporal(mCtx, &tf, dColor, mGuide[0], normal, position, mGuide[3], prev, mPrevGuide[0], mPrevGuide[1], mPrevGuide[2], mRectifyImage,
+                            mFast[1 - mFastStored], nullptr),
+               "skh_temporal"))
+        return false;
+    mRectifyFastApplied = tf.max_history;
+    return true; // (the stored fast history stays the stored one until the long history's call has succeeded: rectifyHistory)
+}
+
+void HipRender::rectifyHistory(const skh_temporal_params& tp, void* dImage, void* dHistory)
+{
+    const skh_rectify_params rp = hipRectifyParams(mRectifySetting, tp.width, tp.height, tp.albedo_floor);
+    mFastStored = 1 - mFastStored, mFastValid = true; // (the two histories advance together)
+    if (check(skh_rectify(mCtx, &rp, dImage, mGuide[0], mGuide[3], dHistory, mFast[mFastStored], dImage, dHistory, nullptr), "skh_rectify"))
+        mRectifyApplied = rp;
+}
+
 // With object motion on, when the instance tables of the two guide sets differ in a transform: the current set's position and normal planes, rewound into the
 // previous frame's world, in mRewound.  false: nothing moved (or the feature is off, or a call failed) -- the caller hands on the true planes.
 bool HipRender::rewindGuides(uint32_t width, uint32_t height)
@@ -399,7 +455,7 @@ bool HipRender::rewindGuides(uint32_t width, uint32_t height)
 // (ids, normal, position) and its world_to_clip first become the previous frame's.
 bool HipRender::renderGuides()
 {
-    if (mGuideWidth != mWidth || mGuideHeight != mHeight || (mTemporal && !mHistory[0]))
+    if (mGuideWidth != mWidth || mGuideHeight != mHeight || (mTemporal && !mHistory[0]) || (mTemporal && mRectify && !mFast[0]))
     {
         freeGuides();
         for (void*& g : mGuide)
@@ -407,6 +463,10 @@ bool HipRender::renderGuides()
                 return false;
         if (mTemporal)
             for (void** g : { &mPrevGuide[0], &mPrevGuide[1], &mPrevGuide[2], &mHistory[0], &mHistory[1] })
+                if (!check(skh_buffer_alloc(mCtx, (size_t)16 * mWidth * mHeight, g), "skh_buffer_alloc"))
+                    return false;
+        if (mTemporal && mRectify) // (history rectification's three buffers: here, before the guide pass and the sample, not between two image passes)
+            for (void** g : { &mFast[0], &mFast[1], &mRectifyImage })
                 if (!check(skh_buffer_alloc(mCtx, (size_t)16 * mWidth * mHeight, g), "skh_buffer_alloc"))
                     return false;
         mGuideWidth = mWidth, mGuideHeight = mHeight;
@@ -899,11 +959,16 @@ void HipRender::render(Buffer* output)
         const bool rewound = had && rewindGuides(width, height);
         const void* tNormal = rewound ? mRewound[1] : mGuide[1];
         const void* tPosition = rewound ? mRewound[0] : mGuide[2];
+        // history rectification: the fast history first, from the same planes
+        const bool rectified = had && fastHistory(tp, dImage, tNormal, tPosition);
         // the blended image goes to this object's buffer: the output image keeps the raw sample for skh_moments, then takes the filtered result
         if (check(skh_temporal(mCtx, &tp, dImage, mGuide[0], tNormal, tPosition, mGuide[3], had ? mHistory[mHistoryStored] : nullptr, mPrevGuide[0], mPrevGuide[1],
                                mPrevGuide[2], mVarianceImage, mHistory[next], mMotion),
                   "skh_temporal"))
         {
+            mFastValid = false; // (the history stored here is both, unless the next line stores a fast one beside it)
+            if (rectified)
+                rectifyHistory(tp, mVarianceImage, mHistory[next]);
             mHistoryStored = next, mHistoryValid = true;
             mTemporalApplied = tp, mTemporalHadPrevious = had;
             if (check(skh_moments(mCtx, &tp, dImage, mGuide[0], tPosition, mGuide[3], hadMoments ? mMotion : nullptr, hadMoments ? mMoments[mMomentsStored] : nullptr,
@@ -930,11 +995,17 @@ void HipRender::render(Buffer* output)
             const bool had = mHistoryValid && mPrevGuidesValid;
             const skh_temporal_params tp = hipTemporalParams(mTemporalSetting, width, height, had ? mPrevWorldToClip : nullptr, 1.0f, mSceneDiagonal);
             const bool rewound = had && rewindGuides(width, height); // (moved instances: the rewound normal and position planes)
-            if (check(skh_temporal(mCtx, &tp, dImage, mGuide[0], rewound ? mRewound[1] : mGuide[1], rewound ? mRewound[0] : mGuide[2], mGuide[3],
-                                   had ? mHistory[mHistoryStored] : nullptr, mPrevGuide[0], mPrevGuide[1],
+            const void* tNormal = rewound ? mRewound[1] : mGuide[1];
+            const void* tPosition = rewound ? mRewound[0] : mGuide[2];
+            // history rectification: the fast history first, while the output image still holds the raw sample
+            const bool rectified = had && fastHistory(tp, dImage, tNormal, tPosition);
+            if (check(skh_temporal(mCtx, &tp, dImage, mGuide[0], tNormal, tPosition, mGuide[3], had ? mHistory[mHistoryStored] : nullptr, mPrevGuide[0], mPrevGuide[1],
                                    mPrevGuide[2], dImage, mHistory[next], nullptr),
                       "skh_temporal"))
             {
+                mFastValid = false; // (the history stored here is both, unless the next line stores a fast one beside it)
+                if (rectified)
+                    rectifyHistory(tp, dImage, mHistory[next]);
                 mHistoryStored = next, mHistoryValid = true;
                 mTemporalApplied = tp, mTemporalHadPrevious = had;
             }
@@ -949,7 +1020,7 @@ void HipRender::render(Buffer* output)
                                    mHistory[mHistoryStored], nullptr),
                       "skh_temporal"))
             {
-                mHistoryValid = true;
+                mHistoryValid = true, mFastValid = false; // (the accumulator is both histories)
                 mTemporalApplied = tp, mTemporalHadPrevious = false;
             }
         }

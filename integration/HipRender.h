@@ -138,6 +138,29 @@ inline skh_vdenoise_params hipVarianceParams(const HipVariance& v, const HipDeno
     return p;
 }
 
+struct HipRectify // HipRender::setHistoryRectification: a numeric field that is 0 takes its default (docs/LOG.md, "History rectification", has the table they come from)
+{
+    uint32_t radius = 0;       // 1: a 3 x 3 window; 2 and 3 are legal
+    float k = 0.0f;            // 2: the long history is clamped to the fast one's mean +- 2 standard deviations
+    float fastHistory = 0.0f;  // 4: the fast history's max_history
+    bool shorten = true;       // a clamped pixel's history is no longer than its fast history (SKH_RECTIFY_SHORTEN)
+};
+
+// the skh_rectify_params render() hands to skh_rectify for a HipRectify setting: REMODULATE (hipTemporalParams demodulates), the temporal call's albedo floor;
+// *fastHistory, when given: the max_history of the fast history's skh_temporal call
+inline skh_rectify_params hipRectifyParams(const HipRectify& r, uint32_t width, uint32_t height, float albedoFloor, float* fastHistory = nullptr)
+{
+    skh_rectify_params p = {};
+    p.width = width, p.height = height;
+    p.radius = r.radius != 0u ? r.radius : 1u;
+    p.k = r.k != 0.0f ? r.k : 2.0f;
+    p.albedo_floor = albedoFloor;
+    p.flags = SKH_RECTIFY_REMODULATE | (r.shorten ? SKH_RECTIFY_SHORTEN : 0u);
+    if (fastHistory)
+        *fastHistory = r.fastHistory != 0.0f ? r.fastHistory : 4.0f;
+    return p;
+}
+
 class HipRender : public Render
 {
 public:
@@ -230,7 +253,8 @@ public:
     //   a call that continues one                shows the accumulator's image as before and stores it as the history, with its true length
     //                                            min(samples accumulated, maxHistory): skh_temporal without a previous frame, its image output discarded
     //   the history is dropped after             a resize, setLightShapes / setEnvironment changes, the settings changes that restart the accumulation, setTemporal.
-    //                                            Moved instances keep it: the plane test answers for the geometry (their shadows lag)
+    //                                            Moved instances keep it: the plane test answers for the geometry, and their shadows on other surfaces
+    //                                            follow within a few frames with setHistoryRectification
     //   rotateSamples                            a start call whose camera differs from the previous call's is traced with enable_accumulation = 0 and
     //                                            subframe_index = (a counter advanced per such call) % sppTotal: the raw sample of that index, so that consecutive
     //                                            moving frames do not repeat sample 0's random numbers.  mSubframeIndex stays 0: the first still call starts a
@@ -269,6 +293,26 @@ public:
     // skh_denoise_variance and the stored guide sets keep the true planes.  With it off -- and on every call that does not reproject across a transform
     // change -- render() makes the calls it made before.
     void setInstanceMotion(bool on);
+    // History rectification (skh_rectify; new), OFF by default.  It acts only with setTemporal on, and only on a render() that reprojects a stored history.  On
+    // such a call a second skh_temporal call -- the same planes, the rewound ones when setInstanceMotion rewound them; max_history = fastHistory and initial_length
+    // min'ed to it; the previous history the stored FAST history; its image output discarded into a buffer of this object -- writes the new fast history, and after
+    // the long history's skh_temporal call one skh_rectify call clamps image and long history in place to the fast history's window.  (The fast call comes first:
+    // the long one works in place on the raw sample both read.)  skh_moments and the two filters then run on the rectified image as they ran on skh_temporal's.
+    // Two fast-history buffers change places as the histories do and are dropped whenever the history is.  A call that continues an accumulation, or starts one
+    // without a stored history, makes exactly the calls it makes without the setting: the history it stores is both histories -- the next fast call reads it under
+    // its own max_history, which gives it the length min(samples, fastHistory).  params == nullptr: every default.  false: the setting was refused
+    // (skh_rectify_check, and a fastHistory that is not finite or < 1; the previous one stays).  The history is dropped by a call that changes the setting (not by
+    // turning off what is off); the three buffers are allocated with the guide buffers, by the next guide pass.  With it off, render() makes
+    // the calls it made before.  A light change still drops the history (setLightShapes / setEnvironment): keeping it for this pass to correct is the follow-up.
+    bool setHistoryRectification(bool on, const HipRectify* params = nullptr);
+    // what the last rectifying render() handed to skh_rectify (false: none yet); fastHistory: the max_history of that call's fast skh_temporal call
+    bool rectifyParams(skh_rectify_params& p, float* fastHistory = nullptr) const
+    {
+        p = mRectifyApplied;
+        if (fastHistory)
+            *fastHistory = mRectifyFastApplied;
+        return mRectifyApplied.width != 0u;
+    }
     // the frame parameters' sample choice of the last render(): subframe_index and enable_accumulation as handed to skh_render_subframe
     void lastSample(uint32_t& subframeIndex, uint32_t& enableAccumulation) const
     {
@@ -340,10 +384,23 @@ private:
     std::vector<skh_instance> mGuideInstances, mPrevGuideInstances; // the instance table as sent when mGuide / mPrevGuide were rendered (setInstanceMotion)
     void* mRewound[2] = {};  // position | normal of mGuide in the previous frame's world (skh_rewind_guides' outputs)
     bool rewindGuides(uint32_t width, uint32_t height); // true: mRewound holds this call's rewound planes
+    bool mRectify = false;
+    HipRectify mRectifySetting;
+    skh_rectify_params mRectifyApplied = {};
+    float mRectifyFastApplied = 0.0f;
+    void* mFast[2] = {};            // the fast history, {illumination.rgb, n} per pixel; mFast[mFastStored] is the stored one
+    int mFastStored = 0;
+    bool mFastValid = false;        // false: the stored long history is the fast one too (a continued accumulation, a first frame)
+    void* mRectifyImage = nullptr;  // the fast skh_temporal call's image output: discarded
+    // the fast history's skh_temporal call for the temporal call `tp` on the raw image dColor; true: mFast[1 - mFastStored] holds this frame's fast history (not yet the stored one)
+    bool fastHistory(const skh_temporal_params& tp, const void* dColor, const void* normal, const void* position);
+    // after the long history's call succeeded: that fast history becomes the stored one, and skh_rectify runs in place on dImage and dHistory (what the long call wrote)
+    void rectifyHistory(const skh_temporal_params& tp, void* dImage, void* dHistory);
     void dropHistory()
     {
         mHistoryValid = false;
         mMomentsValid = false;
+        mFastValid = false;
     }
     void uploadMaterials(); // MaterialDescription list -> skh_material blocks + textures (OptixRender.cpp:1270-1433)
 };

@@ -37,7 +37,8 @@ SYMBOLS = ["skh_create", "skh_destroy", "skh_last_error", "skh_abi_version", "sk
            "skh_denoise_check", "skh_denoise", "skh_get_denoise_info", "skh_buffer_upload",
            "skh_temporal_check", "skh_temporal", "skh_get_temporal_info",
            "skh_moments", "skh_get_moments_info", "skh_vdenoise_check", "skh_denoise_variance", "skh_get_vdenoise_info",
-           "skh_instance_motion_from_transforms", "skh_instance_motion_check", "skh_set_instance_motion", "skh_rewind_guides", "skh_get_rewind_info"]
+           "skh_instance_motion_from_transforms", "skh_instance_motion_check", "skh_set_instance_motion", "skh_rewind_guides", "skh_get_rewind_info",
+           "skh_rectify_check", "skh_rectify", "skh_get_rectify_info"]
 
 BUILD_INFO = np.dtype([("triangles", np.uint32), ("nodes", np.uint32), ("reinsert_rounds", np.uint32), ("reinsert_moves", np.uint32),
                        ("reinsert_min_size", np.uint32), ("refit", np.uint32), ("cost_before", np.float64), ("cost_after", np.float64),
@@ -70,6 +71,8 @@ VDENOISE_INFO = np.dtype([("calls", np.uint64), ("pixels", np.uint64), ("ms_last
 assert VDENOISE_INFO.itemsize == 32
 REWIND_INFO = np.dtype([("calls", np.uint64), ("pixels", np.uint64), ("ms_last", np.float64), ("entries", np.uint64)])
 assert REWIND_INFO.itemsize == 32
+RECTIFY_INFO = np.dtype([("calls", np.uint64), ("pixels", np.uint64), ("ms_last", np.float64)])
+assert RECTIFY_INFO.itemsize == 24
 # skh_light_shape_probe: kind -> (number, words in, words out) per record
 LSHAPE_PROBES = {"sample": (0, 6, 13), "pdf": (1, 7, 2)}
 # skh_emitter_probe: kind -> (number, words in, words out) per record
@@ -159,6 +162,9 @@ def load():
     lib.skh_set_instance_motion.argtypes = [vp, vp, u32]
     lib.skh_rewind_guides.argtypes = [vp, u32, u32, vp, vp, vp, vp, vp]
     lib.skh_get_rewind_info.argtypes = [vp, vp]
+    lib.skh_rectify_check.argtypes = [vp]
+    lib.skh_rectify.argtypes = [vp] * 10
+    lib.skh_get_rectify_info.argtypes = [vp, vp]
     lib.skh_buffer_upload.argtypes = [vp, vp, vp, C.c_size_t]
     lib.skh_resize.argtypes = [vp, u32, u32]
     lib.skh_set_tiles.argtypes = [vp, u32, vp, u32]
@@ -229,6 +235,12 @@ def temporal_check(params):
     """skh_temporal_check: would skh_temporal accept these S.TEMPORAL_PARAMS?  (needs no context and no GPU)"""
     p = np.ascontiguousarray(params, dtype=S.TEMPORAL_PARAMS)
     return load().skh_temporal_check(_p(p)) == 0
+
+
+def rectify_check(params):
+    """skh_rectify_check: would skh_rectify accept these S.RECTIFY_PARAMS?  (needs no context and no GPU)"""
+    p = np.ascontiguousarray(params, dtype=S.RECTIFY_PARAMS)
+    return load().skh_rectify_check(_p(p)) == 0
 
 
 def moments_check(params):
@@ -751,6 +763,29 @@ class Context:
     def rewind_info(self):
         """skh_get_rewind_info: calls and pixels since the last reset_stats, the last call's wall time, the entries of the table in force"""
         return self._info("skh_get_rewind_info", REWIND_INFO)
+
+    def rectify_device(self, params, d_image, d_ids, d_albedo, d_history, d_fast, d_out, d_history_out, d_info=None):
+        """skh_rectify on caller-owned device planes (d_out may be d_image and d_history_out may be d_history; neither may be d_fast; d_albedo may be None without
+        REMODULATE; d_info None = no info plane)"""
+        p = np.ascontiguousarray(params, dtype=S.RECTIFY_PARAMS)
+        self._ck(self.lib.skh_rectify(self.h, _p(p), d_image, d_ids, d_albedo, d_history, d_fast, d_out, d_history_out, d_info), "skh_rectify")
+
+    def rectify(self, image, guides, history, fast, params, info=True):
+        """skh_rectify, numpy in and numpy out: `image` and `history` as temporal() returned them, `fast` the "history" of the temporal() call with the short
+        max_history, `guides` {"ids", "albedo"} of the current frame ("albedo" may be missing without REMODULATE), `params` S.rectify_params ->
+        {"image", "history", "info"}, (h, w, 4) float32 each (without `info` the call gets no d_info and "info" is missing)"""
+        p = np.array(params, dtype=S.RECTIFY_PARAMS)
+        h, w = int(p["height"]), int(p["width"])
+        f32 = lambda a: None if a is None else np.ascontiguousarray(a, np.float32)
+        planes = {"image_in": f32(image), "ids": None if guides.get("ids") is None else np.ascontiguousarray(guides["ids"], np.uint32),
+                  "albedo": f32(guides.get("albedo")), "history_in": f32(history), "fast": f32(fast)}
+        outputs = ("image", "history", "info") if info else ("image", "history")
+        return self._with_planes(planes, h, w, outputs, lambda b: self.rectify_device(
+            p, b.get("image_in"), b.get("ids"), b.get("albedo"), b.get("history_in"), b.get("fast"), b["image"], b["history"], b.get("info")))
+
+    def rectify_info(self):
+        """skh_get_rectify_info: calls and pixels since the last reset_stats, the last call's wall time"""
+        return self._info("skh_get_rectify_info", RECTIFY_INFO)
 
     def render_subframe(self, params, d_image=None):
         p = np.ascontiguousarray(params, dtype=S.FRAME_PARAMS)

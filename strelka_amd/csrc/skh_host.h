@@ -440,6 +440,12 @@ struct skh_context
         uint32_t entries = 0;
         skh_rewind_info info = {};
     } rw;
+
+    // history rectification (skh_rectify; skh_rectify.h): no scratch, nothing but this lives between two calls
+    struct Rectify
+    {
+        skh_rectify_info info = {};
+    } rc;
 };
 
 // A caller changed `in`: every derived state that depends on it is invalidated (the table: skh_stale.h).

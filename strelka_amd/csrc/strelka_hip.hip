@@ -41,6 +41,7 @@ static_assert(sizeof(skh_hit) == 20 && sizeof(Light) == 112 && sizeof(Material) 
 #include "skh_temporal.h"
 #include "skh_variance.h"
 #include "skh_motion.h"
+#include "skh_rectify.h"
 
 // Sobol generator matrices for the 5 dimensions the reference tabulates (RandomSampler.h:139-164), produced from the
 // Joe-Kuo recurrences (d=2: s=1 a=0 m={1}; d=3: s=2 a=1 m={1,3}; d=4: s=3 a=1 m={1,3,1}; d=5: s=3 a=2 m={1,1,1}).
@@ -2382,7 +2383,11 @@ skh_status skh_buffer_alloc(skh_context* c, size_t bytes, void** out)
     (void)hipSetDevice(c->dev.device);
     *out = nullptr;
     SKH_TRY(c, hipMalloc(out, bytes ? bytes : 16));
-    SKH_TRY(c, hipMemset(*out, 0, bytes ? bytes : 16));
+    // (cleared on the stream that skh_buffer_upload and the image passes use, and waited for: a null-stream memset queues behind a pass traced ahead on the main
+    // stream and would land after an upload or a kernel that the side stream has already run on the new buffer)
+    hipStream_t st = side_stream(c);
+    SKH_TRY(c, hipMemsetAsync(*out, 0, bytes ? bytes : 16, st));
+    SKH_TRY(c, hipStreamSynchronize(st));
     return SKH_OK;
 }
 skh_status skh_buffer_free(skh_context* c, void* p)
@@ -3495,6 +3500,88 @@ skh_status skh_get_rewind_info(skh_context* c, skh_rewind_info* out)
     return SKH_OK;
 }
 
+// ---- history rectification (skh_rectify.h): skh_rectify_check, skh_rectify, skh_get_rectify_info ----
+static_assert(sizeof(skh_rectify_params) == 56 && sizeof(skh_rectify_info) == 24, "ABI layout");
+
+// why *p is refused, or nullptr
+static const char* rectify_refusal(const skh_rectify_params* p)
+{
+    if (!p)
+        return "no parameters";
+    if (p->width == 0u || p->height == 0u || (uint64_t)p->width * p->height > (1ull << 26))
+        return "an empty image, or one of more than 2^26 pixels";
+    if (p->radius < 1u || p->radius > 3u)
+        return "a radius outside 1 ... 3";
+    if (!(p->k > 0.0f)) // (a NaN too; +inf is legal)
+        return "a k that is <= 0 or NaN";
+    if (!std::isfinite(p->albedo_floor) || !(p->albedo_floor > 0.0f))
+        return "an albedo_floor that is <= 0 or not finite";
+    if (p->flags & ~(SKH_RECTIFY_REMODULATE | SKH_RECTIFY_SHORTEN))
+        return "an unknown flag bit";
+    for (uint32_t r : p->reserved)
+        if (r != 0u)
+            return "a non-zero reserved word";
+    return nullptr;
+}
+
+skh_status skh_rectify_check(const skh_rectify_params* p)
+{
+    return rectify_refusal(p) ? SKH_INVALID_ARGUMENT : SKH_OK;
+}
+
+skh_status skh_rectify(skh_context* c, const skh_rectify_params* p, const void* d_image, const void* d_ids, const void* d_albedo, const void* d_history,
+                       const void* d_fast, void* d_out, void* d_history_out, void* d_info)
+{
+    if (!c)
+        return SKH_INVALID_ARGUMENT;
+    (void)hipSetDevice(c->dev.device);
+    const char* why = rectify_refusal(p);
+    if (!why && (!d_image || !d_ids || !d_history || !d_fast || !d_out || !d_history_out))
+        why = "a NULL image";
+    if (!why && (p->flags & SKH_RECTIFY_REMODULATE) && !d_albedo)
+        why = "a flag that needs the albedo plane, and no albedo plane";
+    if (!why && (d_history_out == d_fast || d_out == d_fast))
+        why = "an output that is d_fast (the window reads neighbours)";
+    if (why)
+    {
+        c->dev.err = std::string("skh_rectify: ") + why;
+        return SKH_INVALID_ARGUMENT;
+    }
+    const auto t0 = std::chrono::steady_clock::now();
+    hipStream_t st = side_stream(c); // (skh_temporal's stream)
+    RcP rp;
+    rp.width = p->width, rp.height = p->height, rp.k = p->k, rp.albedoFloor = p->albedo_floor, rp.flags = p->flags, rp.kInf = std::isinf(p->k) ? 1u : 0u;
+    const dim3 grid(((p->width + 63u) / 64u) * ((p->height + 3u) / 4u)), block(64, 4); // (<= 2^24 + 2^20 tiles of 64 x 4 pixels, row-major)
+    const uint4* image = reinterpret_cast<const uint4*>(d_image);
+    const uint4* ids = reinterpret_cast<const uint4*>(d_ids);
+    const float4* albedo = reinterpret_cast<const float4*>(d_albedo);
+    const uint4* history = reinterpret_cast<const uint4*>(d_history);
+    const float4* fast = reinterpret_cast<const float4*>(d_fast);
+    uint4* out = reinterpret_cast<uint4*>(d_out);
+    uint4* historyOut = reinterpret_cast<uint4*>(d_history_out);
+    float4* info = reinterpret_cast<float4*>(d_info);
+    if (p->radius == 1u)
+        k_rc_rectify<1><<<grid, block, 0, st>>>(rp, image, ids, albedo, history, fast, out, historyOut, info);
+    else if (p->radius == 2u)
+        k_rc_rectify<2><<<grid, block, 0, st>>>(rp, image, ids, albedo, history, fast, out, historyOut, info);
+    else
+        k_rc_rectify<3><<<grid, block, 0, st>>>(rp, image, ids, albedo, history, fast, out, historyOut, info);
+    SKH_TRY(c, hipGetLastError());
+    SKH_TRY(c, hipStreamSynchronize(st));
+    c->rc.info.calls++;
+    c->rc.info.pixels += (uint64_t)p->width * p->height;
+    c->rc.info.ms_last = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    return SKH_OK;
+}
+
+skh_status skh_get_rectify_info(skh_context* c, skh_rectify_info* out)
+{
+    if (!c || !out)
+        return SKH_INVALID_ARGUMENT;
+    *out = c->rc.info;
+    return SKH_OK;
+}
+
 // ---- skh_set_option: one row per name ----
 // What setting an option costs beyond the store.  OPT_REBUILD: a hierarchy depends on it -- the build is invalidated, and with it skh_update_accel's in-place
 // path (include/strelka_hip.h).  OPT_FRAME: the frame's buffers are sized by it -- they are allocated again when a frame exists.
@@ -3764,6 +3851,7 @@ skh_status skh_reset_stats(skh_context* c)
     c->mo.info.calls = c->mo.info.pixels = 0;
     c->vd.info.calls = c->vd.info.pixels = 0;
     c->rw.info.calls = c->rw.info.pixels = 0;
+    c->rc.info.calls = c->rc.info.pixels = 0;
     for (int k = 0; k < KC_COUNT; ++k)
     {
         c->timing.msClass[k] = 0.0;

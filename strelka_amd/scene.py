@@ -757,6 +757,26 @@ def instance_motion(prev_instances, instances):
     return table
 
 
+RECTIFY_PARAMS = np.dtype([("width", np.uint32), ("height", np.uint32), ("radius", np.uint32), ("k", np.float32), ("albedo_floor", np.float32), ("flags", np.uint32),
+                           ("reserved", np.uint32, 8)])  # skh_rectify_params, 56 B
+assert RECTIFY_PARAMS.itemsize == 56
+RECTIFY_REMODULATE, RECTIFY_SHORTEN = 1, 2
+# the defaults of rectify_params (DESIGN.md section 2 "History rectification"; the figures are from the table in docs/LOG.md, "History rectification")
+RECTIFY_RADIUS = 1            # 3 x 3.  Error on the changed / unchanged region 8 frames after the step: 0.0203 / 0.0116; radius 2 0.0230 / 0.0118, radius 3 0.0254 / 0.0147, at 2.4 and 4.2 x the time
+RECTIFY_K = 2.0               # k 1: 0.0146 / 0.0152, 11.9 % of the unchanged pixels clamped every frame (k 2: 1.5 %); k 3: 0.0248 / 0.0109
+RECTIFY_FAST_HISTORY = 4.0    # the fast history's max_history; with 8: 0.0361 / 0.0105 (it still holds the old shadow itself)
+RECTIFY_SHORTEN_DEFAULT = True  # without it a clamped pixel keeps alpha 1 / 32: 0.0250 / 0.0108; today's skh_temporal alone: 0.0500 / 0.0111
+
+
+def rectify_params(width, height, radius=RECTIFY_RADIUS, k=RECTIFY_K, shorten=RECTIFY_SHORTEN_DEFAULT, albedo_floor=DENOISE_ALBEDO_FLOOR, remodulate=True):
+    """skh_rectify_params.  The fast history skh_rectify reads is what temporal_params(..., max_history=RECTIFY_FAST_HISTORY) makes skh_temporal write from the
+    previous fast history; `remodulate` goes with a temporal call that demodulated."""
+    p = np.zeros((), RECTIFY_PARAMS)
+    p["width"], p["height"], p["radius"], p["k"], p["albedo_floor"] = width, height, radius, k, albedo_floor
+    p["flags"] = (RECTIFY_REMODULATE if remodulate else 0) | (RECTIFY_SHORTEN if shorten else 0)
+    return p
+
+
 VDENOISE_PARAMS = np.dtype([("width", np.uint32), ("height", np.uint32), ("first_level", np.uint32), ("levels", np.uint32), ("sigma_luminance", np.float32),
                             ("sigma_normal", np.float32), ("sigma_plane", np.float32), ("albedo_floor", np.float32), ("epsilon", np.float32),
                             ("min_history", np.float32), ("flags", np.uint32), ("reserved", np.uint32, 5)])  # skh_vdenoise_params, 64 B
