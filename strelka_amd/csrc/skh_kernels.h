@@ -643,7 +643,7 @@ SKH_DI bool slot_to_pixel(const FrameP& fp, const uint32_t* __restrict__ tileXY,
 // workgroup (a single queue-tail word sustains only ~88 returning atomics per microsecond on MI355X, so per-wave
 // atomics would serialise a 2 M-path launch for ~0.4 ms).  All threads of the block must call it.
 #define SKH_COMPACT_MAX_WAVES 8
-SKH_DI uint32_t block_compact(bool emit, uint32_t* counter, uint32_t* s_wave /*[SKH_COMPACT_MAX_WAVES + 1]*/)
+SKH_DI uint32_t block_compact(bool emit, uint32_t* counter, uint32_t* s_wave /*[SKH_COMPACT_MAX_WAVES + 1]*/, bool reuse = true /* s_wave serves another call behind this one */)
 {
     const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6, nw = blockDim.x >> 6;
     const unsigned long long m = __ballot(emit);
@@ -663,7 +663,8 @@ SKH_DI uint32_t block_compact(bool emit, uint32_t* counter, uint32_t* s_wave /*[
     }
     __syncthreads();
     const uint32_t r = s_wave[SKH_COMPACT_MAX_WAVES] + s_wave[wave] + rank_below(m);
-    __syncthreads(); // s_wave is reused by the next call
+    if (reuse)
+        __syncthreads(); // s_wave is reused by the next call
     return r;
 }
 // Two compactions with one round of barriers and both queue-tail atomics in flight together (k_shade emits a continuation
@@ -1024,7 +1025,33 @@ __global__ void __launch_bounds__(256) k_emit_probe_mtex(EmitP em, MtexP mt, Dev
                                                 // continuation code is gone): kitchen k_shade 30.7 -> 27.8 ms, Cornell 8.97 -> 8.20; six waves spill 27 dwords (30.2 ms); the hair build
                                                 // (Chiang BSDF) spills 27 at five (16.7 -> 18.2 ms) and stays at four
 #endif
-#define SKH_SHADE_ATTR(HAIR) __attribute__((amdgpu_waves_per_eu(SKH_SHADE_WAVES(HAIR), SKH_SHADE_WAVES(HAIR))))
+// POS: the bounce's position in the path, a constant of the build (launch_shade picks it from the bounce index and the pass's rounds).
+//   SHADE_FIRST   bounce 0 (of any max_depth, 1 included: its runtime `prdDepth >= maxDepth` ends the path as before): the PerRayData initial values are
+//                 constants, nothing of the path state is loaded, the event bits are set here and only here
+//   SHADE_MIDDLE  bounces 1 .. max_depth - 2
+//   SHADE_LAST    bounce max_depth - 1 > 0: no path survives it (OptixRender.cu:131-153: ++depth reaches max_depth), so it has no continuation -- no next origin /
+//                 direction, no bsdf_over_pdf, no roulette draw, no next-queue compaction -- and stores no throughput, lastBsdfPdf or flags: nothing reads them again
+//                 (the accumulation kernels read the radiance record and the event bits, which bounce 0 wrote)
+//   SHADE_ANY     -DSKH_SHADE_POSITIONS=0: one build for every bounce, `depth` a runtime value (the kernel of before)
+enum
+{
+    SHADE_ANY = 0,
+    SHADE_FIRST,
+    SHADE_MIDDLE,
+    SHADE_LAST
+};
+#ifndef SKH_SHADE_POSITIONS
+#define SKH_SHADE_POSITIONS 1
+#endif
+// waves per SIMD of a LAST build: without its continuation the plain build (and its ENV twin) needs 88 VGPRs at five waves and fits the 80 of six without a
+// spill (kitchen: that launch 6.68 -> 6.25 ms); the EMIT, MTEX and light-shape builds spill 6 ... 75 dwords at six and keep five, the hair builds four
+// (docs/LOG.md "Bounce positions", profiles/shade_positions_kernel_resources*.txt)
+#ifndef SKH_SHADE_WAVES_LAST
+#define SKH_SHADE_WAVES_LAST(HAIR, EMIT, MTEX, LSHAPE) ((HAIR) || (EMIT) || (MTEX) || (LSHAPE) ? SKH_SHADE_WAVES(HAIR) : 6)
+#endif
+#define SKH_SHADE_WAVES_AT(HAIR, EMIT, MTEX, LSHAPE, POS) ((POS) == SHADE_LAST ? SKH_SHADE_WAVES_LAST(HAIR, EMIT, MTEX, LSHAPE) : SKH_SHADE_WAVES(HAIR))
+#define SKH_SHADE_ATTR(HAIR, EMIT, MTEX, LSHAPE, POS) \
+    __attribute__((amdgpu_waves_per_eu(SKH_SHADE_WAVES_AT(HAIR, EMIT, MTEX, LSHAPE, POS), SKH_SHADE_WAVES_AT(HAIR, EMIT, MTEX, LSHAPE, POS))))
 #ifndef SKH_SHADE_BLOCK
 #define SKH_SHADE_BLOCK 256 // 132 VGPRs = 3 waves/SIMD: 256-thread blocks (1 wave per SIMD) fill all three, 512-thread blocks only two
 #endif
@@ -1038,8 +1065,8 @@ __global__ void __launch_bounds__(256) k_emit_probe_mtex(EmitP em, MtexP mt, Dev
 // LSHAPE: the build with light shapes in it (launched when an entry of skh_set_light_shapes' table has a flag that applies to its light's type).  The body is
 // written once, in skh_shade_body.inc, and compiled into two kernels: k_shade -- LSHAPE = false, no `lsh` argument: the sixteen builds of before under the names and
 // with the arguments they had, instruction for instruction (profiles/lshape_kernel_resources*.txt) -- and k_shade_lshape, their sixteen twins with one more argument.
-template <bool HAIR, bool ENV, bool EMIT, bool MTEX>
-__global__ void __launch_bounds__(SKH_SHADE_BLOCK) SKH_SHADE_ATTR(HAIR)
+template <bool HAIR, bool ENV, bool EMIT, bool MTEX, int POS>
+__global__ void __launch_bounds__(SKH_SHADE_BLOCK) SKH_SHADE_ATTR(HAIR, EMIT, MTEX, false, POS)
     k_shade(DevScene sc, FrameP fp, uint32_t sampleOffset, uint32_t depth /* bounce index */, const uint32_t* __restrict__ tileXY, RayQ rq,
             const uint32_t* __restrict__ countPtr, HitQ hq, PathS ps, RayQ nextQ, uint32_t* __restrict__ nextCount, RayQ shadowQ,
             float4* __restrict__ contrib, uint32_t* __restrict__ shadowCount, EnvP env, EmitP emit, MtexP mtex)
@@ -1048,8 +1075,8 @@ __global__ void __launch_bounds__(SKH_SHADE_BLOCK) SKH_SHADE_ATTR(HAIR)
     const LshapeP lsh = { nullptr }; // (never read)
 #include "skh_shade_body.inc"
 }
-template <bool HAIR, bool ENV, bool EMIT, bool MTEX>
-__global__ void __launch_bounds__(SKH_SHADE_BLOCK) SKH_SHADE_ATTR(HAIR)
+template <bool HAIR, bool ENV, bool EMIT, bool MTEX, int POS>
+__global__ void __launch_bounds__(SKH_SHADE_BLOCK) SKH_SHADE_ATTR(HAIR, EMIT, MTEX, true, POS)
     k_shade_lshape(DevScene sc, FrameP fp, uint32_t sampleOffset, uint32_t depth /* bounce index */, const uint32_t* __restrict__ tileXY, RayQ rq,
                    const uint32_t* __restrict__ countPtr, HitQ hq, PathS ps, RayQ nextQ, uint32_t* __restrict__ nextCount, RayQ shadowQ,
                    float4* __restrict__ contrib, uint32_t* __restrict__ shadowCount, EnvP env, EmitP emit, MtexP mtex, LshapeP lsh)

@@ -1,5 +1,11 @@
 // strelka_hip -- the body of k_shade (skh_kernels.h), compiled twice: into k_shade (LSHAPE = false) and into k_shade_lshape (LSHAPE = true, with `lsh`).
-// Included inside the kernel's braces: it sees the kernel's arguments and template flags HAIR, ENV, EMIT, MTEX and the constant LSHAPE.
+// Included inside the kernel's braces: it sees the kernel's arguments and template flags HAIR, ENV, EMIT, MTEX, POS and the constant LSHAPE.
+    // the bounce's position (skh_kernels.h): `depth == 0` and "no path goes on from here" as constants of the build
+    constexpr bool kLast = POS == SHADE_LAST;
+    const bool depth0 = POS == SHADE_ANY ? depth == 0u : POS == SHADE_FIRST;
+    // the path-state loads of a MIDDLE build stay behind the (always true) runtime test they were behind: as straight-line code the scheduler hoists them over the
+    // hit record's and the build spills 8 registers at five waves
+    const bool stateInit = POS == SHADE_MIDDLE ? depth == 0u : depth0;
     // entries of the light pick: the lights, behind them the environment when it is sampled (option env_nee), behind that the emitter set (option emit_nee)
     const uint32_t numPick = (ENV ? sc.numLights + (env.nee ? 1u : 0u) : sc.numLights) + (EMIT ? (emit.nee ? 1u : 0u) : 0u);
     __shared__ uint32_t s_wave[2 * (SKH_COMPACT_MAX_WAVES + 1)];
@@ -81,15 +87,15 @@
         float* P = ps.base;
         const size_t S = ps.stride;
         // (depth 0: the PerRayData initial values, OptixRender.cu:96-109 -- k_raygen does not store them)
-        v3 throughput = depth == 0u ? mk3(1.0f) : mk3(P[pid], P[pid + S], P[pid + 2 * S]);
+        v3 throughput = stateInit ? mk3(1.0f) : mk3(P[pid], P[pid + S], P[pid + 2 * S]);
         // prd.radiance stays in the path state and is read-modify-written only by the branches that change it (a light hit, the debug and error
         // colours; the miss program's `+= throughput * 0` only when that product is not zero, i.e. a non-finite throughput): most paths of most
         // bounces leave it alone, and 12 B read + 12 B written per path were a tenth of this kernel's traffic.  Same values in the same order.
         v3 radiance = mk3(0.0f);
         bool radianceDirty = false;
 #define SKH_RADIANCE_LOAD() radiance = mk3(ps.rad()[pid]), radianceDirty = true
-        float lastBsdfPdf = depth == 0u ? 0.0f : P[pid + 6 * S];
-        uint32_t flags = depth == 0u ? 0u : reinterpret_cast<uint32_t*>(P)[pid + 7 * S];
+        float lastBsdfPdf = stateInit ? 0.0f : P[pid + 6 * S];
+        uint32_t flags = stateInit ? 0u : reinterpret_cast<uint32_t*>(P)[pid + 7 * S];
         bool inside = (flags & PF_INSIDE) != 0;
         bool specularBounce = (flags & PF_SPECULAR) != 0;
         uint32_t firstEvent = (flags >> PF_EVENT_SHIFT) & 3u;
@@ -97,8 +103,8 @@
         const uint32_t sub = pid / fp.numSlots;
         slot_to_pixel(fp, tileXY, pid - sub * fp.numSlots, px, py);
         Sampler smp = init_sampler(px, py, fp.subframeIndex + sampleOffset + sub, fp.sppTotal, 52u);
-        smp.depth = depth; // prd.sampler.depth++ once per bounce (OptixRender.cu:153)
-        uint32_t prdDepth = depth;
+        smp.depth = POS == SHADE_FIRST ? 0u : depth; // prd.sampler.depth++ once per bounce (OptixRender.cu:153)
+        uint32_t prdDepth = smp.depth;
         v3 origin = rayO, dir = rayD; // prd.origin / prd.dir keep their old value when no hit program sets them
 
         if (hinst == 0xffffffffu)
@@ -108,7 +114,7 @@
                 // the environment seen by a ray that leaves the scene: weighted as __closesthit__light weighs a light it hits
                 const EnvEval ee = env_eval(env, rayD);
                 SKH_RADIANCE_LOAD();
-                if (depth == 0 || specularBounce || !env.nee)
+                if (depth0 || specularBounce || !env.nee)
                     radiance = radiance + throughput * ee.Le;
                 else
                 {
@@ -172,7 +178,7 @@
                     {
                         const v3 Li = mk3(l.color) * lshape_cone(lse, -rayD);
                         SKH_RADIANCE_LOAD();
-                        if (depth == 0 || specularBounce)
+                        if (depth0 || specularBounce)
                             radiance = radiance + throughput * Li * -dot(rayD, lightNormal);
                         else
                         {
@@ -188,7 +194,7 @@
                     if (-dot(rayD, lightNormal) > 0.0f)
                     {
                         SKH_RADIANCE_LOAD();
-                        if (depth == 0 || specularBounce)
+                        if (depth0 || specularBounce)
                             radiance = radiance + throughput * mk3(l.color) * -dot(rayD, lightNormal);
                         else
                         {
@@ -291,7 +297,7 @@
                             {
                                 const v3 Le = mk3(matLe.x, matLe.y, matLe.z);
                                 SKH_RADIANCE_LOAD();
-                                if (depth == 0 || specularBounce || !emit.nee)
+                                if (depth0 || specularBounce || !emit.nee)
                                     radiance = radiance + throughput * Le;
                                 else
                                 {
@@ -434,14 +440,14 @@
                     SKH_SP(2) // bsdf_sample
                     if (bs.event_type == EV_ABSORB)
                     {
-                        if (depth == 0)
+                        if (depth0)
                             firstEvent = 1; // eAbsorb
                         throughput = mk3(0.0f);
                     }
                     else
                     {
                         specularBounce = (bs.event_type & EV_SPECULAR) != 0;
-                        if (depth == 0)
+                        if (depth0)
                         {
                             if (bs.event_type & EV_DIFFUSE)
                                 firstEvent = 2;
@@ -490,7 +496,7 @@
                                 }
                             }
                         }
-                        if (!errorOut)
+                        if (!kLast && !errorOut) // (the last bounce has no continuation: nothing below outlives it)
                         {
                             if (bs.event_type & EV_TRANSMISSION)
                             {
@@ -508,49 +514,62 @@
             }
         }
         SKH_SP(5) // rest of the hit program
-        // tail of the bounce loop: OptixRender.cu:131-153
-        bool alive = true;
-        if (prdDepth > 3)
+        if constexpr (kLast)
         {
-            const float p = fmaxf(throughput.x, fmaxf(throughput.y, throughput.z));
-            if (sampler_random_lut(smp, DIM_RR, s_sobol) > p)
-                alive = false;
-            else
-                throughput = throughput * (1.0f / (p + 1e-5f));
+            // depth + 1 == maxDepth: the tail of the bounce loop (OptixRender.cu:131-153) ends every path here whatever the roulette says, and nothing
+            // reads the throughput, lastBsdfPdf or the flags again (the event bits are bounce 0's): only the radiance record is written
+            if (radianceDirty)
+                ps.rad()[pid] = make_float4(radiance.x, radiance.y, radiance.z, 0.0f);
         }
-        if (alive && dot(throughput, throughput) < 1e-5f)
-            alive = false;
-        if (alive)
+        else
         {
-            ++prdDepth;
-            if (fp.debug == 1)
+            // tail of the bounce loop: OptixRender.cu:131-153
+            bool alive = true;
+            if (prdDepth > 3)
+            {
+                const float p = fmaxf(throughput.x, fmaxf(throughput.y, throughput.z));
+                if (sampler_random_lut(smp, DIM_RR, s_sobol) > p)
+                    alive = false;
+                else
+                    throughput = throughput * (1.0f / (p + 1e-5f));
+            }
+            if (alive && dot(throughput, throughput) < 1e-5f)
                 alive = false;
-        }
-        if (alive && prdDepth >= fp.maxDepth)
-            alive = false;
-        emitNext = alive;
-        nextO = origin;
-        nextD = dir;
-        // write back path state
-        P[pid] = throughput.x;
-        P[pid + S] = throughput.y;
-        P[pid + 2 * S] = throughput.z;
-        if (radianceDirty)
-        {
-            ps.rad()[pid] = make_float4(radiance.x, radiance.y, radiance.z, 0.0f);
+            if (alive)
+            {
+                ++prdDepth;
+                if (fp.debug == 1)
+                    alive = false;
+            }
+            if (alive && prdDepth >= fp.maxDepth)
+                alive = false;
+            emitNext = alive;
+            nextO = origin;
+            nextD = dir;
+            // write back path state
+            P[pid] = throughput.x;
+            P[pid + S] = throughput.y;
+            P[pid + 2 * S] = throughput.z;
+            if (radianceDirty)
+            {
+                ps.rad()[pid] = make_float4(radiance.x, radiance.y, radiance.z, 0.0f);
+            }
+            P[pid + 6 * S] = lastBsdfPdf;
+            reinterpret_cast<uint32_t*>(P)[pid + 7 * S] =
+                (inside ? PF_INSIDE : 0u) | (specularBounce ? PF_SPECULAR : 0u) | (firstEvent << PF_EVENT_SHIFT);
         }
 #undef SKH_RADIANCE_LOAD
-        P[pid + 6 * S] = lastBsdfPdf;
-        reinterpret_cast<uint32_t*>(P)[pid + 7 * S] =
-            (inside ? PF_INSIDE : 0u) | (specularBounce ? PF_SPECULAR : 0u) | (firstEvent << PF_EVENT_SHIFT);
     }
     SKH_SP(6) // bounce tail + path-state write
     // stream compaction of live paths / shadow rays: one atomic per queue per workgroup, both in flight together
-    uint32_t ni, si;
-    block_compact2(emitNext, nextCount + shard * SKH_COUNT_STRIDE, emitShadow, shadowCount + shard * SKH_COUNT_STRIDE, s_wave, ni, si);
+    uint32_t ni = 0, si;
+    if constexpr (kLast) // (the shadow queue alone: no ballot, prefix, atomic or store for a next queue that stays empty)
+        si = block_compact(emitShadow, shadowCount + shard * SKH_COUNT_STRIDE, s_wave, false);
+    else
+        block_compact2(emitNext, nextCount + shard * SKH_COUNT_STRIDE, emitShadow, shadowCount + shard * SKH_COUNT_STRIDE, s_wave, ni, si);
     ni += shard * nextQ.region; // (a shard's output never outgrows its region: at most one ray of either kind per input ray)
     si += shard * shadowQ.region;
-    if (emitNext)
+    if (!kLast && emitNext)
     {
         nextQ.plane(0)[ni] = nextO.x;
         nextQ.plane(1)[ni] = nextO.y;

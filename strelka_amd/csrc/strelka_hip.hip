@@ -43,6 +43,7 @@ static_assert(sizeof(skh_hit) == 20 && sizeof(Light) == 112 && sizeof(Material) 
 #include "skh_motion.h"
 #include "skh_rectify.h"
 
+
 // Sobol generator matrices for the 5 dimensions the reference tabulates (RandomSampler.h:139-164), produced from the
 // Joe-Kuo recurrences (d=2: s=1 a=0 m={1}; d=3: s=2 a=1 m={1,3}; d=4: s=3 a=1 m={1,3,1}; d=5: s=3 a=2 m={1,1,1}).
 static void init_sobol_table(uint32_t tab[5][32])
@@ -1969,17 +1970,23 @@ static void fill_queue_constants(skh_context* c, const RenderPass& rp)
     c->frame.queueConstBits[1] = bits[1];
 }
 
-// k_shade for bounce b of sample s: the build by HAIR x ENV x EMIT x MTEX (index 8 4 2 1); every one has a twin with light shapes in it, launched only when a shape
-// is in use (a context without an environment, without emitters and without material textures launches the builds it always launched)
-#define SKH_SHADE_BUILDS(K)                                                                                                                      \
-    {                                                                                                                                            \
-        K<false, false, false, false>, K<false, false, false, true>, K<false, false, true, false>, K<false, false, true, true>,                  \
-        K<false, true, false, false>, K<false, true, false, true>, K<false, true, true, false>, K<false, true, true, true>,                      \
-        K<true, false, false, false>, K<true, false, false, true>, K<true, false, true, false>, K<true, false, true, true>,                      \
-        K<true, true, false, false>, K<true, true, false, true>, K<true, true, true, false>, K<true, true, true, true>                           \
+// k_shade for bounce b of sample s: the build by HAIR x ENV x EMIT x MTEX (index 8 4 2 1) and by the bounce's position (SHADE_FIRST / MIDDLE / LAST, skh_kernels.h);
+// every one has a twin with light shapes in it, launched only when a shape is in use.  -DSKH_SHADE_POSITIONS=0: one build per flag combination, for every bounce.
+#define SKH_SHADE_BUILDS(K, P)                                                                                                                               \
+    {                                                                                                                                                        \
+        K<false, false, false, false, P>, K<false, false, false, true, P>, K<false, false, true, false, P>, K<false, false, true, true, P>,                  \
+        K<false, true, false, false, P>, K<false, true, false, true, P>, K<false, true, true, false, P>, K<false, true, true, true, P>,                      \
+        K<true, false, false, false, P>, K<true, false, false, true, P>, K<true, false, true, false, P>, K<true, false, true, true, P>,                      \
+        K<true, true, false, false, P>, K<true, true, false, true, P>, K<true, true, true, false, P>, K<true, true, true, true, P>                           \
     }
-static const decltype(&k_shade<false, false, false, false>) kShadeKernels[16] = SKH_SHADE_BUILDS(k_shade);
-static const decltype(&k_shade_lshape<false, false, false, false>) kShadeLshapeKernels[16] = SKH_SHADE_BUILDS(k_shade_lshape);
+#if SKH_SHADE_POSITIONS
+#define SKH_SHADE_TABLE(K) { SKH_SHADE_BUILDS(K, SHADE_FIRST), SKH_SHADE_BUILDS(K, SHADE_MIDDLE), SKH_SHADE_BUILDS(K, SHADE_LAST) }
+#else
+#define SKH_SHADE_TABLE(K) { SKH_SHADE_BUILDS(K, SHADE_ANY), SKH_SHADE_BUILDS(K, SHADE_ANY), SKH_SHADE_BUILDS(K, SHADE_ANY) }
+#endif
+static const decltype(&k_shade<false, false, false, false, SHADE_ANY>) kShadeKernels[3][16] = SKH_SHADE_TABLE(k_shade);
+static const decltype(&k_shade_lshape<false, false, false, false, SHADE_ANY>) kShadeLshapeKernels[3][16] = SKH_SHADE_TABLE(k_shade_lshape);
+#undef SKH_SHADE_TABLE
 #undef SKH_SHADE_BUILDS
 
 static void launch_shade(skh_context* c, const RenderPass& rp, uint32_t s, uint32_t b)
@@ -1990,12 +1997,14 @@ static void launch_shade(skh_context* c, const RenderPass& rp, uint32_t s, uint3
     const dim3 sg(SKH_SHARDS * ((perShard + SKH_SHADE_BLOCK - 1) / SKH_SHADE_BLOCK));
     const uint32_t build = (c->scene.hasHairMaterial ? 8u : 0u) | (c->env.w ? 4u : 0u) | (rp.emitp.count ? 2u : 0u) | (rp.mtexp.count ? 1u : 0u), QW = rp.QW;
     uint32_t* counts = rp.counts;
+    // bounce 0 runs the FIRST build whatever max_depth is (max_depth 1: its runtime depth test ends the paths); the last of several bounces the LAST build
+    const uint32_t pos = b == 0u ? 0u : b + 1u == rp.rounds ? 2u : 1u;
     if (rp.lshp.table)
-        kShadeLshapeKernels[build]<<<sg, SKH_SHADE_BLOCK, 0, rp.st>>>(rp.sc, rp.fp, s, b, rp.tiles, rp.rq[b & 1], counts + 2 * b * QW, rp.hq, rp.ps, rp.rq[(b + 1) & 1],
+        kShadeLshapeKernels[pos][build]<<<sg, SKH_SHADE_BLOCK, 0, rp.st>>>(rp.sc, rp.fp, s, b, rp.tiles, rp.rq[b & 1], counts + 2 * b * QW, rp.hq, rp.ps, rp.rq[(b + 1) & 1],
                                                                       counts + 2 * (b + 1) * QW, rp.shq, c->frame.dContrib.as<float4>(), counts + (2 * b + 1) * QW, rp.envp,
                                                                       rp.emitp, rp.mtexp, rp.lshp);
     else
-        kShadeKernels[build]<<<sg, SKH_SHADE_BLOCK, 0, rp.st>>>(rp.sc, rp.fp, s, b, rp.tiles, rp.rq[b & 1], counts + 2 * b * QW, rp.hq, rp.ps, rp.rq[(b + 1) & 1],
+        kShadeKernels[pos][build]<<<sg, SKH_SHADE_BLOCK, 0, rp.st>>>(rp.sc, rp.fp, s, b, rp.tiles, rp.rq[b & 1], counts + 2 * b * QW, rp.hq, rp.ps, rp.rq[(b + 1) & 1],
                                                                 counts + 2 * (b + 1) * QW, rp.shq, c->frame.dContrib.as<float4>(), counts + (2 * b + 1) * QW, rp.envp, rp.emitp,
                                                                 rp.mtexp);
 }
