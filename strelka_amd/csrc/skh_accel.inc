@@ -151,18 +151,32 @@ static skh_status lbvh_ploc(skh_context* c, const LbvhArgs& a, const LbvhOut& ou
                                   bt.nodeLo.as<float4>(), bt.nodeHi.as<float4>(), so.keyShift);
     uint32_t m = n;
     int cur = 0;
-    for (int iter = 0; m > nonEmpty && iter < 4096; ++iter)
-    {
+    bool paired = false;
+    int slow = 0;
+    // one round: name a partner per cluster, merge the pairs that name each other, compact.  `adjacent` < 0: the cost search (k_ploc_nn); 0 / 1: the
+    // round of last resort with that parity (k_ploc_nn_adjacent).  -> hc[3] = clusters left
+    auto round = [&](int adjacent) -> skh_status {
         const uint32_t gm = (m + SKH_PLOC_BLOCK - 1) / SKH_PLOC_BLOCK;
-        if (a.search == 1)
-            k_ploc_nn<SKH_PLOC_RADIUS_TLAS><<<gm, SKH_PLOC_BLOCK, 0, st>>>(cLo[cur].as<float4>(), cHi[cur].as<float4>(), m, nn.as<uint32_t>());
-        else if (a.search == 2)
-            k_ploc_nn<SKH_PLOC_RADIUS_SEGS><<<gm, SKH_PLOC_BLOCK, 0, st>>>(cLo[cur].as<float4>(), cHi[cur].as<float4>(), m, nn.as<uint32_t>());
-        else if (m <= c->opt.plocTop)
-            // the top of the tree -- the levels every ray walks -- clustered with the wide search of the TLAS builder (few clusters left: cheap)
-            k_ploc_nn<SKH_PLOC_RADIUS_TLAS><<<gm, SKH_PLOC_BLOCK, 0, st>>>(cLo[cur].as<float4>(), cHi[cur].as<float4>(), m, nn.as<uint32_t>());
+        if (adjacent >= 0)
+            k_ploc_nn_adjacent<<<(m + B - 1) / B, B, 0, st>>>(cHi[cur].as<float4>(), m, (uint32_t)adjacent, nn.as<uint32_t>());
         else
-            k_ploc_nn<SKH_PLOC_RADIUS><<<gm, SKH_PLOC_BLOCK, 0, st>>>(cLo[cur].as<float4>(), cHi[cur].as<float4>(), m, nn.as<uint32_t>());
+        {
+            // the top of a triangle tree -- the levels every ray walks -- is clustered with the wide search of the TLAS builder (option ploc_top; few clusters left: cheap)
+            const int radius = a.search == 1 ? SKH_PLOC_RADIUS_TLAS : a.search == 2 ? SKH_PLOC_RADIUS_SEGS : m <= c->opt.plocTop ? SKH_PLOC_RADIUS_TLAS : SKH_PLOC_RADIUS;
+            auto search = [&](auto r) {
+                constexpr int R = decltype(r)::value;
+                if (paired)
+                    k_ploc_nn<R, true><<<gm, SKH_PLOC_BLOCK, 0, st>>>(cLo[cur].as<float4>(), cHi[cur].as<float4>(), m, nn.as<uint32_t>());
+                else
+                    k_ploc_nn<R, false><<<gm, SKH_PLOC_BLOCK, 0, st>>>(cLo[cur].as<float4>(), cHi[cur].as<float4>(), m, nn.as<uint32_t>());
+            };
+            if (radius == SKH_PLOC_RADIUS_TLAS)
+                search(std::integral_constant<int, SKH_PLOC_RADIUS_TLAS>());
+            else if (radius == SKH_PLOC_RADIUS_SEGS)
+                search(std::integral_constant<int, SKH_PLOC_RADIUS_SEGS>());
+            else
+                search(std::integral_constant<int, SKH_PLOC_RADIUS>());
+        }
         k_ploc_merge<<<(m + B - 1) / B, B, 0, st>>>(cLo[cur].as<float4>(), cHi[cur].as<float4>(), nn.as<uint32_t>(), m, (int)n,
                                                     bt.childL.as<int>(), bt.childR.as<int>(), wk.nodeSize.as<int>(), bt.nodeLo.as<float4>(),
                                                     bt.nodeHi.as<float4>(), wk.ctr.as<uint32_t>() + 2, pflags.as<uint32_t>(), a.riRounds ? bt.parent.as<int>() : nullptr);
@@ -178,10 +192,37 @@ static skh_status lbvh_ploc(skh_context* c, const LbvhArgs& a, const LbvhOut& ou
                                                       wk.ctr.as<uint32_t>() + 3);
         SKH_TRY(c, hipMemcpyAsync(hc, wk.ctr.p, sizeof(hc), hipMemcpyDeviceToHost, st));
         SKH_TRY(c, hipStreamSynchronize(st));
+        return SKH_OK;
+    };
+    for (int iter = 0; m > nonEmpty && iter < SKH_PLOC_MAX_ROUNDS; ++iter)
+    {
+        SKH_CHECK(round(-1));
         if (hc[3] >= m) // no progress: cannot happen (a mutually-nearest pair always exists), but never spin
             break;
+        // Two rounds in a row that each did less than a sixteenth of the merges still to do (m - nonEmpty: a finished group's cluster does not count): tied
+        // boxes chain under "the lowest index wins" (k_ploc_nn), one merge a round.  The rest of this build breaks ties the PAIRED way.
+        slow = (uint64_t)(m - hc[3]) * 16u < m - nonEmpty ? slow + 1 : 0;
+        if (slow >= 2)
+            paired = true;
         m = hc[3];
         cur ^= 1;
+    }
+    // Every primitive handed in is in the hierarchy: whatever the search left unmerged -- it ran out of rounds, or left its loop on a round without a merge -- is paired off by position (skh_bvh.h
+    // k_ploc_nn_adjacent).  Two rounds of alternating parity in a row without a merge cannot happen while a group holds two clusters.
+    for (int iter = 0, idle = 0; m > nonEmpty && idle < 2 && iter < 128; ++iter)
+    {
+        SKH_CHECK(round(iter & 1));
+        idle = hc[3] >= m ? idle + 1 : 0;
+        if (hc[3] < m)
+        {
+            m = hc[3];
+            cur ^= 1;
+        }
+    }
+    if (m != nonEmpty) // k_ploc_roots writes one root per cluster: with more clusters than groups all but one of a group's subtrees would be lost
+    {
+        c->dev.err = "lbvh_build: the clustering ended with " + std::to_string(m) + " clusters for " + std::to_string(nonEmpty) + " non-empty groups";
+        return SKH_FAIL;
     }
     k_ploc_roots<<<(m + B - 1) / B, B, 0, st>>>(cLo[cur].as<float4>(), cHi[cur].as<float4>(), m, out.groupRoot.as<int>());
     nInternal = hc[2];
@@ -208,7 +249,7 @@ static skh_status lbvh_reinsert_refit(skh_context* c, uint32_t n, uint32_t round
             SKH_TRY(c, hipMemsetAsync(lv + cn, 0, sizeof(uint32_t), st));
         k_ri_refit_level<<<256, B, 0, st>>>(lists[k & 1], lv + ci, lists[(k + 1) & 1], lv + cn, bt.parent.as<int>(), bt.childL.as<int>(), bt.childR.as<int>(),
                                             rflags.as<uint32_t>(), bt.nodeLo.as<float4>(), bt.nodeHi.as<float4>(), wk.nodeSize.as<int>(), (int)n);
-        if ((k & 15u) == 15u)
+        if ((k & 15u) == 15u || k + 1u == n) // (and after the last level: a tree of fewer than 16 levels has no sixteenth)
         {
             uint32_t next = 0;
             SKH_TRY(c, hipMemcpyAsync(&next, lv + cn, sizeof(uint32_t), hipMemcpyDeviceToHost, st));

@@ -988,6 +988,9 @@ __global__ void k_permute_u32(const uint32_t* __restrict__ src, const uint32_t* 
 #define SKH_PLOC_RADIUS_SEGS 8
 #endif
 #define SKH_PLOC_BLOCK 256
+#ifndef SKH_PLOC_MAX_ROUNDS
+#define SKH_PLOC_MAX_ROUNDS 4096 // rounds of the cost search before lbvh_ploc pairs what is left by position (tests/test_gpu_build_edges.py builds a variant with 1)
+#endif
 __global__ void k_ploc_init(const uint32_t* __restrict__ sortedVals, const uint64_t* __restrict__ sortedKeys,
                             const float4* __restrict__ boxLo, const float4* __restrict__ boxHi, uint32_t n,
                             float4* __restrict__ cLo, float4* __restrict__ cHi, float4* __restrict__ nodeLo,
@@ -1012,7 +1015,7 @@ __global__ void k_ploc_init(const uint32_t* __restrict__ sortedVals, const uint6
 #ifndef SKH_PLOC_RADIUS_TLAS
 #define SKH_PLOC_RADIUS_TLAS 96
 #endif
-template <int RADIUS>
+template <int RADIUS, bool PAIRED>
 __global__ void __launch_bounds__(SKH_PLOC_BLOCK) k_ploc_nn(const float4* __restrict__ cLo, const float4* __restrict__ cHi, uint32_t m,
                                                            uint32_t* __restrict__ nn)
 {
@@ -1043,24 +1046,59 @@ __global__ void __launch_bounds__(SKH_PLOC_BLOCK) k_ploc_nn(const float4* __rest
     const uint32_t grp = __float_as_uint(hi.w);
     float bestCost = INFINITY;
     uint32_t best = 0xffffffffu;
-    for (int d = -SKH_PLOC_RADIUS_; d <= SKH_PLOC_RADIUS_; ++d)
-    {
-        if (d == 0)
-            continue;
+    auto offer = [&](int d) {
         const float4 olo = sLo[me + d], ohi = sHi[me + d];
         if (__float_as_uint(ohi.w) != grp)
-            continue;
+            return;
         const float ex = fmaxf(hi.x, ohi.x) - fminf(lo.x, olo.x);
         const float ey = fmaxf(hi.y, ohi.y) - fminf(lo.y, olo.y);
         const float ez = fmaxf(hi.z, ohi.z) - fminf(lo.z, olo.z);
         const float cost = ex * ey + ey * ez + ez * ex;
-        if (cost < bestCost) // ties: the first (lowest index) candidate wins, on both sides of a pair
+        if (cost < bestCost)
         {
             bestCost = cost;
             best = (uint32_t)((int)i + d);
         }
+    };
+    if constexpr (!PAIRED)
+    {
+        // ties: the first (lowest index) candidate wins, on both sides of a pair.  On a run of tied clusters -- identical boxes, a straight strip, a row of equal
+        // instances -- every cluster then names its LEFT neighbour and one pair merges per round, at the front: lbvh_ploc watches for that and switches to PAIRED
+        for (int d = -SKH_PLOC_RADIUS_; d <= SKH_PLOC_RADIUS_; ++d)
+            if (d != 0)
+                offer(d);
+    }
+    else
+    {
+        // ties: the nearer candidate wins; of the two at the same distance k, the one on the side that floor(i / k) names -- even: i + k, odd: i - k.
+        // Clusters i and i + k with floor(i / k) even then name EACH OTHER: a run of tied clusters pairs off in one round.
+#pragma unroll
+        for (int k = 1; k <= SKH_PLOC_RADIUS_; ++k)
+        {
+            const int first = ((i / (uint32_t)k) & 1u) ? -k : k;
+            offer(first);
+            offer(-first);
+        }
     }
     nn[i] = best;
+}
+// The round of last resort (lbvh_ploc, when the search above has stopped merging or has used up its rounds): clusters i and i + 1 of one group name
+// each other where i has the round's parity, whatever their boxes.  Every group of two or more clusters holds such a pair under one parity or the
+// other, and a run of L clusters keeps at most L / 2 + 1: alternating the parity ends in one cluster per group after about log2 of the longest run.
+__global__ void k_ploc_nn_adjacent(const float4* __restrict__ cHi, uint32_t m, uint32_t parity, uint32_t* __restrict__ nn)
+{
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= m)
+        return;
+    const bool lower = (i & 1u) == parity;
+    uint32_t j = 0xffffffffu;
+    if (lower ? i + 1u < m : i > 0u)
+    {
+        const uint32_t o = lower ? i + 1u : i - 1u;
+        if (__float_as_uint(cHi[o].w) == __float_as_uint(cHi[i].w))
+            j = o;
+    }
+    nn[i] = j;
 }
 __global__ void k_ploc_merge(float4* __restrict__ cLo, float4* __restrict__ cHi, const uint32_t* __restrict__ nn, uint32_t m, int n,
                              int* __restrict__ childL, int* __restrict__ childR, int* __restrict__ nodeSize,
