@@ -306,7 +306,7 @@ static inline void inflate(Aabb& b)
     b.lo = b.lo - mk3(e);
     b.hi = b.hi + mk3(e);
 }
-static inline bool slab(const Aabb& b, const f3& o, const f3& inv, float tmin, float tmax)
+static inline bool slab(const Aabb& b, const f3& o, const f3& inv, int kz, float tmin, float tmax)
 {
     // The subtraction (plane - o) rounds at the magnitude of the LARGER operand: with the ray origin far from a small box (object
     // space of a strongly scaled instance: |o| = |R^-1| |o_world - T|) that absolute error exceeds the 2^-20 relative inflation of the
@@ -324,8 +324,12 @@ static inline bool slab(const Aabb& b, const f3& o, const f3& inv, float tmin, f
     float t0z = ((b.lo.z - pz) - o.z) * inv.z, t1z = ((b.hi.z + pz) - o.z) * inv.z;
     // NaN-safe ordering (0 * inf): fminf/fmaxf drop NaNs
     const float tn = fmaxf(fmaxf(fminf(t0x, t1x), fminf(t0y, t1y)), fmaxf(fminf(t0z, t1z), tmin));
-    const float tf = fminf(fminf(fmaxf(t0x, t1x), fmaxf(t0y, t1y)), fminf(fmaxf(t0z, t1z), tmax));
-    return tn <= tf * 1.00000095367431640625f; // 1 + 2^-20
+    const float tf = fminf(fminf(fmaxf(t0x, t1x), fmaxf(t0y, t1y)), fmaxf(t0z, t1z));
+    // tmax -- the best t so far -- culls by the ray's dominant axis kz alone: the triangle test's t is a mean of the vertices' depths along kz with the rounded edge
+    // functions as weights, inside the triangle's slab on that axis whatever their errors, but for a sliver seen along its plane possibly in front of the box's entry
+    // on another axis (the padding above was wide enough for the architectural kitchen's record 865 and not for tests/treeref.py's mechanism_scene)
+    const float nk = kz == 0 ? fminf(t0x, t1x) : (kz == 1 ? fminf(t0y, t1y) : fminf(t0z, t1z));
+    return tn <= tf * 1.00000095367431640625f && nk <= tmax * 1.00000095367431640625f; // 1 + 2^-20
 }
 
 struct BvhNode

@@ -151,7 +151,7 @@ static skh_status lbvh_ploc(skh_context* c, const LbvhArgs& a, const LbvhOut& ou
                                   bt.nodeLo.as<float4>(), bt.nodeHi.as<float4>(), so.keyShift);
     uint32_t m = n;
     int cur = 0;
-    bool paired = false;
+    bool paired = SKH_PLOC_PAIRED_FIRST != 0;
     int slow = 0;
     // one round: name a partner per cluster, merge the pairs that name each other, compact.  `adjacent` < 0: the cost search (k_ploc_nn); 0 / 1: the
     // round of last resort with that parity (k_ploc_nn_adjacent).  -> hc[3] = clusters left

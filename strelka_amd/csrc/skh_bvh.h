@@ -991,6 +991,9 @@ __global__ void k_permute_u32(const uint32_t* __restrict__ src, const uint32_t* 
 #ifndef SKH_PLOC_MAX_ROUNDS
 #define SKH_PLOC_MAX_ROUNDS 4096 // rounds of the cost search before lbvh_ploc pairs what is left by position (tests/test_gpu_build_edges.py builds a variant with 1)
 #endif
+#ifndef SKH_PLOC_PAIRED_FIRST
+#define SKH_PLOC_PAIRED_FIRST 0 // 1: the cost search breaks ties the paired way from its first round -- another valid tree of the same scene (tests/test_gpu_tree_independence.py builds that variant)
+#endif
 __global__ void k_ploc_init(const uint32_t* __restrict__ sortedVals, const uint64_t* __restrict__ sortedKeys,
                             const float4* __restrict__ boxLo, const float4* __restrict__ boxHi, uint32_t n,
                             float4* __restrict__ cLo, float4* __restrict__ cHi, float4* __restrict__ nodeLo,

@@ -583,6 +583,27 @@
                 const uint32_t nxw = __float_as_uint(px ? w1.x : w2.x), fxw = __float_as_uint(px ? w2.x : w1.x);
                 const uint32_t nyw = __float_as_uint(py ? w1.y : w2.y), fyw = __float_as_uint(py ? w2.y : w1.y);
                 const uint32_t nzw = __float_as_uint(pz ? w1.z : w2.z), fzw = __float_as_uint(pz ? w2.z : w1.z);
+                // The cull against the best t so far looks at the ray's DOMINANT axis alone (make_shear's kz).  The intersector's t is
+                // (U Az + V Bz + W Cz) / (U + V + W) with the same rounded, same-signed U, V, W above and below: a mean of the vertices' depths along kz, inside
+                // the triangle's slab on THAT axis whatever the weights' errors -- and, for a sliver seen along its plane (|det| << S), anywhere inside it: in
+                // front of the entry into its own box, which another axis sets.  A box culled because it starts behind best.t could then hold the smaller
+                // computed t, and the record would depend on the visit order (docs/LOG.md "A hit record that depended on the tree").  The box's three slabs
+                // still decide whether the ray meets it at all.
+                // kz: the world-only triangle builds keep the shear across the loop, and hand it to a lane that takes over a stack entry (SPLIT's tail phase,
+                // which does not hand over d); the other builds -- the shear is made at the leaf, or belongs to the instance last entered -- take it from the d
+                // of the space the node lives in, as make_shear does.
+                bool kz0, kz1;
+                if constexpr (WORLD && !CURVES)
+                {
+                    const int kz = sh.perm & 3;
+                    kz0 = kz == 0, kz1 = kz == 1;
+                }
+                else
+                {
+                    const float adx = fabsf(d.x), ady = fabsf(d.y), adz = fabsf(d.z);
+                    kz0 = adx > ady && adx > adz, kz1 = !(adx > ady) && ady > adz;
+                }
+                const float bestSlack = best.t * SKH_SLAB_SLACK;
                 float tn[4];
                 int rf[4];
                 rf[0] = __float_as_int(w3.x), rf[1] = __float_as_int(w3.y), rf[2] = __float_as_int(w3.z), rf[3] = __float_as_int(w3.w);
@@ -593,10 +614,11 @@
                     const float ny = fmaf((float)((nyw >> (8 * k)) & 0xffu), ay, by), fy = fmaf((float)((fyw >> (8 * k)) & 0xffu), ay, by);
                     const float nz = fmaf((float)((nzw >> (8 * k)) & 0xffu), az, bz), fz = fmaf((float)((fzw >> (8 * k)) & 0xffu), az, bz);
                     const float tnear = fmaxf(fmaxf(nx, ny), fmaxf(nz, tmin));
-                    const float tfar = fminf(fminf(fx, fy), fminf(fz, best.t));
+                    const float tfar = fminf(fminf(fx, fy), fz);
+                    const float nk = kz0 ? nx : (kz1 ? ny : nz);
                     // (an empty slot is stored as the inverted box 255 > 0 on every axis and fails this test by itself; should rounding
                     // ever let one through, its SKH_REF_INVALID is pushed and skipped when popped)
-                    const bool hit = tnear <= tfar * SKH_SLAB_SLACK;
+                    const bool hit = tnear <= tfar * SKH_SLAB_SLACK && nk <= bestSlack;
                     tn[k] = hit ? tnear : INFINITY;
                 }
                 if (CURVES && SKH_SEGNODE && ((uint32_t)cur & SKH_REF_SEGNODE) != 0u)
