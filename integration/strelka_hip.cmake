@@ -25,7 +25,8 @@ add_custom_command(
           -mllvm -amdgpu-sched-strategy=max-ilp -fPIC -shared -std=c++17
           -o ${SKH_LIBRARY} ${SKH_SRC_DIR}/strelka_hip.hip
   DEPENDS ${SKH_SRC_DIR}/strelka_hip.hip ${SKH_SRC_DIR}/skh_kernels.h ${SKH_SRC_DIR}/skh_device.h ${SKH_SRC_DIR}/skh_bvh.h
-          ${SKH_SRC_DIR}/skh_probes.inc ${SKH_SRC_DIR}/skh_stale.h ${STRELKA_HIP_DIR}/include/strelka_hip.h
+          ${SKH_SRC_DIR}/skh_probes.inc ${SKH_SRC_DIR}/skh_stale.h ${SKH_SRC_DIR}/skh_image.h ${SKH_SRC_DIR}/skh_image.inc
+          ${STRELKA_HIP_DIR}/include/strelka_hip.h
   COMMENT "hipcc: libstrelka_hip.so (${STRELKA_HIP_ARCH})"
   VERBATIM)
 add_custom_target(strelka_hip_kernels DEPENDS ${SKH_LIBRARY})

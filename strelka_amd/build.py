@@ -6,7 +6,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 ROOT = os.path.dirname(HERE)
 LIB = os.environ.get("SKH_LIB") or os.path.join(HERE, "libstrelka_hip.so")  # SKH_LIB: A/B builds of the same HIP source
 SRC = os.path.join(HERE, "csrc", "strelka_hip.hip")
-DEPS = [SRC] + [os.path.join(HERE, "csrc", f) for f in ("skh_device.h", "skh_bvh.h", "skh_env.h", "skh_emit.h", "skh_blend.h", "skh_adapt.h", "skh_aov.h", "skh_denoise.h", "skh_temporal.h", "skh_variance.h", "skh_motion.h", "skh_rectify.h", "skh_lshape.h", "skh_kernels.h", "skh_shade_body.inc", "skh_trace_body.inc", "skh_libm.h", "skh_host.h", "skh_stale.h", "skh_order.h", "skh_accel.inc", "skh_probes.inc")] + [
+DEPS = [SRC] + [os.path.join(HERE, "csrc", f) for f in ("skh_device.h", "skh_bvh.h", "skh_env.h", "skh_emit.h", "skh_blend.h", "skh_adapt.h", "skh_aov.h", "skh_image.h", "skh_denoise.h", "skh_temporal.h", "skh_variance.h", "skh_motion.h", "skh_rectify.h", "skh_lshape.h", "skh_kernels.h", "skh_shade_body.inc", "skh_trace_body.inc", "skh_libm.h", "skh_host.h", "skh_stale.h", "skh_order.h", "skh_accel.inc", "skh_probes.inc", "skh_image.inc")] + [
     os.path.join(ROOT, "include", "strelka_hip.h"), os.path.abspath(__file__)]  # (this file: the flags)
 # -fno-slp-vectorize: the SLP pass pairs scalar float ops into v_pk_* and pays for it in v_mov packing and registers (k_shade
 #   128 -> 112 VGPRs, k_trace 80 + 4 spilled -> 77; kitchen +3 %, hair +13 %); max-ilp scheduling: another +0.5 %.  Neither changes

@@ -3,11 +3,12 @@
 //   k_mo_rewind   one lane, one pixel: expresses the pixel's first-hit position and normal in the previous frame's world, through the motion entry of the
 //                 pixel's instance.  skh_temporal and skh_moments, handed the two planes it writes, then follow a moved instance with no change of their own.
 //
-// A workgroup is 64 x 4 pixels as in k_dn_level: a wave is 64 consecutive pixels of one row, so that each load of a plane is one 1024-byte row segment.
+// Workgroups and the grid are skh_image.h's.
 // No LDS, no atomics, no scratch.  The six float4 of the table entry are gathered with the index clamped to a legal entry, before the first of them is used; where
 // the entry does not apply the pixel's own words are SELECTED (as words: a NaN keeps its payload).  The only branch is the exit at the image's edge.
 #pragma once
 #include "../../include/strelka_hip.h"
+#include "skh_image.h"
 
 namespace skh
 {
@@ -16,12 +17,9 @@ namespace skh
 __global__ void __launch_bounds__(256) k_mo_rewind(uint32_t width, uint32_t height, uint32_t n, const float4* __restrict__ table, const uint4* __restrict__ ids,
                                                     const float4* position, const float4* normal, float4* positionOut, float4* normalOut)
 {
-    // (a one-dimensional grid of row-major 64 x 4 tiles, as k_dn_level's)
-    const uint32_t tilesX = (width + 63u) / 64u, tileY = blockIdx.x / tilesX;
-    const uint32_t x = (blockIdx.x - tileY * tilesX) * 64u + threadIdx.x, y = tileY * 4u + threadIdx.y;
-    if (x >= width || y >= height)
+    uint32_t x, y, i;
+    if (!img_pixel(width, height, x, y, i))
         return;
-    const uint32_t i = y * width + x;
     const uint4 id = ids[i];
     const float4 P = position[i], N = normal[i];
     const uint32_t e = id.x < n ? id.x : n - 1u; // (a legal entry whatever the pixel holds)

@@ -4,15 +4,14 @@
 //                     taps on the pixel's own surface in two sweeps, clamps the pixel's long history to mean +- k sd per channel, and writes the output image,
 //                     the long history to store and (optionally) the info plane.
 //
-// A workgroup is 64 x 4 pixels as in k_dn_level: a wave is 64 consecutive pixels of one row, so that each load of a plane is one 1024-byte row segment.
-// No LDS, no atomics, no scratch.  The plain gather of k_vr_estimate: the first sweep loads a tap's fast record and its ids record (16 bytes each: one full-width
-// load per plane and tap), with the address clamped to the pixel's own where the tap lies outside the image, and keeps which taps it took as one bit each.  For the
+// Workgroups, the grid and the clamped taps are skh_image.h's.  No LDS, no atomics, no scratch.  The plain gather of k_vr_estimate: the first sweep loads a tap's
+// fast record and its ids record (16 bytes each: one full-width load per plane and tap) and keeps which taps it took as one bit each.  For the
 // second sweep the 3 x 3 window's nine records stay in registers; the wider windows load the fast records again (they are in the cache the first sweep filled).
 // Either way it SELECTS by those bits -- a skipped tap never enters a sum.  The only branches are uniform ones (an info plane or none) and the exit of pixels
 // that are not rectified.
 #pragma once
 #include "../../include/strelka_hip.h"
-#include "skh_denoise.h"
+#include "skh_image.h"
 
 namespace skh
 {
@@ -37,12 +36,9 @@ __global__ void __launch_bounds__(256) k_rc_rectify(RcP rp, const uint4* image, 
                                                      const uint4* history, const float4* __restrict__ fast, uint4* out, uint4* historyOut,
                                                      float4* __restrict__ info)
 {
-    // (a one-dimensional grid of row-major 64 x 4 tiles, as k_dn_level's)
-    const uint32_t tilesX = (rp.width + 63u) / 64u, tileY = blockIdx.x / tilesX;
-    const uint32_t x = (blockIdx.x - tileY * tilesX) * 64u + threadIdx.x, y = tileY * 4u + threadIdx.y;
-    if (x >= rp.width || y >= rp.height)
+    uint32_t x, y, i;
+    if (!img_pixel(rp.width, rp.height, x, y, i))
         return;
-    const uint32_t i = y * rp.width + x;
     const uint4 cw = image[i], hw = history[i];
     const uint32_t inst = ids[i].x, kind = ids[i].w;
     const float4 h = make_float4(__uint_as_float(hw.x), __uint_as_float(hw.y), __uint_as_float(hw.z), __uint_as_float(hw.w));
@@ -66,16 +62,13 @@ __global__ void __launch_bounds__(256) k_rc_rectify(RcP rp, const uint4* image, 
 #pragma unroll ROWS
     for (int dy = -R; dy <= R; ++dy)
     {
-        const int qy = (int)y + dy;
-        const bool rowIn = qy >= 0 && qy < H;
-        const uint32_t row = (uint32_t)(rowIn ? qy : (int)y) * rp.width;
+        const ImgRow row = img_row(y, dy, rp.width, H);
         uint32_t rowTaken = 0u;
 #pragma unroll
         for (int dx = -R; dx <= R; ++dx)
         {
-            const int qx = (int)x + dx;
-            const bool in = rowIn && qx >= 0 && qx < W;
-            const uint32_t j = in ? row + (uint32_t)qx : i; // (an address outside the image: the pixel's own)
+            uint32_t j;
+            const bool in = img_tap(row, x, dx, W, j);
             const float4 f = fast[j];
             const uint4 iq = ids[j];
             const bool t = in && iq.w == kind && iq.x == inst && rc_record(f);
@@ -94,15 +87,13 @@ __global__ void __launch_bounds__(256) k_rc_rectify(RcP rp, const uint4* image, 
 #pragma unroll ROWS
     for (int dy = -R; dy <= R; ++dy)
     {
-        const int qy = (int)y + dy;
-        const bool rowIn = qy >= 0 && qy < H;
-        const uint32_t row = (uint32_t)(rowIn ? qy : (int)y) * rp.width;
+        const ImgRow row = img_row(y, dy, rp.width, H);
         const uint32_t rowTaken = (uint32_t)(taken >> ((dy + R) * D));
 #pragma unroll
         for (int dx = -R; dx <= R; ++dx)
         {
-            const int qx = (int)x + dx;
-            const uint32_t j = (rowIn && qx >= 0 && qx < W) ? row + (uint32_t)qx : i;
+            uint32_t j;
+            img_tap(row, x, dx, W, j);
             float3 f;
             if (KEEP)
                 f = kept[(dy + R) * D + (dx + R)];
@@ -132,8 +123,8 @@ __global__ void __launch_bounds__(256) k_rc_rectify(RcP rp, const uint4* image, 
     float ox = rx, oy = ry, oz = rz;
     if (rp.flags & SKH_RECTIFY_REMODULATE)
     {
-        const float4 a = albedo[i];
-        ox = rx * dn_floor(a.x, rp.albedoFloor), oy = ry * dn_floor(a.y, rp.albedoFloor), oz = rz * dn_floor(a.z, rp.albedoFloor);
+        const float3 a = img_albedo(albedo[i], rp.albedoFloor);
+        ox = rx * a.x, oy = ry * a.y, oz = rz * a.z;
     }
     out[i] = make_uint4(__float_as_uint(ox), __float_as_uint(oy), __float_as_uint(oz), cw.w);
     if (info)

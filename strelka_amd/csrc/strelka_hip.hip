@@ -37,6 +37,7 @@ static_assert(sizeof(skh_hit) == 20 && sizeof(Light) == 112 && sizeof(Material) 
 
 #include "skh_host.h"
 #include "skh_aov.h"
+#include "skh_image.h"
 #include "skh_denoise.h"
 #include "skh_temporal.h"
 #include "skh_variance.h"
@@ -2902,6 +2903,8 @@ skh_status skh_trace(skh_context* c, const skh_ray* rays, uint32_t n_rays, uint3
     return s;
 }
 
+#include "skh_image.inc"
+
 // ---- first-hit AOVs (skh_aov.h): skh_aov_check, skh_render_aovs, skh_get_aov_info ----
 static_assert(sizeof(skh_aov_params) == 240 && sizeof(skh_aov_info) == 32, "ABI layout");
 
@@ -2922,10 +2925,7 @@ static const char* aov_refusal(const skh_aov_params* p, uint32_t image_w, uint32
         return "tmin negative or not finite";
     if (p->sample_index != SKH_AOV_PIXEL_CENTRE && (p->spp_total == 0u || p->sample_index >= p->spp_total))
         return "sample_index outside the sequence of spp_total samples";
-    for (uint32_t r : p->reserved)
-        if (r != 0u)
-            return "a non-zero reserved word";
-    return nullptr;
+    return reserved_refusal(p->reserved);
 }
 
 skh_status skh_aov_check(const skh_aov_params* p, uint32_t image_w, uint32_t image_h)
@@ -2997,598 +2997,7 @@ skh_status skh_render_aovs(skh_context* c, const skh_aov_params* p, uint32_t pla
 
 skh_status skh_get_aov_info(skh_context* c, skh_aov_info* out)
 {
-    if (!c || !out)
-        return SKH_INVALID_ARGUMENT;
-    *out = c->aov.info;
-    return SKH_OK;
-}
-
-// ---- the denoiser (skh_denoise.h): skh_denoise_check, skh_denoise, skh_get_denoise_info ----
-static_assert(sizeof(skh_denoise_params) == 64 && sizeof(skh_denoise_info) == 32, "ABI layout");
-
-// why *p is refused, or nullptr
-static const char* denoise_refusal(const skh_denoise_params* p)
-{
-    if (!p)
-        return "no parameters";
-    if (p->width == 0u || p->height == 0u || (uint64_t)p->width * p->height > (1ull << 26))
-        return "an empty image, or one of more than 2^26 pixels";
-    if (p->levels == 0u || p->first_level > SKH_DENOISE_MAX_LEVEL || p->levels > SKH_DENOISE_MAX_LEVEL || p->first_level + p->levels > SKH_DENOISE_MAX_LEVEL)
-        return "no level, or a level beyond first_level + levels <= 8";
-    for (float s : { p->sigma_color, p->sigma_normal, p->sigma_plane })
-        if (!(s > 0.0f)) // (a NaN too)
-            return "a sigma that is <= 0 or NaN";
-    if (!std::isfinite(p->albedo_floor) || !(p->albedo_floor > 0.0f))
-        return "an albedo_floor that is <= 0 or not finite";
-    if (p->flags & ~(SKH_DENOISE_DEMODULATE | SKH_DENOISE_REMODULATE))
-        return "an unknown flag bit";
-    for (uint32_t r : p->reserved)
-        if (r != 0u)
-            return "a non-zero reserved word";
-    return nullptr;
-}
-
-skh_status skh_denoise_check(const skh_denoise_params* p)
-{
-    return denoise_refusal(p) ? SKH_INVALID_ARGUMENT : SKH_OK;
-}
-
-static uint64_t denoise_scratch_bytes(const skh_context* c)
-{
-    return (uint64_t)c->dn.dColor[0].bytes + c->dn.dColor[1].bytes + c->dn.dG0.bytes + c->dn.dG1.bytes;
-}
-
-skh_status skh_denoise(skh_context* c, const skh_denoise_params* p, const void* d_color, const void* d_ids, const void* d_normal, const void* d_position,
-                       const void* d_albedo, void* d_out)
-{
-    if (!c)
-        return SKH_INVALID_ARGUMENT;
-    (void)hipSetDevice(c->dev.device);
-    if (!p) // free the scratch
-    {
-        dev_free(c->dn.dColor[0]), dev_free(c->dn.dColor[1]), dev_free(c->dn.dG0), dev_free(c->dn.dG1);
-        return SKH_OK;
-    }
-    const char* why = denoise_refusal(p);
-    if (!why && (!d_color || !d_ids || !d_normal || !d_position || !d_out))
-        why = "a NULL image";
-    if (!why && p->flags != 0u && !d_albedo)
-        why = "a flag that needs the albedo plane, and no albedo plane";
-    if (why)
-    {
-        c->dev.err = std::string("skh_denoise: ") + why;
-        return SKH_INVALID_ARGUMENT;
-    }
-    const auto t0 = std::chrono::steady_clock::now();
-    const size_t n = (size_t)p->width * p->height;
-    SKH_CHECK(dev_alloc(c, c->dn.dColor[0], 16 * n));
-    if (p->levels > 1u)
-        SKH_CHECK(dev_alloc(c, c->dn.dColor[1], 16 * n));
-    SKH_CHECK(dev_alloc(c, c->dn.dG0, 16 * n));
-    SKH_CHECK(dev_alloc(c, c->dn.dG1, 8 * n));
-    hipStream_t st = side_stream(c); // (beside a pass traced ahead, not behind it: skh_tonemap's choice)
-    DnP dp;
-    dp.width = p->width, dp.height = p->height, dp.step = 1u, dp.kc = 0.0f;
-    dp.kn = 1.0f / (p->sigma_normal * p->sigma_normal), dp.kp = 1.0f / (p->sigma_plane * p->sigma_plane);
-    dp.albedoFloor = p->albedo_floor, dp.flags = p->flags;
-    k_dn_pack<<<(uint32_t)((n + 255) / 256), 256, 0, st>>>(dp, reinterpret_cast<const float4*>(d_color), reinterpret_cast<const uint4*>(d_ids),
-                                                          reinterpret_cast<const float4*>(d_normal), reinterpret_cast<const float4*>(d_position),
-                                                          reinterpret_cast<const float4*>(d_albedo), c->dn.dColor[0].as<float4>(), c->dn.dG0.as<float4>(),
-                                                          c->dn.dG1.as<float2>());
-    const dim3 grid(((p->width + 63u) / 64u) * ((p->height + 3u) / 4u)), block(64, 4); // (<= 2^24 + 2^20 tiles of 64 x 4 pixels, row-major)
-    for (uint32_t k = 0; k < p->levels; ++k)
-    {
-        const uint32_t level = p->first_level + k;
-        const float sc = p->sigma_color * (1.0f / (float)(1u << level)); // (exact: a power of two)
-        dp.step = 1u << level, dp.kc = 1.0f / (sc * sc);
-        const float4* cin = c->dn.dColor[k & 1u].as<float4>();
-        if (k + 1u < p->levels)
-            k_dn_level<false><<<grid, block, 0, st>>>(dp, cin, c->dn.dG0.as<float4>(), c->dn.dG1.as<float2>(), c->dn.dColor[(k + 1u) & 1u].as<float4>(), nullptr, nullptr, nullptr);
-        else
-            k_dn_level<true><<<grid, block, 0, st>>>(dp, cin, c->dn.dG0.as<float4>(), c->dn.dG1.as<float2>(), nullptr, reinterpret_cast<const uint4*>(d_color),
-                                                    reinterpret_cast<const float4*>(d_albedo), reinterpret_cast<uint4*>(d_out));
-    }
-    SKH_TRY(c, hipGetLastError());
-    SKH_TRY(c, hipStreamSynchronize(st));
-    c->dn.info.calls++;
-    c->dn.info.pixels += n;
-    c->dn.info.ms_last = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
-    return SKH_OK;
-}
-
-skh_status skh_get_denoise_info(skh_context* c, skh_denoise_info* out)
-{
-    if (!c || !out)
-        return SKH_INVALID_ARGUMENT;
-    *out = c->dn.info;
-    out->scratch_bytes = denoise_scratch_bytes(c);
-    return SKH_OK;
-}
-
-// ---- temporal accumulation (skh_temporal.h): skh_temporal_check, skh_temporal, skh_get_temporal_info ----
-static_assert(sizeof(skh_temporal_params) == 128 && sizeof(skh_temporal_info) == 24, "ABI layout");
-
-// why *p is refused, or nullptr
-static const char* temporal_refusal(const skh_temporal_params* p)
-{
-    if (!p)
-        return "no parameters";
-    if (p->width == 0u || p->height == 0u || (uint64_t)p->width * p->height > (1ull << 26))
-        return "an empty image, or one of more than 2^26 pixels";
-    for (float m : p->prev_world_to_clip)
-        if (!std::isfinite(m))
-            return "a matrix entry that is not finite";
-    if (!(p->normal_min >= -1.0f && p->normal_min <= 1.0f)) // (a NaN too)
-        return "a normal_min outside [-1, 1] or NaN";
-    if (!(p->plane_tolerance > 0.0f))
-        return "a plane_tolerance that is <= 0 or NaN";
-    if (!std::isfinite(p->max_history) || !(p->max_history >= 1.0f))
-        return "a max_history that is < 1 or not finite";
-    if (!std::isfinite(p->initial_length) || !(p->initial_length >= 1.0f) || !(p->initial_length <= p->max_history))
-        return "an initial_length that is < 1, above max_history or not finite";
-    if (!std::isfinite(p->albedo_floor) || !(p->albedo_floor > 0.0f))
-        return "an albedo_floor that is <= 0 or not finite";
-    if (p->flags & ~SKH_TEMPORAL_DEMODULATE)
-        return "an unknown flag bit";
-    for (uint32_t r : p->reserved)
-        if (r != 0u)
-            return "a non-zero reserved word";
-    return nullptr;
-}
-
-skh_status skh_temporal_check(const skh_temporal_params* p)
-{
-    return temporal_refusal(p) ? SKH_INVALID_ARGUMENT : SKH_OK;
-}
-
-skh_status skh_temporal(skh_context* c, const skh_temporal_params* p, const void* d_color, const void* d_ids, const void* d_normal, const void* d_position,
-                        const void* d_albedo, const void* d_prev_history, const void* d_prev_ids, const void* d_prev_normal, const void* d_prev_position,
-                        void* d_out, void* d_history_out, void* d_motion)
-{
-    if (!c)
-        return SKH_INVALID_ARGUMENT;
-    (void)hipSetDevice(c->dev.device);
-    const char* why = temporal_refusal(p);
-    if (!why && (!d_color || !d_ids || !d_normal || !d_position || !d_out || !d_history_out))
-        why = "a NULL image";
-    if (!why && (p->flags & SKH_TEMPORAL_DEMODULATE) && !d_albedo)
-        why = "a flag that needs the albedo plane, and no albedo plane";
-    if (!why && d_prev_history && (!d_prev_ids || !d_prev_normal || !d_prev_position))
-        why = "a previous history without its guide planes";
-    if (!why && d_prev_history && d_history_out == d_prev_history)
-        why = "d_history_out == d_prev_history (taps read neighbours)";
-    if (why)
-    {
-        c->dev.err = std::string("skh_temporal: ") + why;
-        return SKH_INVALID_ARGUMENT;
-    }
-    const auto t0 = std::chrono::steady_clock::now();
-    const size_t n = (size_t)p->width * p->height;
-    hipStream_t st = side_stream(c); // (skh_denoise's stream: beside a pass traced ahead, not behind it)
-    TpP tp;
-    tp.width = p->width, tp.height = p->height;
-    for (int k = 0; k < 16; ++k)
-        tp.prevWorldToClip[k] = p->prev_world_to_clip[k];
-    tp.normalMin = p->normal_min, tp.planeTolerance = p->plane_tolerance, tp.maxHistory = p->max_history, tp.initialLength = p->initial_length;
-    tp.albedoFloor = p->albedo_floor, tp.flags = p->flags, tp.hasPrev = d_prev_history ? 1u : 0u;
-    const dim3 grid(((p->width + 63u) / 64u) * ((p->height + 3u) / 4u)), block(64, 4); // (<= 2^24 + 2^20 tiles of 64 x 4 pixels, row-major)
-    k_tp_reproject<<<grid, block, 0, st>>>(tp, reinterpret_cast<const uint4*>(d_color), reinterpret_cast<const uint4*>(d_ids), reinterpret_cast<const float4*>(d_normal),
-                                           reinterpret_cast<const float4*>(d_position), reinterpret_cast<const float4*>(d_albedo),
-                                           reinterpret_cast<const float4*>(d_prev_history), reinterpret_cast<const uint4*>(d_prev_ids),
-                                           reinterpret_cast<const float4*>(d_prev_normal), reinterpret_cast<const float4*>(d_prev_position),
-                                           reinterpret_cast<uint4*>(d_out), reinterpret_cast<float4*>(d_history_out), reinterpret_cast<float4*>(d_motion));
-    SKH_TRY(c, hipGetLastError());
-    SKH_TRY(c, hipStreamSynchronize(st));
-    c->tp.info.calls++;
-    c->tp.info.pixels += n;
-    c->tp.info.ms_last = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
-    return SKH_OK;
-}
-
-skh_status skh_get_temporal_info(skh_context* c, skh_temporal_info* out)
-{
-    if (!c || !out)
-        return SKH_INVALID_ARGUMENT;
-    *out = c->tp.info;
-    return SKH_OK;
-}
-
-// ---- variance guidance (skh_variance.h): skh_moments, skh_get_moments_info, skh_vdenoise_check, skh_denoise_variance, skh_get_vdenoise_info ----
-static_assert(sizeof(skh_moments_info) == 24 && sizeof(skh_vdenoise_params) == 64 && sizeof(skh_vdenoise_info) == 32, "ABI layout");
-
-skh_status skh_moments(skh_context* c, const skh_temporal_params* p, const void* d_color, const void* d_ids, const void* d_position, const void* d_albedo,
-                       const void* d_motion, const void* d_prev_moments, void* d_moments_out)
-{
-    if (!c)
-        return SKH_INVALID_ARGUMENT;
-    (void)hipSetDevice(c->dev.device);
-    const char* why = temporal_refusal(p);
-    if (!why && (!d_color || !d_ids || !d_position || !d_moments_out))
-        why = "a NULL image";
-    if (!why && (p->flags & SKH_TEMPORAL_DEMODULATE) && !d_albedo)
-        why = "a flag that needs the albedo plane, and no albedo plane";
-    if (!why && (d_motion == nullptr) != (d_prev_moments == nullptr))
-        why = "exactly one of d_motion and d_prev_moments";
-    if (!why && d_prev_moments && d_moments_out == d_prev_moments)
-        why = "d_moments_out == d_prev_moments (taps read neighbours)";
-    if (why)
-    {
-        c->dev.err = std::string("skh_moments: ") + why;
-        return SKH_INVALID_ARGUMENT;
-    }
-    const auto t0 = std::chrono::steady_clock::now();
-    const size_t n = (size_t)p->width * p->height;
-    hipStream_t st = side_stream(c); // (skh_temporal's stream)
-    TpP tp;
-    tp.width = p->width, tp.height = p->height;
-    for (int k = 0; k < 16; ++k)
-        tp.prevWorldToClip[k] = p->prev_world_to_clip[k];
-    tp.normalMin = p->normal_min, tp.planeTolerance = p->plane_tolerance, tp.maxHistory = p->max_history, tp.initialLength = p->initial_length;
-    tp.albedoFloor = p->albedo_floor, tp.flags = p->flags, tp.hasPrev = d_prev_moments ? 1u : 0u;
-    const dim3 grid(((p->width + 63u) / 64u) * ((p->height + 3u) / 4u)), block(64, 4);
-    k_vr_moments<<<grid, block, 0, st>>>(tp, reinterpret_cast<const float4*>(d_color), reinterpret_cast<const uint4*>(d_ids),
-                                         reinterpret_cast<const float4*>(d_position), reinterpret_cast<const float4*>(d_albedo),
-                                         reinterpret_cast<const float4*>(d_motion), reinterpret_cast<const float4*>(d_prev_moments),
-                                         reinterpret_cast<float4*>(d_moments_out));
-    SKH_TRY(c, hipGetLastError());
-    SKH_TRY(c, hipStreamSynchronize(st));
-    c->mo.info.calls++;
-    c->mo.info.pixels += n;
-    c->mo.info.ms_last = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
-    return SKH_OK;
-}
-
-skh_status skh_get_moments_info(skh_context* c, skh_moments_info* out)
-{
-    if (!c || !out)
-        return SKH_INVALID_ARGUMENT;
-    *out = c->mo.info;
-    return SKH_OK;
-}
-
-// why *p is refused, or nullptr
-static const char* vdenoise_refusal(const skh_vdenoise_params* p)
-{
-    if (!p)
-        return "no parameters";
-    if (p->width == 0u || p->height == 0u || (uint64_t)p->width * p->height > (1ull << 26))
-        return "an empty image, or one of more than 2^26 pixels";
-    if (p->levels == 0u || p->first_level > SKH_DENOISE_MAX_LEVEL || p->levels > SKH_DENOISE_MAX_LEVEL || p->first_level + p->levels > SKH_DENOISE_MAX_LEVEL)
-        return "no level, or a level beyond first_level + levels <= 8";
-    for (float s : { p->sigma_luminance, p->sigma_normal, p->sigma_plane })
-        if (!(s > 0.0f)) // (a NaN too)
-            return "a sigma that is <= 0 or NaN";
-    if (!std::isfinite(p->albedo_floor) || !(p->albedo_floor > 0.0f))
-        return "an albedo_floor that is <= 0 or not finite";
-    if (!std::isfinite(p->epsilon) || !(p->epsilon > 0.0f))
-        return "an epsilon that is <= 0 or not finite";
-    if (!std::isfinite(p->min_history) || !(p->min_history >= 1.0f))
-        return "a min_history that is < 1 or not finite";
-    if (p->flags & ~(SKH_DENOISE_DEMODULATE | SKH_DENOISE_REMODULATE | SKH_VDENOISE_ESTIMATE))
-        return "an unknown flag bit";
-    for (uint32_t r : p->reserved)
-        if (r != 0u)
-            return "a non-zero reserved word";
-    return nullptr;
-}
-
-skh_status skh_vdenoise_check(const skh_vdenoise_params* p)
-{
-    return vdenoise_refusal(p) ? SKH_INVALID_ARGUMENT : SKH_OK;
-}
-
-skh_status skh_denoise_variance(skh_context* c, const skh_vdenoise_params* p, const void* d_color, const void* d_ids, const void* d_normal,
-                                const void* d_position, const void* d_albedo, const void* d_moments, void* d_out, void* d_moments_out)
-{
-    if (!c)
-        return SKH_INVALID_ARGUMENT;
-    if (!p) // free the scratch: skh_denoise's
-        return skh_denoise(c, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr);
-    (void)hipSetDevice(c->dev.device);
-    const char* why = vdenoise_refusal(p);
-    if (!why && (!d_color || !d_ids || !d_normal || !d_position || !d_moments || !d_out))
-        why = "a NULL image";
-    if (!why && (p->flags & (SKH_DENOISE_DEMODULATE | SKH_DENOISE_REMODULATE)) && !d_albedo)
-        why = "a flag that needs the albedo plane, and no albedo plane";
-    if (why)
-    {
-        c->dev.err = std::string("skh_denoise_variance: ") + why;
-        return SKH_INVALID_ARGUMENT;
-    }
-    const auto t0 = std::chrono::steady_clock::now();
-    const size_t n = (size_t)p->width * p->height;
-    const uint32_t est = (p->flags & SKH_VDENOISE_ESTIMATE) ? 1u : 0u;
-    SKH_CHECK(dev_alloc(c, c->dn.dColor[0], 16 * n));
-    if (p->levels + est > 1u)
-        SKH_CHECK(dev_alloc(c, c->dn.dColor[1], 16 * n));
-    SKH_CHECK(dev_alloc(c, c->dn.dG0, 16 * n));
-    SKH_CHECK(dev_alloc(c, c->dn.dG1, 8 * n));
-    hipStream_t st = side_stream(c);
-    VrP vp;
-    vp.width = p->width, vp.height = p->height, vp.step = 1u;
-    vp.lumOff = std::isinf(p->sigma_luminance) ? 1u : 0u;
-    vp.sigmaLuminance = vp.lumOff ? 0.0f : p->sigma_luminance, vp.epsilon = p->epsilon;
-    vp.kn = 1.0f / (p->sigma_normal * p->sigma_normal), vp.kp = 1.0f / (p->sigma_plane * p->sigma_plane);
-    vp.albedoFloor = p->albedo_floor, vp.minHistory = p->min_history, vp.flags = p->flags;
-    const float4* g0 = c->dn.dG0.as<float4>();
-    const float2* g1 = c->dn.dG1.as<float2>();
-    const float4* mom = reinterpret_cast<const float4*>(d_moments);
-    k_vr_pack<<<(uint32_t)((n + 255) / 256), 256, 0, st>>>(vp, reinterpret_cast<const float4*>(d_color), reinterpret_cast<const uint4*>(d_ids),
-                                                          reinterpret_cast<const float4*>(d_normal), reinterpret_cast<const float4*>(d_position),
-                                                          reinterpret_cast<const float4*>(d_albedo), mom, c->dn.dColor[0].as<float4>(), c->dn.dG0.as<float4>(),
-                                                          c->dn.dG1.as<float2>());
-    const dim3 grid(((p->width + 63u) / 64u) * ((p->height + 3u) / 4u)), block(64, 4); // (<= 2^24 + 2^20 tiles of 64 x 4 pixels, row-major)
-    if (est)
-        k_vr_estimate<<<grid, block, 0, st>>>(vp, c->dn.dColor[0].as<float4>(), g0, g1, mom, c->dn.dColor[1].as<float4>());
-    for (uint32_t k = 0; k < p->levels; ++k)
-    {
-        vp.step = 1u << (p->first_level + k);
-        const float4* cin = c->dn.dColor[(k + est) & 1u].as<float4>();
-        if (k + 1u < p->levels)
-            k_vr_level<false><<<grid, block, 0, st>>>(vp, cin, g0, g1, c->dn.dColor[(k + est + 1u) & 1u].as<float4>(), nullptr, nullptr, nullptr, nullptr, nullptr);
-        else
-            k_vr_level<true><<<grid, block, 0, st>>>(vp, cin, g0, g1, nullptr, reinterpret_cast<const uint4*>(d_color), reinterpret_cast<const float4*>(d_albedo),
-                                                    reinterpret_cast<uint4*>(d_out), mom, reinterpret_cast<float4*>(d_moments_out));
-    }
-    SKH_TRY(c, hipGetLastError());
-    SKH_TRY(c, hipStreamSynchronize(st));
-    c->vd.info.calls++;
-    c->vd.info.pixels += n;
-    c->vd.info.ms_last = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
-    return SKH_OK;
-}
-
-skh_status skh_get_vdenoise_info(skh_context* c, skh_vdenoise_info* out)
-{
-    if (!c || !out)
-        return SKH_INVALID_ARGUMENT;
-    *out = c->vd.info;
-    out->scratch_bytes = denoise_scratch_bytes(c);
-    return SKH_OK;
-}
-
-// ---- object motion (skh_motion.h): skh_instance_motion_from_transforms, skh_instance_motion_check, skh_set_instance_motion, skh_rewind_guides ----
-static_assert(sizeof(skh_instance_motion) == 96 && sizeof(skh_rewind_info) == 32, "ABI layout");
-
-// inverse of the row-major 3 x 3 `m` by adjugate / determinant, in the operation order the header writes out; false when the determinant is 0 or not finite
-static bool motion_inverse(const double m[3][3], double inv[3][3])
-{
-    double adj[3][3];
-    for (int i = 0; i < 3; ++i)
-        for (int j = 0; j < 3; ++j)
-            adj[i][j] = m[(j + 1) % 3][(i + 1) % 3] * m[(j + 2) % 3][(i + 2) % 3] - m[(j + 1) % 3][(i + 2) % 3] * m[(j + 2) % 3][(i + 1) % 3];
-    const double det = (m[0][0] * adj[0][0] + m[0][1] * adj[1][0]) + m[0][2] * adj[2][0];
-    if (det == 0.0 || !std::isfinite(det))
-        return false;
-    for (int i = 0; i < 3; ++i)
-        for (int j = 0; j < 3; ++j)
-            inv[i][j] = adj[i][j] / det;
-    return true;
-}
-
-skh_status skh_instance_motion_from_transforms(const float prev[12], const float cur[12], skh_instance_motion* out)
-{
-    if (!prev || !cur || !out)
-        return SKH_INVALID_ARGUMENT;
-    skh_instance_motion e = {};
-    e.to_prev[0] = e.to_prev[5] = e.to_prev[10] = 1.0f;
-    e.normal_to_prev[0] = e.normal_to_prev[4] = e.normal_to_prev[8] = 1.0f;
-    if (std::memcmp(prev, cur, 12 * sizeof(float)) == 0)
-    {
-        *out = e; // flags 0: the entry is skipped
-        return SKH_OK;
-    }
-    skh_instance_motion moved = e;
-    bool ok = true;
-    double A[3][3], B[3][3], a[3], b[3], Ai[3][3], Bi[3][3];
-    for (int i = 0; i < 3; ++i)
-    {
-        for (int j = 0; j < 3; ++j)
-            A[i][j] = prev[4 * i + j], B[i][j] = cur[4 * i + j];
-        a[i] = prev[4 * i + 3], b[i] = cur[4 * i + 3];
-    }
-    for (int k = 0; k < 12; ++k)
-        ok = ok && std::isfinite(prev[k]) && std::isfinite(cur[k]);
-    ok = ok && motion_inverse(B, Bi) && motion_inverse(A, Ai);
-    if (ok)
-        for (int i = 0; i < 3; ++i)
-        {
-            double L[3];
-            for (int j = 0; j < 3; ++j)
-            {
-                L[j] = (A[i][0] * Bi[0][j] + A[i][1] * Bi[1][j]) + A[i][2] * Bi[2][j];
-                moved.to_prev[4 * i + j] = (float)L[j];
-                const double K = (Ai[0][i] * B[j][0] + Ai[1][i] * B[j][1]) + Ai[2][i] * B[j][2];
-                moved.normal_to_prev[3 * i + j] = (float)K;
-            }
-            moved.to_prev[4 * i + 3] = (float)(a[i] - ((L[0] * b[0] + L[1] * b[1]) + L[2] * b[2]));
-        }
-    for (int k = 0; ok && k < 12; ++k)
-        ok = std::isfinite(moved.to_prev[k]);
-    for (int k = 0; ok && k < 9; ++k)
-        ok = std::isfinite(moved.normal_to_prev[k]);
-    if (ok)
-        moved.flags = SKH_MOTION_MOVED, *out = moved;
-    else
-        e.flags = SKH_MOTION_MOVED | SKH_MOTION_DROP, *out = e;
-    return SKH_OK;
-}
-
-// why the table is refused, or nullptr
-static const char* motion_refusal(const skh_instance_motion* table, uint32_t n)
-{
-    if (n > 0u && !table)
-        return "no table for n > 0";
-    for (uint32_t i = 0; i < n; ++i)
-    {
-        const skh_instance_motion& e = table[i];
-        if (e.flags & ~(SKH_MOTION_MOVED | SKH_MOTION_DROP))
-            return "an unknown flag bit";
-        if ((e.flags & SKH_MOTION_DROP) && !(e.flags & SKH_MOTION_MOVED))
-            return "DROP without MOVED";
-        if (e.reserved[0] != 0u || e.reserved[1] != 0u)
-            return "a non-zero reserved word";
-        if (e.flags == SKH_MOTION_MOVED)
-        {
-            for (float m : e.to_prev)
-                if (!std::isfinite(m))
-                    return "a matrix word that is not finite in a moved entry";
-            for (float m : e.normal_to_prev)
-                if (!std::isfinite(m))
-                    return "a matrix word that is not finite in a moved entry";
-        }
-    }
-    return nullptr;
-}
-
-skh_status skh_instance_motion_check(const skh_instance_motion* table, uint32_t n)
-{
-    return motion_refusal(table, n) ? SKH_INVALID_ARGUMENT : SKH_OK;
-}
-
-skh_status skh_set_instance_motion(skh_context* c, const skh_instance_motion* table, uint32_t n)
-{
-    if (!c)
-        return SKH_INVALID_ARGUMENT;
-    (void)hipSetDevice(c->dev.device);
-    if (const char* why = motion_refusal(table, n))
-    {
-        c->dev.err = std::string("skh_set_instance_motion: ") + why;
-        return SKH_INVALID_ARGUMENT;
-    }
-    if (n == 0u)
-    {
-        dev_free(c->rw.dTable);
-        c->rw.entries = 0;
-        return SKH_OK;
-    }
-    c->rw.entries = 0; // (until the new table is in place: a failed upload leaves none)
-    SKH_CHECK(dev_upload(c, c->rw.dTable, table, sizeof(skh_instance_motion) * (size_t)n));
-    c->rw.entries = n;
-    return SKH_OK;
-}
-
-skh_status skh_rewind_guides(skh_context* c, uint32_t width, uint32_t height, const void* d_ids, const void* d_position, const void* d_normal, void* d_position_out,
-                             void* d_normal_out)
-{
-    if (!c)
-        return SKH_INVALID_ARGUMENT;
-    (void)hipSetDevice(c->dev.device);
-    const char* why = nullptr;
-    if (width == 0u || height == 0u || (uint64_t)width * height > (1ull << 26))
-        why = "an empty image, or one of more than 2^26 pixels";
-    if (!why && (!d_ids || !d_position || !d_normal || !d_position_out || !d_normal_out))
-        why = "a NULL plane";
-    if (!why && (c->rw.entries == 0u || !c->rw.dTable.p))
-        why = "no motion table set (skh_set_instance_motion)";
-    if (why)
-    {
-        c->dev.err = std::string("skh_rewind_guides: ") + why;
-        return SKH_INVALID_ARGUMENT;
-    }
-    const auto t0 = std::chrono::steady_clock::now();
-    hipStream_t st = side_stream(c); // (skh_temporal's stream)
-    const dim3 grid(((width + 63u) / 64u) * ((height + 3u) / 4u)), block(64, 4); // (<= 2^24 + 2^20 tiles of 64 x 4 pixels, row-major)
-    k_mo_rewind<<<grid, block, 0, st>>>(width, height, c->rw.entries, c->rw.dTable.as<float4>(), reinterpret_cast<const uint4*>(d_ids),
-                                        reinterpret_cast<const float4*>(d_position), reinterpret_cast<const float4*>(d_normal),
-                                        reinterpret_cast<float4*>(d_position_out), reinterpret_cast<float4*>(d_normal_out));
-    SKH_TRY(c, hipGetLastError());
-    SKH_TRY(c, hipStreamSynchronize(st));
-    c->rw.info.calls++;
-    c->rw.info.pixels += (uint64_t)width * height;
-    c->rw.info.ms_last = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
-    return SKH_OK;
-}
-
-skh_status skh_get_rewind_info(skh_context* c, skh_rewind_info* out)
-{
-    if (!c || !out)
-        return SKH_INVALID_ARGUMENT;
-    *out = c->rw.info;
-    out->entries = c->rw.entries;
-    return SKH_OK;
-}
-
-// ---- history rectification (skh_rectify.h): skh_rectify_check, skh_rectify, skh_get_rectify_info ----
-static_assert(sizeof(skh_rectify_params) == 56 && sizeof(skh_rectify_info) == 24, "ABI layout");
-
-// why *p is refused, or nullptr
-static const char* rectify_refusal(const skh_rectify_params* p)
-{
-    if (!p)
-        return "no parameters";
-    if (p->width == 0u || p->height == 0u || (uint64_t)p->width * p->height > (1ull << 26))
-        return "an empty image, or one of more than 2^26 pixels";
-    if (p->radius < 1u || p->radius > 3u)
-        return "a radius outside 1 ... 3";
-    if (!(p->k > 0.0f)) // (a NaN too; +inf is legal)
-        return "a k that is <= 0 or NaN";
-    if (!std::isfinite(p->albedo_floor) || !(p->albedo_floor > 0.0f))
-        return "an albedo_floor that is <= 0 or not finite";
-    if (p->flags & ~(SKH_RECTIFY_REMODULATE | SKH_RECTIFY_SHORTEN))
-        return "an unknown flag bit";
-    for (uint32_t r : p->reserved)
-        if (r != 0u)
-            return "a non-zero reserved word";
-    return nullptr;
-}
-
-skh_status skh_rectify_check(const skh_rectify_params* p)
-{
-    return rectify_refusal(p) ? SKH_INVALID_ARGUMENT : SKH_OK;
-}
-
-skh_status skh_rectify(skh_context* c, const skh_rectify_params* p, const void* d_image, const void* d_ids, const void* d_albedo, const void* d_history,
-                       const void* d_fast, void* d_out, void* d_history_out, void* d_info)
-{
-    if (!c)
-        return SKH_INVALID_ARGUMENT;
-    (void)hipSetDevice(c->dev.device);
-    const char* why = rectify_refusal(p);
-    if (!why && (!d_image || !d_ids || !d_history || !d_fast || !d_out || !d_history_out))
-        why = "a NULL image";
-    if (!why && (p->flags & SKH_RECTIFY_REMODULATE) && !d_albedo)
-        why = "a flag that needs the albedo plane, and no albedo plane";
-    if (!why && (d_history_out == d_fast || d_out == d_fast))
-        why = "an output that is d_fast (the window reads neighbours)";
-    if (why)
-    {
-        c->dev.err = std::string("skh_rectify: ") + why;
-        return SKH_INVALID_ARGUMENT;
-    }
-    const auto t0 = std::chrono::steady_clock::now();
-    hipStream_t st = side_stream(c); // (skh_temporal's stream)
-    RcP rp;
-    rp.width = p->width, rp.height = p->height, rp.k = p->k, rp.albedoFloor = p->albedo_floor, rp.flags = p->flags, rp.kInf = std::isinf(p->k) ? 1u : 0u;
-    const dim3 grid(((p->width + 63u) / 64u) * ((p->height + 3u) / 4u)), block(64, 4); // (<= 2^24 + 2^20 tiles of 64 x 4 pixels, row-major)
-    const uint4* image = reinterpret_cast<const uint4*>(d_image);
-    const uint4* ids = reinterpret_cast<const uint4*>(d_ids);
-    const float4* albedo = reinterpret_cast<const float4*>(d_albedo);
-    const uint4* history = reinterpret_cast<const uint4*>(d_history);
-    const float4* fast = reinterpret_cast<const float4*>(d_fast);
-    uint4* out = reinterpret_cast<uint4*>(d_out);
-    uint4* historyOut = reinterpret_cast<uint4*>(d_history_out);
-    float4* info = reinterpret_cast<float4*>(d_info);
-    if (p->radius == 1u)
-        k_rc_rectify<1><<<grid, block, 0, st>>>(rp, image, ids, albedo, history, fast, out, historyOut, info);
-    else if (p->radius == 2u)
-        k_rc_rectify<2><<<grid, block, 0, st>>>(rp, image, ids, albedo, history, fast, out, historyOut, info);
-    else
-        k_rc_rectify<3><<<grid, block, 0, st>>>(rp, image, ids, albedo, history, fast, out, historyOut, info);
-    SKH_TRY(c, hipGetLastError());
-    SKH_TRY(c, hipStreamSynchronize(st));
-    c->rc.info.calls++;
-    c->rc.info.pixels += (uint64_t)p->width * p->height;
-    c->rc.info.ms_last = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
-    return SKH_OK;
-}
-
-skh_status skh_get_rectify_info(skh_context* c, skh_rectify_info* out)
-{
-    if (!c || !out)
-        return SKH_INVALID_ARGUMENT;
-    *out = c->rc.info;
-    return SKH_OK;
+    return get_info(c, &skh_context::aov, out);
 }
 
 // ---- skh_set_option: one row per name ----

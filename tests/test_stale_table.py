@@ -46,6 +46,6 @@ def test_the_header_has_no_hip_in_it_and_is_a_dependency_of_the_build():
 def test_no_setter_sets_the_flags_by_hand():
     """Outside the builders and *_ensure functions, which CLEAR what they have just derived, no host file raises a stale / edited flag or drops a ready flag."""
     pat = re.compile(r"\b(stale|vertsEdited|curvePointsEdited) = true|\b(built|refitReady) = false")
-    for fn in ("strelka_hip.hip", "skh_accel.inc", "skh_probes.inc", "skh_host.h"):
+    for fn in ("strelka_hip.hip", "skh_accel.inc", "skh_probes.inc", "skh_image.inc", "skh_host.h"):
         text = open(os.path.join(CSRC, fn)).read()
         assert [m.group(0) for m in pat.finditer(text) if not text[:m.start()].endswith("bool ")] == [], fn
